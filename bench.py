@@ -12,6 +12,9 @@ N>1: one process per GPU, weak scaling (B=32 per rank), CondBN statistics all-re
 `python bench.py --gpus N` WITHOUT a launcher (no WORLD_SIZE in the environment) starts the N ranks itself through
 torch.distributed.run - before anything touches a GPU - and exits non-zero when fewer than N devices are visible:
 it never reports a smaller run than the one asked for.  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times the steps and prints the headline (`value`, `ms_per_step`, ...); `--full` adds the roofline, the
+other precisions and configurations, the training step, the RCCL sync overhead and the CPU baseline to the same line.
+`--dump-outputs DIR` writes what the last timed step returned, for comparing two builds on the same seeded inputs.
 """
 import argparse
 from statistics import mean, median
@@ -21,6 +24,8 @@ import socket
 import subprocess
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -185,9 +190,10 @@ def schedule_traffic(per_kernel: dict, suffix: str, step_s: float):
     return dict(counter_bytes_per_step=total, hbm_frac_counter=total / step_s / 1e9 / PEAK_HBM_GBS, source=src)
 
 
-def run_steps(g, inp, steps, warmup, barrier=lambda: None):
+def run_steps(g, inp, steps, warmup, barrier=lambda: None, last=None):
     """EXACTLY `steps` forwards between barrier + synchronize pairs (wall clock), HIP events on the launching stream around every
-    step as well (event-timed median).  Returns (elapsed seconds, per-step milliseconds)."""
+    step as well (event-timed median).  Returns (elapsed seconds, per-step milliseconds); `last` (a list) receives the
+    output of the last timed step."""
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     with torch.no_grad():
         for _ in range(warmup):
@@ -197,8 +203,10 @@ def run_steps(g, inp, steps, warmup, barrier=lambda: None):
         t0 = time.perf_counter()
         evs[0].record()
         for i in range(steps):
-            g(*inp)
+            y = g(*inp)
             evs[i + 1].record()
+        if last is not None:
+            last.append(y)
         torch.cuda.synchronize()
         barrier()
         elapsed = time.perf_counter() - t0
@@ -632,6 +640,24 @@ def write_detail(out):
         return None
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, y, limit=DUMP_LIMIT_BYTES):
+    """`--dump-outputs DIR`: what the timed forward returned in its last step, the audio `y` (B, 1, T x 320), as DIR/y.npy in float32, so
+    that two builds run with the same arguments (same seeded weights and inputs) can be compared output for output.  When the whole
+    tensor is larger than `limit`, a fixed seeded sample of its batch rows is written instead, and their indices as DIR/y_rows.npy."""
+    y = y.detach().float().cpu().numpy()
+    os.makedirs(dirpath, exist_ok=True)
+    row_bytes = y[0].nbytes
+    if y.nbytes > limit - (1 << 20):
+        k = max(1, (limit - (1 << 20)) // row_bytes)
+        rows = np.sort(np.random.default_rng(0).choice(y.shape[0], size=k, replace=False))
+        np.save(os.path.join(dirpath, 'y_rows.npy'), rows.astype(np.float64))
+        y = y[rows]
+    np.save(os.path.join(dirpath, 'y.npy'), np.ascontiguousarray(y))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -647,9 +673,15 @@ def main():
     ap.add_argument('--resblock', default='2', choices=['1', '2'], help="'1': the ResBlock1 generator (h.resblock == '1'); default ResBlock2")
     ap.add_argument('--force-pg', action='store_true',
                     help='--gpus 1 only: create a ONE-rank RCCL process group and keep the CondBN statistics all-reduces inside the timed region')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline steps, measure everything else as well: roofline of the dominant kernel, the f16x3 mode, the '
+                         'other BASELINE configurations, ResBlock1, inference, training step, RCCL sync overhead and the CPU baseline '
+                         '(default: the headline steps only)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help="write what the last timed step returned (rank 0's audio y) as DIR/y.npy, float32, at most 64 MB")
     ap.add_argument('--verbose', action='store_true',
-                    help='print the full line (per-kernel tables, launch tags, every sub-measurement); default: the compact line '
-                         '(< 8 KB, ends in `summary`), the full one goes to gpurun_out/bench_detail.json')
+                    help='with --full: print the full line (per-kernel tables, launch tags, every sub-measurement); default: the compact '
+                         'line (< 8 KB, ends in `summary`), the full one goes to the detail file (write_detail)')
     ap.add_argument('--dry-run', action='store_true',
                     help='first-contact check of the N-rank plumbing WITHOUT a GPU: launcher, rendezvous (set V2W_BENCH_BACKEND=gloo), per-rank '
                          'seeds and shards, barrier, max-over-ranks and the one JSON line are exercised; no forward runs and `value` is null')
@@ -657,6 +689,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit('--gpus must be >= 1')
+    if args.steps < 1:
+        raise SystemExit('--steps must be >= 1')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         raise SystemExit(self_launch(args))
     rank = int(os.environ.get('RANK', '0'))
@@ -718,17 +752,22 @@ def main():
         return v
 
     # ---- the timed region
-    elapsed, step_ms = run_steps(g, inp, args.steps, args.warmup, barrier)
+    last = []
+    elapsed, step_ms = run_steps(g, inp, args.steps, args.warmup, barrier, last)
     elapsed = max_over_ranks(elapsed)
     event_median_ms = max_over_ranks(median(step_ms)) if step_ms else None
     rccl_ranks = dist.get_world_size() if (grouped and backend == 'nccl') else (1 if world == 1 else None)
-    extras = world == 1 and rank == 0 and args.algo == 'auto' and not args.no_alt and args.precision == 'f32' and args.resblock == '2' \
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last[0])
+    del last
+    # everything below the headline runs only with --full
+    extras = args.full and world == 1 and rank == 0 and args.algo == 'auto' and not args.no_alt and args.precision == 'f32' and args.resblock == '2' \
         and (B, T) == (32, 256)
 
     # ---- the same step with Generator.precision = 'f16x3' (wide Conv1d layers on the f16 matrix pipe with split operands,
     # fp32 accumulation; same parity bar).  Reported BESIDE the exact-fp32 `value`, never instead of it.
     alt = None
-    if args.algo == 'auto' and not args.no_alt and args.precision == 'f32' and args.resblock == '2':
+    if args.full and args.algo == 'auto' and not args.no_alt and args.precision == 'f32' and args.resblock == '2':
         with torch.no_grad():
             y32 = g(*inp).clone()
             g.precision = 'f16x3'
@@ -749,11 +788,11 @@ def main():
         suffix = {'f32': '_cfg2_hbm_traffic.json', 'bf16': '_cfg2_bf16_hbm_traffic.json'}.get(args.precision)
     if (B, T) == (64, 512) and args.precision == 'bf16' and args.resblock == '2':
         suffix = '_cfg3_bf16_hbm_traffic.json'
-    roof = roofline_block(g, h, inp, B, T, args.precision, args.algo, elapsed / args.steps, suffix, record=rank == 0)
+    roof = roofline_block(g, h, inp, B, T, args.precision, args.algo, elapsed / args.steps, suffix, record=rank == 0) if args.full else None
 
     # ---- what the data-parallel statistics exchange costs per forward, on a one-rank RCCL group (the only RCCL run a one-GPU box allows)
     sync = None
-    if extras or (args.force_pg and rank == 0 and world == 1):
+    if extras or (args.full and args.force_pg and rank == 0 and world == 1):
         try:
             sync = stat_sync_overhead(g, inp, dev, max(5, args.steps // 2))
         except Exception as e:            # a box without a usable RCCL must not lose the bench line
@@ -818,7 +857,7 @@ def main():
                 train['alt_precision_' + prec] = {k: alt_t.get(k) for k in ('ms_per_step', 'value', 'tflops', 'workload', 'error') if k in alt_t}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(synthetic.make_hparams(num_wv_feat=768))
 
     if rank == 0:
@@ -837,18 +876,19 @@ def main():
                                    f'{rbname}, train-mode CondBN, {args.precision}', 'global_batch': B * world, 'frames': T,
                        'parallelism': (f'dp{world} (batch shards, RCCL all-reduce of CondBN stats)' if world > 1 else
                                        'single GPU' + (', one-rank RCCL group: the CondBN all-reduces are inside the timed region' if args.force_pg else ''))},
-            'roofline': roof, 'cpu_baseline': cpu, 'alt_precision': alt, 'stat_sync': sync, 'resblock1_f32': rb1, 'cfg3_bf16': cfg3,
-            'cfg2_bf16': cfg2b, 'inference_bf16': infer, 'cfg5_f32': cfg5, 'train_step': train, 'resblock1_bf16': rb1b,
         }
-        blocks = ('alt_precision', 'cfg3_bf16', 'cfg2_bf16', 'inference_bf16', 'cfg5_f32', 'resblock1_f32', 'resblock1_bf16', 'train_step', 'stat_sync')
-        if not args.verbose:
-            detail = write_detail(out)
-            out['roofline'] = compact_roofline(roof)
-            out['cpu_baseline'] = compact_cpu(cpu)
-            for name in blocks:
-                out[name] = compact_block(out[name])
-            out['detail'] = detail
-        out['summary'] = summary_of(out, blocks)          # LAST key: [ms_per_step, hbm_frac, mfma_frac] of every block
+        if args.full:
+            out.update({'roofline': roof, 'cpu_baseline': cpu, 'alt_precision': alt, 'stat_sync': sync, 'resblock1_f32': rb1, 'cfg3_bf16': cfg3,
+                        'cfg2_bf16': cfg2b, 'inference_bf16': infer, 'cfg5_f32': cfg5, 'train_step': train, 'resblock1_bf16': rb1b})
+            blocks = ('alt_precision', 'cfg3_bf16', 'cfg2_bf16', 'inference_bf16', 'cfg5_f32', 'resblock1_f32', 'resblock1_bf16', 'train_step', 'stat_sync')
+            if not args.verbose:
+                detail = write_detail(out)
+                out['roofline'] = compact_roofline(roof)
+                out['cpu_baseline'] = compact_cpu(cpu)
+                for name in blocks:
+                    out[name] = compact_block(out[name])
+                out['detail'] = detail
+            out['summary'] = summary_of(out, blocks)          # LAST key: [ms_per_step, hbm_frac, mfma_frac] of every block
     if dist.is_initialized():
         dist.destroy_process_group()
     redirect.__exit__()

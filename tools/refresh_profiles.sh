@@ -4,8 +4,8 @@
 # usage: V2W_COMMIT=<hash> V2W_DATE=<date> tools/refresh_profiles.sh rNN
 R=$PWD; TAG=${1:-r02}; O=$R/gpurun_out/profiles_new; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-alt"
-B3="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-alt"
+B="python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-alt"
+B3="python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-alt"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o ks -- $B > $O/ks.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o pf -- $B3 > $O/pf.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o pw -- $B3 > $O/pw.log 2>&1
@@ -21,10 +21,10 @@ timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/ks_lat -o ks -- p
 # one train.py GAN iteration (generator, mel, D step, G step) at the cfg2 shape: kernel stats of 1 + 2 warm-up iterations
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_gan -o ks -- python3 $R/tools/gan_step_bench.py 32 256 1 > $O/ks_gan.log 2>&1
 # the north-star shape B = 32 x T = 256 in the bf16 arithmetic: fabric traffic per kernel (bench.py reads cfg2_bf16's `traffic` from it)
-B3B="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-alt --precision bf16"
+B3B="python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-alt --precision bf16"
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/c2b_fetch -o pf -- $B3B > $O/c2bpf.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/c2b_write -o pw -- $B3B > $O/c2bpw.log 2>&1
-B3C="python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-alt --precision bf16 --batch 64 --frames 512"
+B3C="python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-alt --precision bf16 --batch 64 --frames 512"
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/c3_fetch -o pf -- $B3C > $O/c3pf.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/c3_write -o pw -- $B3C > $O/c3pw.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA GRBM_GUI_ACTIVE --output-format csv -d $O/c3_sq_a -o sa -- $B3C > $O/c3sa.log 2>&1
@@ -44,7 +44,7 @@ python3 tools/pmc_sq.py $O/c3_sq_a $O/c3_sq_b > $O/cfg3_bf16_sq_counters.json 2>
 cp $O/hbm_traffic.json profiles/${TAG}_cfg2_hbm_traffic.json    # bench.py reads the traffic of its dominant kernel from here
 cp $O/cfg3_bf16_hbm_traffic.json profiles/${TAG}_cfg3_bf16_hbm_traffic.json
 cp $O/cfg2_bf16_hbm_traffic.json profiles/${TAG}_cfg2_bf16_hbm_traffic.json
-timeout 900 python3 bench.py > $O/bench.json 2> $O/bench.err            # the driver's line (compact: ends in `summary`)
+timeout 900 python3 bench.py --full > $O/bench.json 2> $O/bench.err            # the driver's line (compact: ends in `summary`)
 cp gpurun_out/bench_detail.json $O/bench_detail.json                   # ... and the full-precision line with every per-kernel table
 # the RCCL branch on a one-rank communicator: the per-step cost of the five statistics all-reduces (bench.py `stat_sync`)
 python3 - "$O" > $O/sync_overhead.txt <<'PYEOF'
