@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define V2W_ABI_VERSION 34
+#define V2W_ABI_VERSION 35
 
 #define V2W_E_ARG      (-1)  /* null pointer / non-positive size */
 #define V2W_E_SHAPE    (-2)  /* shape not supported by the requested algorithm */
@@ -44,6 +44,12 @@ extern "C" {
 #define V2W_ALGO_SPLIT  3    /* split-f16 MFMA: x = hi + lo halves, x_hi*w_hi + x_hi*w_lo + x_lo*w_hi accumulated in fp32 (~22-bit
                               * products; v_mfma_f32_32x32x16_f16); needs wps / winv from v2w_pack_split; Conv1d with
                               * C_in % 16 == 0, C_out % 64 == 0 and an odd k >= 3, else V2W_E_SHAPE */
+#define V2W_ALGO_WINO   5    /* (ABI v35) exact-fp32 Winograd F(2,3) over output pairs (t, t + dil) on v_mfma_f32_32x32x2_f32: 4 / 10 / 15 products
+                              * per output pair and channel pair for k = 3 / 7 / 11 against 6 / 14 / 22; `wp` holds the v2w_pack_wino stream.
+                              * Conv1d with C_in % 32 == 0, C_in >= 64, C_out % 64 == 0, an odd k >= 3 and symmetric padding; unit input stride,
+                              * no channel slices, no mask / rowsum_part / out_slope, more than 128 workgroups (sum over the problems of
+                              * B * ceil(pairs / 64) * C_out / 64, pairs = dil * ceil(L / (2 dil))); else V2W_E_SHAPE and nothing is launched
+                              * (the caller runs V2W_ALGO_MFMA).  Not taken by V2W_ALGO_AUTO. */
 
 int         v2w_abi_version(void);
 const char* v2w_build_arch(void);       /* "gfx950" */
@@ -90,6 +96,11 @@ int v2w_pack_mfma(const float* wf, float* wp, int k, int c_in, int c_out, int u,
 int v2w_pack_mfma_dgrad(const float* wf, float* wp, int k, int c_in, int c_out, void* stream);
 /* n matrices back to back -> n packed streams back to back in one launch (the groups of a grouped conv) */
 int v2w_pack_mfma_batch(const float* wf, float* wp, int k, int c_in, int c_out, int u, int n, void* stream);
+/* V2W_ALGO_WINO (ABI v35): wf [k][c_in][c_out] -> wpw, v2w_wino_terms(k) * c_in * c_out floats: the transformed weights of every segment
+ * term (G0 = g0, G1 = (g0+g1+g2)/2, G2 = (g0-g1+g2)/2, G3 = g2 for 3 taps; g0, g0+g1, g1 for 2; g0, -g0 for 1) in MFMA A-fragment order
+ * [32-row block][32-channel chunk][segment][4-k-step unit][term].  V2W_E_SHAPE unless k is odd and >= 3, c_in % 32 == 0, c_out % 32 == 0. */
+int v2w_pack_wino(const float* wf, float* wpw, int k, int c_in, int c_out, void* stream);
+int v2w_wino_terms(int k);   /* weight matrices of the Winograd form of a k-tap conv: 4 (k/3) + {0, 2, 3}[k % 3]; 0 for even k or k < 3 */
 
 /* Batched form of fold + pack for every MFMA layer of a generator: two launches instead of three per layer.
  *   v2w_fold_plan       (host only) fills mf/ck of each descriptor and starts[2*(n+1)] (block prefix sums of the scale
@@ -108,6 +119,8 @@ typedef struct {
     float* wpd;         /* optional (ABI v28; Conv1d layers with C_in == C_out whose tile configuration has MF == CK only, else must be NULL):
                          * the fragment stream of the layer's INPUT-GRADIENT conv (tap-reversed transpose, what v2w_pack_mfma_dgrad builds
                          * from wf) in the same pass */
+    float* wpw;         /* optional (ABI v35; Conv1d layers whose tile configuration is MF == CK == 32 with an odd k >= 3, else must be NULL):
+                         * the V2W_ALGO_WINO stream of the layer (what v2w_pack_wino builds from wf) in the same pass */
 } v2w_fold_desc;
 int v2w_fold_plan(v2w_fold_desc* descs, int n, int32_t* starts);
 int v2w_fold_pack_batch(const v2w_fold_desc* descs_dev, const int32_t* starts_dev, int n,

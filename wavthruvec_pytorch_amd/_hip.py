@@ -13,10 +13,10 @@ import threading
 
 from . import build as _build
 
-ABI_VERSION = 34
+ABI_VERSION = 35
 V2W_MAX_STAGES = 8
 V2W_BN_SPLITS = 64
-ALGO_AUTO, ALGO_DIRECT, ALGO_MFMA, ALGO_SPLIT, ALGO_BF16 = 0, 1, 2, 3, 4
+ALGO_AUTO, ALGO_DIRECT, ALGO_MFMA, ALGO_SPLIT, ALGO_BF16, ALGO_WINO = 0, 1, 2, 3, 4, 5
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -61,7 +61,7 @@ class StageArgs(C.Structure):
 class FoldDesc(C.Structure):
     _fields_ = [('v', _fp), ('g', _fp), ('wp', _fp), ('scale', _fp),
                 ('c_in', C.c_int32), ('c_out', C.c_int32), ('k', C.c_int32), ('u', C.c_int32), ('transposed', C.c_int32),
-                ('mf', C.c_int32), ('ck', C.c_int32), ('_pad', C.c_int32), ('wf', _fp), ('wpd', _fp)]
+                ('mf', C.c_int32), ('ck', C.c_int32), ('_pad', C.c_int32), ('wf', _fp), ('wpd', _fp), ('wpw', _fp)]
 
 
 _P4 = _fp * 4
@@ -119,6 +119,8 @@ SIGNATURES = {
     'v2w_pack_mfma': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     'v2w_pack_mfma_batch': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     'v2w_pack_mfma_dgrad': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
+    'v2w_pack_wino': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
+    'v2w_wino_terms': (C.c_int, [C.c_int]),
     'v2w_split_supported': (C.c_int, [C.c_int, C.c_int, C.c_int]),
     'v2w_pack_split': (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     'v2w_mel_phases': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),

@@ -5,6 +5,7 @@ int v2w_conv1d_mfma(const v2w_conv1d_args* a, int n, hipStream_t stream, int* cf
 int v2w_convt1d_mfma(const v2w_convt1d_args* a, hipStream_t stream, int* cfg_out, long long* ws_query = nullptr);
 int v2w_conv1d_split(const v2w_conv1d_args* a, int n, hipStream_t stream, bool bf16);
 int v2w_conv1d_direct(const v2w_conv1d_args* a, hipStream_t stream);
+int v2w_conv1d_wino(const v2w_conv1d_args* a, int n, hipStream_t stream);
 int v2w_convt1d_direct(const v2w_convt1d_args* a, hipStream_t stream);
 
 extern "C" int v2w_abi_version(void) { return V2W_ABI_VERSION; }
@@ -44,6 +45,7 @@ extern "C" int v2w_conv1d_fwd(const v2w_conv1d_args* a, void* stream) {
         case V2W_ALGO_MFMA: return v2w_conv1d_mfma(a, 1, st, nullptr);
         case V2W_ALGO_SPLIT: return v2w_conv1d_split(a, 1, st, false);
         case V2W_ALGO_BF16: return v2w_conv1d_split(a, 1, st, true);
+        case V2W_ALGO_WINO: return v2w_conv1d_wino(a, 1, st);
         case V2W_ALGO_AUTO: {
             const int rc = v2w_conv1d_mfma(a, 1, st, nullptr);
             return rc == V2W_E_SHAPE ? (a->wf ? v2w_conv1d_direct(a, st) : V2W_E_ARG) : rc;
@@ -104,5 +106,6 @@ extern "C" int v2w_conv1d_fwd_multi(const v2w_conv1d_args* a, int n, void* strea
     }
     if (a[0].algo == V2W_ALGO_SPLIT || a[0].algo == V2W_ALGO_BF16)
         return v2w_conv1d_split(a, n, (hipStream_t)stream, a[0].algo == V2W_ALGO_BF16);
+    if (a[0].algo == V2W_ALGO_WINO) return v2w_conv1d_wino(a, n, (hipStream_t)stream);
     return v2w_conv1d_mfma(a, n, (hipStream_t)stream, nullptr);
 }

@@ -29,6 +29,7 @@
 //                64-lane fragments: lane&(MF-1) = row/col inside the MFMA tile, lane/MF = k index.
 #include <type_traits>
 #include "v2w_tile.h"
+#include "v2w_wino.h"
 
 #ifdef V2W_TIMELINE   // diagnostic build only (see v2w_common.h)
 V2W_TL_SETTER(v2w_timeline_set_tile)
@@ -883,6 +884,19 @@ fold_pack_batch_kernel(const v2w_fold_desc* __restrict__ descs, const int32_t* _
         const int c = gg * CKG + j * KSTEP + lane / MF, co = lane % MF;
         dst[o] = d.transposed ? tile[c * rstride + co * K + t] : tile[co * rstride + c * K + t];
     }
+    // ---- ... and as block (mb, ch) of the Winograd F(2,3) stream (v2w_pack_wino's layout; MF == CK == 32 Conv1d layers only)
+    if (d.wpw) {
+        const int nfr = wino_terms(K) * GPC;
+        float* dw = d.wpw + (size_t)(mb * nch + ch) * nfr * 256;
+        for (int o = threadIdx.x; o < nfr * 256; o += 256) {
+            const int j = o & 3, lane = (o >> 2) & 63;
+            int s0, ntap, gg, term;
+            wino_frag(K, GPC, o >> 8, s0, ntap, gg, term);
+            const int c = gg * CKG + j * KSTEP + lane / MF, co = lane % MF;
+            const float* w = tile + co * rstride + c * K + s0;
+            dw[o] = wino_weight(ntap, term, w[0], ntap > 1 ? w[1] : 0.f, ntap > 2 ? w[2] : 0.f);
+        }
+    }
     // ---- the same sub-block in the plain layout wf [k][C_in][C_out] (a training forward: the gradient kernels read it), coalesced along C_out
     if (d.wf) {
         for (int idx = threadIdx.x; idx < K * CK * MF; idx += 256) {
@@ -1052,7 +1066,8 @@ extern "C" int v2w_fold_plan(v2w_fold_desc* descs, int n, int32_t* starts) {
         const LayerCfg cfg = v2w_layer_cfg(d.c_in, d.c_out, d.transposed ? d.u : 1);
         if (!cfg.mf) return V2W_E_SHAPE;
         d.mf = cfg.mf; d.ck = cfg.ck;
-        if (d.wpd && (d.transposed || d.c_in != d.c_out || cfg.mf != cfg.ck)) return V2W_E_ARG;   // the gradient stream comes from the same LDS block only then
+        if (d.wpd && (d.transposed || d.c_in != d.c_out || cfg.mf != cfg.ck)) return V2W_E_ARG;
+        if (d.wpw && (d.transposed || cfg.mf != 32 || cfg.ck != 32 || wino_terms(d.k) == 0)) return V2W_E_ARG;   // the Winograd stream: v2w_pack_wino's shapes   // the gradient stream comes from the same LDS block only then
         starts[i] = bs; starts[n + 1 + i] = bp;
         bs += d.transposed ? d.c_in : d.c_out;
         bp += (d.c_out / cfg.mf) * (d.c_in / cfg.ck);

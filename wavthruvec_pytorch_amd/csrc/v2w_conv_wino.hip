@@ -1,0 +1,390 @@
+// Winograd F(2,3) Conv1d on the gfx950 f32 MFMA pipe (V2W_ALGO_WINO): the wide residual convs of the generator
+// (models.py:65-70 of the reference: leaky_relu -> dilated Conv1d, odd k, stride 1) with fewer multiplies.
+//
+// The arithmetic is in v2w_wino.h: the outputs go in pairs (t, t + dil), every segment of <= 3 taps feeds four accumulator classes,
+// and a k = 3 / 7 / 11 conv issues 4 / 10 / 15 products per output pair and channel pair instead of 6 / 14 / 22 (x0.69 over a ResBlock2
+// layer triple).  Every coefficient is 0, +-1 or 1/2, folded into the weights by the packers; the input side is x_j -+ x_j'.
+//
+// GEMM view per workgroup: M = MT output channels, N = NTP output PAIRS (2 NTP positions), K = C_in x terms, four accumulator sets.
+// The staging is conv_tile_kernel's (v2w_conv_mfma.hip): the activated signal (CondBN affine + leaky_relu applied once) in the LDS tile
+// Xs[positions][36 floats], position-major, channels permuted so that a lane's four k-steps are one ds_read_b128; double-buffered over
+// chunks of 32 input channels.  Unlike there the next chunk is loaded and written after the MFMA phase (its registers would cost the third
+// wave per SIMD; the other workgroups on the CU cover the latency).
+// Lane column j of a wave owns pair P; pair P's first output sits at t(P) = 2 dil (P / dil) + P % dil, so every operand x_j of
+// every segment is a row offset from the lane's base row.  Per unit (4 k-steps) of a 3-tap segment a lane reads x0..x3 (4 x
+// ds_read_b128), forms u0..u3 (16 VALU adds against 16 MI MFMAs) and runs MI MFMAs per term and k-step.
+// A (weights): v2w_pack_wino / the batched fold store the transformed weights in MFMA A-fragment order, [row block][chunk][segment]
+// [unit][term], 1 KiB per fragment, a 4-deep ring in registers as in conv_tile_kernel.
+// Tile: 64 output channels x 64 pairs (MI = 1), 4 accumulator sets = 64 registers per lane; launch bound three waves per SIMD (measured
+// at B = 32 x T = 256: two waves per SIMD with the register-prefetched staging ran 10-20 % slower, MI = 2 at one wave slower still: 9.95 against 8.97 ms per forward).
+// Epilogue: the output transform in registers, then bias [+ res_a*res + res_s] [+ add0 (+ add1) | + out] [/ out_div] per element
+// in conv_tile_kernel's order; second outputs of a pair at or past L are not stored.  Fixed summation order, no atomics.
+#include "v2w_tile.h"
+#include "v2w_wino.h"
+
+namespace {
+
+constexpr int WCK = 32;                 // channels per chunk
+constexpr int WRS = 36;                 // floats per LDS row (TileGeom<32, 32>::RS)
+constexpr int WGPC = 4;                 // A fragments (units of 4 k-steps) per chunk and term
+constexpr int WHMAX = 32;               // staging slots cover 2 NTP + 2 WHMAX rows
+__host__ __device__ constexpr int wslot(int c) { return (c & ~7) + 4 * (c & 1) + ((c & 7) >> 1); }
+__host__ __device__ constexpr int wpair_c0(int P) { return 8 * (P >> 2) + 4 * (P & 1) + ((P >> 1) & 1); }
+__host__ __device__ inline int wino_tpos(int P, int d) { const int q = P / d; return 2 * d * q + (P - q * d); }
+
+template <int MI, int WN, int NPF, bool VEC>
+__global__ void __launch_bounds__(128 * WN, 3)
+conv_wino_kernel(const MultiArgs m) {
+    typedef Frag<32> F;
+    typedef F::acc_t acc_t;
+    constexpr int WM = 2;
+    constexpr int NTHREADS = 64 * WM * WN;
+    constexpr int MT = 32 * MI * WM;
+    constexpr int NTP = 32 * WN;
+    constexpr int RING = 4;
+
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+
+    int pq = 0;
+#pragma unroll
+    for (int i = 1; i < V2W_MAX_MULTI; ++i) pq += (int)blockIdx.x >= m.start[i] ? 1 : 0;
+    const TileArgs& p = m.p[pq];
+    const int mtiles = p.Cout / MT;
+    const int id = blockIdx.x - m.start[pq];
+    const int grp = id / (8 * mtiles), rem = id % (8 * mtiles);
+    const int mt = rem >> 3;
+    const int tile = grp * 8 + (rem & 7);
+    if (tile >= p.ntiles) return;
+    const int b = tile / p.ntl;
+    const int P0 = (tile % p.ntl) * NTP;     // first output pair of the tile
+    const int m0 = mt * MT;
+    const int d = p.dil;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lr = lane & 31;
+    const int hk = lane >> 5;
+    const int wm0 = (wave / WN) * (32 * MI);
+    const int wn0 = (wave % WN) * 32;
+    const int L = p.L, K = p.K;
+    const float slope = p.slope;
+    const int nch = p.Cin / WCK;
+    const int pos0 = (wino_tpos(P0, d) - p.hl) & ~3;     // position of LDS row 0 (floor to a float4)
+    const int bufsz = p.xrows * WRS;
+    float* const etab = smem + p.atab_off;   // bias, res_a, res_s [MT] each
+    float* const atab = etab + 3 * MT;       // folded CondBN affine of this batch item: a[Cin] then s[Cin]
+
+    acc_t acc[4][MI];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[c][i][e] = 0.f;
+
+    // ---- signal staging: conv_tile_kernel's (an item = one slot-adjacent channel pair x 4 positions)
+    const int nq = p.xrows >> 2;
+    const int nq8 = (nq + 7) >> 3;
+    const unsigned magic = (unsigned)(((1ull << 32) + nq8 - 1) / nq8);
+    f32x4 pf[NPF][2];
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    auto item = [&](int s, int& c0, int& row, bool& in_img, bool& in_seq) {
+        int t = tid;
+        asm volatile("" : "+v"(t));
+        const int idx = t + s * NTHREADS;
+        const int g = idx >> 4;
+        const int pg = (int)__umulhi((unsigned)g, magic);
+        const int quad = (g - pg * nq8) * 8 + (idx & 7);
+        const int P = 2 * pg + ((idx >> 3) & 1);
+        row = quad * 4;
+        in_img = quad < nq && P < WCK / 2;
+        c0 = wpair_c0(in_img ? P : 0);
+        const int pos = pos0 + row;
+        in_seq = in_img && pos >= 0 && pos < L;
+    };
+    auto prefetch = [&](int ci0) {
+        const float* src = p.in + (size_t)(b * p.CinT + ci0) * L + pos0;
+#pragma unroll
+        for (int s = 0; s < NPF; ++s) {
+            int c0, row; bool in_img, in_seq;
+            item(s, c0, row, in_img, in_seq);
+            pf[s][0] = zero4; pf[s][1] = zero4;
+            if (in_seq) {
+                pf[s][0] = *reinterpret_cast<const f32x4*>(src + (size_t)c0 * L + row);
+                pf[s][1] = *reinterpret_cast<const f32x4*>(src + (size_t)(c0 + 2) * L + row);
+            }
+        }
+    };
+    auto commit = [&](int ci0, float* Xs) {
+#pragma unroll
+        for (int s = 0; s < NPF; ++s) {
+            int c0, row; bool in_img, in_seq;
+            item(s, c0, row, in_img, in_seq);
+            if (!in_img) continue;
+            float a0 = 1.f, s0 = 0.f, a1 = 1.f, s1 = 0.f;
+            if (p.in_a) {
+                a0 = atab[ci0 + c0]; s0 = atab[p.Cin + ci0 + c0];
+                a1 = atab[ci0 + c0 + 2]; s1 = atab[p.Cin + ci0 + c0 + 2];
+            }
+            float* dst = Xs + row * WRS + wslot(c0);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                f32x2 v = {0.f, 0.f};        // padding stays exactly 0 (it pads the ACTIVATED signal)
+                if (in_seq) { v[0] = v2w_lrelu(fmaf(a0, pf[s][0][e], s0), slope); v[1] = v2w_lrelu(fmaf(a1, pf[s][1][e], s1), slope); }
+                *reinterpret_cast<f32x2*>(dst + e * WRS) = v;
+            }
+        }
+    };
+    auto stage_scalar = [&](int ci0, float* Xs) {   // any L / alignment: dword loads straight into LDS
+        for (int c = wave; c < WCK; c += WM * WN) {
+            const int ch = b * p.CinT + ci0 + c;
+            const float* src = p.in + (size_t)ch * L;
+            const float av = p.in_a ? p.in_a[ch] : 1.f;
+            const float sv = p.in_s ? p.in_s[ch] : 0.f;
+            float* dst = Xs + wslot(c);
+            for (int j = lane; j < p.xrows; j += 64) {
+                const int l = pos0 + j;
+                float v = 0.f;
+                if (l >= 0 && l < L) v = v2w_lrelu(fmaf(av, src[l], sv), slope);
+                dst[j * WRS] = v;
+            }
+        }
+    };
+
+    // ---- weight ring: fragments in consumption order, "next" is always +1 KiB per row block
+    const int nfrag = nch * wino_terms(K) * WGPC;
+    const f32x4* ap[MI];
+#pragma unroll
+    for (int i = 0; i < MI; ++i)
+        ap[i] = reinterpret_cast<const f32x4*>(p.wp) + ((size_t)((m0 + wm0) / 32 + i) * nfrag) * 64;
+    int fidx = 0;
+    f32x4 ar[RING][MI];
+    const unsigned lane16 = (unsigned)lane * 16u;
+    auto load_next = [&](f32x4 (&a)[MI]) {
+        const int f = fidx < nfrag ? fidx : nfrag - 1;
+        unsigned l16 = lane16;
+        asm volatile("" : "+v"(l16));
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+            a[i] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(ap[i] + (size_t)f * 64) + l16);
+        ++fidx;
+    };
+
+    // ---- one segment of NTAP taps whose x0 sits at `x` (this lane's float4 of unit 0), rows `dstep` floats apart.  Each segment
+    // consumes NTERM * 4 fragments - a multiple of the ring - so every segment starts at ring slot 0.
+    auto segment = [&](auto ntap_c, const float* x, int dstep) {
+        constexpr int NTAP = decltype(ntap_c)::value;
+        constexpr int NX = NTAP + 1;
+        constexpr int NTERM = wino_seg_terms(NTAP);
+#pragma unroll
+        for (int gg = 0; gg < WGPC; ++gg) {
+            f32x4 xr[NX];
+#pragma unroll
+            for (int j = 0; j < NX; ++j) xr[j] = *reinterpret_cast<const f32x4*>(x + j * dstep + 8 * gg);
+            f32x4 u[NTERM];
+            if constexpr (NTAP == 3) {
+                u[0] = xr[0] - xr[2]; u[1] = xr[1] + xr[2];
+                u[2] = xr[2] - xr[1]; u[3] = xr[1] - xr[3];
+            } else if constexpr (NTAP == 2) {
+                u[0] = xr[0] - xr[1]; u[1] = xr[1]; u[2] = xr[1] - xr[2];
+            } else {
+                u[0] = xr[0]; u[1] = xr[1];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int t = 0; t < NTERM; ++t) {
+                const int cls = NTAP == 3 ? t : (NTAP == 2 ? (t == 2 ? 3 : t) : (t == 1 ? 3 : 0));    // accumulator class of the term
+                const int slot = (gg * NTERM + t) % RING;
+                load_next(ar[(slot + RING - 1) % RING]);
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+                    for (int i = 0; i < MI; ++i) acc[cls][i] = F::mfma(ar[slot][i][kk], u[t][kk], acc[cls][i]);
+            }
+        }
+    };
+
+    // ---- prologue: epilogue constants, affine table, chunk 0, first fragments
+    for (int c = tid; c < MT; c += NTHREADS) {
+        etab[c] = p.bias ? p.bias[m0 + c] : 0.f;
+        etab[MT + c] = p.res_a ? p.res_a[b * p.Cout + m0 + c] : 1.f;
+        etab[2 * MT + c] = p.res_a ? p.res_s[b * p.Cout + m0 + c] : 0.f;
+    }
+    if (p.in_a) {
+        for (int c = tid; c < p.Cin; c += NTHREADS) {
+            atab[c] = p.in_a[b * p.Cin + c];
+            atab[p.Cin + c] = p.in_s[b * p.Cin + c];
+        }
+        __syncthreads();
+    }
+    if constexpr (VEC) { prefetch(0); commit(0, smem); }
+    else stage_scalar(0, smem);
+#pragma unroll
+    for (int g = 0; g + 1 < RING; ++g) load_next(ar[g]);
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();
+
+    const int P = P0 + wn0 + lr;                   // this lane's output pair
+    const int t0 = wino_tpos(P, d);                // ... and its first output position
+    const int lbase = (t0 - p.hl - pos0) * WRS + 4 * hk;   // x of tap 0 for output t0, unit 0
+    const int dstep = d * WRS;
+    typedef std::integral_constant<int, 3> S3;
+    typedef std::integral_constant<int, 2> S2;
+    typedef std::integral_constant<int, 1> S1;
+    for (int ch = 0; ch < nch; ++ch) {
+        const float* Xs = smem + (ch & 1) * bufsz;
+        float* Xn = smem + ((ch + 1) & 1) * bufsz;
+        const bool more = ch + 1 < nch;
+        const float* xt = Xs + lbase;
+        int s = 0;
+        for (; s + 3 <= K; s += 3) segment(S3{}, xt + s * dstep, dstep);
+        if (K - s == 2) segment(S2{}, xt + s * dstep, dstep);
+        else if (K - s == 1) segment(S1{}, xt + s * dstep, dstep);
+        if (more) {
+            if constexpr (VEC) { prefetch((ch + 1) * WCK); commit((ch + 1) * WCK, Xn); }
+            else stage_scalar((ch + 1) * WCK, Xn);
+            __syncthreads();
+        }
+    }
+
+    // ---- epilogue: output transform, then + bias [+ residual] [+ addends | + out] [/ out_div], conv_tile_kernel's order
+    float* const outp = p.out;
+    const float dinv = p.out_div != 0.f ? 1.f / p.out_div : 1.f;
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            const int col = wm0 + i * 32 + F::row(e, hk);
+            const float M0 = acc[0][i][e], M1 = acc[1][i][e], M2 = acc[2][i][e], M3 = acc[3][i][e];
+            const float y[2] = {(M0 + M1) + M2, (M1 - M2) - M3};
+            const size_t rowoff = ((size_t)b * p.CoutT + m0 + col) * L;
+            const float bias = etab[col], ra = etab[MT + col], rs = etab[2 * MT + col];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int pos = t0 + h * d;
+                if (pos >= L) continue;
+                const size_t go = rowoff + pos;
+                float t = y[h] + bias;
+                if (p.res) t += fmaf(ra, p.res[go], rs);
+                if (p.add1) t += p.add0[go] + p.add1[go];      // (add0 + add1) + value: the reference's `xs += ...` order
+                else if (p.accumulate) t += outp[go];
+                else if (p.add0) t += p.add0[go];
+                if (p.out_div != 0.f) t = v2w_div_by(t, p.out_div, dinv);
+                outp[go] = t;
+            }
+        }
+    }
+}
+
+template <int MI, int WN>
+int launch_wino(const TileArgs* ps, int nprob, hipStream_t stream) {
+    constexpr int MT = 64 * MI, NTP = 32 * WN, NTHREADS = 128 * WN;
+    constexpr int NPF = ((WCK / 2) * (((2 * NTP + 2 * WHMAX) / 4 + 7) / 8 * 8) + NTHREADS - 1) / NTHREADS;
+    static_assert(NTHREADS * NPF < 8 * 8192, "item index range of the magic division");
+    MultiArgs m{};
+    size_t lds = 0;
+    int grid = 0;
+    bool vec = true;
+    for (int i = 0; i < nprob; ++i) {
+        TileArgs p = ps[i];
+        if (p.Cout % MT != 0) return V2W_E_SHAPE;
+        const int d = p.dil;
+        const int npairs = d * ((p.L + 2 * d - 1) / (2 * d));
+        p.ntl = (npairs + NTP - 1) / NTP;
+        p.ntiles = p.B * p.ntl;
+        int rows = 0;                       // LDS rows the widest tile reads: x_K of the last pair's second output
+        for (int tl = 0; tl < p.ntl; ++tl) {
+            const int P0 = tl * NTP;
+            const int pos0 = (wino_tpos(P0, d) - p.hl) & ~3;
+            const int r = wino_tpos(P0 + NTP - 1, d) + d + p.hr - pos0 + 1;
+            if (r > rows) rows = r;
+        }
+        p.xrows = (rows + 3) & ~3;
+        if (p.xrows > 2 * NTP + 2 * WHMAX) return V2W_E_SHAPE;
+        p.vec4 = (p.L % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.in) & 15) == 0);
+        vec = vec && p.vec4;
+        const int nbuf = p.Cin / WCK > 1 ? 2 : 1;
+        p.atab_off = nbuf * p.xrows * WRS;
+        const size_t l = ((size_t)p.atab_off + 3 * MT + (p.in_a ? 2 * p.Cin : 0)) * sizeof(float);
+        if (l > lds) lds = l;
+        m.p[i] = p;
+        m.start[i] = grid;
+        grid += ((p.ntiles + 7) / 8) * 8 * (p.Cout / MT);
+    }
+    m.start[nprob] = grid;
+    for (int i = nprob + 1; i <= V2W_MAX_MULTI; ++i) m.start[i] = 0x7fffffff;
+    if (lds > 160 * 1024) return V2W_E_SHAPE;
+    auto kern = vec ? conv_wino_kernel<MI, WN, NPF, true> : conv_wino_kernel<MI, WN, NPF, false>;
+    if (lds > 64 * 1024) {
+        hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kern), (int)lds, stream);
+        if (e != hipSuccess) return (int)e;
+    }
+    V2W_LAUNCH(kern, dim3(grid), dim3(NTHREADS), lds, stream, m);
+    return v2w_launch_status();
+}
+
+// wpw float index o = (((mb * nch + ch) * nfr + fi) * 64 + lane) * 4 + j, nfr = wino_terms(k) * 4, fragment fi = (segment, unit gg, term)
+// (wino_frag) holds the term's transformed weight at channel ch*32 + gg*8 + 2j + lane/32, output channel mb*32 + lane%32.
+__global__ void __launch_bounds__(256)
+pack_wino_kernel(const float* __restrict__ wf, float* __restrict__ wp, int K, int Cin, int Cout) {
+    const int nch = Cin / WCK, nfr = wino_terms(K) * WGPC;
+    const size_t total = (size_t)(Cout / 32) * nch * nfr * 256;
+    for (size_t o = (size_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (size_t)gridDim.x * 256) {
+        const int j = o & 3, lane = (o >> 2) & 63;
+        size_t rest = o >> 8;
+        const int fi = rest % nfr; rest /= nfr;
+        const int ch = rest % nch;
+        const int mb = rest / nch;
+        int s0, ntap, gg, term;
+        wino_frag(K, WGPC, fi, s0, ntap, gg, term);
+        const int c = ch * WCK + gg * 8 + 2 * j + lane / 32, co = mb * 32 + lane % 32;
+        auto g = [&](int t) { return t < ntap ? wf[((size_t)(s0 + t) * Cin + c) * Cout + co] : 0.f; };
+        wp[o] = wino_weight(ntap, term, g(0), g(1), g(2));
+    }
+}
+
+}  // namespace
+
+// Which shapes the Winograd kernel serves (V2W_E_SHAPE otherwise; the caller then uses the direct-form f32 MFMA kernel):
+// C_in % 32 == 0 and >= 64, C_out % 64 == 0, odd k >= 3 with symmetric padding, plain unit-stride input, no channel slices, none of
+// the backward / discriminator epilogues, and launches of more than 128 workgroups of 64 channels x 64 pairs.
+int v2w_conv1d_wino(const v2w_conv1d_args* a, int n, hipStream_t stream) {
+    if (n < 1 || n > V2W_MAX_MULTI) return V2W_E_ARG;
+    TileArgs ps[V2W_MAX_MULTI];
+    long wgs = 0;
+    const int MT = 64;
+    for (int i = 0; i < n; ++i) {
+        const v2w_conv1d_args* q = a + i;
+        if (q->B != a->B || q->C_in != a->C_in || q->C_out != a->C_out || q->L != a->L) return V2W_E_SHAPE;
+        if (q->C_in % WCK != 0 || q->C_in < 64 || q->C_out % 64 != 0 || wino_terms(q->k) == 0 || q->pad_left >= 0) return V2W_E_SHAPE;
+        if (q->in_stride > 1 || q->mask_src || q->rowsum_part || (q->out_slope != 0.f && q->out_slope != 1.f)) return V2W_E_SHAPE;
+        if ((q->in_ct > 0 && q->in_ct != q->C_in) || (q->out_ct > 0 && q->out_ct != q->C_out)) return V2W_E_SHAPE;
+        if (!q->wp) return V2W_E_ARG;
+        TileArgs p{};
+        p.in = q->in; p.in_a = q->in_a; p.in_s = q->in_s; p.wp = q->wp; p.bias = q->bias;
+        p.res = q->res; p.res_a = q->res_a; p.res_s = q->res_s; p.out = q->out;
+        p.add0 = q->add0; p.add1 = q->add1;
+        p.B = q->B; p.Cin = q->C_in; p.Cout = q->C_out; p.L = q->L; p.K = q->k; p.dil = q->dil;
+        p.CinT = q->C_in; p.CoutT = q->C_out;
+        p.hl = p.hr = q->dil * (q->k - 1) / 2;
+        p.slope = q->slope; p.accumulate = q->accumulate; p.out_div = q->out_div;
+        ps[i] = p;
+        const int npairs = q->dil * ((q->L + 2 * q->dil - 1) / (2 * q->dil));
+        wgs += (long)q->B * ((npairs + 63) / 64) * (q->C_out / MT);
+    }
+    if (wgs <= 128) return V2W_E_SHAPE;     // (the f32 MFMA path splits such launches over C_in: inference at B = 1)
+    // (MI = 2, a 128 x 64-pair tile with 128 accumulators per lane, spills at two waves per SIMD and ran slower at one)
+    return launch_wino<1, 2>(ps, n, stream);
+}
+
+extern "C" int v2w_wino_terms(int k) { return wino_terms(k); }
+
+extern "C" int v2w_pack_wino(const float* wf, float* wpw, int k, int c_in, int c_out, void* stream) {
+    if (!wf || !wpw || k <= 0 || c_in <= 0 || c_out <= 0) return V2W_E_ARG;
+    if (wino_terms(k) == 0 || c_in % WCK != 0 || c_out % 32 != 0) return V2W_E_SHAPE;
+    const size_t total = (size_t)wino_terms(k) * c_in * c_out;
+    int grid = (int)((total + 255) / 256); if (grid > 4096) grid = 4096;
+    V2W_LAUNCH(pack_wino_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, wf, wpw, k, c_in, c_out);
+    return v2w_launch_status();
+}

@@ -249,6 +249,9 @@ class ForwardPlanner:
             return dict(algo=hipops.ALGO_BF16 if g.precision == 'bf16' else hipops.ALGO_SPLIT, wps=self.wps[nm])
         if self.st:
             raise RuntimeError(f'bf16 storage: layer {nm} has no bf16 kernel (set generator.bf16_storage = False)')
+        wpw = g._fold_key.get('wpw', {}).get(nm)
+        if wpw is not None:     # the Winograd F(2,3) kernel, with this f32 MFMA stream for a launch it declines (hipops.conv1d_wino_multi)
+            return dict(algo=self.algo, wp=self.wp[nm], wpw=wpw)
         return dict(algo=self.algo, wp=self.wp[nm])
 
     # ---------------------------------------------------------------------------------------------------------------------------

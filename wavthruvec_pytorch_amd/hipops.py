@@ -13,8 +13,8 @@ import torch
 
 from . import _hip
 
-ALGO_AUTO, ALGO_DIRECT, ALGO_MFMA, ALGO_SPLIT, ALGO_BF16 = (_hip.ALGO_AUTO, _hip.ALGO_DIRECT, _hip.ALGO_MFMA, _hip.ALGO_SPLIT,
-                                                             _hip.ALGO_BF16)
+ALGO_AUTO, ALGO_DIRECT, ALGO_MFMA, ALGO_SPLIT, ALGO_BF16, ALGO_WINO = (_hip.ALGO_AUTO, _hip.ALGO_DIRECT, _hip.ALGO_MFMA, _hip.ALGO_SPLIT,
+                                                                        _hip.ALGO_BF16, _hip.ALGO_WINO)
 
 
 def _chk(t: Optional[torch.Tensor], name: str, dtype=torch.float32):
@@ -132,6 +132,27 @@ def split_units_halves(k, c_in, c_out):
     return k * c_in * ((c_out + 31) // 32 * 32) * 2
 
 
+def wino_terms(k):
+    """Weight matrices of the Winograd F(2,3) form of a k-tap conv (4 / 10 / 15 for k = 3 / 7 / 11); 0 when k is not served."""
+    return int(_hip.load().v2w_wino_terms(k))
+
+
+def pack_wino(wf, out=None):
+    """wf [k][C_in][C_out] -> the ALGO_WINO weight stream (v2w_pack_wino: the transformed weights of every segment term in A-fragment
+    order), or None when the shape is not served."""
+    k, ci, co = wf.shape
+    n = wino_terms(k) * ci * co
+    if n == 0:
+        return None
+    if out is None:
+        out = torch.empty((n,), device=wf.device, dtype=torch.float32)
+    rc = _hip.load().v2w_pack_wino(wf.data_ptr(), out.data_ptr(), k, ci, co, _stream(wf))
+    if rc == -2:
+        return None
+    _hip.check(rc, 'v2w_pack_wino')
+    return out
+
+
 def pack_split(wf, out=None, sc=None, bf16=False):
     """wf [k][C_in][C_out] -> (wps, sc): the (hi, lo) half-precision MFMA fragments of scale*wf for ALGO_SPLIT and the 4-float
     scale record (sc[0] = 1/scale is the kernel's `winv`)."""
@@ -227,6 +248,10 @@ def _splitk_bytes(a, n):
 def conv1d(x, wf, bias, out, splitk_ws=None, **kw):
     """Fused [affine] -> leaky_relu -> dilated Conv1d -> +bias [+res] [+= out | + add0 (+ add1)] [/ out_div]; see the header.
     splitk_ws: a SplitKSlab (f32 MFMA path only; without one a small launch simply runs unsplit)."""
+    if kw.get('wpw') is not None:
+        conv1d_wino_multi([(x, wf, bias, out, kw)], splitk_ws=splitk_ws)
+        return out
+    kw.pop('wpw', None)
     a = _hip.Conv1dArgs()
     _conv1d_args(a, x, wf, bias, out, **kw)
     if splitk_ws is not None:
@@ -239,6 +264,9 @@ def conv1d_multi(problems, splitk_ws=None):
     """`problems`: list of (x, wf, bias, out, kwargs) sharing B, C_in, C_out, L.  One launch when the MFMA path takes them
     (heaviest first), otherwise one launch each."""
     n = len(problems)
+    if any(kw.get('wpw') is not None for *_r, kw in problems):
+        return conv1d_wino_multi(problems, splitk_ws=splitk_ws)
+    problems = [(x, wf, bias, out, {q: v for q, v in kw.items() if q != 'wpw'}) for x, wf, bias, out, kw in problems]
     if 1 < n <= 4:
         arr = (_hip.Conv1dArgs * n)()
         for a, (x, wf, bias, out, kw) in zip(arr, problems):
@@ -252,6 +280,22 @@ def conv1d_multi(problems, splitk_ws=None):
             _hip.check(rc, 'v2w_conv1d_fwd_multi')
     for x, wf, bias, out, kw in problems:
         conv1d(x, wf, bias, out, splitk_ws=splitk_ws, **kw)
+
+
+def conv1d_wino_multi(problems, splitk_ws=None):
+    """conv1d_multi on the Winograd F(2,3) kernel (ALGO_WINO): every problem's kwargs carry `wpw=` (its pack_wino stream) next to the
+    f32 MFMA `algo` / `wp` it runs on when the Winograd kernel declines the launch (V2W_E_SHAPE: nothing was launched)."""
+    n = len(problems)
+    if 1 <= n <= 4 and all(kw.get('wpw') is not None for *_r, kw in problems):
+        arr = (_hip.Conv1dArgs * n)()
+        for a, (x, wf, bias, out, kw) in zip(arr, problems):
+            _conv1d_args(a, x, wf, bias, out, **{**{q: v for q, v in kw.items() if q != 'wpw'}, 'algo': ALGO_WINO, 'wp': kw['wpw']})
+        rc = _hip.load().v2w_conv1d_fwd_multi(arr, n, _stream(problems[0][0]))
+        if rc == 0:
+            return
+        if rc != -2:
+            _hip.check(rc, 'v2w_conv1d_fwd_multi')
+    conv1d_multi([(x, wf, bias, out, {q: v for q, v in kw.items() if q != 'wpw'}) for x, wf, bias, out, kw in problems], splitk_ws=splitk_ws)
 
 
 def convt1d(x, wf, bias, out, *, k, u, slope=1.0, algo=ALGO_AUTO, wp=None, stats_part=None, splitk_ws=None):
@@ -495,18 +539,19 @@ class FoldPlan:
     """Device-resident descriptor table for v2w_fold_pack_batch: every MFMA layer folded + packed in two launches."""
 
     def __init__(self, layers, device):
-        """layers: list of (v, g|None, wp, c_in, c_out, k, u, transposed[, wf|None[, wpd|None]]) with tensors already on `device`; wf: the plain
-        layout [k][C_in][C_out] as well, wpd: the fragment stream of the layer's input-gradient conv as well (training forwards)."""
+        """layers: list of (v, g|None, wp, c_in, c_out, k, u, transposed[, wf|None[, wpd|None[, wpw|None]]]) with tensors already on `device`; wf: the
+        plain layout [k][C_in][C_out] as well, wpd: the fragment stream of the layer's input-gradient conv as well (training forwards), wpw: the
+        layer's ALGO_WINO stream as well."""
         n = len(layers)
         self.n = n
-        layers = [tuple(l) + (None,) * (10 - len(l)) for l in layers]
+        layers = [tuple(l) + (None,) * (11 - len(l)) for l in layers]
         rows = [(l[3] if l[7] else l[4]) for l in layers]
         self.scale = torch.empty((sum(rows),), device=device, dtype=torch.float32)
         descs = (_hip.FoldDesc * n)()
         off = 0
-        for d, (v, g, wp, ci, co, k, u, tr, wf, wpd), r in zip(descs, layers, rows):
+        for d, (v, g, wp, ci, co, k, u, tr, wf, wpd, wpw), r in zip(descs, layers, rows):
             d.v = v.data_ptr(); d.g = _hip.ptr(g); d.wp = wp.data_ptr()
-            d.wf = _hip.ptr(wf); d.wpd = _hip.ptr(wpd)
+            d.wf = _hip.ptr(wf); d.wpd = _hip.ptr(wpd); d.wpw = _hip.ptr(wpw)
             d.scale = self.scale.data_ptr() + 4 * off
             d.c_in, d.c_out, d.k, d.u, d.transposed = ci, co, k, u, int(tr)
             off += r

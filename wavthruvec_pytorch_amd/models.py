@@ -213,6 +213,9 @@ class Generator(nn.Module):
         self.fuse_up = True                   # bf16 storage: the NEXT stage's transposed conv (stride 2 / 4) inside the kernel of a stage (C = 32 .. 256):
                                               # the stage's output never leaves the chip, one launch less per stage
         self.fuse_bn_finalize = True          # train mode: a stage's statistics reduction and its finalisation as one launch (v2w_bn_reduce_finalize) where nothing is all-reduced in between
+        self.wino = True                      # precision 'f32': conv_pre and the wide residual convs (but the 64-channel dilation-3 ones) on the Winograd F(2,3) kernel
+                                              # (hipops.ALGO_WINO: 4 / 10 / 15 instead of 6 / 14 / 22 products per output pair for k = 3 / 7 / 11),
+                                              # weights transformed by the batched fold; a launch the kernel declines runs on the direct-form tile
         self.merge_waits = True               # bf16 storage: one wait per side stream and call, earlier steps of the stream count as met (forward_plan.need)
         self.cond_stream = None               # bf16 storage, train mode: the conditioning chain on a second side stream, beside the weight folds instead of between them.  None: where it pays - while conv_pre + ups.0 are shorter than the one side stream's chain + folds (measured, tools/exp/cond_stream_sweep.py: -26 / -12 us at B x T = 4 096 / 8 192 frames, +8 at 2 048, +13 .. +28 from 12 288 up); True / False: always / never
         self.fuse_post = True                 # leaky_relu -> conv_post -> tanh inside the kernel of the last (C = 16) stage (bf16 storage, and - round 5 - the fp32 stage kernel): the stage's
@@ -395,12 +398,14 @@ class Generator(nn.Module):
         for name, m in layers:
             ps = (m.weight_v, m.weight_g) if m.weight_normed else (m.weight,)
             vers.append(tuple((p.data_ptr(), p._version) for p in ps))
-        state = (tuple(vers), self.algo, str(device), need_wf, bf16_only)
+        wino = self.wino and self.precision == 'f32' and self.algo != hipops.ALGO_DIRECT
+        state = (tuple(vers), self.algo, str(device), need_wf, bf16_only, wino)
         force = (self.training and self.always_refold) or need_wf
         if not force and self._fold_key.get('state') == state:
             return self._fold_key['wf'], self._fold_key['wp']
         wf, wp, batch = {}, {}, []
         wpd = {}        # need_wf: fragment streams of the input-gradient convs of the C -> C residual convs (backward.py), from the same pass
+        wpw = {}        # wino: the Winograd F(2,3) streams of the layers that kernel serves (forward_plan.ck), from the same pass
         for name, m in layers:
             if bf16_only and name != 'conv_post':      # bf16 activation storage: every other layer runs on its bf16 fragments (_split_weights):
                 wf[name], wp[name] = None, None        # no fp32 fold / fragment stream is read, none is built
@@ -410,6 +415,12 @@ class Generator(nn.Module):
             mfma_ok = (self.algo != hipops.ALGO_DIRECT and name != 'conv_post' and
                        hipops.conv_tile_config(1, m.in_channels, m.out_channels, 64, m.kernel_size,
                                                1 if m.transposed else m.dilation, u) is not None)
+            wpwb = None
+            # (every layer it serves except the dilation-3 convs of 64 channels: those ran 10-15 % slower on it at B = 32 x T = 256; the others
+            # ran 3-21 % faster, stage 0's lone k = 11 launch even - profiles/r07_cfg2_wino_per_layer.txt)
+            if (mfma_ok and wino and not m.transposed and hipops.wino_terms(m.kernel_size) and m.in_channels % 32 == 0 and m.in_channels >= 64
+                    and m.out_channels % 64 == 0 and (m.out_channels >= 128 or m.dilation == 1)):
+                wpwb = wpw[name] = self._wbuf('wpw.' + name, (hipops.wino_terms(m.kernel_size) * m.in_channels * m.out_channels,), device=device)
             if mfma_ok and need_wf:     # a forward that will be back-propagated: dgrad / wgrad also read the plain layout - written by the
                 # same batched fold (was: three launches per layer, ~100 host-bound launches and 1.6 ms in front of every training forward)
                 n_el = m.kernel_size * m.in_channels * m.out_channels
@@ -418,11 +429,11 @@ class Generator(nn.Module):
                 wdb = None
                 if not m.transposed and m.in_channels == m.out_channels and name.startswith('resblocks.'):
                     wdb = wpd[name] = self._wbuf('wpd.' + name, (n_el,), device=device)
-                batch.append((v, g, wpb, m.in_channels, m.out_channels, m.kernel_size, u, m.transposed, wfb, wdb))
+                batch.append((v, g, wpb, m.in_channels, m.out_channels, m.kernel_size, u, m.transposed, wfb, wdb, wpwb))
                 wf[name], wp[name] = wfb, wpb
             elif mfma_ok:
                 wpb = self._wbuf('wp.' + name, (m.kernel_size * m.in_channels * m.out_channels,), device=device)
-                batch.append((v, g, wpb, m.in_channels, m.out_channels, m.kernel_size, u, m.transposed))
+                batch.append((v, g, wpb, m.in_channels, m.out_channels, m.kernel_size, u, m.transposed, None, None, wpwb))
                 wf[name], wp[name] = None, wpb
             else:
                 wfb = self._wbuf('wf.' + name, (m.kernel_size, m.in_channels, m.out_channels), device=device)
@@ -431,7 +442,7 @@ class Generator(nn.Module):
                 wf[name], wp[name] = wfb, None
         if batch:
             key = tuple((q[0].data_ptr(), 0 if q[1] is None else q[1].data_ptr(), q[2].data_ptr(),
-                         0 if len(q) < 9 or q[8] is None else q[8].data_ptr()) for q in batch)
+                         0 if len(q) < 9 or q[8] is None else q[8].data_ptr(), 0 if len(q) < 11 or q[10] is None else q[10].data_ptr()) for q in batch)
             plan = self._fold_key.get('plan')
             if plan is None or plan.key != key:
                 self._drop_tapes()            # (recorded launch plans point at the old plan's descriptor table)
@@ -439,7 +450,7 @@ class Generator(nn.Module):
                 plan.key = key
                 self._fold_key['plan'] = plan
             plan.run()
-        self._fold_key.update(state=state, wf=wf, wp=wp, wpd=wpd, vers=tuple(vers), gen=self._fold_key.get('gen', 0) + 1)
+        self._fold_key.update(state=state, wf=wf, wp=wp, wpd=wpd, wpw=wpw, vers=tuple(vers), gen=self._fold_key.get('gen', 0) + 1)
         return wf, wp
 
     def _split_weights(self, device, all_ups=False, ups_stream=None, mark=None, between=None):
@@ -614,7 +625,7 @@ class Generator(nn.Module):
         ptrs = tuple(p.data_ptr() for p in self.parameters()) + tuple(b.data_ptr() for b in self.buffers())
         return (tuple(x.shape), str(x.device), torch.cuda.current_stream(x.device).cuda_stream, self.training, self.precision, self.algo, self.bf16_storage, tuple(self.fuse_stage), tuple(self.fuse_pairs),
                 self.fuse_wide, self.fuse_wide_stage, self.fuse_up, self.fuse_post, self.fuse_bn_finalize, self.cond_stream, self.merge_waits, self.split_min_channels,
-                self.always_refold, ptrs)
+                self.always_refold, self.wino, ptrs)
 
     def _forward_hip(self, x, spk, nz, save):
         """One forward through the C ABI.  `save` (a dict) asks for the back-propagatable form (forward_plan.py).  A no-grad forward is PLANNED
