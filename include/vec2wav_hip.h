@@ -508,6 +508,19 @@ int v2w_conv_post_tanh_bf16in(const void* x_bf16, const float* wf, const float* 
 int v2w_conv_post_tanh(const float* in, const float* wf, const float* bias, float* out,
                        int B, int C_in, int L, int k, float slope, void* stream);
 
+/* ---- Batches of unequal lengths (additive entry points; the argument structs above are unchanged).  `len` is a DEVICE array of B int32 and
+ * len_mul >= 1: item b's sequence ends at Lb = len[b] * len_mul positions of the call's INPUT rate (clamped to L).  Inputs at or past Lb count
+ * as zero padding after the activation, whatever the tensor holds there (stale workspace, NaN); each item computes what its own unpadded
+ * call would.  Outputs at or past Lb (Lb * u for a transposed conv) are unspecified and workgroups whose outputs all lie there return at once -
+ * except in the generator's last layer (the stage kernel's fused tail, v2w_conv_post_tanh_len), which stores exactly 0 there.  The grids do not
+ * depend on the values.  V2W_E_ARG: len == NULL, len_mul < 1, or a call these kernels do not serve - any algorithm but V2W_ALGO_AUTO / _MFMA /
+ * _WINO (no direct-kernel fallback), mask_src / rowsum_part / out_slope / channel slices / in_stride > 1, stats_part, the input-gradient form. */
+int v2w_conv1d_fwd_len(const v2w_conv1d_args* a, int n, const int32_t* len, int len_mul, void* stream);   /* n <= 4 problems as _fwd_multi */
+int v2w_convt1d_fwd_len(const v2w_convt1d_args* a, const int32_t* len, int len_mul, void* stream);
+int v2w_resblock2_stage_fwd_len(const v2w_stage_args* a, const int32_t* len, int len_mul, void* stream);
+int v2w_conv_post_tanh_len(const float* in, const float* wf, const float* bias, float* out,
+                           int B, int C_in, int L, int k, float slope, const int32_t* len, int len_mul, void* stream);
+
 /* ---- mel_spectrogram of the generated audio (vec2wav/dataset.py:53-77, train.py:172-174,266-269).
  * The STFT itself is a Conv1d over the hop-phase de-interleaved signal and runs through v2w_conv1d_fwd (hop input channels,
  * n_fft/hop taps, pad_left = 0, windowed DFT rows as weights: see wavthruvec_pytorch_amd/mel.py); these are its two ends:

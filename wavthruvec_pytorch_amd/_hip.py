@@ -191,6 +191,11 @@ SIGNATURES = {
     'v2w_cond_bwd': (C.c_int, [_fp] * 13 + [C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     'v2w_conv_post_tanh_bf16in': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp]),
     'v2w_conv_post_tanh': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp]),
+    # batches of unequal lengths (per-item valid lengths: a device int32 array and len_mul; the argument structs are unchanged)
+    'v2w_conv1d_fwd_len': (C.c_int, [C.POINTER(Conv1dArgs), C.c_int, _fp, C.c_int, _fp]),
+    'v2w_convt1d_fwd_len': (C.c_int, [C.POINTER(ConvT1dArgs), _fp, C.c_int, _fp]),
+    'v2w_resblock2_stage_fwd_len': (C.c_int, [C.POINTER(StageArgs), _fp, C.c_int, _fp]),
+    'v2w_conv_post_tanh_len': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, C.c_int, _fp]),
 }
 
 # entry points that LAUNCH (their last argument is the stream); the others are host-only queries.  schedule.Recorder tapes the former.

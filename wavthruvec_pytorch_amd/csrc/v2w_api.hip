@@ -1,11 +1,13 @@
 // extern "C" dispatch of the conv entry points declared in include/vec2wav_hip.h.
 #include "v2w_common.h"
 
-int v2w_conv1d_mfma(const v2w_conv1d_args* a, int n, hipStream_t stream, int* cfg_out, long long* ws_query = nullptr);
-int v2w_convt1d_mfma(const v2w_convt1d_args* a, hipStream_t stream, int* cfg_out, long long* ws_query = nullptr);
+int v2w_conv1d_mfma(const v2w_conv1d_args* a, int n, hipStream_t stream, int* cfg_out, long long* ws_query = nullptr,
+                    const int32_t* len = nullptr, int len_mul = 1);
+int v2w_convt1d_mfma(const v2w_convt1d_args* a, hipStream_t stream, int* cfg_out, long long* ws_query = nullptr,
+                     const int32_t* len = nullptr, int len_mul = 1);
 int v2w_conv1d_split(const v2w_conv1d_args* a, int n, hipStream_t stream, bool bf16);
 int v2w_conv1d_direct(const v2w_conv1d_args* a, hipStream_t stream);
-int v2w_conv1d_wino(const v2w_conv1d_args* a, int n, hipStream_t stream);
+int v2w_conv1d_wino(const v2w_conv1d_args* a, int n, hipStream_t stream, const int32_t* len = nullptr, int len_mul = 1);
 int v2w_convt1d_direct(const v2w_convt1d_args* a, hipStream_t stream);
 
 extern "C" int v2w_abi_version(void) { return V2W_ABI_VERSION; }
@@ -108,4 +110,28 @@ extern "C" int v2w_conv1d_fwd_multi(const v2w_conv1d_args* a, int n, void* strea
         return v2w_conv1d_split(a, n, (hipStream_t)stream, a[0].algo == V2W_ALGO_BF16);
     if (a[0].algo == V2W_ALGO_WINO) return v2w_conv1d_wino(a, n, (hipStream_t)stream);
     return v2w_conv1d_mfma(a, n, (hipStream_t)stream, nullptr);
+}
+
+// ---- batches of unequal lengths (include/vec2wav_hip.h): the f32 MFMA and Winograd kernels serve them; nothing falls back to a kernel
+// that does not (the direct kernels, split-f16 / bf16) - those calls return V2W_E_ARG.
+extern "C" int v2w_conv1d_fwd_len(const v2w_conv1d_args* a, int n, const int32_t* len, int len_mul, void* stream) {
+    if (!a || n < 1 || n > 4 || !len || len_mul < 1) return V2W_E_ARG;
+    for (int i = 0; i < n; ++i) {
+        if (const int rc = check_conv1d(a + i)) return rc;
+        if (a[i].algo != a[0].algo) return V2W_E_ARG;
+        if (a[i].algo != V2W_ALGO_AUTO && a[i].algo != V2W_ALGO_MFMA && a[i].algo != V2W_ALGO_WINO) return V2W_E_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (a[0].algo == V2W_ALGO_WINO) return v2w_conv1d_wino(a, n, st, len, len_mul);
+    const int rc = v2w_conv1d_mfma(a, n, st, nullptr, nullptr, len, len_mul);
+    return rc == V2W_E_SHAPE && a[0].algo == V2W_ALGO_AUTO && n == 1 ? V2W_E_ARG : rc;      // (no direct kernel with lengths)
+}
+
+extern "C" int v2w_convt1d_fwd_len(const v2w_convt1d_args* a, const int32_t* len, int len_mul, void* stream) {
+    if (!a || !a->in || !a->wp || !a->out || a->io_bf16 != 0 || !len || len_mul < 1 || a->stats_part) return V2W_E_ARG;
+    if (a->B <= 0 || a->C_in <= 0 || a->C_out <= 0 || a->L <= 0 || a->k <= 0 || a->u <= 0) return V2W_E_ARG;
+    if (a->algo != V2W_ALGO_AUTO && a->algo != V2W_ALGO_MFMA) return V2W_E_ARG;
+    if (a->k < a->u || ((a->k - a->u) & 1)) return V2W_E_SHAPE;
+    const int rc = v2w_convt1d_mfma(a, (hipStream_t)stream, nullptr, nullptr, len, len_mul);
+    return rc == V2W_E_SHAPE && a->algo == V2W_ALGO_AUTO ? V2W_E_ARG : rc;
 }

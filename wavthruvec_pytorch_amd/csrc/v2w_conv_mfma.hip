@@ -61,9 +61,13 @@ template <int MF, int CK> struct TileGeom {
 // VEC: every problem of the launch has float4-aligned, unit-stride input (the vector staging path).  A template parameter, not a
 // run-time flag: with the element-wise fallback in the same kernel its (never taken) loads join the hot path, and hipcc then waits
 // vmcnt(0) in front of every chunk's prefetch and again right behind it - the prefetch's memory latency in the open, once per chunk.
+// EPI 3 = none of them, but per-item valid lengths (v2w_conv1d_fwd_len; LEN below): the item's sequence ends at Lb = min(L, len[b] * len_mul)
+// input positions - staging selects 0 at and past Lb (whatever the tensor holds there: stale workspace, NaN), a tile whose outputs all lie past
+// it returns at once, the outputs past it inside a tile are unspecified.  Every other EPI compiles to the code it had without lengths.
 template <int MF, int U, int MI, int NI, int WM, int WN, int CK, int NPF, int RING, int EPI, bool VEC>
 __global__ void __launch_bounds__(64 * WM * WN, (U == 1 && MI * NI >= 4) ? 3 : 1)
 conv_tile_kernel(const MultiArgs m) {
+    constexpr bool LEN = EPI == 3;
     typedef Frag<MF> F;
     typedef typename F::acc_t acc_t;
     constexpr int NTHREADS = 64 * WM * WN;
@@ -99,6 +103,10 @@ conv_tile_kernel(const MultiArgs m) {
     const int b = tile / p.ntl;
     const int n0 = (tile % p.ntl) * NT;   // first input-rate position of the tile
     const int m0 = mt * MT;
+    const int Lb = LEN ? min(p.L, p.len[b] * p.len_mul) : p.L;    // end of this item's sequence (LEN; else the tensor's)
+    if constexpr (LEN) {
+        if (n0 >= Lb) return;              // every output of the tile lies past the item's end
+    }
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -183,7 +191,10 @@ conv_tile_kernel(const MultiArgs m) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 f32x2 v = {0.f, 0.f};        // padding stays exactly 0 (it pads the ACTIVATED signal)
-                if (in_seq) { v[0] = v2w_lrelu(fmaf(a0, pf[s][0][e], s0), slope); v[1] = v2w_lrelu(fmaf(a1, pf[s][1][e], s1), slope); }
+                // (LEN: Lb need not be a multiple of 4 - the float4 was loaded whole from the L-long row, the positions past Lb select 0)
+                if (in_seq && (!LEN || pos0 + row + e < Lb)) {
+                    v[0] = v2w_lrelu(fmaf(a0, pf[s][0][e], s0), slope); v[1] = v2w_lrelu(fmaf(a1, pf[s][1][e], s1), slope);
+                }
                 *reinterpret_cast<f32x2*>(dst + e * RS) = v;
             }
         }
@@ -198,7 +209,7 @@ conv_tile_kernel(const MultiArgs m) {
             for (int j = lane; j < p.xrows; j += 64) {
                 const int l = pos0 + j;
                 float v = 0.f;
-                if (l >= 0 && l < L) v = v2w_lrelu(fmaf(av, src[(size_t)l * p.in_stride], sv), slope);
+                if (l >= 0 && l < Lb) v = v2w_lrelu(fmaf(av, src[(size_t)l * p.in_stride], sv), slope);
                 dst[j * RS] = v;
             }
         }
@@ -753,8 +764,18 @@ int launch_tile(const TileArgs* ps, int nprob, hipStream_t stream) {
         }
     }
     if (m.p[0].ws_query) { *m.p[0].ws_query = 0; return 0; }
-    bool vec = true;
-    for (int i = 0; i < nprob; ++i) vec = vec && m.p[i].vec4;
+    bool vec = true, len = false;
+    for (int i = 0; i < nprob; ++i) { vec = vec && m.p[i].vec4; len = len || m.p[i].len; }
+    if (len) {                                   // (every problem of the launch carries them: v2w_conv1d_mfma / v2w_convt1d_mfma)
+        if (epi != 0) return V2W_E_ARG;
+        auto kl = vec ? conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 3, true> : conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 3, false>;
+        if (lds > 64 * 1024) {
+            if (lds > 160 * 1024) return V2W_E_SHAPE;
+            hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kl), (int)lds, stream);
+            if (e != hipSuccess) return (int)e;
+        }
+        V2W_LAUNCH(kl, dim3(grid), dim3(NTHREADS), lds, stream, m);
+    } else {
     auto kern = vec ? (epi == 1 ? conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 1, true>
                        : (epi == 2 ? conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 2, true> : conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 0, true>))
                     : (epi == 1 ? conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 1, false>
@@ -765,6 +786,7 @@ int launch_tile(const TileArgs* ps, int nprob, hipStream_t stream) {
         if (e != hipSuccess) return (int)e;
     }
     V2W_LAUNCH(kern, dim3(grid), dim3(NTHREADS), lds, stream, m);
+    }
     if (S > 1) {
         const int rc = v2w_launch_status();
         if (rc != 0) return rc;
@@ -976,7 +998,8 @@ extern "C" int v2w_pack_mfma_batch(const float* wf, float* wp, int k, int c_in, 
 
 // Called by v2w_api.hip.  Returns V2W_E_SHAPE when no tile configuration fits (caller falls back to the direct kernel).
 // n problems (1 <= n <= V2W_MAX_MULTI) that share B, C_in, C_out, L - hence the tile configuration - in ONE launch.
-int v2w_conv1d_mfma(const v2w_conv1d_args* a, int n, hipStream_t stream, int* cfg_out, long long* ws_query) {
+// len / len_mul (v2w_conv1d_fwd_len): per-item valid lengths for every problem of the launch, or NULL.
+int v2w_conv1d_mfma(const v2w_conv1d_args* a, int n, hipStream_t stream, int* cfg_out, long long* ws_query, const int32_t* len, int len_mul) {
     if (n < 1 || n > V2W_MAX_MULTI) return V2W_E_ARG;
     const LayerCfg cfg = v2w_layer_cfg(a->C_in, a->C_out, 1);
     if (!cfg.mf) return V2W_E_SHAPE;
@@ -1001,6 +1024,11 @@ int v2w_conv1d_mfma(const v2w_conv1d_args* a, int n, hipStream_t stream, int* cf
         p.in_stride = q->in_stride > 0 ? q->in_stride : 1; p.in_phase = q->in_phase;
         p.slope = q->slope; p.accumulate = q->accumulate; p.out_div = q->out_div;
         p.splitk_ws = a->splitk_ws; p.splitk_ws_bytes = a->splitk_ws ? a->splitk_ws_bytes : 0; p.ws_query = ws_query;
+        if (len) {                       // per-item lengths: the forward's plain epilogue on plain tensors only
+            if (len_mul < 1 || q->mask_src || q->rowsum_part || p.out_slope != 1.f || p.in_stride != 1 || p.CinT != p.Cin || p.CoutT != p.Cout)
+                return V2W_E_ARG;
+            p.len = len; p.len_mul = len_mul;
+        }
         ps[i] = p;
         tiles128 += (long)p.B * ((p.L + 127) / 128) * (p.Cout / 128);
     }
@@ -1028,13 +1056,15 @@ int v2w_conv1d_mfma(const v2w_conv1d_args* a, int n, hipStream_t stream, int* cf
     return V2W_E_SHAPE;
 }
 
-int v2w_convt1d_mfma(const v2w_convt1d_args* a, hipStream_t stream, int* cfg_out, long long* ws_query) {
+int v2w_convt1d_mfma(const v2w_convt1d_args* a, hipStream_t stream, int* cfg_out, long long* ws_query, const int32_t* len, int len_mul) {
     const LayerCfg cfg = v2w_layer_cfg(a->C_in, a->C_out, a->u);
     if ((!a->wp && !cfg_out && !ws_query) || !cfg.mf) return V2W_E_SHAPE;
     TileArgs p{};
     p.cfg_out = cfg_out;
     p.splitk_ws = a->splitk_ws; p.splitk_ws_bytes = a->splitk_ws ? a->splitk_ws_bytes : 0; p.ws_query = ws_query;
     p.in = a->in; p.wp = a->wp; p.bias = a->bias; p.out = a->out; p.stats_part = a->stats_part;
+    if (len && (len_mul < 1 || a->stats_part)) return V2W_E_ARG;
+    p.len = len; p.len_mul = len_mul;
     p.B = a->B; p.Cin = a->C_in; p.Cout = a->C_out; p.L = a->L; p.K = a->k; p.dil = 1;
     p.CinT = p.Cin; p.CoutT = p.Cout; p.out_slope = 1.f;
     p.pad = (a->k - a->u) / 2;

@@ -32,9 +32,10 @@ __host__ __device__ constexpr int wslot(int c) { return (c & ~7) + 4 * (c & 1) +
 __host__ __device__ constexpr int wpair_c0(int P) { return 8 * (P >> 2) + 4 * (P & 1) + ((P >> 1) & 1); }
 __host__ __device__ inline int wino_tpos(int P, int d) { const int q = P / d; return 2 * d * q + (P - q * d); }
 
-template <int MI, int WN, int NPF, bool VEC>
-__global__ void __launch_bounds__(128 * WN, 3)
-conv_wino_kernel(const MultiArgs m) {
+// LEN: per-item valid lengths, as in conv_tile_body (v2w_conv_mfma.hip): inputs at and past Lb = min(L, len[b] * len_mul) select 0, a tile
+// whose first output position lies there returns at once; its own kernel name (conv_wino_len_kernel).
+template <int MI, int WN, int NPF, bool VEC, bool LEN>
+__device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
     typedef Frag<32> F;
     typedef F::acc_t acc_t;
     constexpr int WM = 2;
@@ -59,6 +60,12 @@ conv_wino_kernel(const MultiArgs m) {
     const int P0 = (tile % p.ntl) * NTP;     // first output pair of the tile
     const int m0 = mt * MT;
     const int d = p.dil;
+    int Lb = p.L;                            // end of this item's sequence (LEN; else the tensor's)
+    if constexpr (LEN) {
+        const int lv = p.len[b] * p.len_mul;
+        Lb = lv < p.L ? lv : p.L;
+        if (wino_tpos(P0, d) >= Lb) return;  // the tile's first (smallest) output position lies past the item's end
+    }
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -131,7 +138,9 @@ conv_wino_kernel(const MultiArgs m) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 f32x2 v = {0.f, 0.f};        // padding stays exactly 0 (it pads the ACTIVATED signal)
-                if (in_seq) { v[0] = v2w_lrelu(fmaf(a0, pf[s][0][e], s0), slope); v[1] = v2w_lrelu(fmaf(a1, pf[s][1][e], s1), slope); }
+                if (in_seq && (!LEN || pos0 + row + e < Lb)) {      // (LEN: per element - Lb need not be a multiple of 4)
+                    v[0] = v2w_lrelu(fmaf(a0, pf[s][0][e], s0), slope); v[1] = v2w_lrelu(fmaf(a1, pf[s][1][e], s1), slope);
+                }
                 *reinterpret_cast<f32x2*>(dst + e * WRS) = v;
             }
         }
@@ -146,7 +155,7 @@ conv_wino_kernel(const MultiArgs m) {
             for (int j = lane; j < p.xrows; j += 64) {
                 const int l = pos0 + j;
                 float v = 0.f;
-                if (l >= 0 && l < L) v = v2w_lrelu(fmaf(av, src[l], sv), slope);
+                if (l >= 0 && l < Lb) v = v2w_lrelu(fmaf(av, src[l], sv), slope);
                 dst[j * WRS] = v;
             }
         }
@@ -277,6 +286,18 @@ conv_wino_kernel(const MultiArgs m) {
     }
 }
 
+template <int MI, int WN, int NPF, bool VEC>
+__global__ void __launch_bounds__(128 * WN, 3)
+conv_wino_kernel(const MultiArgs m) {
+    conv_wino_body<MI, WN, NPF, VEC, false>(m);
+}
+
+template <int MI, int WN, int NPF, bool VEC>
+__global__ void __launch_bounds__(128 * WN, 3)
+conv_wino_len_kernel(const MultiArgs m) {
+    conv_wino_body<MI, WN, NPF, VEC, true>(m);
+}
+
 template <int MI, int WN>
 int launch_wino(const TileArgs* ps, int nprob, hipStream_t stream) {
     constexpr int MT = 64 * MI, NTP = 32 * WN, NTHREADS = 128 * WN;
@@ -315,7 +336,9 @@ int launch_wino(const TileArgs* ps, int nprob, hipStream_t stream) {
     m.start[nprob] = grid;
     for (int i = nprob + 1; i <= V2W_MAX_MULTI; ++i) m.start[i] = 0x7fffffff;
     if (lds > 160 * 1024) return V2W_E_SHAPE;
-    auto kern = vec ? conv_wino_kernel<MI, WN, NPF, true> : conv_wino_kernel<MI, WN, NPF, false>;
+    const bool lens = m.p[0].len != nullptr;      // (all problems of the launch or none: v2w_conv1d_wino)
+    auto kern = lens ? (vec ? conv_wino_len_kernel<MI, WN, NPF, true> : conv_wino_len_kernel<MI, WN, NPF, false>)
+                    : (vec ? conv_wino_kernel<MI, WN, NPF, true> : conv_wino_kernel<MI, WN, NPF, false>);
     if (lds > 64 * 1024) {
         hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kern), (int)lds, stream);
         if (e != hipSuccess) return (int)e;
@@ -349,7 +372,7 @@ pack_wino_kernel(const float* __restrict__ wf, float* __restrict__ wp, int K, in
 // Which shapes the Winograd kernel serves (V2W_E_SHAPE otherwise; the caller then uses the direct-form f32 MFMA kernel):
 // C_in % 32 == 0 and >= 64, C_out % 64 == 0, odd k >= 3 with symmetric padding, plain unit-stride input, no channel slices, none of
 // the backward / discriminator epilogues, and launches of more than 128 workgroups of 64 channels x 64 pairs.
-int v2w_conv1d_wino(const v2w_conv1d_args* a, int n, hipStream_t stream) {
+int v2w_conv1d_wino(const v2w_conv1d_args* a, int n, hipStream_t stream, const int32_t* len, int len_mul) {
     if (n < 1 || n > V2W_MAX_MULTI) return V2W_E_ARG;
     TileArgs ps[V2W_MAX_MULTI];
     long wgs = 0;
@@ -361,7 +384,9 @@ int v2w_conv1d_wino(const v2w_conv1d_args* a, int n, hipStream_t stream) {
         if (q->in_stride > 1 || q->mask_src || q->rowsum_part || (q->out_slope != 0.f && q->out_slope != 1.f)) return V2W_E_SHAPE;
         if ((q->in_ct > 0 && q->in_ct != q->C_in) || (q->out_ct > 0 && q->out_ct != q->C_out)) return V2W_E_SHAPE;
         if (!q->wp) return V2W_E_ARG;
+        if (len && len_mul < 1) return V2W_E_ARG;
         TileArgs p{};
+        p.len = len; p.len_mul = len_mul;
         p.in = q->in; p.in_a = q->in_a; p.in_s = q->in_s; p.wp = q->wp; p.bias = q->bias;
         p.res = q->res; p.res_a = q->res_a; p.res_s = q->res_s; p.out = q->out;
         p.add0 = q->add0; p.add1 = q->add1;

@@ -295,6 +295,49 @@ conv_post_tanh_vec4_kernel(const typename IN::elem_t* __restrict__ in, const flo
     *reinterpret_cast<f32x4*>(out + (size_t)b * L + l0) = y;
 }
 
+// The tail of a batch of unequal lengths (v2w_conv_post_tanh_len): item b's sequence ends at Lb = min(L, len[b] * len_mul) - inputs at and past
+// it select 0 (conv_post zero-pads), outputs there are stored as exactly 0 (the generator's last layer); a thread whose 4 outputs all lie past
+// Lb reads nothing.
+template <int KMAX>
+__global__ void __launch_bounds__(256)
+conv_post_tanh_len_kernel(const float* __restrict__ in, const float* __restrict__ wf, const float* __restrict__ bias,
+                          float* __restrict__ out, int B, int Cin, int L, int k, float slope, const int32_t* __restrict__ len, int len_mul) {
+    extern __shared__ float w_s[];   // [k][Cin]
+    for (int i = threadIdx.x; i < k * Cin; i += blockDim.x) w_s[i] = wf[i];
+    __syncthreads();
+    const int pad = (k - 1) / 2;
+    const int b = blockIdx.y;
+    const int l0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (l0 >= L) return;
+    const int lv = len[b] * len_mul;
+    const int Lb = lv < L ? lv : L;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    if (l0 < Lb) {
+        for (int ci = 0; ci < Cin; ++ci) {
+            const size_t src = ((size_t)b * Cin + ci) * L;
+            float win[4 + KMAX - 1];
+#pragma unroll
+            for (int j = 0; j < 4 + KMAX - 1; ++j) {
+                const int li = l0 - pad + j;
+                win[j] = (j < 4 + k - 1 && li >= 0 && li < Lb) ? v2w_lrelu(in[src + li], slope) : 0.f;
+            }
+#pragma unroll
+            for (int t = 0; t < KMAX; ++t) {
+                if (t < k) {
+                    const float w = w_s[t * Cin + ci];
+#pragma unroll
+                    for (int o = 0; o < 4; ++o) acc[o] = fmaf(w, win[o + t], acc[o]);
+                }
+            }
+        }
+    }
+    const float bv = bias ? bias[0] : 0.f;
+    float* dst = out + (size_t)b * L + l0;
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+        if (l0 + o < L) dst[o] = l0 + o < Lb ? tanhf(acc[o] + bv) : 0.f;
+}
+
 }  // namespace
 
 int v2w_conv1d_direct(const v2w_conv1d_args* a, hipStream_t stream) {
@@ -349,6 +392,18 @@ static int conv_post_tanh_impl(const typename IN::elem_t* in, const float* wf, c
 extern "C" int v2w_conv_post_tanh(const float* in, const float* wf, const float* bias, float* out,
                                   int B, int C_in, int L, int k, float slope, void* stream) {
     return conv_post_tanh_impl<InF32>(in, wf, bias, out, B, C_in, L, k, slope, stream);
+}
+
+extern "C" int v2w_conv_post_tanh_len(const float* in, const float* wf, const float* bias, float* out,
+                                      int B, int C_in, int L, int k, float slope, const int32_t* len, int len_mul, void* stream) {
+    if (!in || !wf || !out || !len || len_mul < 1 || B <= 0 || C_in <= 0 || L <= 0 || k <= 0 || (k & 1) == 0) return V2W_E_ARG;
+    if (k > 15) return V2W_E_SHAPE;
+    dim3 grid((L + 1023) / 1024, B);
+    const size_t lds = (size_t)k * C_in * sizeof(float);
+    hipStream_t s = (hipStream_t)stream;
+    if (k <= 7) V2W_LAUNCH((conv_post_tanh_len_kernel<7>), grid, dim3(256), lds, s, in, wf, bias, out, B, C_in, L, k, slope, len, len_mul);
+    else V2W_LAUNCH((conv_post_tanh_len_kernel<15>), grid, dim3(256), lds, s, in, wf, bias, out, B, C_in, L, k, slope, len, len_mul);
+    return v2w_launch_status();
 }
 
 int v2w_conv_post_tanh_bf16_mfma(const unsigned short* in, const float* wf, const float* bias, float* out,

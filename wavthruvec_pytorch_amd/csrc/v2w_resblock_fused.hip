@@ -378,6 +378,7 @@ struct StageArgs {
     float* rowsum[V2W_STAGE_MAXB];   // optional [tiles * WN][C][2]: per (tile, wave) channel sums of dt1_j over the positions the tile owns (, 0)
     const float* mask2; const float* mask2_a; const float* mask2_s;
     float mask_slope;
+    const int* len; int len_mul;     // LEN instantiations: item b's sequence ends at min(L, len[b] * len_mul)
 };
 
 template <int MF> struct StageGeom {
@@ -468,7 +469,11 @@ struct StageConv {
 // gradients: no activation), no biases; mask1[j] = the forward's t1_j, mask2 = the forward's xr.  dr is read ONCE for the three branches, every
 // dt1_j is written once and never read back by this kernel, the branch sum stays in registers: 9 tensor passes instead of the 18 of the
 // three merged launches.
-template <int MF, int NI, int WN, bool POST = false, bool BWD = false>
+// LEN (forward form only): per-item valid lengths (v2w_resblock2_stage_fwd_len).  x and t1_j select 0 at and past the item's end Lb = min(L, len[b] *
+// len_mul) - conv1 and conv2 zero-pad there, whatever `in` holds - and a tile whose outputs all lie past it returns at once; with the fused
+// tail (the generator's last layer) it stores y = 0 there instead, and y past Lb inside a tile is 0 too.  LEN = false compiles to the code the
+// kernel had without lengths.
+template <int MF, int NI, int WN, bool POST = false, bool BWD = false, bool LEN = false>
 __global__ void __launch_bounds__(64 * WN)
 resblock2_stage_kernel(const StageArgs p) {
     typedef Frag<MF> F;
@@ -496,6 +501,18 @@ resblock2_stage_kernel(const StageArgs p) {
     float* const etab = Ta + (W + p.h2max) * RS;     // bias1[nk][C], bias2[nk][C]
     const int pos0 = n0 - p.h2max - p.h1max - p.xoff;   // position of X row 0
     const int xc0 = p.xoff + p.h1max;                // X row of window column 0 (position n0 - h2max)
+    const int Lb = LEN ? min(L, p.len[b] * p.len_mul) : L;     // end of this item's sequence (LEN; else the tensor's)
+    if constexpr (LEN) {
+        if (n0 + p.hout >= Lb) {                     // every output of the tile lies past the item's end
+            if constexpr (POST) {                    // ... the last layer: y is exactly 0 there
+                for (int m = tid; m < p.nadv; m += NTHREADS) {
+                    const int pos = n0 + p.hout + m;
+                    if (pos < L) p.post_out[(size_t)b * L + pos] = 0.f;
+                }
+            }
+            return;
+        }
+    }
     V2W_STAMP(0);
     for (int i = tid; i < p.nk * C; i += NTHREADS) {
         const int j = i / C, c = i - j * C;
@@ -550,7 +567,7 @@ resblock2_stage_kernel(const StageArgs p) {
                 f32x4 raw, act;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    raw[i] = ok ? fmaf(av[s][i], g[s][i][e], sv[s][i]) : 0.f;
+                    raw[i] = ok && (!LEN || pos0 + r0 + e < Lb) ? fmaf(av[s][i], g[s][i][e], sv[s][i]) : 0.f;
                     act[i] = v2w_lrelu(raw[i], slope);
                 }
                 const int r = r0 + e;
@@ -562,7 +579,7 @@ resblock2_stage_kernel(const StageArgs p) {
         for (int i = tid; i < C * p.xrows; i += NTHREADS) {
             const int c = i / p.xrows, r = i - c * p.xrows, pos = pos0 + r;
             float raw = 0.f;
-            if (pos >= 0 && pos < L) {
+            if (pos >= 0 && pos < Lb) {
                 const int ch = b * C + c;
                 raw = fmaf(p.in_a ? p.in_a[ch] : 1.f, p.in[(size_t)ch * L + pos], p.in_s ? p.in_s[ch] : 0.f);
             }
@@ -708,7 +725,7 @@ resblock2_stage_kernel(const StageArgs p) {
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
             const int pos = n0 - p.h2max + wn0 + j * MF + lr;
-            const bool in_seq = pos >= 0 && pos < L;            // conv2 zero-pads t1 outside the sequence
+            const bool in_seq = pos >= 0 && pos < Lb;           // conv2 zero-pads t1 outside the sequence (LEN: the item's)
 #pragma unroll
             for (int e = 0; e < NR; ++e) t1r[j][e] = in_seq ? acc[j][e] + xres[j][e] : 0.f;
         }
@@ -755,7 +772,7 @@ resblock2_stage_kernel(const StageArgs p) {
             if constexpr (POST) {
                 // the tail's operand z = leaky_relu(out / nk, post_slope), exactly 0 outside the sequence (conv_post zero-pads)
                 const int pos = n0 - p.h2max + wn0 + j * MF + lr;
-                const bool in_seq = pos >= 0 && pos < L;
+                const bool in_seq = pos >= 0 && pos < Lb;
 #pragma unroll
                 for (int e = 0; e < NR; ++e) {
                     float v = oacc[j][e];
@@ -808,7 +825,7 @@ resblock2_stage_kernel(const StageArgs p) {
 #pragma unroll
                 for (int g2 = 1; g2 < 4; ++g2) y += *reinterpret_cast<const f32x4*>(part + (g2 * nq + qd) * 4);
 #pragma unroll
-                for (int x = 0; x < 4; ++x) y[x] = tanhf(y[x] + pb);
+                for (int x = 0; x < 4; ++x) y[x] = !LEN || p0 + x < Lb ? tanhf(y[x] + pb) : 0.f;
                 float* dst = p.post_out + (size_t)b * L + p0;
                 if (p.vec4) {
                     *reinterpret_cast<f32x4*>(dst) = y;
@@ -845,7 +862,7 @@ resblock2_stage_kernel(const StageArgs p) {
 }
 
 template <int MF, int NI, int WN>
-int launch_stage(const v2w_stage_args* q, hipStream_t stream) {
+int launch_stage(const v2w_stage_args* q, hipStream_t stream, const int32_t* len, int len_mul) {
     const bool post = q->post_out != nullptr;
     typedef StageGeom<MF> G;
     constexpr int W = MF * NI * WN;
@@ -894,8 +911,13 @@ int launch_stage(const v2w_stage_args* q, hipStream_t stream) {
         }
         p.mask2 = q->bwd_mask2; p.mask2_a = q->bwd_mask2_a; p.mask2_s = q->bwd_mask2_s; p.mask_slope = q->bwd_slope;
     }
+    if (len) {
+        if (bwd || len_mul < 1) return V2W_E_ARG;
+        p.len = len; p.len_mul = len_mul;
+    }
     auto kern = bwd ? resblock2_stage_kernel<MF, NI, WN, false, true>
-                    : (post ? resblock2_stage_kernel<MF, NI, WN, (MF == 16)> : resblock2_stage_kernel<MF, NI, WN, false>);
+                    : (len ? (post ? resblock2_stage_kernel<MF, NI, WN, (MF == 16), false, true> : resblock2_stage_kernel<MF, NI, WN, false, false, true>)
+                              : (post ? resblock2_stage_kernel<MF, NI, WN, (MF == 16)> : resblock2_stage_kernel<MF, NI, WN, false>));
     if (lds > 64 * 1024) {
         hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kern), (int)lds, stream);
         if (e != hipSuccess) return (int)e;
@@ -937,7 +959,7 @@ extern "C" int v2w_resblock2_stage_bwd_rows(const v2w_stage_args* a) {
     return rows > 0x7fffffffll ? 0 : (int)rows;
 }
 
-extern "C" int v2w_resblock2_stage_fwd(const v2w_stage_args* a, void* stream) {
+static int stage_fwd(const v2w_stage_args* a, void* stream, const int32_t* len, int len_mul) {
     if (!a || !a->in || (!a->out && !a->post_out) || a->nk < 1 || a->nk > V2W_STAGE_MAXB) return V2W_E_ARG;
     if (a->B <= 0 || a->C <= 0 || a->L <= 0) return V2W_E_ARG;
     if ((a->in_a == nullptr) != (a->in_s == nullptr) || (a->bwd_mask2_a == nullptr) != (a->bwd_mask2_s == nullptr)) return V2W_E_ARG;
@@ -954,7 +976,15 @@ extern "C" int v2w_resblock2_stage_fwd(const v2w_stage_args* a, void* stream) {
     for (int j = 0; j < a->nk; ++j) { const int h2 = a->dil2[j] * (a->k[j] - 1) / 2; if (h2 > h2max) h2max = h2; }
     const int nto = (256 - 2 * h2max) & ~3;
     const bool small = nto > 0 && (long long)a->B * ((a->L + nto - 1) / nto) < 224 && 128 - 2 * h2max >= 64;
-    if (a->C == 32) return small ? launch_stage<32, 1, 4>(a, st) : launch_stage<32, 2, 4>(a, st);
-    if (a->C == 16) return small ? launch_stage<16, 2, 4>(a, st) : launch_stage<16, 4, 4>(a, st);
+    if (a->C == 32) return small ? launch_stage<32, 1, 4>(a, st, len, len_mul) : launch_stage<32, 2, 4>(a, st, len, len_mul);
+    if (a->C == 16) return small ? launch_stage<16, 2, 4>(a, st, len, len_mul) : launch_stage<16, 4, 4>(a, st, len, len_mul);
     return V2W_E_SHAPE;
+}
+
+extern "C" int v2w_resblock2_stage_fwd(const v2w_stage_args* a, void* stream) { return stage_fwd(a, stream, nullptr, 1); }
+
+// Per-item valid lengths (include/vec2wav_hip.h): the forward form only - the input-gradient form (bwd_mask2) returns V2W_E_ARG.
+extern "C" int v2w_resblock2_stage_fwd_len(const v2w_stage_args* a, const int32_t* len, int len_mul, void* stream) {
+    if (!len || len_mul < 1 || (a && a->bwd_mask2)) return V2W_E_ARG;
+    return stage_fwd(a, stream, len, len_mul);
 }

@@ -40,6 +40,7 @@ struct TileArgs {
     int* cfg_out; // host-only: when set, launch_tile reports its template configuration instead of launching
     float* splitk_ws; long long splitk_ws_bytes;   // host-only (f32 tile kernel): the caller's split-over-C_in scratch (v2w_conv1d_args::splitk_ws)
     long long* ws_query;                           // host-only: when set, launch_tile reports the bytes of splitk_ws it would use instead of launching
+    const int* len; int len_mul;   // LEN instantiations (v2w_conv1d_fwd_len, v2w_convt1d_fwd_len): item b's sequence ends at min(L, len[b] * len_mul) input positions
 };
 
 // The tile kernels pick their problem with a per-workgroup index into MultiArgs::p, so every `p.field` is a scalar load from the

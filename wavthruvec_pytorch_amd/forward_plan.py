@@ -65,8 +65,10 @@ def _branches(rbs, names, wps):
 
 
 class ForwardPlanner:
-    def __init__(self, g, x, spk, nz, save, S):
+    def __init__(self, g, x, spk, nz, save, S, lens=None):
         self.g, self.x, self.spk, self.nz, self.save, self.S = g, x, spk, nz, save, S
+        self.lens = lens           # per-item valid lengths (B,) int32 on the device, or None (Generator.forward(lengths=...))
+        self.lmul = 1              # product of the upsample rates in front of the current layer: its input rate's len_mul
         self.dev = x.device
         self.B, _, self.T = x.shape
         self.training = g.training
@@ -185,6 +187,13 @@ class ForwardPlanner:
     def buf(self, name, shape, dtype=torch.float32):
         return self.g._buf(name, shape, dtype=dtype, device=self.dev)
 
+    def lkw(self, mul=None):
+        """Keyword arguments of a launch that serves per-item lengths: none without them, else the lengths and the launch's len_mul (the
+        product of the rates in front of its input)."""
+        if self.lens is None:
+            return {}
+        return dict(lengths=self.lens, len_mul=self.lmul if mul is None else mul)
+
     # ---------------------------------------------------------------------------------------------------------------------------
     def weights(self):
         """K0 + K3.  bf16 storage: the side stream's work - conv_post's fold, ups.0's fragments, the conditioning chain (train mode at mid sizes:
@@ -259,10 +268,11 @@ class ForwardPlanner:
         g = self.g
         self.cur = self.buf('act.pre', (self.B, g.h.upsample_initial_channel, self.T), dtype=self.adt)
         self.timed('conv_pre', hipops.conv1d, self.x, self.wf['conv_pre'], g.conv_pre.bias.detach(), self.cur, k=7, dil=1,
-                   slope=1.0, splitk_ws=self.slab, **self.ck('conv_pre', io=2))        # (the latents arrive as fp32)
+                   slope=1.0, splitk_ws=self.slab, **self.ck('conv_pre', io=2), **self.lkw())        # (the latents arrive as fp32)
         self.L = self.T
 
     def stage(self, i):
+        self.stage_i = i
         up = self.g.ups[i]
         self.C, self.Lo = up.out_channels, self.L * up.stride
         self.xr = self.buf(f'act.up{i}', (self.B, self.C, self.Lo), dtype=self.adt)
@@ -273,6 +283,7 @@ class ForwardPlanner:
         self.xs = self.buf(f'act.rb{i}', (self.B, self.C, self.Lo), dtype=self.adt)
         self.residual(i)
         self.cur, self.L = self.xs, self.Lo
+        self.lmul *= self.g.ups[i].stride
 
     def upsample(self, i):
         """K2: leaky_relu(0.1) -> ConvTranspose1d (+ the per-tile BatchNorm sums of its output)."""
@@ -303,7 +314,7 @@ class ForwardPlanner:
             raise RuntimeError(f'bf16 storage: ups.{i} has no bf16 kernel (set generator.bf16_storage = False)')
         else:
             self.timed(f'ups.{i}', hipops.convt1d, self.cur, self.wf[f'ups.{i}'], up.bias.detach(), self.xr, k=up.kernel_size,
-                       u=up.stride, slope=LRELU_SLOPE, algo=self.algo, wp=self.wp[f'ups.{i}'], stats_part=part, splitk_ws=self.slab)
+                       u=up.stride, slope=LRELU_SLOPE, algo=self.algo, wp=self.wp[f'ups.{i}'], stats_part=part, splitk_ws=self.slab, **self.lkw())
         self.up_done = None
         return nt_stats, part
 
@@ -381,6 +392,9 @@ class ForwardPlanner:
 
     def launch(self, tag_sfx, probs):
         probs = [probs[j] for j in self.heavy_first if j in probs]
+        if self.lens is not None:      # (the residual convs run at the stage's output rate)
+            lk = self.lkw(self.lmul * self.g.ups[self.stage_i].stride)
+            probs = [(j, (*pr[:4], {**pr[4], **lk})) for j, pr in probs]
         tag = '+'.join(f'{self.names[j]}.{tag_sfx}' for j, _ in probs)
         self.timed(tag, hipops.conv1d_multi, [pr for _, pr in probs], splitk_ws=self.slab)
 
@@ -456,14 +470,16 @@ class ForwardPlanner:
         if self.st or not (self.C in self.fuse_stage and self.all_wp):
             return False
         branches = self._f32_branches(self.wp, 'wp1', 'wp2')
+        lk = self.lkw(self.lmul * g.ups[i].stride)
         kp = g.conv_post.kernel_size
         if g.fuse_post and i == self.ns - 1 and self.C == 16 and kp <= 9 and kp % 2 == 1 and g.conv_post.in_channels == 16:
             y = torch.empty((self.B, 1, self.Lo), device=self.dev, dtype=torch.float32)
             if self.timed(self.stage_tag('+conv_post'), hipops.resblock2_stage, self.xr, self.aff, branches, None, slope=LRELU_SLOPE,
-                          out_div=float(self.nk), post=(self.wf['conv_post'], g.conv_post.bias.detach(), y, kp, 0.01)):
+                          out_div=float(self.nk), post=(self.wf['conv_post'], g.conv_post.bias.detach(), y, kp, 0.01), **lk):
                 self.y = y
                 return True
-        return self.timed(self.stage_tag(), hipops.resblock2_stage, self.xr, self.aff, branches, self.xs, slope=LRELU_SLOPE, out_div=float(self.nk))
+        return self.timed(self.stage_tag(), hipops.resblock2_stage, self.xr, self.aff, branches, self.xs, slope=LRELU_SLOPE, out_div=float(self.nk),
+                          **lk)
 
     def rb2_stage_small(self, i):
         """8 channels (the sixth stage of a x640 generator): below every MFMA tile - the whole section as one FMA kernel."""
@@ -482,7 +498,7 @@ class ForwardPlanner:
         return done
 
     def fused_pair_ok(self, keys):
-        return (not self.st and self.C in self.fuse_pairs and self.C in (16, 32)
+        return (self.lens is None and not self.st and self.C in self.fuse_pairs and self.C in (16, 32)
                 and all(self.wp.get(f'{nm}.{c}') is not None for nm in self.names for c in keys))
 
     def rb2_pairs(self, i):
@@ -619,7 +635,8 @@ class ForwardPlanner:
             self.S.join()
         if self.y is None:
             self.y = torch.empty((self.B, 1, self.L), device=self.dev, dtype=torch.float32)
-            self.timed('conv_post', hipops.conv_post_tanh, self.cur, self.wf['conv_post'], g.conv_post.bias.detach(), self.y, k=7, slope=0.01)
+            self.timed('conv_post', hipops.conv_post_tanh, self.cur, self.wf['conv_post'], g.conv_post.bias.detach(), self.y, k=7, slope=0.01,
+                       **self.lkw())
         return self.y
 
     def hand_over(self, y):

@@ -203,6 +203,22 @@ def _conv1d_args(a, x, wf, bias, out, *, k, dil=1, slope=1.0, in_affine=None, re
     a.slope = slope; a.accumulate = int(accumulate); a.out_div = out_div; a.algo = algo
 
 
+def _len_ptr(lengths, len_mul):
+    """Per-item valid lengths of a launch (the *_fwd_len entry points): `lengths` a (B,) int32 tensor on the launch's device - item b's sequence
+    ends at lengths[b] * len_mul positions of the call's input rate.  Returns its device pointer."""
+    if lengths.dtype != torch.int32 or not lengths.is_cuda or lengths.dim() != 1 or not lengths.is_contiguous():
+        raise ValueError('lengths must be a contiguous 1-d int32 tensor on the GPU')
+    if int(len_mul) < 1:
+        raise ValueError('len_mul must be >= 1')
+    return lengths.data_ptr()
+
+
+def _pop_len(kw):
+    """(kwargs without lengths / len_mul, lengths, len_mul)"""
+    kw = dict(kw)
+    return kw, kw.pop('lengths', None), int(kw.pop('len_mul', 1))
+
+
 class SplitKSlab:
     """Caller-owned scratch of the split over C_in (v2w_conv1d_args::splitk_ws, ABI v28): launches too small to fill the chip - inference at
     B = 1 - store per-slice partial sums here and a second kernel adds them.  The library allocates nothing: the OWNER of a slab (a
@@ -252,10 +268,14 @@ def conv1d(x, wf, bias, out, splitk_ws=None, **kw):
         conv1d_wino_multi([(x, wf, bias, out, kw)], splitk_ws=splitk_ws)
         return out
     kw.pop('wpw', None)
+    kw, lengths, len_mul = _pop_len(kw)
     a = _hip.Conv1dArgs()
     _conv1d_args(a, x, wf, bias, out, **kw)
     if splitk_ws is not None:
         _attach_slab(a, splitk_ws, _splitk_bytes(a, 1), x.device)
+    if lengths is not None:       # per-item valid lengths (v2w_conv1d_fwd_len; f32 MFMA / Winograd kernels only)
+        _hip.check(_hip.load().v2w_conv1d_fwd_len(C.byref(a), 1, _len_ptr(lengths, len_mul), len_mul, _stream(x)), 'v2w_conv1d_fwd_len')
+        return out
     _hip.check(_hip.load().v2w_conv1d_fwd(C.byref(a), _stream(x)), 'v2w_conv1d_fwd')
     return out
 
@@ -269,11 +289,16 @@ def conv1d_multi(problems, splitk_ws=None):
     problems = [(x, wf, bias, out, {q: v for q, v in kw.items() if q != 'wpw'}) for x, wf, bias, out, kw in problems]
     if 1 < n <= 4:
         arr = (_hip.Conv1dArgs * n)()
+        lengths = len_mul = None
         for a, (x, wf, bias, out, kw) in zip(arr, problems):
+            kw, lengths, len_mul = _pop_len(kw)          # (every problem of a launch carries the same lengths, or none does)
             _conv1d_args(a, x, wf, bias, out, **kw)
         if splitk_ws is not None:
             _attach_slab(arr[0], splitk_ws, _splitk_bytes(arr, n), problems[0][0].device)
-        rc = _hip.load().v2w_conv1d_fwd_multi(arr, n, _stream(problems[0][0]))
+        if lengths is not None:
+            rc = _hip.load().v2w_conv1d_fwd_len(arr, n, _len_ptr(lengths, len_mul), len_mul, _stream(problems[0][0]))
+        else:
+            rc = _hip.load().v2w_conv1d_fwd_multi(arr, n, _stream(problems[0][0]))
         if rc == 0:
             return
         if rc != -2:
@@ -288,9 +313,14 @@ def conv1d_wino_multi(problems, splitk_ws=None):
     n = len(problems)
     if 1 <= n <= 4 and all(kw.get('wpw') is not None for *_r, kw in problems):
         arr = (_hip.Conv1dArgs * n)()
+        lengths = len_mul = None
         for a, (x, wf, bias, out, kw) in zip(arr, problems):
-            _conv1d_args(a, x, wf, bias, out, **{**{q: v for q, v in kw.items() if q != 'wpw'}, 'algo': ALGO_WINO, 'wp': kw['wpw']})
-        rc = _hip.load().v2w_conv1d_fwd_multi(arr, n, _stream(problems[0][0]))
+            kw2, lengths, len_mul = _pop_len({q: v for q, v in kw.items() if q != 'wpw'})
+            _conv1d_args(a, x, wf, bias, out, **{**kw2, 'algo': ALGO_WINO, 'wp': kw['wpw']})
+        if lengths is not None:
+            rc = _hip.load().v2w_conv1d_fwd_len(arr, n, _len_ptr(lengths, len_mul), len_mul, _stream(problems[0][0]))
+        else:
+            rc = _hip.load().v2w_conv1d_fwd_multi(arr, n, _stream(problems[0][0]))
         if rc == 0:
             return
         if rc != -2:
@@ -298,8 +328,9 @@ def conv1d_wino_multi(problems, splitk_ws=None):
     conv1d_multi([(x, wf, bias, out, {q: v for q, v in kw.items() if q != 'wpw'}) for x, wf, bias, out, kw in problems], splitk_ws=splitk_ws)
 
 
-def convt1d(x, wf, bias, out, *, k, u, slope=1.0, algo=ALGO_AUTO, wp=None, stats_part=None, splitk_ws=None):
-    """Fused leaky_relu -> ConvTranspose1d(k, stride u, padding (k-u)//2) -> +bias."""
+def convt1d(x, wf, bias, out, *, k, u, slope=1.0, algo=ALGO_AUTO, wp=None, stats_part=None, splitk_ws=None, lengths=None, len_mul=1):
+    """Fused leaky_relu -> ConvTranspose1d(k, stride u, padding (k-u)//2) -> +bias.  lengths / len_mul: per-item valid lengths at the INPUT
+    rate (see _len_ptr; v2w_convt1d_fwd_len); outputs past lengths[b] * len_mul * u are unspecified."""
     B, ci, L = x.shape
     a = _hip.ConvT1dArgs()
     a.in_ = x.data_ptr(); a.wf = _hip.ptr(wf); a.wp = _hip.ptr(wp); a.bias = _hip.ptr(bias); a.out = out.data_ptr()
@@ -308,6 +339,9 @@ def convt1d(x, wf, bias, out, *, k, u, slope=1.0, algo=ALGO_AUTO, wp=None, stats
     a.slope = slope; a.algo = algo
     if splitk_ws is not None:
         _attach_slab(a, splitk_ws, _hip.load().v2w_convt1d_splitk_ws_bytes(C.byref(a)), x.device)
+    if lengths is not None:
+        _hip.check(_hip.load().v2w_convt1d_fwd_len(C.byref(a), _len_ptr(lengths, len_mul), int(len_mul), _stream(x)), 'v2w_convt1d_fwd_len')
+        return out
     _hip.check(_hip.load().v2w_convt1d_fwd(C.byref(a), _stream(x)), 'v2w_convt1d_fwd')
     return out
 
@@ -448,8 +482,15 @@ def affine_apply(x, a, s, out):
     return out
 
 
-def conv_post_tanh(x, wf, bias, out, *, k, slope):
+def conv_post_tanh(x, wf, bias, out, *, k, slope, lengths=None, len_mul=1):
+    """lengths / len_mul (fp32 input only): per-item valid lengths; out[b, 0, lengths[b] * len_mul:] is stored as exactly 0."""
     B, ci, L = x.shape
+    if lengths is not None:
+        if x.dtype != torch.float32:
+            raise NotImplementedError('conv_post_tanh: per-item lengths need fp32 input')
+        _hip.check(_hip.load().v2w_conv_post_tanh_len(x.data_ptr(), wf.data_ptr(), _hip.ptr(bias), out.data_ptr(),
+                                                      B, ci, L, k, slope, _len_ptr(lengths, len_mul), int(len_mul), _stream(x)), 'v2w_conv_post_tanh_len')
+        return out
     if x.dtype == torch.bfloat16:        # bf16 activation storage: the tail reads bf16, computes and writes fp32
         _hip.check(_hip.load().v2w_conv_post_tanh_bf16in(x.data_ptr(), wf.data_ptr(), _hip.ptr(bias), out.data_ptr(),
                                                          B, ci, L, k, slope, _stream(x)), 'v2w_conv_post_tanh_bf16in')
@@ -748,11 +789,13 @@ def branch_convs_bf16(mode, ins, in_affine, wps, biases, outs, ks, dils, *, slop
     return True
 
 
-def resblock2_stage(x, in_affine, branches, out, *, slope, out_div, post=None, bwd=None):
+def resblock2_stage(x, in_affine, branches, out, *, slope, out_div, post=None, bwd=None, lengths=None, len_mul=1):
     """Whole ResBlock2 residual section of a narrow stage in one kernel.  `branches`: list of dicts(wp1, b1, wp2, b2, k, dil1, dil2).
     post = (wf [k][C][1], bias | None, y (B, 1, L) fp32, k, slope): the generator's tail fused behind the 16-channel stage - `out` may be None,
     it is not written.  bwd = (t1s [nk], dt1s [nk], xr, (a, s) | None, mask_slope[, rowsums [nk]]): the section's input gradient instead (v2w_stage_args::bwd_*:
     x = dL/d(out), in_affine = (1 / nk, 0), wp1 / wp2 the transposed streams of conv2 / conv1, slope 1).
+    lengths / len_mul (forward form): per-item valid lengths (see _len_ptr; v2w_resblock2_stage_fwd_len); with `post`, y[b, 0, lengths[b] *
+    len_mul:] is exactly 0.
     Returns False (nothing launched) when the shape is not taken."""
     B, Cc, L = x.shape
     a = _hip.StageArgs()
@@ -777,7 +820,10 @@ def resblock2_stage(x, in_affine, branches, out, *, slope, out_div, post=None, b
         a.bwd_mask2 = xr.data_ptr()
         a.bwd_mask2_a, a.bwd_mask2_s = (xaff[0].data_ptr(), xaff[1].data_ptr()) if xaff is not None else (None, None)
         a.bwd_slope = mslope
-    rc = _hip.load().v2w_resblock2_stage_fwd(C.byref(a), _stream(x))
+    if lengths is not None:
+        rc = _hip.load().v2w_resblock2_stage_fwd_len(C.byref(a), _len_ptr(lengths, len_mul), int(len_mul), _stream(x))
+    else:
+        rc = _hip.load().v2w_resblock2_stage_fwd(C.byref(a), _stream(x))
     if rc == -2:
         return False
     _hip.check(rc, 'v2w_resblock2_stage_fwd')

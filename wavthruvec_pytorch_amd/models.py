@@ -590,8 +590,12 @@ class Generator(nn.Module):
 
     # -------------------------------------------------------------------------------------------
     @_hip.on_tensor_device
-    def forward(self, x, spk_emb=None, noise=None):
-        """x (B, num_wv_feat, T) channels-first, spk_emb (B, spk_dim), noise (B, noise_dim) -> (B, 1, T*prod(rates))."""
+    def forward(self, x, spk_emb=None, noise=None, lengths=None):
+        """x (B, num_wv_feat, T) channels-first, spk_emb (B, spk_dim), noise (B, noise_dim) -> (B, 1, T*prod(rates)).
+
+        lengths (optional; eval mode, no gradients, precision 'f32'): B valid frame counts 1 <= n_b <= T (a list or an integer tensor on any
+        device; a GPU tensor's values are not read back on the host, the kernels clamp them to T).  y[b, 0, :n_b * H] is then what the forward of
+        x[b:b+1, :, :n_b] alone gives (H = prod(upsample_rates)), y[b, 0, n_b * H:] is exactly 0, and x[b, :, n_b:] has no effect."""
         if spk_emb is None or noise is None:
             # the reference's torch.cat((None, None)) raises TypeError (SURVEY.md Q13)
             raise TypeError('Generator.forward: spk_emb and noise are required')
@@ -610,6 +614,9 @@ class Generator(nn.Module):
         nz = noise.detach().contiguous().float()
         if spk.shape != (x.shape[0], self.h.spk_dim) or nz.shape != (x.shape[0], self.h.noise_dim):
             raise RuntimeError('spk_emb / noise must be (B, spk_dim) / (B, noise_dim)')
+        if lengths is not None:
+            lens = self._lengths_buffer(lengths, x, needs_grad)
+            return self._forward_hip(x, spk, nz, None, lens=lens)
         if needs_grad:
             if self.algo == hipops.ALGO_DIRECT:
                 raise NotImplementedError('Generator (HIP): the scalar cross-check kernels (algo = ALGO_DIRECT) serve no-grad forwards only; '
@@ -619,6 +626,37 @@ class Generator(nn.Module):
             return GeneratorFunction.apply(self, names, x_in if x_in.requires_grad else x, spk, nz, *params)
         return self._forward_hip(x, spk, nz, None)
 
+    def _lengths_buffer(self, lengths, x, needs_grad):
+        """Check a ragged forward's arguments and configuration (before anything is launched) and copy the lengths, in stream order, into the
+        module-owned int32 buffer the recorded launch plans read (its values are not part of the plan key)."""
+        if self.training:
+            raise ValueError('Generator.forward(lengths=...): eval mode only - BatchNorm batch statistics over a padded batch are not the '
+                             "reference's per-utterance semantics")
+        if needs_grad:
+            raise NotImplementedError('Generator.forward(lengths=...): no-grad forwards only (run it under torch.no_grad())')
+        if self.precision != 'f32':
+            raise NotImplementedError(f"Generator.forward(lengths=...): precision 'f32' only, not {self.precision!r}")
+        if self.algo != hipops.ALGO_AUTO:
+            raise NotImplementedError('Generator.forward(lengths=...): algo = ALGO_AUTO only')
+        if not all(isinstance(rb, ResBlock2) for rb in self.resblocks) or self.num_upsamples != 5 or self.num_kernels > 3:
+            raise NotImplementedError('Generator.forward(lengths=...): ResBlock2 generators with five upsample stages and at most three '
+                                      'branches only')
+        B, T = x.shape[0], x.shape[2]
+        if torch.is_tensor(lengths):
+            if lengths.dtype.is_floating_point or lengths.dtype.is_complex or lengths.dtype == torch.bool or tuple(lengths.shape) != (B,):
+                raise ValueError(f'lengths must hold {B} integers')
+            src = lengths.detach()
+        else:
+            vals = [int(n) for n in lengths]
+            if len(vals) != B:
+                raise ValueError(f'lengths must hold {B} integers, got {len(vals)}')
+            src = torch.tensor(vals, dtype=torch.int32)
+        if not src.is_cuda and (src.numel() and (int(src.min()) < 1 or int(src.max()) > T)):
+            raise ValueError(f'lengths must lie in [1, T = {T}]')
+        buf = self._buf('lengths', (B,), dtype=torch.int32, device=x.device)
+        buf.copy_(src.to(torch.int32))     # (on the current stream: in order with the forward's launches, the previous forward's included)
+        return buf
+
     def _plan_key(self, x):
         """What a recorded launch plan depends on besides the values of the inputs: shape, mode, every switch the planner reads, and the
         storage of every parameter and buffer (a `.to()`, a `load_state_dict(assign=True)` or a replaced Parameter moves them)."""
@@ -627,7 +665,7 @@ class Generator(nn.Module):
                 self.fuse_wide, self.fuse_wide_stage, self.fuse_up, self.fuse_post, self.fuse_bn_finalize, self.cond_stream, self.merge_waits, self.split_min_channels,
                 self.always_refold, self.wino, ptrs)
 
-    def _forward_hip(self, x, spk, nz, save):
+    def _forward_hip(self, x, spk, nz, save, lens=None):
         """One forward through the C ABI.  `save` (a dict) asks for the back-propagatable form (forward_plan.py).  A no-grad forward is PLANNED
         once per configuration - forward_plan.ForwardPlanner decides and launches it under a schedule.Recorder - and replayed from the tape
         afterwards: prebuilt argument structs, three input pointers and the output rebound (`use_launch_plan = False`: plan every forward)."""
@@ -636,8 +674,9 @@ class Generator(nn.Module):
         dev = x.device
         main, side, side2 = torch.cuda.current_stream(dev), self._side_stream(dev), self._side_stream(dev, 1)
         if save is not None or not self.use_launch_plan or self.stat_sync is not None:
-            return ForwardPlanner(self, x, spk, nz, save, DirectStreams(main, side, side2)).run()
+            return ForwardPlanner(self, x, spk, nz, save, DirectStreams(main, side, side2), lens=lens).run()
         key, refold = self._tape_key(x)
+        key = key + (('lengths',) if lens is not None else ())     # (whether the lengths are given, not their values: the buffer is bound)
         tape = self._tapes.get(key)
         if tape is not None:
             y = torch.empty(tape.out[0], device=dev, dtype=tape.out[1])
@@ -656,12 +695,12 @@ class Generator(nn.Module):
                 self._fold_key.pop('sigma', None)       # (sigma_ws now holds this forward's own power-iteration values, as the planned forward notes)
             return y
         if self._profile is not None:                   # (a profiled forward of a configuration without a plan yet: planned, timed, not recorded)
-            return ForwardPlanner(self, x, spk, nz, None, DirectStreams(main, side, side2)).run()
+            return ForwardPlanner(self, x, spk, nz, None, DirectStreams(main, side, side2), lens=lens).run()
         rec = schedule.Recorder(_hip.load(), main, side, side2)
         epoch = self._ws_epoch
         prev = _hip.set_recorder(rec)
         try:
-            y = ForwardPlanner(self, x, spk, nz, None, rec).run()
+            y = ForwardPlanner(self, x, spk, nz, None, rec, lens=lens).run()
         finally:
             _hip.set_recorder(prev)
         binds = dict(x=x.data_ptr(), spk=spk.data_ptr(), nz=nz.data_ptr(), y=y.data_ptr())
