@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
+#include <utility>
 #include "../../include/vec2wav_hip.h"
 
 #define V2W_WAVE 64  // CDNA wavefront width (hard-coded: warpSize folds to 64 on gfx950)
@@ -12,6 +14,17 @@
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int raw16 __attribute__((ext_vector_type(4)));   // one 16-byte MFMA operand fragment, type-agnostic
+typedef __bf16 b8 __attribute__((ext_vector_type(8)));
+typedef __bf16 b4 __attribute__((ext_vector_type(4)));
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+
+// The unit of the packed weights (v2w_pack_split / v2w_pack_bf16 / v2w_split_pack_batch): bytes of the MFMA A fragments of one
+// (32-row block, 16-channel k-step, tap), [hi, lo][64 lanes][16 B]; the bf16 packs fill the first KiB only.
+#define V2W_FRAG_UNIT 2048
 
 static inline int v2w_launch_status() {
     hipError_t e = hipGetLastError();
@@ -102,6 +115,60 @@ __device__ __forceinline__ T v2w_block_sum(T v, T* red) {
     T t = 0;
     for (int i = 0; i < nw; ++i) t += red[i];  // fixed order: deterministic
     return t;
+}
+
+// ---- bf16 storage format on raw words: element 0 of a packed pair is the low half
+__device__ __forceinline__ unsigned int v2w_bf16x2(float lo, float hi) {
+    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
+    b2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;          // plain casts: v_cvt_pk_bf16_f32 (round to nearest even, NaN stays NaN)
+    return __builtin_bit_cast(unsigned int, v);
+}
+__device__ __forceinline__ float v2w_bf16_lo(unsigned int w) { return __builtin_bit_cast(float, w << 16); }
+__device__ __forceinline__ float v2w_bf16_hi(unsigned int w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
+
+// ---- wave primitives
+// a wave-uniform value as a scalar register (the pointer form, over pin_s, is in v2w_tile.h)
+__device__ __forceinline__ int v2w_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// DPP move inside rows of 16 lanes, e.g. quad_perm [1,0,3,2] (0xB1) / [2,3,0,1] (0x4E): the value of lane ^ 1 / lane ^ 2 in every group of four
+template <int CTRL> __device__ __forceinline__ float v2w_dpp(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float v2w_readlane(float v, int l) {           // (the builtin is typed int: a float argument would be CONVERTED)
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+}
+// sum over the 16 lanes of a DPP row, in every lane of the row (fixed order): quad xor 1, quad xor 2, half mirror, mirror
+__device__ __forceinline__ float v2w_row16_sum(float v) {
+    v += v2w_dpp<0xB1>(v);
+    v += v2w_dpp<0x4E>(v);
+    v += v2w_dpp<0x141>(v);
+    v += v2w_dpp<0x140>(v);
+    return v;
+}
+
+// One-instruction VALU forms.  max(v, w): fmaxf(v, w) costs two v_max here - hipcc first canonicalises an operand that comes out of an
+// MFMA with v_max_f32(v, v).  Scalar-form multiplies and adds beside MFMAs: left to -O3 these are SLP-packed into v_pk_mul_f32 /
+// v_pk_add_f32, which issue at well under half the rate of two plain instructions next to matrix work (MI355X guide, 'price of one
+// filler beside MFMAs').
+__device__ __forceinline__ float v2w_max(float v, float w) { float t; asm("v_max_f32 %0, %1, %2" : "=v"(t) : "v"(v), "v"(w)); return t; }
+__device__ __forceinline__ float v2w_mul(float v, float w) { float t; asm("v_mul_f32 %0, %1, %2" : "=v"(t) : "v"(v), "v"(w)); return t; }
+__device__ __forceinline__ float v2w_fma(float a, float b, float c) { float t; asm("v_fma_f32 %0, %1, %2, %3" : "=v"(t) : "v"(a), "v"(b), "v"(c)); return t; }
+__device__ __forceinline__ float v2w_add(float v, float w) { float t; asm("v_add_f32 %0, %1, %2" : "=v"(t) : "v"(v), "v"(w)); return t; }
+
+// f(std::integral_constant<int, I>{}) for every I of the sequence, in order
+template <int... I, class F> __device__ __forceinline__ void v2w_static_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
+
+// Workgroup barrier for LDS hand-overs only: __syncthreads() also fences global memory - a wave that has just issued its tile's output
+// stores would wait vmcnt(0) (the stores' acknowledgement, thousands of cycles under load) before it may even arrive at the barrier.
+__device__ __forceinline__ void v2w_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// LDS-DMA: 16 bytes per lane from `src` to LDS byte address lds + 16 * lane (lds wave-uniform: it goes through M0).  Inline asm ON
+// PURPOSE: hipcc orders every later LDS read behind a builtin LDS-DMA with s_waitcnt vmcnt(0) (it cannot prove the buffers distinct),
+// which would serialise copy and compute.  Hidden from its bookkeeping, the copy only makes the compiler's own vmcnt waits more
+// conservative (vmcnt retires in order); the caller waits for the data itself, with a counted vmcnt.
+__device__ __forceinline__ void v2w_lds_dma16(unsigned lds, const void* src) {
+    unsigned m0_save;                                    // M0 is a reserved register: hand it back as found
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(m0_save) : "s"(lds), "v"(src) : "memory");
 }
 
 // ---- f32 MFMA fragments shared by the tile kernels.  A/B operands are ONE float per lane; for the 32x32x2 shape lane l

@@ -26,25 +26,11 @@
 
 namespace {
 
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 #define V2W_BF_CK 32        // channels per chunk (two MFMA k-steps)
 #define V2W_BF_ROWB 80      // bytes per staged position: 32 ch bf16 (64 B) + 16 B pad: conflict-free ds_read_b128
-#define V2W_BF_UNIT 2048    // byte pitch of the packed fragments of one (32-row block, 16-channel k-step, tap); the first KiB is bf16
 
-__device__ __forceinline__ unsigned int pack_bf16x2(float lo, float hi) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    b2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;          // plain casts: v_cvt_pk_bf16_f32 (round to nearest even, NaN stays NaN)
-    return __builtin_bit_cast(unsigned int, v);
-}
-
-// bf16 <-> fp32 on raw words: element 0 of a packed pair is the low half
-__device__ __forceinline__ float bf_lo(unsigned int w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float bf_hi(unsigned int w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-__device__ __forceinline__ f32x4 bf4_to_f32(u32x2 w) { return f32x4{bf_lo(w[0]), bf_hi(w[0]), bf_lo(w[1]), bf_hi(w[1])}; }
-__device__ __forceinline__ u32x2 f32_to_bf4(f32x4 v) { return u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])}; }
+__device__ __forceinline__ f32x4 bf4_to_f32(u32x2 w) { return f32x4{v2w_bf16_lo(w[0]), v2w_bf16_hi(w[0]), v2w_bf16_lo(w[1]), v2w_bf16_hi(w[1])}; }
+__device__ __forceinline__ u32x2 f32_to_bf4(f32x4 v) { return u32x2{v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])}; }
 
 // IN_BF / OUT_BF: activation STORAGE in bf16 (`in`; `out`, `res`, `add0`, `add1`): 8-byte loads / stores of 4 positions instead of 16.
 // CKT: channels per chunk.  32 (two k-steps per tap); 64 for the C_in = 64 layers, which then are ONE chunk: no chunk loop, twice the
@@ -155,11 +141,11 @@ conv_bf16_kernel(const MultiArgs m) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     float xv;
-                    if constexpr (IN_BF) xv = (e & 1) ? bf_hi(pf[s][i][e >> 1]) : bf_lo(pf[s][i][e >> 1]);
+                    if constexpr (IN_BF) xv = (e & 1) ? v2w_bf16_hi(pf[s][i][e >> 1]) : v2w_bf16_lo(pf[s][i][e >> 1]);
                     else xv = pf[s][i][e];
                     a[i] = v2w_lrelu(fmaf(av[i], xv, sv[i]), slope);
                 }
-                u32x2 v = {pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3])};
+                u32x2 v = {v2w_bf16x2(a[0], a[1]), v2w_bf16x2(a[2], a[3])};
                 if (!in_seq) v = u32x2{0u, 0u};             // padding stays exactly 0 (it pads the ACTIVATED signal)
                 *reinterpret_cast<u32x2*>(dst + e * ROWB) = v;
             }
@@ -173,7 +159,7 @@ conv_bf16_kernel(const MultiArgs m) {
                 const int l = pos0 + j;
                 float v = 0.f;
                 if (l >= 0 && l < L) {
-                    const float xv = IN_BF ? bf_lo(gptr<const unsigned short>(p.in)[(size_t)ch * L + l]) : gptr<const float>(p.in)[(size_t)ch * L + l];
+                    const float xv = IN_BF ? v2w_bf16_lo(gptr<const unsigned short>(p.in)[(size_t)ch * L + l]) : gptr<const float>(p.in)[(size_t)ch * L + l];
                     v = v2w_lrelu(fmaf(av, xv, sv), slope);
                 }
                 reinterpret_cast<__bf16*>(Xs + j * ROWB)[c] = (__bf16)v;
@@ -181,12 +167,12 @@ conv_bf16_kernel(const MultiArgs m) {
         }
     };
 
-    // ---- weights: fragment (row block, 16-channel k-step c16, tap t) sits at ((rb * nst + c16 * K + t) * V2W_BF_UNIT) + lane * 16
+    // ---- weights: fragment (row block, 16-channel k-step c16, tap t) sits at ((rb * nst + c16 * K + t) * V2W_FRAG_UNIT) + lane * 16
     const int nst = KS * nch * K;                            // fragments per row block
     const unsigned char* ap[MI];
 #pragma unroll
     for (int i = 0; i < MI; ++i)
-        ap[i] = reinterpret_cast<const unsigned char*>(p.wps) + (size_t)((m0 + wm0) / 32 + i) * nst * V2W_BF_UNIT;
+        ap[i] = reinterpret_cast<const unsigned char*>(p.wps) + (size_t)((m0 + wm0) / 32 + i) * nst * V2W_FRAG_UNIT;
     const unsigned lane16 = (unsigned)lane * 16u;
     // ring of four fragments, each refilled right after its use with the fragment four k-steps on: three k-steps (3 x 32 MI NI cycles of
     // MFMA issue) ahead of an L2 round trip of 500+.  CK = 64: a slot per k-step of a tap.  CK = 32 (two k-steps per tap): the taps of the
@@ -199,7 +185,7 @@ conv_bf16_kernel(const MultiArgs m) {
         const int chc = ch < nch ? ch : nch - 1;
 #pragma unroll
         for (int i = 0; i < MI; ++i)
-            a[i] = *gptr<const u32x4>(ap[i] + (size_t)((KS * chc + s) * K + t) * V2W_BF_UNIT + l16);
+            a[i] = *gptr<const u32x4>(ap[i] + (size_t)((KS * chc + s) * K + t) * V2W_FRAG_UNIT + l16);
     };
 
     // ---- B operands: one 16-byte fragment per column block, refilled right after its last use in the running k-step
@@ -228,7 +214,7 @@ conv_bf16_kernel(const MultiArgs m) {
         else *gptr<f32x4>(base + off) = v;
     };
     auto ld1 = [&](const float* base, size_t off) {
-        if constexpr (OUT_BF) return bf_lo(gptr<const unsigned short>(base)[off]);
+        if constexpr (OUT_BF) return v2w_bf16_lo(gptr<const unsigned short>(base)[off]);
         else return gptr<const float>(base)[off];
     };
     auto st1 = [&](float* base, size_t off, float v) {
@@ -984,7 +970,7 @@ extern "C" int v2w_pack_bf16_convt(const float* wf, void* wps, int k, int c_in, 
         const size_t total2 = (size_t)(c_out * u / 32) * (c_in / 16) * g.KV * 64;
         int grid2 = (int)((total2 + 255) / 256); if (grid2 > 4096) grid2 = 4096;
         V2W_LAUNCH(pack_bf16_convt_kernel, dim3(grid2), dim3(256), 0, (hipStream_t)stream, wf,
-                           reinterpret_cast<b8*>(reinterpret_cast<unsigned char*>(wps) + total / 64 * V2W_BF_UNIT), k, c_in, c_out, u, u, g.hl, g.KV);
+                           reinterpret_cast<b8*>(reinterpret_cast<unsigned char*>(wps) + total / 64 * V2W_FRAG_UNIT), k, c_in, c_out, u, u, g.hl, g.KV);
     }
     return v2w_launch_status();
 }
@@ -993,7 +979,7 @@ extern "C" long long v2w_pack_bf16_convt_bytes(int k, int c_in, int c_out, int u
     if (k <= 0 || c_in <= 0 || c_out <= 0 || u <= 1 || k < u || ((k - u) & 1) || u > 8 || c_in % 32 != 0) return 0;
     const ConvtGeom g = convt_geom(k, u);
     if ((c_out * g.UP) % 32 != 0) return 0;
-    return (long long)(c_out * g.UP / 32 + (convt_exact_region(c_out, u, g.UP) ? c_out * u / 32 : 0)) * (c_in / 16) * g.KV * V2W_BF_UNIT;
+    return (long long)(c_out * g.UP / 32 + (convt_exact_region(c_out, u, g.UP) ? c_out * u / 32 : 0)) * (c_in / 16) * g.KV * V2W_FRAG_UNIT;
 }
 extern "C" int v2w_convt1d_bf16_fwd(const v2w_convt1d_args* a, void* stream) {
     if (!a || !a->in || !a->wp || !a->out) return V2W_E_ARG;

@@ -28,12 +28,7 @@
 
 namespace {
 
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 #define V2W_RS_MAXB 3
-#define V2W_RS_UNIT 2048     // byte pitch of the packed fragments of one (32-row block, 16-channel k-step, tap)
 #define V2W_RS_HMAX 32
 
 struct ResArgs {
@@ -48,31 +43,15 @@ struct ResArgs {
     float slope, inv_slope, out_div;
 };
 
-__device__ __forceinline__ unsigned int rs_pack2(float lo, float hi) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    b2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned int, v);
-}
-__device__ __forceinline__ float rs_lo(unsigned int w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float rs_hi(unsigned int w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-__device__ __forceinline__ int rs_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-template <typename T> __device__ __forceinline__ T* rs_uni(T* v) { pin_s(v); return v; }
-
-// quad_perm [1,0,3,2] / [2,3,0,1]: the value of lane ^ 1 / lane ^ 2 inside every group of four lanes
-__device__ __forceinline__ float rs_xor1(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float rs_xor2(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-}
 // 4 x 4 transpose across a lane quad: afterwards register r of quad lane q holds what register q of quad lane r held
+// (DPP quad_perm 0xB1 / 0x4E: the value of lane ^ 1 / lane ^ 2)
 __device__ __forceinline__ void rs_quad_transpose(float (&x)[4], bool b0, bool b1) {
-    const float r0 = rs_xor1(b0 ? x[0] : x[1]);
-    const float r1 = rs_xor1(b0 ? x[2] : x[3]);
+    const float r0 = v2w_dpp<0xB1>(b0 ? x[0] : x[1]);
+    const float r1 = v2w_dpp<0xB1>(b0 ? x[2] : x[3]);
     x[0] = b0 ? r0 : x[0]; x[1] = b0 ? x[1] : r0;
     x[2] = b0 ? r1 : x[2]; x[3] = b0 ? x[3] : r1;
-    const float r2 = rs_xor2(b1 ? x[0] : x[2]);
-    const float r3 = rs_xor2(b1 ? x[1] : x[3]);
+    const float r2 = v2w_dpp<0x4E>(b1 ? x[0] : x[2]);
+    const float r3 = v2w_dpp<0x4E>(b1 ? x[1] : x[3]);
     x[0] = b1 ? r2 : x[0]; x[2] = b1 ? x[2] : r2;
     x[1] = b1 ? r3 : x[1]; x[3] = b1 ? x[3] : r3;
 }
@@ -87,7 +66,7 @@ conv_bf16_res_kernel(const ResArgs a) {
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_r[];
 
-    const int C = rs_uni(a.C), L = rs_uni(a.L), xrows = rs_uni(a.xrows), hla = rs_uni(a.hla), nbr = rs_uni(a.nbr);
+    const int C = v2w_uni(a.C), L = v2w_uni(a.L), xrows = v2w_uni(a.xrows), hla = v2w_uni(a.hla), nbr = v2w_uni(a.nbr);
     const int nch = C >> 5, psz = xrows * 64;
     const float slope = a.slope, inv_slope = a.inv_slope;
     float* const btab = reinterpret_cast<float*>(smem_r + nch * psz);       // bias[nbr][MT] (mode 1: their sum in row 0)
@@ -104,7 +83,7 @@ conv_bf16_res_kernel(const ResArgs a) {
     const int m0 = mt * MT;
 
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = rs_uni(tid >> 6);
+    const int wave = v2w_uni(tid >> 6);
     const int lr = lane & 31, hk = lane >> 5;
     const int wm0 = (wave / WN) * (32 * MI);
     const int wn0 = (wave % WN) * (32 * NI);
@@ -160,11 +139,11 @@ conv_bf16_res_kernel(const ResArgs a) {
                 float v[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    float xv = (e & 1) ? rs_hi(pf[s][i][e >> 1]) : rs_lo(pf[s][i][e >> 1]);
+                    float xv = (e & 1) ? v2w_bf16_hi(pf[s][i][e >> 1]) : v2w_bf16_lo(pf[s][i][e >> 1]);
                     if constexpr (MODE == 0) xv = fmaf(av[i], xv, sv[i]);
                     v[i] = v2w_lrelu(xv, slope);
                 }
-                u32x2 w = {rs_pack2(v[0], v[1]), rs_pack2(v[2], v[3])};
+                u32x2 w = {v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
                 if (!in_seq[s]) w = u32x2{0u, 0u};            // the padding of the ACTIVATED signal is exactly 0
                 *reinterpret_cast<u32x2*>(dst + e * 64) = w;
             }
@@ -251,7 +230,7 @@ conv_bf16_res_kernel(const ResArgs a) {
         asm volatile("" : "+v"(row));                    // recomputed at every use: hoisted out of the branch loop these addresses spill
         const unsigned q = (unsigned)(((m0 + wm0) / 32 + i) * psz + (row + 32 * j) * 64 + ((g ^ ((row >> 2) & 3)) << 4) + 8 * hk);
         const u32x2 w = *reinterpret_cast<const u32x2*>(smem_r + q);
-        const float v[4] = {rs_lo(w[0]), rs_hi(w[0]), rs_lo(w[1]), rs_hi(w[1])};
+        const float v[4] = {v2w_bf16_lo(w[0]), v2w_bf16_hi(w[0]), v2w_bf16_lo(w[1]), v2w_bf16_hi(w[1])};
 #pragma unroll
         for (int x = 0; x < 4; ++x) r[x] = v[x] > 0.f ? v[x] : v[x] * inv_slope;
     };
@@ -288,7 +267,7 @@ conv_bf16_res_kernel(const ResArgs a) {
         const int nst = 2 * nch * K;
         const unsigned char* ap[MI];
 #pragma unroll
-        for (int i = 0; i < MI; ++i) ap[i] = wps + (size_t)((m0 + wm0) / 32 + i) * nst * V2W_RS_UNIT;
+        for (int i = 0; i < MI; ++i) ap[i] = wps + (size_t)((m0 + wm0) / 32 + i) * nst * V2W_FRAG_UNIT;
         u32x4 ar[4][MI];
         auto load_frag = [&](u32x4 (&av)[MI], int ch, int s, int t) {     // k-step s of (chunk ch, tap t); clamped past the end
             unsigned l16 = lane16;
@@ -296,7 +275,7 @@ conv_bf16_res_kernel(const ResArgs a) {
             const int chc = ch < nch ? ch : nch - 1;
 #pragma unroll
             for (int i = 0; i < MI; ++i)
-                av[i] = *gptr<const u32x4>(ap[i] + (size_t)((2 * chc + s) * K + t) * V2W_RS_UNIT + l16);
+                av[i] = *gptr<const u32x4>(ap[i] + (size_t)((2 * chc + s) * K + t) * V2W_FRAG_UNIT + l16);
         };
         load_frag(ar[0], 0, 0, 0);
         load_frag(ar[1], 0, 1, 0);
@@ -369,7 +348,7 @@ conv_bf16_res_kernel(const ResArgs a) {
                         for (int x = 0; x < 4; ++x) v[x] = v2w_div_by(v[x], div, dinv);
                     }
                     rs_quad_transpose(v, q0, q1);
-                    const u32x2 w = {rs_pack2(v[0], v[1]), rs_pack2(v[2], v[3])};
+                    const u32x2 w = {v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
                     // uniform base of the batch item (64-bit, scalar) + a 32-bit offset: uniform part + the lane's (C * L * 2 < 2^31: checked by the launcher)
                     const unsigned uo = (unsigned)((m0 + wm0 + 32 * i + 8 * g) * L + q) * 2u;
                     if (ok) *gptr<u32x2>(obase + (uo + vo)) = w;
@@ -387,26 +366,26 @@ conv_bf16_res_kernel(const ResArgs a) {
         for (int j = 0; j < nbr; ++j) {
             init_acc(j);
             V2W_STAMP(3 + 3 * j);
-            conv(rs_uni(a.wps[j]), rs_uni(a.K[j]), rs_uni(a.dil[j]));
+            conv(v2w_uni(a.wps[j]), v2w_uni(a.K[j]), v2w_uni(a.dil[j]));
             V2W_STAMP(4 + 3 * j);
-            store_tile(rs_uni(a.out[j]), true, 0.f);
+            store_tile(v2w_uni(a.out[j]), true, 0.f);
             V2W_STAMP(5 + 3 * j);
         }
     } else {
         for (int j = 0; j < nbr; ++j) {
             if (j > 0) __syncthreads();                      // every wave is done with the previous branch's tile
             V2W_STAMP(1 + 5 * j);
-            stage(rs_uni(a.in[j]));
+            stage(v2w_uni(a.in[j]));
             V2W_STAMP(2 + 5 * j);
             __syncthreads();
             V2W_STAMP(3 + 5 * j);
             if (j == 0) init_acc(0);
             add_residual();
             V2W_STAMP(4 + 5 * j);
-            conv(rs_uni(a.wps[j]), rs_uni(a.K[j]), rs_uni(a.dil[j]));
+            conv(v2w_uni(a.wps[j]), v2w_uni(a.K[j]), v2w_uni(a.dil[j]));
             V2W_STAMP(5 + 5 * j);
         }
-        store_tile(rs_uni(a.out[0]), false, a.out_div);
+        store_tile(v2w_uni(a.out[0]), false, a.out_div);
     }
     V2W_STAMP(20);
 }

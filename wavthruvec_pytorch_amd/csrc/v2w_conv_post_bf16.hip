@@ -17,9 +17,6 @@
 
 namespace {
 
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 
 struct PostArgs {
@@ -34,11 +31,6 @@ struct PostArgs {
 constexpr int PM_NT = V2W_PM_NT;                  // tiles of 256 outputs per wave and job
 constexpr int PM_JOB = 4 * PM_NT * 256;           // outputs per workgroup job (4 waves)
 
-__device__ __forceinline__ unsigned int pm_bf16_pair(float lo, float hi) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    b2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned int, v);
-}
 __device__ __forceinline__ float pm_round_bf16(float v) { return (float)(__bf16)v; }
 __device__ __forceinline__ unsigned int pm_relu2(unsigned int w) {
     return __builtin_bit_cast(unsigned int, __builtin_elementwise_max(__builtin_bit_cast(s16x2, w), s16x2{0, 0}));
@@ -69,9 +61,9 @@ conv_post_tanh_mfma_kernel(const PostArgs a) {
             wh[e] = pm_round_bf16(w2);
             wl[e] = w2 - wh[e];
         }
-        aimg[(c * 3 + 0) * 64 + l] = u32x4{pm_bf16_pair(w1[0], w1[1]), pm_bf16_pair(w1[2], w1[3]), pm_bf16_pair(w1[4], w1[5]), pm_bf16_pair(w1[6], w1[7])};
-        aimg[(c * 3 + 1) * 64 + l] = u32x4{pm_bf16_pair(wh[0], wh[1]), pm_bf16_pair(wh[2], wh[3]), pm_bf16_pair(wh[4], wh[5]), pm_bf16_pair(wh[6], wh[7])};
-        aimg[(c * 3 + 2) * 64 + l] = u32x4{pm_bf16_pair(wl[0], wl[1]), pm_bf16_pair(wl[2], wl[3]), pm_bf16_pair(wl[4], wl[5]), pm_bf16_pair(wl[6], wl[7])};
+        aimg[(c * 3 + 0) * 64 + l] = u32x4{v2w_bf16x2(w1[0], w1[1]), v2w_bf16x2(w1[2], w1[3]), v2w_bf16x2(w1[4], w1[5]), v2w_bf16x2(w1[6], w1[7])};
+        aimg[(c * 3 + 1) * 64 + l] = u32x4{v2w_bf16x2(wh[0], wh[1]), v2w_bf16x2(wh[2], wh[3]), v2w_bf16x2(wh[4], wh[5]), v2w_bf16x2(wh[6], wh[7])};
+        aimg[(c * 3 + 2) * 64 + l] = u32x4{v2w_bf16x2(wl[0], wl[1]), v2w_bf16x2(wl[2], wl[3]), v2w_bf16x2(wl[4], wl[5]), v2w_bf16x2(wl[6], wl[7])};
     }
     __syncthreads();
     const float bv = a.bias ? a.bias[0] : 0.f;

@@ -16,22 +16,15 @@
 //              padding happen once at staging; a tap is a ROW offset into the same tile.
 // A (weights): v2w_pack_split() stores, per 32-row block, chunk and tap, the four MFMA A fragments (2 k-steps x hi/lo,
 //              1 KiB each) contiguously; a stage (= all row blocks of the workgroup for one chunk x tap) is copied
-//              global -> LDS by global_load_lds_dwordx4 (no registers), two stages ahead of its use.
+//              global -> LDS by LDS-DMA (v2w_lds_dma16: no registers), two stages ahead of its use.
 // Sync       : one workgroup barrier per tap; the async copies are fenced with explicit s_waitcnt vmcnt (see the loop).
 #include "v2w_tile.h"
 
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-typedef unsigned int raw16 __attribute__((ext_vector_type(4)));   // one 16-byte MFMA operand fragment, type-agnostic
-
 #define V2W_SPLIT_CK 16        // input channels per stage = one MFMA k-step
 #define V2W_SPLIT_ROWB 80       // bytes per staged position: 16 ch hi (32 B) | 16 ch lo (32 B) | 16 B pad
-#define V2W_SPLIT_UNIT 2048     // bytes of the A fragments of one (32-row block, chunk, tap): [hi, lo][64 lanes][16 B]
 #define V2W_SPLIT_HMAX 32       // largest halo per side
 #define V2W_SPLIT_NAB 4         // weight stages resident in LDS: one computing, one published for the next stage, two in flight
 #define V2W_SPLIT_WPE 2         // waves per SIMD the register allocation targets (= workgroups per CU)
@@ -39,7 +32,6 @@ typedef unsigned int raw16 __attribute__((ext_vector_type(4)));   // one 16-byte
 #define V2W_SPLIT_FORCE 0       // experiments: 1 = 64 x 128 tiles, 2 = 128 x 128 tiles for every C_out % 128 == 0 layer
 
 #define V2W_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-#define V2W_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 // BF = false: split f16x3 (three MFMAs per product).  BF = true: plain bf16 operands, ONE v_mfma_f32_32x32x16_bf16 per product
 // (BASELINE configs[2] 'bf16 compute / fp32 accumulate'): same tiles, same fragment layout with the lo halves unused.
@@ -55,7 +47,7 @@ conv_split_kernel(const MultiArgs m) {
     constexpr int MT = 32 * MI * WM, NT = 32 * NI * WN, CK = V2W_SPLIT_CK;
     constexpr int ROWB = V2W_SPLIT_ROWB;
     constexpr int NMT = MT / 32;                                // 32-row blocks per workgroup
-    constexpr int ASTAGE = NMT * V2W_SPLIT_UNIT;                // bytes of one weight stage
+    constexpr int ASTAGE = NMT * V2W_FRAG_UNIT;                // bytes of one weight stage
     constexpr int NAB = V2W_SPLIT_NAB;
     // async 16-B copies per thread and stage; bf16 moves only the hi half of every unit (1 KiB = one wave copy per unit)
     constexpr int ADMA = BF ? (NMT + 3) / 4 : ASTAGE / (NTHREADS * 16);
@@ -118,26 +110,21 @@ conv_split_kernel(const MultiArgs m) {
     for (int i = 0; i < ADMA; ++i) {
         const int q = i * NTHREADS + tid;                        // 16-B element of the stage; 128 of them per unit (bf16: the first 64)
         const int unit = BF ? (q >> 6) % NMT : q >> 7, off = BF ? (q & 63) : (q & 127);     // bf16, NMT < 4: waves 2, 3 repeat 0, 1
-        dsrc[i] = reinterpret_cast<const unsigned char*>(p.wps) + (size_t)(m0 / 32 + unit) * nst * V2W_SPLIT_UNIT + off * 16;
+        dsrc[i] = reinterpret_cast<const unsigned char*>(p.wps) + (size_t)(m0 / 32 + unit) * nst * V2W_FRAG_UNIT + off * 16;
     }
     const unsigned a_lds = __builtin_amdgcn_readfirstlane(
         (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)(As0 + wave * 1024));
     const unsigned a_lds_bf = __builtin_amdgcn_readfirstlane(    // bf16: wave w fills the hi half of unit (w % NMT)
-        (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)(As0 + (wave % NMT) * V2W_SPLIT_UNIT));
+        (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)(As0 + (wave % NMT) * V2W_FRAG_UNIT));
     int dma_slot = 0;                                            // ring slot the next copy fills
     auto dma_next = [&]() __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < ADMA; ++i) {
-            // Issued through inline asm ON PURPOSE: hipcc orders every later LDS read behind a builtin LDS-DMA with
-            // s_waitcnt vmcnt(0) (it cannot prove the buffers distinct), which would serialise copy and compute.  Hidden
-            // from its bookkeeping, the copy only makes the compiler's own vmcnt waits more conservative (vmcnt retires in
-            // order); the waits THIS data needs are the explicit V2W_WAIT_VM below.  M0 = LDS byte address of lane 0.
-            const unsigned lds = BF ? a_lds_bf + dma_slot * ASTAGE + i * (4 * V2W_SPLIT_UNIT)
+            // hidden from hipcc's vmcnt bookkeeping: the waits THIS data needs are the explicit V2W_WAIT_VM below
+            const unsigned lds = BF ? a_lds_bf + dma_slot * ASTAGE + i * (4 * V2W_FRAG_UNIT)
                                     : a_lds + dma_slot * ASTAGE + i * (NTHREADS * 16);
-            unsigned m0_save;                                    // M0 is a reserved register: hand it back as found
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(m0_save) : "s"(lds), "v"(dsrc[i]) : "memory");
-            dsrc[i] += V2W_SPLIT_UNIT;
+            v2w_lds_dma16(lds, dsrc[i]);
+            dsrc[i] += V2W_FRAG_UNIT;
         }
         dma_slot = dma_slot + 1 == NAB ? 0 : dma_slot + 1;
     };
@@ -169,11 +156,7 @@ conv_split_kernel(const MultiArgs m) {
     auto prefetch = [&](int ci0) __attribute__((always_inline)) {
         const float* src = p.in + (size_t)(b * p.CinT + ci0) * L;      // (CinT: channels of the tensor `in` points into - a group's slice)
 #pragma unroll
-        for (int i = 0; i < NSIG; ++i) {
-            unsigned m0_save;
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0"
-                         : "=&s"(m0_save) : "s"(r_lds + __builtin_amdgcn_readfirstlane(rbase[i])), "v"(src + soff[i]) : "memory");
-        }
+        for (int i = 0; i < NSIG; ++i) v2w_lds_dma16(r_lds + __builtin_amdgcn_readfirstlane(rbase[i]), src + soff[i]);
     };
     auto act = [&](float v) __attribute__((always_inline)) {     // leaky_relu, then into the f16 range (see the header)
         v = slope <= 1.f ? fmaxf(v, v * slope) : v2w_lrelu(v, slope);
@@ -255,13 +238,13 @@ conv_split_kernel(const MultiArgs m) {
     if constexpr (VEC) {
         prefetch(0);
         V2W_WAIT_VM(0);
-        V2W_BARRIER();                                           // raw chunk 0 (and the first weight stages) landed
+        v2w_lds_barrier();                                           // raw chunk 0 (and the first weight stages) landed
         commit(0, Xs0);
     } else {
         stage_scalar(0, Xs0);
         V2W_WAIT_VM(0);
     }
-    V2W_BARRIER();
+    v2w_lds_barrier();
 
     const int rowbase = wn0 + lr + p.hla - p.hl;                 // LDS row of this lane's column for tap 0
     int st = 0;
@@ -296,11 +279,11 @@ conv_split_kernel(const MultiArgs m) {
     // chunk starts on the other one: the two chunk bodies below keep every register index static.
     int ring = 0;                                                // ring slot of the stage being computed
     auto read_a = [&](raw16 (&h)[MI], raw16 (&l)[BF ? 1 : MI], int slot) __attribute__((always_inline)) {
-        const unsigned char* Ab = As0 + slot * ASTAGE + (wmi * MI) * V2W_SPLIT_UNIT + lane * 16;
+        const unsigned char* Ab = As0 + slot * ASTAGE + (wmi * MI) * V2W_FRAG_UNIT + lane * 16;
 #pragma unroll
         for (int i = 0; i < MI; ++i) {
-            h[i] = *reinterpret_cast<const raw16*>(Ab + i * V2W_SPLIT_UNIT);
-            if constexpr (!BF) l[i] = *reinterpret_cast<const raw16*>(Ab + i * V2W_SPLIT_UNIT + 1024);
+            h[i] = *reinterpret_cast<const raw16*>(Ab + i * V2W_FRAG_UNIT);
+            if constexpr (!BF) l[i] = *reinterpret_cast<const raw16*>(Ab + i * V2W_FRAG_UNIT + V2W_FRAG_UNIT / 2);
         }
     };
     auto stage = [&](raw16 (&ah)[MI], raw16 (&al)[BF ? 1 : MI], raw16 (&nh)[MI], raw16 (&nl)[BF ? 1 : MI],
@@ -359,7 +342,7 @@ conv_split_kernel(const MultiArgs m) {
         else if (sig) V2W_WAIT_VM(ADMA + NSIG);
         else V2W_WAIT_VM(ADMA);
         // LDS reads in flight (next operands) need not drain before the barrier; the LDS WRITES of a commit must
-        if (COMMIT) V2W_BARRIER(); else asm volatile("s_barrier" ::: "memory");
+        if (COMMIT) v2w_lds_barrier(); else asm volatile("s_barrier" ::: "memory");
         ++st;
     };
     raw16 a0h[MI], a0l[BF ? 1 : MI], a1h[MI], a1l[BF ? 1 : MI];
@@ -498,7 +481,7 @@ int launch_split(const TileArgs* ps, int nprob, hipStream_t stream, bool bf) {
         p.vec4 = (p.L % 4 == 0) && p.L >= 4 && al16(p.in) && p.in_stride == 1;
         p.evec = (p.L % 4 == 0) && al16(p.out) && al16(p.res) && al16(p.add0) && al16(p.add1) && al16(p.mask_src);
         const size_t rawb = ((size_t)CK * (p.xcols / 4) * 16 + 1023) & ~(size_t)1023;
-        size_t l = (size_t)2 * p.xcols * V2W_SPLIT_ROWB + (size_t)V2W_SPLIT_NAB * (MT / 32) * V2W_SPLIT_UNIT + rawb;
+        size_t l = (size_t)2 * p.xcols * V2W_SPLIT_ROWB + (size_t)V2W_SPLIT_NAB * (MT / 32) * V2W_FRAG_UNIT + rawb;
         const size_t tl = ((size_t)4 * 32 * RS + 5 * MT) * sizeof(float);   // epilogue: transpose tiles + constants overlay the stage buffers
         if (tl > l) l = tl;
         p.atab_off = (int)l;

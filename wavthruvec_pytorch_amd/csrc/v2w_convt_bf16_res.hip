@@ -26,12 +26,6 @@
 
 namespace {
 
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-#define V2W_CT_UNIT 2048
-
 struct CtArgs {
     const unsigned short* in; const unsigned char* wps; const float* bias; unsigned short* out; float* stats_part;
     int B, Cin, CoutR, L;      // CoutR: real output channels; the kernel's rows are CoutR * UP
@@ -39,30 +33,6 @@ struct CtArgs {
     int hla, xrows, ntl, ntiles;
     float slope;
 };
-
-__device__ __forceinline__ unsigned int ct_pack2(float lo, float hi) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    b2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned int, v);
-}
-__device__ __forceinline__ float ct_lo(unsigned int w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float ct_hi(unsigned int w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-__device__ __forceinline__ int ct_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-template <int CTRL> __device__ __forceinline__ float ct_dpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float ct_readlane(float v, int l) {           // (the builtin is typed int: a float argument would be CONVERTED)
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-// sum over the 16 lanes of a DPP row, in every lane of the row (fixed order): quad xor 1, quad xor 2, half mirror, mirror
-__device__ __forceinline__ float ct_row_sum(float v) {
-    v += ct_dpp<0xB1>(v);
-    v += ct_dpp<0x4E>(v);
-    v += ct_dpp<0x141>(v);
-    v += ct_dpp<0x140>(v);
-    return v;
-}
 
 // workgroups (of 4 waves) per CU the register budget is cut for
 constexpr int ct_wgs(int mi, int ni) { return mi * ni >= 8 ? 2 : (mi * ni >= 4 ? 3 : 4); }
@@ -81,8 +51,8 @@ convt_bf16_res_kernel(const CtArgs a) {
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_c[];
 
-    const int Cin = ct_uni(a.Cin), L = ct_uni(a.L), xrows = ct_uni(a.xrows), hla = ct_uni(a.hla), KV = ct_uni(a.KV);
-    const int CoutR = ct_uni(a.CoutR);
+    const int Cin = v2w_uni(a.Cin), L = v2w_uni(a.L), xrows = v2w_uni(a.xrows), hla = v2w_uni(a.hla), KV = v2w_uni(a.KV);
+    const int CoutR = v2w_uni(a.CoutR);
     const int nch = Cin >> 5, psz = xrows * 64;
     // bias of this M-tile's channels [MT / UP]: behind the tile - and behind the waves' scratch of the U = 5 epilogue, which reads it (a tile
     // of few input channels is smaller than that scratch)
@@ -102,7 +72,7 @@ convt_bf16_res_kernel(const CtArgs a) {
     const int m0 = mt * MT;
 
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = ct_uni(tid >> 6);
+    const int wave = v2w_uni(tid >> 6);
     const int lr = lane & 31, hk = lane >> 5;
     const int wm0 = (wave / WN) * (32 * MI);
     const int wn0 = (wave % WN) * (32 * NI);
@@ -146,10 +116,10 @@ convt_bf16_res_kernel(const CtArgs a) {
                     float v[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        const float xv = (e & 1) ? ct_hi(pf[s][i][e >> 1]) : ct_lo(pf[s][i][e >> 1]);
+                        const float xv = (e & 1) ? v2w_bf16_hi(pf[s][i][e >> 1]) : v2w_bf16_lo(pf[s][i][e >> 1]);
                         v[i] = fmaxf(xv, xv * slope);
                     }
-                    u32x2 w = {ct_pack2(v[0], v[1]), ct_pack2(v[2], v[3])};
+                    u32x2 w = {v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
                     if (!in_seq[s]) w = u32x2{0u, 0u};
                     *reinterpret_cast<u32x2*>(dst + e * 64) = w;
                 }
@@ -196,7 +166,7 @@ convt_bf16_res_kernel(const CtArgs a) {
         const int nst = 2 * nch * K;
         const unsigned char* ap[MI];
 #pragma unroll
-        for (int i = 0; i < MI; ++i) ap[i] = a.wps + (size_t)((m0 + wm0) / 32 + i) * nst * V2W_CT_UNIT;
+        for (int i = 0; i < MI; ++i) ap[i] = a.wps + (size_t)((m0 + wm0) / 32 + i) * nst * V2W_FRAG_UNIT;
         constexpr int RD = 2;                                                   // taps of weight fragments in flight (2 k-steps each)
         u32x4 ar[2 * RD][MI];
         auto load_frag = [&](u32x4 (&av)[MI], int ch, int s, int t) {
@@ -205,7 +175,7 @@ convt_bf16_res_kernel(const CtArgs a) {
             const int chc = ch < nch ? ch : nch - 1;
 #pragma unroll
             for (int i = 0; i < MI; ++i)
-                av[i] = *gptr<const u32x4>(ap[i] + (size_t)((2 * chc + s) * K + t) * V2W_CT_UNIT + l16);
+                av[i] = *gptr<const u32x4>(ap[i] + (size_t)((2 * chc + s) * K + t) * V2W_FRAG_UNIT + l16);
         };
 #pragma unroll
         for (int d = 0; d < RD; ++d) {
@@ -217,7 +187,7 @@ convt_bf16_res_kernel(const CtArgs a) {
         __builtin_amdgcn_sched_barrier(0);
         int ch = 0, t = 0, qc = 0, qt = RD;
         while (qt >= K) { qt -= K; ++qc; }
-        const int r0 = hla - ct_uni(a.hl) + wn0 + lr;
+        const int r0 = hla - v2w_uni(a.hl) + wn0 + lr;
         unsigned xt = baddr(0, r0);
         u32x4 bb[2][NI];
 #pragma unroll
@@ -294,7 +264,7 @@ convt_bf16_res_kernel(const CtArgs a) {
                     const int idx = lane + 64 * g;
                     const int c = idx / 40, q4 = idx - 40 * c;
                     const f32x4 v = *reinterpret_cast<const f32x4*>(scr + 4 * idx);
-                    *gptr<u32x2>(ob0 + ub + (unsigned)(c * Lout + 4 * q4) * 2u) = u32x2{ct_pack2(v[0], v[1]), ct_pack2(v[2], v[3])};
+                    *gptr<u32x2>(ob0 + ub + (unsigned)(c * Lout + 4 * q4) * 2u) = u32x2{v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
                 }
                 if (stats) {
                     const float* row = scr + cS * 160 + qS * 40;
@@ -359,7 +329,7 @@ convt_bf16_res_kernel(const CtArgs a) {
                     const float bias = btab[(wm0 / UP) + CPB * i + cl];
                     v += f32x4{bias, bias, bias, bias};
                     if (stats) { sa[g] += v; sq[g] += v * v; }
-                    *gptr<u32x2>(ob0 + ub + (unsigned)(cl * Lout + 4 * c4) * 2u) = u32x2{ct_pack2(v[0], v[1]), ct_pack2(v[2], v[3])};
+                    *gptr<u32x2>(ob0 + ub + (unsigned)(cl * Lout + 4 * c4) * 2u) = u32x2{v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -409,11 +379,11 @@ convt_bf16_res_kernel(const CtArgs a) {
                 if (ok) {
                     const int c = cw0 + CPB * i + cl;
                     if constexpr (UP == 2) {
-                        *gptr<unsigned>(obase + (unsigned)(c * Lout + 2 * q) * 2u) = ct_pack2(v[0], v[1]);
-                        *gptr<unsigned>(obase + (unsigned)((c + 1) * Lout + 2 * q) * 2u) = ct_pack2(v[2], v[3]);
+                        *gptr<unsigned>(obase + (unsigned)(c * Lout + 2 * q) * 2u) = v2w_bf16x2(v[0], v[1]);
+                        *gptr<unsigned>(obase + (unsigned)((c + 1) * Lout + 2 * q) * 2u) = v2w_bf16x2(v[2], v[3]);
                     } else {
                         const int o = UP == 4 ? 4 * q : 8 * q + 4 * hk;
-                        *gptr<u32x2>(obase + (unsigned)(c * Lout + o) * 2u) = u32x2{ct_pack2(v[0], v[1]), ct_pack2(v[2], v[3])};
+                        *gptr<u32x2>(obase + (unsigned)(c * Lout + o) * 2u) = u32x2{v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
                     }
                 }
             }
@@ -422,11 +392,11 @@ convt_bf16_res_kernel(const CtArgs a) {
                 // rows of a half (and the halves) in a fixed order
 #pragma unroll
                 for (int n = 0; n < NC; ++n) {
-                    const float r1 = ct_row_sum(s1[n]), r2 = ct_row_sum(s2[n]);
-                    const float a1 = ct_readlane(r1, 0) + ct_readlane(r1, 16);
-                    const float b1 = ct_readlane(r1, 32) + ct_readlane(r1, 48);
-                    const float a2 = ct_readlane(r2, 0) + ct_readlane(r2, 16);
-                    const float b2 = ct_readlane(r2, 32) + ct_readlane(r2, 48);
+                    const float r1 = v2w_row16_sum(s1[n]), r2 = v2w_row16_sum(s2[n]);
+                    const float a1 = v2w_readlane(r1, 0) + v2w_readlane(r1, 16);
+                    const float b1 = v2w_readlane(r1, 32) + v2w_readlane(r1, 48);
+                    const float a2 = v2w_readlane(r2, 0) + v2w_readlane(r2, 16);
+                    const float b2 = v2w_readlane(r2, 32) + v2w_readlane(r2, 48);
                     float* rd = red + ((wave % WN) * (MT / UP) + (wm0 / UP) + CPB * i) * 2;
                     if constexpr (UP == 8) {
                         if (lane == 0) { rd[2 * g] = a1 + b1; rd[2 * g + 1] = a2 + b2; }
@@ -502,7 +472,7 @@ int v2w_convt1d_bf16_res(const v2w_convt1d_args* a, int UP, int hl, int KV, hipS
         // positions per workgroup; whole tiles, C_out in steps of 128
         if (a->C_out % 128 == 0 && a->L % 64 == 0 && a->C_in % 32 == 0) {
             CtArgs q = p;
-            q.wps = p.wps + (size_t)(a->C_out * 8 / 32) * (a->C_in / 16) * KV * V2W_CT_UNIT;
+            q.wps = p.wps + (size_t)(a->C_out * 8 / 32) * (a->C_in / 16) * KV * V2W_FRAG_UNIT;
             const int rc = launch_ct<5, 2, 4, 1, 5, 5>(q, stream, ntiles_out, cfg);
             if (rc != V2W_E_SHAPE) return rc;
         }

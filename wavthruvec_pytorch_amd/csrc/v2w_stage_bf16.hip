@@ -16,13 +16,8 @@
 
 namespace {
 
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 #define V2W_SB_MAXB 4
 #define V2W_SB_KMAX 11
-#define V2W_SB_UNIT 2048
 
 struct StageBfArgs {
     const float* in; const float* in_a; const float* in_s;
@@ -36,15 +31,6 @@ struct StageBfArgs {
     int vec4;
     float slope, out_div;
 };
-
-__device__ __forceinline__ unsigned int sb_pack2(float lo, float hi) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    b2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned int, v);
-}
-
-__device__ __forceinline__ float sb_lo(unsigned int w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float sb_hi(unsigned int w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
 
 // IO_BF: `in` and `out` are bf16 tensors (activation storage of BASELINE configs[2]); arithmetic stays fp32
 template <int C, bool IO_BF>
@@ -131,11 +117,11 @@ stage_bf16_kernel(const StageBfArgs p) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     float xv;
-                    if constexpr (IO_BF) xv = (e & 1) ? sb_hi(g[s][i][e >> 1]) : sb_lo(g[s][i][e >> 1]);
+                    if constexpr (IO_BF) xv = (e & 1) ? v2w_bf16_hi(g[s][i][e >> 1]) : v2w_bf16_lo(g[s][i][e >> 1]);
                     else xv = g[s][i][e];
                     a[i] = v2w_lrelu(fmaf(av[i], xv, sv[i]), slope);
                 }
-                u32x2 v = {sb_pack2(a[0], a[1]), sb_pack2(a[2], a[3])};
+                u32x2 v = {v2w_bf16x2(a[0], a[1]), v2w_bf16x2(a[2], a[3])};
                 if (!ok) v = u32x2{0u, 0u};
                 *reinterpret_cast<u32x2*>(Xa + (pq * 4 + e) * ROWB + cq * 8) = v;
                 if constexpr (IO_BF) {
@@ -163,7 +149,7 @@ stage_bf16_kernel(const StageBfArgs p) {
             float v = 0.f;
             if (pos >= 0 && pos < L) {
                 const int ch = b * C + c;
-                const float xv = IO_BF ? sb_lo(reinterpret_cast<const unsigned short*>(p.in)[(size_t)ch * L + pos]) : p.in[(size_t)ch * L + pos];
+                const float xv = IO_BF ? v2w_bf16_lo(reinterpret_cast<const unsigned short*>(p.in)[(size_t)ch * L + pos]) : p.in[(size_t)ch * L + pos];
                 v = v2w_lrelu(fmaf(p.in_a ? p.in_a[ch] : 1.f, xv, p.in_s ? p.in_s[ch] : 0.f), slope);
             }
             reinterpret_cast<__bf16*>(Xa + r * ROWB)[c] = (__bf16)v;
@@ -186,7 +172,7 @@ stage_bf16_kernel(const StageBfArgs p) {
                 const int ch = b * C + F::row(e, hk);
                 float v = 0.f;
                 if (in_seq) {
-                    const float xv = IO_BF ? sb_lo(reinterpret_cast<const unsigned short*>(p.in)[(size_t)ch * L + pos]) : p.in[(size_t)ch * L + pos];
+                    const float xv = IO_BF ? v2w_bf16_lo(reinterpret_cast<const unsigned short*>(p.in)[(size_t)ch * L + pos]) : p.in[(size_t)ch * L + pos];
                     v = fmaf(p.in_a ? p.in_a[ch] : 1.f, xv, p.in_s ? p.in_s[ch] : 0.f);
                 }
                 xres[j][e] = v;
@@ -210,7 +196,7 @@ stage_bf16_kernel(const StageBfArgs p) {
         for (int i = 0; i < NWL; ++i) {
             const int v = wave + 4 * i;                      // consumption-order index: tap v / KS, k-step v % KS
             const int vc = v < K * KS ? v : K * KS - 1;
-            wl[i] = *reinterpret_cast<const u32x4*>(wbase + (size_t)((vc % KS) * K + vc / KS) * V2W_SB_UNIT + l16);
+            wl[i] = *reinterpret_cast<const u32x4*>(wbase + (size_t)((vc % KS) * K + vc / KS) * V2W_FRAG_UNIT + l16);
         }
     };
     auto wstore = [&](int K) {
@@ -281,10 +267,10 @@ stage_bf16_kernel(const StageBfArgs p) {
                 const u32x2 raw = *reinterpret_cast<const u32x2*>(row + 2 * (8 * g4 + 4 * hk));
                 const f32x4 a4 = *reinterpret_cast<const f32x4*>(atab + 8 * g4 + 4 * hk);
                 const f32x4 s4 = *reinterpret_cast<const f32x4*>(atab + C + 8 * g4 + 4 * hk);
-                xres[j][4 * g4 + 0] = in_seq ? fmaf(a4[0], sb_lo(raw[0]), s4[0]) : 0.f;
-                xres[j][4 * g4 + 1] = in_seq ? fmaf(a4[1], sb_hi(raw[0]), s4[1]) : 0.f;
-                xres[j][4 * g4 + 2] = in_seq ? fmaf(a4[2], sb_lo(raw[1]), s4[2]) : 0.f;
-                xres[j][4 * g4 + 3] = in_seq ? fmaf(a4[3], sb_hi(raw[1]), s4[3]) : 0.f;
+                xres[j][4 * g4 + 0] = in_seq ? fmaf(a4[0], v2w_bf16_lo(raw[0]), s4[0]) : 0.f;
+                xres[j][4 * g4 + 1] = in_seq ? fmaf(a4[1], v2w_bf16_hi(raw[0]), s4[1]) : 0.f;
+                xres[j][4 * g4 + 2] = in_seq ? fmaf(a4[2], v2w_bf16_lo(raw[1]), s4[2]) : 0.f;
+                xres[j][4 * g4 + 3] = in_seq ? fmaf(a4[3], v2w_bf16_hi(raw[1]), s4[3]) : 0.f;
             }
         }
     }
@@ -314,7 +300,7 @@ stage_bf16_kernel(const StageBfArgs p) {
                 float a[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) a[r] = v2w_lrelu(t1r[j][4 * g4 + r], slope);
-                *reinterpret_cast<u32x2*>(row + 2 * (8 * g4 + 4 * hk)) = u32x2{sb_pack2(a[0], a[1]), sb_pack2(a[2], a[3])};
+                *reinterpret_cast<u32x2*>(row + 2 * (8 * g4 + 4 * hk)) = u32x2{v2w_bf16x2(a[0], a[1]), v2w_bf16x2(a[2], a[3])};
             }
         }
         wstore(K);                                           // (every wave is past conv1_j: the barrier above)
@@ -371,7 +357,7 @@ stage_bf16_kernel(const StageBfArgs p) {
             if constexpr (IO_BF) {
                 unsigned short* dst = reinterpret_cast<unsigned short*>(p.out) + doff;
                 if (p.vec4) {
-                    *reinterpret_cast<u32x2*>(dst) = u32x2{sb_pack2(v[0], v[1]), sb_pack2(v[2], v[3])};
+                    *reinterpret_cast<u32x2*>(dst) = u32x2{v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
                 } else {
 #pragma unroll
                     for (int x = 0; x < 4; ++x)

@@ -21,10 +21,6 @@
 
 namespace {
 
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 struct N16Args {
     const unsigned short* in; const float* in_a; const float* in_s;
     const unsigned char* w1[3]; const float* bias1[3];
@@ -39,20 +35,6 @@ struct N16Args {
     float post_slope;
     int nadv, hout;
 };
-
-__device__ __forceinline__ unsigned int n16_pack2(float lo, float hi) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    b2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned int, v);
-}
-__device__ __forceinline__ float n16_lo(unsigned int w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float n16_hi(unsigned int w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-
-template <int... I, class F> __device__ __forceinline__ void n16_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
-
-// Workgroup barrier for LDS hand-overs only: __syncthreads() also fences global memory - a wave that has just issued its tile's output
-// stores would wait vmcnt(0) (the stores' acknowledgement, thousands of cycles under load) before it may even arrive at the barrier.
-__device__ __forceinline__ void n16_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 constexpr int N16_H1 = 5, N16_H2 = 15;           // halos of the widest branch: 11 taps at dilation 1 / 3
 constexpr int N16_NB = 8;                        // 16-column blocks per wave (128 columns)
@@ -87,7 +69,7 @@ n16_stage_kernel(const N16Args a) {
                 if (2 * p >= K) break;
                 const int t = 2 * p + (kg >> 1);
                 u32x4 v = {0u, 0u, 0u, 0u};
-                if (t < K) v = *reinterpret_cast<const u32x4*>(w + (size_t)t * 2048 + lo16);
+                if (t < K) v = *reinterpret_cast<const u32x4*>(w + (size_t)t * V2W_FRAG_UNIT + lo16);
                 wa[s][p0 + p] = v;
             }
         };
@@ -128,12 +110,12 @@ n16_stage_kernel(const N16Args a) {
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         // (the zero tap past the end reads the last real tap's rows: finite values under zero weights)
-        n16_for(std::make_integer_sequence<int, RING>{}, [&ring, &ab, &ab2](auto n_c) {
+        v2w_static_for(std::make_integer_sequence<int, RING>{}, [&ring, &ab, &ab2](auto n_c) {
             constexpr int n = decltype(n_c)::value, p = n / NB, cb = n % NB;
             if constexpr (2 * p + 1 >= K) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[n]) : "v"(ab), "n"((2 * p * DIL + 16 * cb) * RB));
             else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[n]) : "v"(ab2), "n"((2 * p * DIL + 16 * cb) * RB));
         });
-        n16_for(std::make_integer_sequence<int, N>{}, [&ring, &ab, &ab2, &acc, &wa, &mfma](auto n_c) {
+        v2w_static_for(std::make_integer_sequence<int, N>{}, [&ring, &ab, &ab2, &acc, &wa, &mfma](auto n_c) {
             constexpr int n = decltype(n_c)::value;
             constexpr int left = (N - 1 - n) < (RING - 1) ? (N - 1 - n) : (RING - 1);
             asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(ring[n % RING]) : "n"(left));
@@ -186,12 +168,12 @@ n16_stage_kernel(const N16Args a) {
                 float y[4], v[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float xv = (e & 1) ? n16_hi(pf[s][i][e >> 1]) : n16_lo(pf[s][i][e >> 1]);
+                    const float xv = (e & 1) ? v2w_bf16_hi(pf[s][i][e >> 1]) : v2w_bf16_lo(pf[s][i][e >> 1]);
                     y[i] = fmaf(av[i], xv, sv[i]);
                     v[i] = fmaxf(y[i], y[i] * slope);
                 }
-                u32x2 w = {n16_pack2(v[0], v[1]), n16_pack2(v[2], v[3])};
-                u32x2 r = {n16_pack2(y[0], y[1]), n16_pack2(y[2], y[3])};
+                u32x2 w = {v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
+                u32x2 r = {v2w_bf16x2(y[0], y[1]), v2w_bf16x2(y[2], y[3])};
                 if (!ok) { w = u32x2{0u, 0u}; r = w; }                          // the padding of the ACTIVATED signal is exactly 0
                 *reinterpret_cast<u32x2*>(dst + e * RB) = w;
                 *reinterpret_cast<u32x2*>(dst + e * RB + RT) = r;
@@ -209,11 +191,11 @@ n16_stage_kernel(const N16Args a) {
         const int b = tile / a.ntl, n0 = (tile - b * a.ntl) * a.nadv - a.hout;
         // a tile whose window and halo lie inside the sequence needs no per-position checks in the epilogues
         const bool edge = n0 - N16_H2 < 0 || n0 - N16_H2 + W > L;
-        n16_lds_barrier();                                                        // the previous tile's stores have read the scratch
+        v2w_lds_barrier();                                                        // the previous tile's stores have read the scratch
         V2W_STAMP(0);
         commit_x(n0 - N16_H1 - N16_H2);                                         // (position of x row 0: a multiple of 4)
         V2W_STAMP(1);
-        n16_lds_barrier();
+        v2w_lds_barrier();
         V2W_STAMP(2);
 
         f32x4 oacc[NB];
@@ -229,7 +211,7 @@ n16_stage_kernel(const N16Args a) {
             // conv1_j: window column col <-> x row col + 5
             conv(k_c, std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{}, p_c, acc1, XB, col0 + N16_H1 - h1);
             V2W_STAMP(3 + 5 * JB);
-            n16_lds_barrier();                                                    // conv2 of the previous branch has read the t1 tile
+            v2w_lds_barrier();                                                    // conv2 of the previous branch has read the t1 tile
             V2W_STAMP(4 + 5 * JB);
             // t1 = acc + x (the r tile); the running output takes t1 in fp32, the t1 tile lrelu(t1) as bf16.  Registers 0 .. 3 of block cb
             // <-> channels 4 kg .. 4 kg + 3 at column 16 cb + j of this wave
@@ -242,7 +224,7 @@ n16_stage_kernel(const N16Args a) {
             for (int cb = 0; cb < NB; ++cb) {
                 const int col = colv + 16 * cb;
                 const u32x2 w = rw[cb];
-                const f32x4 xr = {n16_lo(w[0]), n16_hi(w[0]), n16_lo(w[1]), n16_hi(w[1])};
+                const f32x4 xr = {v2w_bf16_lo(w[0]), v2w_bf16_hi(w[0]), v2w_bf16_lo(w[1]), v2w_bf16_hi(w[1])};
                 f32x4 t1v = acc1[cb] + xr;                                      // (vector forms: v_pk_add_f32 / v_pk_mul_f32)
                 if (edge) {                                                     // conv2 zero-pads t1 outside the sequence
                     const int pos = n0 - N16_H2 + col;
@@ -252,10 +234,10 @@ n16_stage_kernel(const N16Args a) {
                 const f32x4 ts = t1v * slope;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) t1v[r] = fmaxf(t1v[r], ts[r]);
-                *reinterpret_cast<u32x2*>(smem_n + TB + col * RB + 8 * kg) = u32x2{n16_pack2(t1v[0], t1v[1]), n16_pack2(t1v[2], t1v[3])};
+                *reinterpret_cast<u32x2*>(smem_n + TB + col * RB + 8 * kg) = u32x2{v2w_bf16x2(t1v[0], t1v[1]), v2w_bf16x2(t1v[2], t1v[3])};
             }
             V2W_STAMP(5 + 5 * JB);
-            n16_lds_barrier();
+            v2w_lds_barrier();
             V2W_STAMP(6 + 5 * JB);
             // conv2_j on the same window (taps that reach past the t1 tile read the x tile / the slack behind it: columns that are never stored)
             conv(k_c, std::integral_constant<int, 3>{}, std::integral_constant<int, 1>{}, p_c, oacc, TB, col0 - h2);
@@ -267,7 +249,7 @@ n16_stage_kernel(const N16Args a) {
 
         // ---- the nto valid columns (window columns 15 .. 15 + nto) through an fp32 scratch [16][SRS] over the dead tiles: scratch column
         // = window column + 1 (output quads 16-byte aligned), then 8-byte bf16 stores along positions
-        n16_lds_barrier();
+        v2w_lds_barrier();
         V2W_STAMP(18);
         {
             float* const scr = reinterpret_cast<float*>(smem_n);
@@ -298,7 +280,7 @@ n16_stage_kernel(const N16Args a) {
                 for (int r = 0; r < 4; ++r) scr[(4 * kg + r) * SRS + col + 1] = oacc[cb][r];
             }
             }
-            n16_lds_barrier();
+            v2w_lds_barrier();
             V2W_STAMP(19);
             // the next tile's x: in flight under this tile's stores (unconditional - past the end the last tile again, never committed: under
             // a condition the old values would stay live through the whole iteration as the other input of the join)
@@ -334,7 +316,7 @@ n16_stage_kernel(const N16Args a) {
                     }
                     if (hf == 1) *reinterpret_cast<f32x4*>(part + 4 * q) = y;
                 }
-                n16_lds_barrier();
+                v2w_lds_barrier();
                 if (act && hf == 0) {
                     const int p0 = n0 + a.hout + 4 * q;
                     if (p0 < L) {
@@ -359,7 +341,7 @@ n16_stage_kernel(const N16Args a) {
 #pragma unroll
                     for (int x = 0; x < 4; ++x) v[x] = v2w_div_by(v[x], a.out_div, dinv);
                 }
-                *gptr<u32x2>(obase + (unsigned)(row * L + pos) * 2u) = u32x2{n16_pack2(v[0], v[1]), n16_pack2(v[2], v[3])};
+                *gptr<u32x2>(obase + (unsigned)(row * L + pos) * 2u) = u32x2{v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
             }
             }     // (!POST)
         }
@@ -447,7 +429,7 @@ n16_pair_kernel(const N16PairArgs a) {
             for (int p = 0; p < NP; ++p) {
                 const int t = 2 * p + (kg >> 1);
                 u32x4 v = {0u, 0u, 0u, 0u};
-                if (t < K) v = *reinterpret_cast<const u32x4*>(w + (size_t)t * 2048 + lo16);
+                if (t < K) v = *reinterpret_cast<const u32x4*>(w + (size_t)t * V2W_FRAG_UNIT + lo16);
                 wa[s][p] = v;
             }
         }
@@ -473,12 +455,12 @@ n16_pair_kernel(const N16PairArgs a) {
         u32x4 ring[RING];
         __builtin_amdgcn_sched_barrier(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        n16_for(std::make_integer_sequence<int, RING>{}, [&ring, &ab, &ab2](auto n_c) {
+        v2w_static_for(std::make_integer_sequence<int, RING>{}, [&ring, &ab, &ab2](auto n_c) {
             constexpr int n = decltype(n_c)::value, p = n / NB, cb = n % NB;
             if constexpr (2 * p + 1 >= K) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[n]) : "v"(ab), "n"((2 * p * DIL + 16 * cb) * RB));
             else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[n]) : "v"(ab2), "n"((2 * p * DIL + 16 * cb) * RB));
         });
-        n16_for(std::make_integer_sequence<int, N>{}, [&ring, &ab, &ab2, &acc, &wa, &mfma](auto n_c) {
+        v2w_static_for(std::make_integer_sequence<int, N>{}, [&ring, &ab, &ab2, &acc, &wa, &mfma](auto n_c) {
             constexpr int n = decltype(n_c)::value;
             constexpr int left = (N - 1 - n) < (RING - 1) ? (N - 1 - n) : (RING - 1);
             asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(ring[n % RING]) : "n"(left));
@@ -528,12 +510,12 @@ n16_pair_kernel(const N16PairArgs a) {
                 float y[4], v[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float xv = (e & 1) ? n16_hi(pf[s][i][e >> 1]) : n16_lo(pf[s][i][e >> 1]);
+                    const float xv = (e & 1) ? v2w_bf16_hi(pf[s][i][e >> 1]) : v2w_bf16_lo(pf[s][i][e >> 1]);
                     y[i] = fmaf(av[i], xv, sv[i]);
                     v[i] = fmaxf(y[i], y[i] * slope);
                 }
-                u32x2 w = {n16_pack2(v[0], v[1]), n16_pack2(v[2], v[3])};
-                u32x2 r = {n16_pack2(y[0], y[1]), n16_pack2(y[2], y[3])};
+                u32x2 w = {v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
+                u32x2 r = {v2w_bf16x2(y[0], y[1]), v2w_bf16x2(y[2], y[3])};
                 if (!ok) { w = u32x2{0u, 0u}; r = w; }
                 *reinterpret_cast<u32x2*>(dst + e * RB) = w;
                 *reinterpret_cast<u32x2*>(dst + e * RB + RT) = r;
@@ -545,9 +527,9 @@ n16_pair_kernel(const N16PairArgs a) {
     for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
         const int b = tile / a.ntl, n0 = (tile - b * a.ntl) * nto;
         const bool edge = n0 - H2 < 0 || n0 - H2 + W > L;
-        n16_lds_barrier();                                                        // the previous tile's stores have read the scratch
+        v2w_lds_barrier();                                                        // the previous tile's stores have read the scratch
         commit_x(n0 - H1 - H2 - XOFF);
-        n16_lds_barrier();
+        v2w_lds_barrier();
 
         f32x4 acc[NB];
 #pragma unroll
@@ -569,10 +551,10 @@ n16_pair_kernel(const N16PairArgs a) {
                 const f32x4 us = u * slope;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) u[r] = fmaxf(u[r], us[r]);
-                *reinterpret_cast<u32x2*>(smem_n + TB + col * RB + 8 * kg) = u32x2{n16_pack2(u[0], u[1]), n16_pack2(u[2], u[3])};
+                *reinterpret_cast<u32x2*>(smem_n + TB + col * RB + 8 * kg) = u32x2{v2w_bf16x2(u[0], u[1]), v2w_bf16x2(u[2], u[3])};
             }
         }
-        n16_lds_barrier();
+        v2w_lds_barrier();
         // conv_b (dilation 1) on the same window + the pair's residual x (the r tile) + b2
         {
             u32x2 rw[NB];
@@ -582,12 +564,12 @@ n16_pair_kernel(const N16PairArgs a) {
             for (int cb = 0; cb < NB; ++cb) rw[cb] = *reinterpret_cast<const u32x2*>(smem_n + RT + (colv + 16 * cb + H1 + XOFF) * RB + 8 * kg);
 #pragma unroll
             for (int cb = 0; cb < NB; ++cb)
-                acc[cb] = f32x4{b2[0], b2[1], b2[2], b2[3]} + f32x4{n16_lo(rw[cb][0]), n16_hi(rw[cb][0]), n16_lo(rw[cb][1]), n16_hi(rw[cb][1])};
+                acc[cb] = f32x4{b2[0], b2[1], b2[2], b2[3]} + f32x4{v2w_bf16_lo(rw[cb][0]), v2w_bf16_hi(rw[cb][0]), v2w_bf16_lo(rw[cb][1]), v2w_bf16_hi(rw[cb][1])};
         }
         conv(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}, acc, TB, col0 - H2);
 
         // ---- the nto valid columns (window columns H2 .. H2 + nto) through the fp32 scratch [16][SRS] over the dead tiles, then 8-byte bf16 stores
-        n16_lds_barrier();
+        v2w_lds_barrier();
         {
             float* const scr = reinterpret_cast<float*>(smem_n);
 #pragma unroll
@@ -598,7 +580,7 @@ n16_pair_kernel(const N16PairArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) scr[(4 * kg + r) * SRS + col + SOFF] = acc[cb][r];
             }
-            n16_lds_barrier();
+            v2w_lds_barrier();
             issue_x(min(tile + (int)gridDim.x, a.ntiles - 1));                    // the next tile's x: in flight under this tile's stores
             const int nq = nto >> 2;
             const unsigned magic = (unsigned)(((1ull << 32) + nq - 1) / nq);
@@ -613,10 +595,10 @@ n16_pair_kernel(const N16PairArgs a) {
                 const unsigned eo = (unsigned)(row * L + pos) * 2u;
                 if (a.add0) {                                                     // ((add0 + add1) + value): the reference's order over the branches
                     const u32x2 p0 = *gptr<const u32x2>(reinterpret_cast<const unsigned char*>(a.add0) + boff + eo);
-                    f32x4 s = {n16_lo(p0[0]), n16_hi(p0[0]), n16_lo(p0[1]), n16_hi(p0[1])};
+                    f32x4 s = {v2w_bf16_lo(p0[0]), v2w_bf16_hi(p0[0]), v2w_bf16_lo(p0[1]), v2w_bf16_hi(p0[1])};
                     if (a.add1) {
                         const u32x2 p1 = *gptr<const u32x2>(reinterpret_cast<const unsigned char*>(a.add1) + boff + eo);
-                        s += f32x4{n16_lo(p1[0]), n16_hi(p1[0]), n16_lo(p1[1]), n16_hi(p1[1])};
+                        s += f32x4{v2w_bf16_lo(p1[0]), v2w_bf16_hi(p1[0]), v2w_bf16_lo(p1[1]), v2w_bf16_hi(p1[1])};
                     }
                     v = s + v;
                 }
@@ -624,7 +606,7 @@ n16_pair_kernel(const N16PairArgs a) {
 #pragma unroll
                     for (int x = 0; x < 4; ++x) v[x] = v2w_div_by(v[x], a.out_div, dinv);
                 }
-                *gptr<u32x2>(obase + eo) = u32x2{n16_pack2(v[0], v[1]), n16_pack2(v[2], v[3])};
+                *gptr<u32x2>(obase + eo) = u32x2{v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
             }
         }
     }

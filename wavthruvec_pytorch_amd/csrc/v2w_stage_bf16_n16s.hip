@@ -29,10 +29,6 @@
 
 namespace {
 
-typedef __bf16 sb8 __attribute__((ext_vector_type(8)));
-typedef unsigned int su32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int su32x4 __attribute__((ext_vector_type(4)));
-
 struct N16SArgs {
     const unsigned short* in; const float* in_a; const float* in_s;
     const unsigned char* w1[3]; const float* bias1[3];
@@ -46,24 +42,6 @@ constexpr int S_BLK = 256;                                               // one 
 constexpr int S_XP = 10 * S_BLK, S_RP = 8 * S_BLK, S_TP = 6 * S_BLK;     // plane strides: x ring (8 + 2 mirrors), raw-x ring (8), t1 / z rings (4 + 2)
 constexpr int S_XOFF = 0, S_ROFF = S_XOFF + 2 * S_XP, S_TOFF = S_ROFF + 2 * S_RP, S_ZOFF = S_TOFF + 6 * S_TP, S_LDS = S_ZOFF + 2 * S_TP;
 static_assert(S_LDS == 21504, "seven waves per CU");
-
-__device__ __forceinline__ unsigned int s_pack2(float lo, float hi) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    b2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned int, v);
-}
-__device__ __forceinline__ float s_lo(unsigned int w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float s_hi(unsigned int w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-
-// max(v, w) as ONE instruction: fmaxf(v, w) costs two here - hipcc first canonicalises an operand that comes out of an MFMA with v_max_f32(v, v)
-__device__ __forceinline__ float s_max(float v, float w) { float t; asm("v_max_f32 %0, %1, %2" : "=v"(t) : "v"(v), "v"(w)); return t; }
-// scalar-form multiplies and adds beside MFMAs: left to -O3 these are SLP-packed into v_pk_mul_f32 / v_pk_add_f32, which issue at well under half the
-// rate of two plain instructions next to matrix work (MI355X guide, 'price of one filler beside MFMAs')
-__device__ __forceinline__ float s_mul(float v, float w) { float t; asm("v_mul_f32 %0, %1, %2" : "=v"(t) : "v"(v), "v"(w)); return t; }
-__device__ __forceinline__ float s_fma(float a, float b, float c) { float t; asm("v_fma_f32 %0, %1, %2, %3" : "=v"(t) : "v"(a), "v"(b), "v"(c)); return t; }
-__device__ __forceinline__ float s_add(float v, float w) { float t; asm("v_add_f32 %0, %1, %2" : "=v"(t) : "v"(v), "v"(w)); return t; }
-
-template <int... I, class F> __device__ __forceinline__ void s_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
 
 // ---- the operand reads and MFMAs of one step, as tables (I = step number mod 4: every ring slot of the step is a compile-time constant)
 struct SRd { int base, imm; };              // base register: 0 conv1 pairs (x ring), 1 conv1 pair 5 (x ring | raw-x ring), 2 conv2 pairs (slot 1: + 3 rows),
@@ -119,18 +97,18 @@ n16s_stage_kernel(const N16SArgs a) {
 
     // ---- every weight of the stage and of the tail into registers (116 of them).  Fragment of tap t (v2w_pack_bf16, 2 KiB): lane' = row + 32 h'
     // holds the input channels 8 h' .. 8 h' + 7 of output channel `row`; this lane is output channel j, k-group kg = (tap slot sl, channel half h).
-    su32x4 W[S_NW];
+    u32x4 W[S_NW];
     {
         const unsigned lo16 = (unsigned)(j + 32 * h) * 16u;
         auto frag = [&](const unsigned char* w, int t, int K) {
-            su32x4 v = {0u, 0u, 0u, 0u};
-            if (t < K) v = *reinterpret_cast<const su32x4*>(w + (size_t)t * 2048 + lo16);
+            u32x4 v = {0u, 0u, 0u, 0u};
+            if (t < K) v = *reinterpret_cast<const u32x4*>(w + (size_t)t * V2W_FRAG_UNIT + lo16);
             return v;
         };
-        su32x4 ident;                                                           // element e of this lane: input channel 8 h + e against output channel j
+        u32x4 ident;                                                           // element e of this lane: input channel 8 h + e against output channel j
 #pragma unroll
         for (int wd = 0; wd < 4; ++wd) ident[wd] = (8 * h + 2 * wd == j ? 0x3f80u : 0u) | (8 * h + 2 * wd + 1 == j ? 0x3f800000u : 0u);
-        const su32x4 zero4 = {0u, 0u, 0u, 0u};
+        const u32x4 zero4 = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int p = 0; p < 6; ++p) W[S_W11 + p] = frag(a.w1[2], 2 * p + sl, 11);
         if (sl) W[S_W11 + 5] = ident;
@@ -149,14 +127,14 @@ n16s_stage_kernel(const N16SArgs a) {
         const float dinv = a.out_div != 0.f ? 1.f / a.out_div : 1.f;
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            su32x4 v = zero4;
+            u32x4 v = zero4;
             const int t = 2 * p + sl;
             if (t < 7 && j < 2) {
 #pragma unroll
                 for (int wd = 0; wd < 4; ++wd) {
                     float f0 = a.post_w[t * 16 + 8 * h + 2 * wd] * dinv, f1 = a.post_w[t * 16 + 8 * h + 2 * wd + 1] * dinv;
                     if (j == 1) { f0 -= (float)(__bf16)f0; f1 -= (float)(__bf16)f1; }
-                    v[wd] = s_pack2(f0, f1);
+                    v[wd] = v2w_bf16x2(f0, f1);
                 }
             }
             W[S_WP + p] = v;
@@ -192,11 +170,11 @@ n16s_stage_kernel(const N16SArgs a) {
     unsigned char* const stx = smem_s + S_XOFF + (cq >> 1) * S_XP + (4 * (cpos & 3)) * 16 + (cq & 1) * 8 + S_BLK;
     unsigned char* const str = smem_s + S_ROFF + (cq >> 1) * S_RP + (4 * (cpos & 3)) * 16 + (cq & 1) * 8;
 
-    auto mfma = [](f32x4 c, su32x4 av, su32x4 bv) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(sb8, av), __builtin_bit_cast(sb8, bv), c, 0, 0, 0);
+    auto mfma = [](f32x4 c, u32x4 av, u32x4 bv) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, av), __builtin_bit_cast(b8, bv), c, 0, 0, 0);
     };
 
-    su32x2 pf[4];
+    u32x2 pf[4];
     float av[4], sv[4];
     f32x4 ts[2] = {b2s, b2s};                                                   // running sums of the t1_j of the blocks s - 1 and s - 2 (+ the b2_j)
 
@@ -217,7 +195,7 @@ n16s_stage_kernel(const N16SArgs a) {
             unsigned vo = (unsigned)(4 * cq * L + (ok ? pos : 0)) * 2u;
             asm volatile("" : "+v"(vo));
 #pragma unroll
-            for (int i = 0; i < 4; ++i) pf[i] = *gptr<const su32x2>(inb + (size_t)i * L * 2 + vo);
+            for (int i = 0; i < 4; ++i) pf[i] = *gptr<const u32x2>(inb + (size_t)i * L * 2 + vo);
         };
         // rows of the x ring: lrelu(x) (the conv operand); rows of the raw-x ring: x itself (the residual); bf16, exactly 0 outside the sequence
         auto commit_x = [&](int k) {
@@ -233,16 +211,16 @@ n16s_stage_kernel(const N16SArgs a) {
                 float y[4], v[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float xv = (e & 1) ? s_hi(pf[i][e >> 1]) : s_lo(pf[i][e >> 1]);
-                    y[i] = s_fma(av[i], xv, sv[i]);
-                    v[i] = s_max(y[i], s_mul(y[i], slope));
+                    const float xv = (e & 1) ? v2w_bf16_hi(pf[i][e >> 1]) : v2w_bf16_lo(pf[i][e >> 1]);
+                    y[i] = v2w_fma(av[i], xv, sv[i]);
+                    v[i] = v2w_max(y[i], v2w_mul(y[i], slope));
                 }
-                su32x2 w = {s_pack2(v[0], v[1]), s_pack2(v[2], v[3])};
-                su32x2 r = {s_pack2(y[0], y[1]), s_pack2(y[2], y[3])};
-                if (!ok) { w = su32x2{0u, 0u}; r = w; }
-                *reinterpret_cast<su32x2*>(dx + e * 16) = w;
-                *reinterpret_cast<su32x2*>(dr + e * 16) = r;
-                if (mir != 0) *reinterpret_cast<su32x2*>(dx + e * 16 + mir) = w;
+                u32x2 w = {v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
+                u32x2 r = {v2w_bf16x2(y[0], y[1]), v2w_bf16x2(y[2], y[3])};
+                if (!ok) { w = u32x2{0u, 0u}; r = w; }
+                *reinterpret_cast<u32x2*>(dx + e * 16) = w;
+                *reinterpret_cast<u32x2*>(dr + e * 16) = r;
+                if (mir != 0) *reinterpret_cast<u32x2*>(dx + e * 16 + mir) = w;
             }
         };
 
@@ -260,7 +238,7 @@ n16s_stage_kernel(const N16SArgs a) {
             S_STAMP(0);
             f32x4 acc[5];
             const f32x4 init[5] = {b1v[0], b1v[1], b1v[2], ts[I & 1], f32x4{0.f, 0.f, 0.f, 0.f}};
-            su32x4 ring[RING];
+            u32x4 ring[RING];
             __builtin_amdgcn_sched_barrier(0);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             auto rd = [&ring, &bx0, &bx1, &bt2, &bt3, &bt4](auto n_c) __attribute__((always_inline)) {
@@ -274,8 +252,8 @@ n16s_stage_kernel(const N16SArgs a) {
                 else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[n % RING]) : "v"(bt4), "n"(imm));
             };
             S_STAMP(1);
-            s_for(std::make_integer_sequence<int, RING>{}, rd);
-            s_for(std::make_integer_sequence<int, S_NM>{}, [&ring, &acc, &init, &W, &rd, &mfma](auto m_c) __attribute__((always_inline)) {
+            v2w_static_for(std::make_integer_sequence<int, RING>{}, rd);
+            v2w_static_for(std::make_integer_sequence<int, S_NM>{}, [&ring, &acc, &init, &W, &rd, &mfma](auto m_c) __attribute__((always_inline)) {
                 constexpr int m = decltype(m_c)::value;
                 constexpr SMm q = kStepProg<I>.mm[m];
                 if constexpr (kStepProg<I>.first_use(q.rd) == m) {
@@ -303,12 +281,12 @@ n16s_stage_kernel(const N16SArgs a) {
                     if (pos1 < 0 || pos1 >= L) t1v = f32x4{0.f, 0.f, 0.f, 0.f};
                 }
 #pragma unroll
-                for (int r = 0; r < 4; ++r) { tsum[r] = s_add(tsum[r], t1v[r]); t1v[r] = s_max(t1v[r], s_mul(t1v[r], slope)); }
-                const su32x2 w = {s_pack2(t1v[0], t1v[1]), s_pack2(t1v[2], t1v[3])};
+                for (int r = 0; r < 4; ++r) { tsum[r] = v2w_add(tsum[r], t1v[r]); t1v[r] = v2w_max(t1v[r], v2w_mul(t1v[r], slope)); }
+                const u32x2 w = {v2w_bf16x2(t1v[0], t1v[1]), v2w_bf16x2(t1v[2], t1v[3])};
                 unsigned char* const d = wbase + S_TOFF + jb * 2 * S_TP;
-                *reinterpret_cast<su32x2*>(d + (I + 1) * S_BLK) = w;
-                if constexpr (I == 0) *reinterpret_cast<su32x2*>(d + 5 * S_BLK) = w;
-                if constexpr (I == 3) *reinterpret_cast<su32x2*>(d) = w;
+                *reinterpret_cast<u32x2*>(d + (I + 1) * S_BLK) = w;
+                if constexpr (I == 0) *reinterpret_cast<u32x2*>(d + 5 * S_BLK) = w;
+                if constexpr (I == 3) *reinterpret_cast<u32x2*>(d) = w;
             }
             ts[I & 1] = tsum;
             S_STAMP(3);
@@ -318,17 +296,17 @@ n16s_stage_kernel(const N16SArgs a) {
                 const bool edge2 = p0 + 16 * s - 32 < 0 || p0 + 16 * s - 16 > L;
                 f32x4 z = acc[3];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) z[r] = s_max(z[r], s_mul(z[r], pslope));
+                for (int r = 0; r < 4; ++r) z[r] = v2w_max(z[r], v2w_mul(z[r], pslope));
                 if (edge2) {
                     asm volatile("" ::: "memory");
                     if (pos2 < 0 || pos2 >= L) z = f32x4{0.f, 0.f, 0.f, 0.f};
                 }
-                const su32x2 w = {s_pack2(z[0], z[1]), s_pack2(z[2], z[3])};
+                const u32x2 w = {v2w_bf16x2(z[0], z[1]), v2w_bf16x2(z[2], z[3])};
                 constexpr int ZS = (I + 2) & 3;
                 unsigned char* const d = wbase + S_ZOFF;
-                *reinterpret_cast<su32x2*>(d + (ZS + 1) * S_BLK) = w;
-                if constexpr (ZS == 0) *reinterpret_cast<su32x2*>(d + 5 * S_BLK) = w;
-                if constexpr (ZS == 3) *reinterpret_cast<su32x2*>(d) = w;
+                *reinterpret_cast<u32x2*>(d + (ZS + 1) * S_BLK) = w;
+                if constexpr (ZS == 0) *reinterpret_cast<u32x2*>(d + 5 * S_BLK) = w;
+                if constexpr (ZS == 3) *reinterpret_cast<u32x2*>(d) = w;
             }
             S_STAMP(4);
             // ---- the tail of block s - 4: rows 0 / 1 of the accumulator (lanes 0 .. 15) hold the hi / lo weight halves' sums for position j

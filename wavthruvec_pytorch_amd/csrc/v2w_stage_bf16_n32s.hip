@@ -24,10 +24,6 @@
 
 namespace {
 
-typedef __bf16 tb8 __attribute__((ext_vector_type(8)));
-typedef unsigned int tu32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int tu32x4 __attribute__((ext_vector_type(4)));
-
 struct N32SArgs {
     const unsigned short* in; const float* in_a; const float* in_s;
     const unsigned char* w1[3]; const float* bias1[3];
@@ -42,23 +38,6 @@ constexpr int T_XP = 10 * T_BLK, T_RP = 8 * T_BLK, T_AP = 6 * T_BLK, T_QP = 4 * 
 constexpr int T_XOFF = 0, T_ROFF = T_XOFF + 4 * T_XP, T_AOFF = T_ROFF + 4 * T_RP, T_QOFF = T_AOFF + 12 * T_AP, T_ZOFF = T_QOFF + 12 * T_QP,
               T_EOFF = T_ZOFF + 4 * T_AP, T_LDS = T_EOFF + 2 * 2048;
 static_assert(T_LDS == 59392, "two teams per CU");
-
-__device__ __forceinline__ unsigned int t_pack2(float lo, float hi) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    b2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned int, v);
-}
-__device__ __forceinline__ float t_lo(unsigned int w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float t_hi(unsigned int w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
-// one-instruction forms: fmaxf canonicalises an MFMA result first (v_max x, x), and -O3 SLP-packs adjacent f32 multiplies into v_pk_mul_f32,
-// which issues slower than two plain multiplies beside matrix work
-__device__ __forceinline__ float t_max(float v, float w) { float t; asm("v_max_f32 %0, %1, %2" : "=v"(t) : "v"(v), "v"(w)); return t; }
-__device__ __forceinline__ float t_mul(float v, float w) { float t; asm("v_mul_f32 %0, %1, %2" : "=v"(t) : "v"(v), "v"(w)); return t; }
-__device__ __forceinline__ float t_fma(float a, float b, float c) { float t; asm("v_fma_f32 %0, %1, %2, %3" : "=v"(t) : "v"(a), "v"(b), "v"(c)); return t; }
-// the team's barrier: LDS traffic only (__syncthreads() would also wait for the acknowledgement of the output stores)
-__device__ __forceinline__ void t_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-template <int... I, class F> __device__ __forceinline__ void t_for(std::integer_sequence<int, I...>, F&& f) { (f(std::integral_constant<int, I>{}), ...); }
 
 // ---- the operand reads and MFMAs of one step of one role, as tables (I = step number mod 4: ring slots are compile-time constants)
 struct TRd { int base, imm; };              // base register: 0 x ring, 1 raw-x ring, 2 lrelu(t1) / z rings, 3 t1 rings
@@ -148,12 +127,12 @@ __device__ __forceinline__ void n32s_role(const N32SArgs& a, unsigned char* cons
 
     // ---- this role's weights.  Fragment unit (16-channel chunk ch, tap t) of a (k, 32, 32) layer (v2w_pack_bf16): 2 KiB, lane' = row + 32 h'
     // holds the input channels 16 ch + 8 h' .. + 7 of output channel `row`.  This lane: output channel 16 mh + j, input channels 8 kg .. 8 kg + 7.
-    tu32x4 W[NW];
+    u32x4 W[NW];
     {
         auto frag = [&](const unsigned char* w, int K, int t, int mh) {
-            return *reinterpret_cast<const tu32x4*>(w + (size_t)((kg >> 1) * K + t) * 2048 + (unsigned)(16 * mh + j + 32 * (kg & 1)) * 16u);
+            return *reinterpret_cast<const u32x4*>(w + (size_t)((kg >> 1) * K + t) * V2W_FRAG_UNIT + (unsigned)(16 * mh + j + 32 * (kg & 1)) * 16u);
         };
-        tu32x4 ident[2];                                                        // element e of this lane: input channel 8 kg + e against output channel 16 mh + j
+        u32x4 ident[2];                                                        // element e of this lane: input channel 8 kg + e against output channel 16 mh + j
 #pragma unroll
         for (int mh = 0; mh < 2; ++mh)
 #pragma unroll
@@ -217,11 +196,11 @@ __device__ __forceinline__ void n32s_role(const N32SArgs& a, unsigned char* cons
     unsigned char* const stx = smem_t + T_XOFF + (cq >> 1) * T_XP + (4 * (cpos & 3)) * 16 + (cq & 1) * 8 + T_BLK;
     unsigned char* const str = smem_t + T_ROFF + (cq >> 1) * T_RP + (4 * (cpos & 3)) * 16 + (cq & 1) * 8;
 
-    auto mfma = [](f32x4 c, tu32x4 av, tu32x4 bv) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(tb8, av), __builtin_bit_cast(tb8, bv), c, 0, 0, 0);
+    auto mfma = [](f32x4 c, u32x4 av, u32x4 bv) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, av), __builtin_bit_cast(b8, bv), c, 0, 0, 0);
     };
 
-    tu32x2 pf[4];
+    u32x2 pf[4];
     float av[4], sv[4];
     f32x4 osum[2][2];                                                           // role 2: its conv2 sums of the blocks s - 2 (this step) and s - 3 (the step before)
     osum[0][0] = osum[0][1] = osum[1][0] = osum[1][1] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -247,7 +226,7 @@ __device__ __forceinline__ void n32s_role(const N32SArgs& a, unsigned char* cons
             unsigned vo = (unsigned)(4 * cq * L + (ok ? pos : 0)) * 2u;
             asm volatile("" : "+v"(vo));
 #pragma unroll
-            for (int i = 0; i < 4; ++i) pf[i] = *gptr<const tu32x2>(inb + (size_t)i * L * 2 + vo);
+            for (int i = 0; i < 4; ++i) pf[i] = *gptr<const u32x2>(inb + (size_t)i * L * 2 + vo);
         };
         // (in two halves - position rows e = 0, 1 then 2, 3 of every quad - in two consecutive steps: the staging waves' extra work per barrier
         // interval is halved)
@@ -264,16 +243,16 @@ __device__ __forceinline__ void n32s_role(const N32SArgs& a, unsigned char* cons
                 float y[4], v[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float xv = (e & 1) ? t_hi(pf[i][e >> 1]) : t_lo(pf[i][e >> 1]);
-                    y[i] = t_fma(av[i], xv, sv[i]);
-                    v[i] = t_max(y[i], t_mul(y[i], slope));
+                    const float xv = (e & 1) ? v2w_bf16_hi(pf[i][e >> 1]) : v2w_bf16_lo(pf[i][e >> 1]);
+                    y[i] = v2w_fma(av[i], xv, sv[i]);
+                    v[i] = v2w_max(y[i], v2w_mul(y[i], slope));
                 }
-                tu32x2 w = {t_pack2(v[0], v[1]), t_pack2(v[2], v[3])};
-                tu32x2 r = {t_pack2(y[0], y[1]), t_pack2(y[2], y[3])};
-                if (!ok) { w = tu32x2{0u, 0u}; r = w; }
-                *reinterpret_cast<tu32x2*>(dx + e * 16) = w;
-                *reinterpret_cast<tu32x2*>(dr + e * 16) = r;
-                if (mir != 0) *reinterpret_cast<tu32x2*>(dx + e * 16 + mir) = w;
+                u32x2 w = {v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
+                u32x2 r = {v2w_bf16x2(y[0], y[1]), v2w_bf16x2(y[2], y[3])};
+                if (!ok) { w = u32x2{0u, 0u}; r = w; }
+                *reinterpret_cast<u32x2*>(dx + e * 16) = w;
+                *reinterpret_cast<u32x2*>(dr + e * 16) = r;
+                if (mir != 0) *reinterpret_cast<u32x2*>(dx + e * 16 + mir) = w;
             }
         };
 
@@ -285,7 +264,7 @@ __device__ __forceinline__ void n32s_role(const N32SArgs& a, unsigned char* cons
             constexpr int NR = Prog::value->nr, NM = Prog::value->nm;
             const unsigned bt2 = rbase[2], bt3 = rbase[3];
             f32x4 acc[NACC];
-            tu32x4 ring[RING];
+            u32x4 ring[RING];
             __builtin_amdgcn_sched_barrier(0);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             auto rd = [&ring, &bx0, &bx1, &bt2, &bt3](auto n_c) __attribute__((always_inline)) {
@@ -297,8 +276,8 @@ __device__ __forceinline__ void n32s_role(const N32SArgs& a, unsigned char* cons
                 else if constexpr (bs == 2) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[n % T_RING]) : "v"(bt2), "n"(imm));
                 else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[n % T_RING]) : "v"(bt3), "n"(imm));
             };
-            t_for(std::make_integer_sequence<int, (NR < RING ? NR : RING)>{}, rd);
-            t_for(std::make_integer_sequence<int, NM>{}, [&ring, &acc, &init, &W, &rd, &mfma](auto m_c) __attribute__((always_inline)) {
+            v2w_static_for(std::make_integer_sequence<int, (NR < RING ? NR : RING)>{}, rd);
+            v2w_static_for(std::make_integer_sequence<int, NM>{}, [&ring, &acc, &init, &W, &rd, &mfma](auto m_c) __attribute__((always_inline)) {
                 constexpr int m = decltype(m_c)::value;
                 constexpr TMm q = Prog::value->mm[m];
                 constexpr int NR = Prog::value->nr, RING = T_RING;
@@ -328,15 +307,15 @@ __device__ __forceinline__ void n32s_role(const N32SArgs& a, unsigned char* cons
                             asm volatile("" ::: "memory");
                             if (pos1 < 0 || pos1 >= L) t1v = f32x4{0.f, 0.f, 0.f, 0.f};
                         }
-                        const tu32x2 raw = {t_pack2(t1v[0], t1v[1]), t_pack2(t1v[2], t1v[3])};
+                        const u32x2 raw = {v2w_bf16x2(t1v[0], t1v[1]), v2w_bf16x2(t1v[2], t1v[3])};
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) t1v[r] = t_max(t1v[r], t_mul(t1v[r], slope));
-                        const tu32x2 w = {t_pack2(t1v[0], t1v[1]), t_pack2(t1v[2], t1v[3])};
-                        *reinterpret_cast<tu32x2*>(wq + T_QOFF + jb * 4 * T_QP + mh * 2 * T_QP + I * T_BLK) = raw;
+                        for (int r = 0; r < 4; ++r) t1v[r] = v2w_max(t1v[r], v2w_mul(t1v[r], slope));
+                        const u32x2 w = {v2w_bf16x2(t1v[0], t1v[1]), v2w_bf16x2(t1v[2], t1v[3])};
+                        *reinterpret_cast<u32x2*>(wq + T_QOFF + jb * 4 * T_QP + mh * 2 * T_QP + I * T_BLK) = raw;
                         unsigned char* const d = wa + T_AOFF + jb * 4 * T_AP + mh * 2 * T_AP;
-                        *reinterpret_cast<tu32x2*>(d + (I + 1) * T_BLK) = w;
-                        if constexpr (I == 0) *reinterpret_cast<tu32x2*>(d + 5 * T_BLK) = w;
-                        if constexpr (I == 3) *reinterpret_cast<tu32x2*>(d) = w;
+                        *reinterpret_cast<u32x2*>(d + (I + 1) * T_BLK) = w;
+                        if constexpr (I == 0) *reinterpret_cast<u32x2*>(d + 5 * T_BLK) = w;
+                        if constexpr (I == 3) *reinterpret_cast<u32x2*>(d) = w;
                     }
                 }
             } else if constexpr (ROLE == 3) {
@@ -359,16 +338,16 @@ __device__ __forceinline__ void n32s_role(const N32SArgs& a, unsigned char* cons
                     // lrelu(sum / nk) = max(sum * (1 / nk), sum * (slope / nk)): two multiplies and a max per element (the quotient by
                     // multiplication is within an ulp of the division - below the bf16 rounding of z by 2^16)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) z[r] = t_max(t_mul(z[r], dinv), t_mul(z[r], dinv_us));
+                    for (int r = 0; r < 4; ++r) z[r] = v2w_max(v2w_mul(z[r], dinv), v2w_mul(z[r], dinv_us));
                     if (edge3) {
                         asm volatile("" ::: "memory");
                         if (pos3 < 0 || pos3 >= L) z = f32x4{0.f, 0.f, 0.f, 0.f};
                     }
-                    const tu32x2 w = {t_pack2(z[0], z[1]), t_pack2(z[2], z[3])};
+                    const u32x2 w = {v2w_bf16x2(z[0], z[1]), v2w_bf16x2(z[2], z[3])};
                     unsigned char* const d = wa + T_ZOFF + mh * 2 * T_AP;
-                    *reinterpret_cast<tu32x2*>(d + (ZS + 1) * T_BLK) = w;
-                    if constexpr (ZS == 0) *reinterpret_cast<tu32x2*>(d + 5 * T_BLK) = w;
-                    if constexpr (ZS == 3) *reinterpret_cast<tu32x2*>(d) = w;
+                    *reinterpret_cast<u32x2*>(d + (ZS + 1) * T_BLK) = w;
+                    if constexpr (ZS == 0) *reinterpret_cast<u32x2*>(d + 5 * T_BLK) = w;
+                    if constexpr (ZS == 3) *reinterpret_cast<u32x2*>(d) = w;
                 }
             }
             if constexpr (UP) {
@@ -380,12 +359,12 @@ __device__ __forceinline__ void n32s_role(const N32SArgs& a, unsigned char* cons
                 // 8-byte stores: lanes j and j ^ 1 hold the output pairs (2 q, 2 q + 1) of two neighbouring input positions for channels c0 and
                 // c0 + 1 - the even lane takes both pairs of channel c0, the odd lane both of c0 + 1 (one DPP swap): per store instruction a
                 // channel row receives 128 contiguous bytes instead of 64.  (q and q ^ 1 are valid together: blocks and L are multiples of 4.)
-                const unsigned pa = t_pack2(u[0], u[1]), pb = t_pack2(u[2], u[3]);
+                const unsigned pa = v2w_bf16x2(u[0], u[1]), pb = v2w_bf16x2(u[2], u[3]);
                 const bool odd = (j & 1) != 0;
                 const unsigned got = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(odd ? pa : pb), 0xB1, 0xF, 0xF, false);     // quad_perm [1, 0, 3, 2]
                 if (valid) {
-                    const tu32x2 w2 = odd ? tu32x2{got, pb} : tu32x2{pa, got};
-                    *gptr<tu32x2>(ob + (unsigned)((c0 + (odd ? 1 : 0)) * Lout + 2 * (q & ~1)) * 2u) = w2;
+                    const u32x2 w2 = odd ? u32x2{got, pb} : u32x2{pa, got};
+                    *gptr<u32x2>(ob + (unsigned)((c0 + (odd ? 1 : 0)) * Lout + 2 * (q & ~1)) * 2u) = w2;
                 }
                 // (a select, not a product: the lead-in steps of a run work on stale rings)
                 const float v0 = valid ? u[0] : 0.f, v1 = valid ? u[1] : 0.f, v2 = valid ? u[2] : 0.f, v3 = valid ? u[3] : 0.f;
@@ -396,30 +375,30 @@ __device__ __forceinline__ void n32s_role(const N32SArgs& a, unsigned char* cons
 
         // ---- the run.  Staging: burst g (blocks 4 g + 1 .. 4 g + 4) is committed in steps 4 g - 2 and 4 g - 1 (half each), one barrier before conv1 first reads it.
         if constexpr (ROLE >= 2) { issue_x(-1); commit_x(-1, 0, 4); issue_x(0); }
-        t_barrier();
+        v2w_lds_barrier();
         {
             unsigned bx0 = rbase[0] + 4u * T_BLK, bx1 = rbase[1] + 4u * T_BLK;
             asm volatile("" : "+v"(bx0), "+v"(bx1));
             step(std::integral_constant<int, 2>{}, -2, bx0, bx1);
             if constexpr (ROLE >= 2) commit_x(0, 0, 2);
-            t_barrier();
+            v2w_lds_barrier();
             step(std::integral_constant<int, 3>{}, -1, bx0, bx1);
             if constexpr (ROLE >= 2) { commit_x(0, 2, 4); issue_x(1); }
-            t_barrier();
+            v2w_lds_barrier();
         }
         for (int g = 0; g < ngrp; ++g) {
             unsigned bx0 = rbase[0] + ((g & 1) ? 4u * T_BLK : 0u), bx1 = rbase[1] + ((g & 1) ? 4u * T_BLK : 0u);
             asm volatile("" : "+v"(bx0), "+v"(bx1));
             step(std::integral_constant<int, 0>{}, 4 * g, bx0, bx1);
-            t_barrier();
+            v2w_lds_barrier();
             step(std::integral_constant<int, 1>{}, 4 * g + 1, bx0, bx1);
-            t_barrier();
+            v2w_lds_barrier();
             step(std::integral_constant<int, 2>{}, 4 * g + 2, bx0, bx1);
             if constexpr (ROLE >= 2) commit_x(g + 1, 0, 2);
-            t_barrier();
+            v2w_lds_barrier();
             step(std::integral_constant<int, 3>{}, 4 * g + 3, bx0, bx1);
             if constexpr (ROLE >= 2) { commit_x(g + 1, 2, 4); issue_x(g + 2); }
-            t_barrier();
+            v2w_lds_barrier();
         }
         // ---- BatchNorm partial sums of this run (one row of up_stats): the 16 lanes of a channel pair in a fixed (butterfly) order
         if constexpr (UP) {

@@ -20,12 +20,7 @@
 
 namespace {
 
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 #define V2W_WS_MAXB 4
-#define V2W_WS_UNIT 2048     // byte pitch of the packed fragments of one (32-row block, 16-channel k-step, tap)
 #define V2W_WS_RING 2        // taps of weight fragments in flight per wave (2 or 4: measured the same, 1074 vs 1092 us at C = 128)
 // Measured inside this kernel in rounds 3-4 and removed again ("measured and rejected"): a persistent tile loop with the next
 // tile's x loads in flight under the stores (0-10 % slower: hardware dispatch of one workgroup per tile keeps the workgroups of a CU out of
@@ -61,39 +56,16 @@ struct WideArgs {
     const unsigned short* add0; const unsigned short* add1;
 };
 
-__device__ __forceinline__ unsigned int ws_pack2(float lo, float hi) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    b2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;
-    return __builtin_bit_cast(unsigned int, v);
-}
-__device__ __forceinline__ float ws_lo(unsigned int w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float ws_hi(unsigned int w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
 // min without the canonicalisation fminf() carries (v_max_f32 x, x, x in front of every v_min_f32: the operands here are bf16 bit patterns moved
 // into a float, which the compiler cannot prove quiet): finite operands only
 __device__ __forceinline__ float ws_min(float a, float b) { return __builtin_amdgcn_fmed3f(a, b, -__builtin_inff()); }   // (the median of (a, b, -inf))
-__device__ __forceinline__ int ws_uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-template <int CTRL> __device__ __forceinline__ float ws_dpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float ws_readlane(float v, int l) {           // (the builtin is typed int: a float argument would be CONVERTED)
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-// sum over the 16 lanes of a DPP row, in every lane of the row (fixed order): quad xor 1, quad xor 2, half mirror, mirror
-__device__ __forceinline__ float ws_row_sum(float v) {
-    v += ws_dpp<0xB1>(v);
-    v += ws_dpp<0x4E>(v);
-    v += ws_dpp<0x141>(v);
-    v += ws_dpp<0x140>(v);
-    return v;
-}
-template <typename T> __device__ __forceinline__ T* ws_uni(T* v) { pin_s(v); return v; }
 
 // MI x NI blocks of 32 x 32 per wave, WM x WN waves: C = 32 MI WM channels, window W = 32 NI WN positions
 // OCC = waves per SIMD the register budget is cut for: 8-wave workgroups (one per CU) and 4-wave workgroups at two per CU: 2 (256 registers);
 // a 4-wave workgroup alone on its CU: 1 (the whole 512-register file)
 // CH = channels of a plane that exist: 32, or 16 for the C = 16 stage (ONE plane of 32-byte rows, one k-step per tap, the MFMA's rows 16-31
 // are the zero rows of the packed fragments: half of every MFMA is padding, on a stage that the vector ALU and the memory bound anyway)
-// WLDS: the weight fragments reach the waves through an LDS ring filled by LDS-DMA (global_load_lds_dwordx4), each fragment fetched ONCE per
+// WLDS: the weight fragments reach the waves through an LDS ring filled by LDS-DMA (v2w_lds_dma16), each fragment fetched ONCE per
 // workgroup and tap instead of once per wave that needs it.  Measured why: with the fragments loaded straight into registers the 8 waves of a
 // C = 128 tile ask the CU's vector memory pipe for 2 KB per 4 MFMAs each - 128 B / clk at full matrix rate against the 64 B / clk it delivers;
 // the conv phases ran at 57 % of the MFMA issue rate (71 % with the loads compiled out).
@@ -132,8 +104,8 @@ wide_stage_bf16_kernel(const WideArgs a) {
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_w[];
 
-    const int L = ws_uni(a.L), xrows = ws_uni(a.xrows), trows = ws_uni(a.trows), nk = ws_uni(a.nk);
-    const int h1max = ws_uni(a.h1max), h2max = ws_uni(a.h2max), nto = ws_uni(a.nto);
+    const int L = v2w_uni(a.L), xrows = v2w_uni(a.xrows), trows = v2w_uni(a.trows), nk = v2w_uni(a.nk);
+    const int h1max = v2w_uni(a.h1max), h2max = v2w_uni(a.h2max), nto = v2w_uni(a.nto);
     const int xpsz = xrows * RB, tpsz = trows * RB;                             // bytes per plane
     const unsigned xbase = 0, tbase = (unsigned)(NCH * xpsz);                   // LDS byte offsets of the two tiles
     float* const btab = reinterpret_cast<float*>(smem_w + tbase + NCHT * tpsz); // bias1[nk][C], then sum_j bias2_j [C], then a[C], s[C]
@@ -142,20 +114,20 @@ wide_stage_bf16_kernel(const WideArgs a) {
     const unsigned wring = tbase + (unsigned)(NCHT * tpsz) + (unsigned)((V2W_WS_MAXB + 3) * C * sizeof(float));     // WLDS: the fragment ring
     const float slope = a.slope, inv_slope = a.inv_slope;
 
-    const int hout = ws_uni(a.hout);
+    const int hout = v2w_uni(a.hout);
     // one tile per workgroup
     int b = 0, n0 = 0, pos0 = 0;                                                // batch item, position of the first valid output column, position of x row 0
     const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = ws_uni(tid >> 6);
+    const int wave = v2w_uni(tid >> 6);
     int lr = lane & 31, hk = lane >> 5;                        // (not const: made opaque again at every tile, see the tile loop)
     const int wm0 = (wave / WN) * (32 * MI);
     const int wn0 = (wave % WN) * (32 * NI);
-    const int xc0 = ws_uni(a.xoff) + h1max;                                     // x row of window column 0 (position n0 - h2max)
+    const int xc0 = v2w_uni(a.xoff) + h1max;                                     // x row of window column 0 (position n0 - h2max)
     auto tile_origin = [&](int tile, int& tb, int& tn0, int& tpos0) {
         if constexpr (!STD) { if (a.rb1) tile %= a.ntiles1; }
         tb = tile / a.ntl;
         tn0 = (tile % a.ntl) * (nto - 2 * hout) - hout;
-        tpos0 = tn0 - h2max - h1max - ws_uni(a.xoff);                           // (a multiple of 4)
+        tpos0 = tn0 - h2max - h1max - v2w_uni(a.xoff);                           // (a multiple of 4)
     };
     V2W_STAMP(0);
 
@@ -202,10 +174,10 @@ wide_stage_bf16_kernel(const WideArgs a) {
                 float v[4];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const float xv = (e & 1) ? ws_hi(pf[s][i][e >> 1]) : ws_lo(pf[s][i][e >> 1]);
+                    const float xv = (e & 1) ? v2w_bf16_hi(pf[s][i][e >> 1]) : v2w_bf16_lo(pf[s][i][e >> 1]);
                     v[i] = v2w_lrelu(fmaf(av[i], xv, sv[i]), slope);
                 }
-                u32x2 w = {ws_pack2(v[0], v[1]), ws_pack2(v[2], v[3])};
+                u32x2 w = {v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
                 if (!ok) w = u32x2{0u, 0u};                 // the padding of the ACTIVATED signal is exactly 0
                 *reinterpret_cast<u32x2*>(dst + e * RB) = w;
             }
@@ -235,7 +207,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
         auto rowaddr = [&](int ch, int row) { return baddr(base, psz, ch, row); };
         if constexpr (WLDS) {
             // ---- fragments through the LDS ring.  A tap = FT = (C / 32) * KS fragments of 1 KiB, fragment f = (row block f / KS, k-step f % KS);
-            // wave w copies fragments w * FPW .. of every tap (one global_load_lds_dwordx4 each: 64 lanes x 16 bytes, the LDS address
+            // wave w copies fragments w * FPW .. of every tap (one LDS-DMA v2w_lds_dma16 each: 64 lanes x 16 bytes, the LDS address
             // in M0).  Three slots: at the top of tap g every wave has waited for its part of tap g + 1 (counted vmcnt: the copies
             // retire in order), the barrier makes the whole tap visible and frees the slot of tap g (its fragments sit in registers since
             // tap g - 1) for the copy of tap g + 3; tap g + 1's fragments are read into the other register set under tap g's MFMAs.
@@ -251,11 +223,8 @@ wide_stage_bf16_kernel(const WideArgs a) {
                     const int f = wave * FPW + u;
                     if (FT < NW && f >= FT) break;               // (more waves than fragments: the first FT waves copy)
                     const int rb = f / KS, sq = f % KS;
-                    const unsigned char* src = wps + ((size_t)rb * nst + (size_t)(KS * chc + sq) * K + t) * V2W_WS_UNIT + lane16w;
-                    const unsigned dst = __builtin_amdgcn_readfirstlane(lds0 + (unsigned)(slot * SLOT + f * 1024));
-                    unsigned keep;
-                    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                                 : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
+                    const unsigned char* src = wps + ((size_t)rb * nst + (size_t)(KS * chc + sq) * K + t) * V2W_FRAG_UNIT + lane16w;
+                    v2w_lds_dma16(__builtin_amdgcn_readfirstlane(lds0 + (unsigned)(slot * SLOT + f * 1024)), src);
                 }
             };
             constexpr int MYF = FT < NW ? 1 : FPW;               // copies a wave has in flight per tap (waves beyond FT: none - they only wait less)
@@ -323,7 +292,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
         }
         const unsigned char* ap[MI];
 #pragma unroll
-        for (int i = 0; i < MI; ++i) ap[i] = wps + (size_t)(wm0 / 32 + i) * nst * V2W_WS_UNIT;
+        for (int i = 0; i < MI; ++i) ap[i] = wps + (size_t)(wm0 / 32 + i) * nst * V2W_FRAG_UNIT;
         // (Measured at C = 128: 3 or 7 k-steps of lookahead time the same - the loop is not bound by the fragments' latency.)
         constexpr int RT = V2W_WS_RING;
         u32x4 ar[KS * RT][MI];
@@ -333,7 +302,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
             const int chc = ch < NCH ? ch : NCH - 1;
 #pragma unroll
             for (int i = 0; i < MI; ++i)
-                av[i] = *gptr<const u32x4>(ap[i] + (size_t)((KS * chc + s) * K + t) * V2W_WS_UNIT + l16);
+                av[i] = *gptr<const u32x4>(ap[i] + (size_t)((KS * chc + s) * K + t) * V2W_FRAG_UNIT + l16);
         };
         int qc = 0, qt = 0;                                  // the tap whose fragments are requested next
 #pragma unroll
@@ -421,7 +390,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
         static_assert(KS == 2 && K >= 2, "64-byte rows");
         const unsigned char* ap[MIX];
 #pragma unroll
-        for (int i = 0; i < MIX; ++i) ap[i] = wps + (size_t)(rb0 + i) * (KS * NCH * K) * V2W_WS_UNIT;
+        for (int i = 0; i < MIX; ++i) ap[i] = wps + (size_t)(rb0 + i) * (KS * NCH * K) * V2W_FRAG_UNIT;
         u32x4 ar[4][MIX];                                     // fragments of two taps: slots 2 (g & 1) + s for global tap g
         unsigned l16 = lane16;
         asm volatile("" : "+v"(l16));
@@ -431,11 +400,11 @@ wide_stage_bf16_kernel(const WideArgs a) {
         };
         auto addr = [&](unsigned pbase, int row) { return pbase + (unsigned)(row * RB + ((hk ^ swz(row)) << 4)); };
         // fragment (plane ch, k-step s, tap t) of a row block sits at ((2 ch + s) K + t) units
-        const int f0 = 2 * padd * K * V2W_WS_UNIT;
+        const int f0 = 2 * padd * K * V2W_FRAG_UNIT;
         frag(ar[0], f0);
-        frag(ar[1], f0 + K * V2W_WS_UNIT);
-        frag(ar[2], f0 + 1 * V2W_WS_UNIT);
-        frag(ar[3], f0 + (K + 1) * V2W_WS_UNIT);
+        frag(ar[1], f0 + K * V2W_FRAG_UNIT);
+        frag(ar[2], f0 + 1 * V2W_FRAG_UNIT);
+        frag(ar[3], f0 + (K + 1) * V2W_FRAG_UNIT);
         u32x4 bb[2][NI];
         {
             const unsigned x0 = addr(base, r0);
@@ -450,7 +419,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
             constexpr int PAR = decltype(par_c)::value;       // parity of the plane's first tap in the global tap order (K is odd)
             const unsigned pbase = base + (unsigned)(ch * psz);
             const bool lastp = ch + 1 >= NCHP;
-            const int fbase = 2 * (PMUL * ch + padd) * K * V2W_WS_UNIT;       // (uniform) the plane's k-step 0, tap 0
+            const int fbase = 2 * (PMUL * ch + padd) * K * V2W_FRAG_UNIT;       // (uniform) the plane's k-step 0, tap 0
 #pragma unroll
             for (int t = 0; t < K; ++t) {
                 const int sl = 2 * ((PAR + t) & 1);
@@ -459,7 +428,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
                 const unsigned xn = wrapn ? (lastp ? addr(pbase, r0 + t * DIL) : addr(pbase + (unsigned)psz, r0)) : addr(pbase, r0 + (t + 1) * DIL);
                 // fragments two taps on: this plane, or the next one (its blocks lie 2 K units further; past the end: this plane's again)
                 const int t2 = (t + 2) % K;
-                const int f2 = fbase + ((t + 2 >= K && !lastp) ? 2 * PMUL * K * V2W_WS_UNIT : 0) + t2 * V2W_WS_UNIT;
+                const int f2 = fbase + ((t + 2 >= K && !lastp) ? 2 * PMUL * K * V2W_FRAG_UNIT : 0) + t2 * V2W_FRAG_UNIT;
 #pragma unroll
                 for (int sq = 0; sq < 2; ++sq) {
 #pragma unroll
@@ -468,7 +437,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
                         for (int i = 0; i < MIX; ++i) acc[i][j] = mfma(acc[i][j], ar[sl + sq][i], bb[sq][j]);
                         bb[sq][j] = *reinterpret_cast<const u32x4*>(smem_w + (sq ? (xn ^ 32u) : xn) + j * CB);
                     }
-                    frag(ar[sl + sq], f2 + sq * K * V2W_WS_UNIT);
+                    frag(ar[sl + sq], f2 + sq * K * V2W_FRAG_UNIT);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             }
@@ -500,10 +469,10 @@ wide_stage_bf16_kernel(const WideArgs a) {
     };
 
     bool rb1 = false;
-    if constexpr (!STD) rb1 = ws_uni(a.rb1) != 0;
+    if constexpr (!STD) rb1 = v2w_uni(a.rb1) != 0;
     auto branch = [&](int jb, auto k_c) __attribute__((always_inline)) {
         constexpr int KC = decltype(k_c)::value;             // > 0: the tap count at compile time (dilations 1 and 3), 0: run-time arguments
-        const int K = KC ? KC : ws_uni(a.K[jb]), d1 = KC ? 1 : ws_uni(a.d1[jb]), d2 = KC ? 3 : ws_uni(a.d2[jb]);
+        const int K = KC ? KC : v2w_uni(a.K[jb]), d1 = KC ? 1 : v2w_uni(a.d1[jb]), d2 = KC ? 3 : v2w_uni(a.d2[jb]);
         const int h1 = d1 * (K - 1) / 2, h2 = d2 * (K - 1) / 2;
         // ---- conv1_j on the window: column col <-> position n0 - h2max + col <-> x row xc0 + col.  (ab: one row block of conv1's accumulators,
         // rowblk: its index among the C / 32 row blocks)
@@ -543,7 +512,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
                     u32x2 packed;
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
-                        const f32x2 xa = {ws_lo(w[h]), ws_hi(w[h])};
+                        const f32x2 xa = {v2w_bf16_lo(w[h]), v2w_bf16_hi(w[h])};
                         const f32x2 xi = xa * isl2;
                         const f32x2 xr = {ws_min(xa[0], xi[0]), ws_min(xa[1], xi[1])};       // lrelu undone (slope < 1)
                         f32x2 t = f32x2{ab[j][4 * g + 2 * h], ab[j][4 * g + 2 * h + 1]};
@@ -553,7 +522,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
                         ob[j][4 * g + 2 * h] += radd[0];
                         ob[j][4 * g + 2 * h + 1] += radd[1];
                         const f32x2 ts = t * sl2;
-                        packed[h] = ws_pack2(fmaxf(t[0], ts[0]), fmaxf(t[1], ts[1]));
+                        packed[h] = v2w_bf16x2(fmaxf(t[0], ts[0]), fmaxf(t[1], ts[1]));
                     }
                     *reinterpret_cast<u32x2*>(smem_w + tq + ((g ^ tsw) << 4)) = packed;
                 }
@@ -565,11 +534,11 @@ wide_stage_bf16_kernel(const WideArgs a) {
             auto pass = [&](auto h_c) __attribute__((always_inline)) {
                 constexpr int H = decltype(h_c)::value;
                 init_acc1(acc1[0], wm0 / 32 + H);
-                conv_ct(k_c, std::integral_constant<int, 1>{}, acc1, wm0 / 32 + H, xbase, xpsz, xc0 - h1 + wn0 + lr, ws_uni(a.w1[jb]), all_planes, 0);
+                conv_ct(k_c, std::integral_constant<int, 1>{}, acc1, wm0 / 32 + H, xbase, xpsz, xc0 - h1 + wn0 + lr, v2w_uni(a.w1[jb]), all_planes, 0);
                 __syncthreads();          // the previous pass's conv2 has finished reading the t1 half tile
                 t1_epi(acc1[0], oacc[H], wm0 / 32 + H, wave / WN);
                 __syncthreads();
-                conv_ct(k_c, std::integral_constant<int, 3>{}, oacc, wm0 / 32, tbase, tpsz, wn0 + lr - h2, ws_uni(a.w2[jb]),
+                conv_ct(k_c, std::integral_constant<int, 3>{}, oacc, wm0 / 32, tbase, tpsz, wn0 + lr - h2, v2w_uni(a.w2[jb]),
                         std::integral_constant<int, NCHT>{}, H);
             };
             pass(std::integral_constant<int, 0>{});
@@ -578,8 +547,8 @@ wide_stage_bf16_kernel(const WideArgs a) {
 #pragma unroll
         for (int i = 0; i < MI1; ++i) init_acc1(acc1[i], wm0 / 32 + i);
         V2W_STAMP(3 + 6 * jb);
-        if constexpr (KC > 0) conv_ct(k_c, std::integral_constant<int, 1>{}, acc1, wm0 / 32, xbase, xpsz, xc0 - h1 + wn0 + lr, ws_uni(a.w1[jb]), all_planes, 0);
-        else conv(acc1, xbase, xpsz, xc0 - h1 + wn0 + lr, ws_uni(a.w1[jb]), K, d1);
+        if constexpr (KC > 0) conv_ct(k_c, std::integral_constant<int, 1>{}, acc1, wm0 / 32, xbase, xpsz, xc0 - h1 + wn0 + lr, v2w_uni(a.w1[jb]), all_planes, 0);
+        else conv(acc1, xbase, xpsz, xc0 - h1 + wn0 + lr, v2w_uni(a.w1[jb]), K, d1);
         V2W_STAMP(4 + 6 * jb);
         __syncthreads();          // conv2 of the previous branch has finished reading the t1 tile
         V2W_STAMP(5 + 6 * jb);
@@ -589,8 +558,8 @@ wide_stage_bf16_kernel(const WideArgs a) {
         __syncthreads();
         V2W_STAMP(7 + 6 * jb);
         // ---- conv2_j on the same window, onto the running accumulator
-        if constexpr (KC > 0) conv_ct(k_c, std::integral_constant<int, 3>{}, oacc, wm0 / 32, tbase, tpsz, wn0 + lr - h2, ws_uni(a.w2[jb]), all_planes, 0);
-        else conv(oacc, tbase, tpsz, wn0 + lr - h2, ws_uni(a.w2[jb]), K, d2);
+        if constexpr (KC > 0) conv_ct(k_c, std::integral_constant<int, 3>{}, oacc, wm0 / 32, tbase, tpsz, wn0 + lr - h2, v2w_uni(a.w2[jb]), all_planes, 0);
+        else conv(oacc, tbase, tpsz, wn0 + lr - h2, v2w_uni(a.w2[jb]), K, d2);
         }
         V2W_STAMP(8 + 6 * jb);
     };
@@ -606,7 +575,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
         const int j = i / C, c = i - j * C;
         btab[i] = a.bias1[j] ? a.bias1[j][c] : 0.f;
     }
-    const int prob = rb1 ? tile / ws_uni(a.ntiles1) : 0;          // ResBlock1 pair mode: this tile's problem = its one branch
+    const int prob = rb1 ? tile / v2w_uni(a.ntiles1) : 0;          // ResBlock1 pair mode: this tile's problem = its one branch
     for (int c = tid; c < C; c += NTH) {
         float v = 0.f;
         for (int j = rb1 ? prob : 0; j < (rb1 ? prob + 1 : nk); ++j) v += a.bias2[j] ? a.bias2[j][c] : 0.f;
@@ -677,7 +646,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
                             }
                             v = v * msk;
                             const f32x2 vs = v * us2;
-                            packed[h] = ws_pack2(fmaxf(v[0], vs[0]), fmaxf(v[1], vs[1]));
+                            packed[h] = v2w_bf16x2(fmaxf(v[0], vs[0]), fmaxf(v[1], vs[1]));
                         }
                         *reinterpret_cast<u32x2*>(smem_w + tq + ((g ^ tsw) << 4)) = packed;
                     }
@@ -723,7 +692,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
             }
         // virtual tap tv reads input position q + tv - 1 (2 U taps at stride U: one input position of halo per side)
         conv_ct(std::integral_constant<int, 3>{}, std::integral_constant<int, 1>{}, uacc, (wm0 / 32) * (UPF / 2) + MIUH * uh, zbase, tpsz,
-                wn0 + lr - 1, ws_uni(a.up_w), all_planes, 0);
+                wn0 + lr - 1, v2w_uni(a.up_w), all_planes, 0);
         V2W_STAMP(22);
         // ---- epilogue: bf16 stores straight from the accumulators (the phases of a channel are adjacent registers of a lane, consecutive
         // lanes = consecutive output positions).  BatchNorm partial sums of the fp32 values: a lane adds up its columns of a channel, the
@@ -751,10 +720,10 @@ wide_stage_bf16_kernel(const WideArgs a) {
                     }
                     if (qo[jj] != 0xffffffffu) {
                         if constexpr (UPF == 2) {
-                            *gptr<unsigned>(obase + crow + qo[jj]) = ws_pack2(v[0], v[1]);
-                            *gptr<unsigned>(obase + crow + (unsigned)Lout * 2u + qo[jj]) = ws_pack2(v[2], v[3]);
+                            *gptr<unsigned>(obase + crow + qo[jj]) = v2w_bf16x2(v[0], v[1]);
+                            *gptr<unsigned>(obase + crow + (unsigned)Lout * 2u + qo[jj]) = v2w_bf16x2(v[2], v[3]);
                         } else {
-                            *gptr<u32x2>(obase + crow + qo[jj]) = u32x2{ws_pack2(v[0], v[1]), ws_pack2(v[2], v[3])};
+                            *gptr<u32x2>(obase + crow + qo[jj]) = u32x2{v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
                         }
                     }
                 }
@@ -837,10 +806,10 @@ wide_stage_bf16_kernel(const WideArgs a) {
                 if (adds) {        // ((r0 + r1) + r2) / nk in the reference's order (models.py:135-141): the other branches' bf16 results first
                     const size_t eo = ((size_t)b * C * L + (size_t)row * L + pos) * 2;
                     const u32x2 w0 = *gptr<const u32x2>(reinterpret_cast<const unsigned char*>(a.add0) + eo);
-                    f32x4 s4 = {ws_lo(w0[0]), ws_hi(w0[0]), ws_lo(w0[1]), ws_hi(w0[1])};
+                    f32x4 s4 = {v2w_bf16_lo(w0[0]), v2w_bf16_hi(w0[0]), v2w_bf16_lo(w0[1]), v2w_bf16_hi(w0[1])};
                     if (a.add1) {
                         const u32x2 w1 = *gptr<const u32x2>(reinterpret_cast<const unsigned char*>(a.add1) + eo);
-                        s4 += f32x4{ws_lo(w1[0]), ws_hi(w1[0]), ws_lo(w1[1]), ws_hi(w1[1])};
+                        s4 += f32x4{v2w_bf16_lo(w1[0]), v2w_bf16_hi(w1[0]), v2w_bf16_lo(w1[1]), v2w_bf16_hi(w1[1])};
                     }
                     v = s4 + v;
                 }
@@ -848,7 +817,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
 #pragma unroll
                     for (int x = 0; x < 4; ++x) v[x] = v2w_div_by(v[x], a.out_div, dinv);
                 }
-                *gptr<u32x2>(obase + (unsigned)(row * L + pos) * 2u) = u32x2{ws_pack2(v[0], v[1]), ws_pack2(v[2], v[3])};
+                *gptr<u32x2>(obase + (unsigned)(row * L + pos) * 2u) = u32x2{v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
             }
         } else {
             // y[p] = tanh(b + sum_{t, c} w[t][c] * z[c][p + t - hout]) for the nto - 2 hout positions p = n0 + hout + m: scratch column of

@@ -22,12 +22,6 @@
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef __bf16 b4 __attribute__((ext_vector_type(4)));
-typedef unsigned int raw16 __attribute__((ext_vector_type(4)));
-
 #define V2W_SS_MAXB 4
 
 struct StageSplitArgs {
@@ -35,7 +29,7 @@ struct StageSplitArgs {
     const unsigned char* w1[V2W_SS_MAXB]; const float* sc1[V2W_SS_MAXB]; const float* bias1[V2W_SS_MAXB];
     const unsigned char* w2[V2W_SS_MAXB]; const float* sc2[V2W_SS_MAXB]; const float* bias2[V2W_SS_MAXB];
     int K[V2W_SS_MAXB], d1[V2W_SS_MAXB], d2[V2W_SS_MAXB];
-    const unsigned char* wbase;   // the 2*nk weight streams lie back to back in execution order (w1_0, w2_0, w1_1, ...): unit g at wbase + g*2048
+    const unsigned char* wbase;   // the 2*nk weight streams lie back to back in execution order (w1_0, w2_0, w1_1, ...): unit g at wbase + g*V2W_FRAG_UNIT
     int ntot;                     // units of all streams
     float* out;
     int nk, B, L;
@@ -179,7 +173,7 @@ stage_split_kernel(const StageSplitArgs p) {
     auto ld = [&](auto slot_c, const unsigned char* ptr) __attribute__((always_inline)) {
         constexpr int sl = decltype(slot_c)::value;
         rh[sl] = *reinterpret_cast<const raw16*>(ptr);
-        if constexpr (!BF) rl[sl] = *reinterpret_cast<const raw16*>(ptr + 1024);
+        if constexpr (!BF) rl[sl] = *reinterpret_cast<const raw16*>(ptr + V2W_FRAG_UNIT / 2);
     };
     auto conv_phase = [&](auto s0_c, int ug0, const unsigned char* src, int rowbase, int maxrow, int K, int dil) __attribute__((always_inline)) {
         constexpr int S0 = decltype(s0_c)::value;
@@ -189,8 +183,8 @@ stage_split_kernel(const StageSplitArgs p) {
             for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
         const int nu = NCH * K;
         // ring prefetch pointer: the streams are contiguous, so the unit three ahead is simply + 3 units (clamped at the very end)
-        const unsigned char* wp_ = p.wbase + (size_t)(ug0 + 3) * 2048 + lane * 16;
-        const unsigned char* const wend = p.wbase + (size_t)(p.ntot - 1) * 2048 + lane * 16;
+        const unsigned char* wp_ = p.wbase + (size_t)(ug0 + 3) * V2W_FRAG_UNIT + lane * 16;
+        const unsigned char* const wend = p.wbase + (size_t)(p.ntot - 1) * V2W_FRAG_UNIT + lane * 16;
         // signal fragments of unit u+1 are read while the MFMAs of unit u run (bn -> bc hand-over in registers)
         raw16 bh[NI], bl[BF ? 1 : NI];
         auto read_b = [&](int u) __attribute__((always_inline)) {
@@ -207,7 +201,7 @@ stage_split_kernel(const StageSplitArgs p) {
         auto unit = [&](auto s_c, int u) __attribute__((always_inline)) {
             constexpr int sl = (S0 + decltype(s_c)::value) & 3, slp = (sl + 3) & 3;
             ld(std::integral_constant<int, slp>{}, wp_ < wend ? wp_ : wend);
-            wp_ += 2048;
+            wp_ += V2W_FRAG_UNIT;
             __builtin_amdgcn_sched_barrier(0);
             raw16 ch_[NI], cl_[BF ? 1 : NI];
 #pragma unroll
@@ -248,7 +242,7 @@ stage_split_kernel(const StageSplitArgs p) {
         ug += NCH * K;
     };
     ld(std::integral_constant<int, 0>{}, p.wbase + lane * 16);
-    ld(std::integral_constant<int, 1>{}, p.wbase + lane * 16 + 2048);
+    ld(std::integral_constant<int, 1>{}, p.wbase + lane * 16 + V2W_FRAG_UNIT);
     ld(std::integral_constant<int, 2>{}, p.wbase + lane * 16 + 4096);
 
     for (int jb = 0; jb < p.nk; ++jb) {
@@ -357,9 +351,9 @@ int launch_stage_split(const v2w_stage_split_args* q, hipStream_t stream) {
     const unsigned char* expect = p.wbase;
     for (int j = 0; j < q->nk; ++j) {
         if (p.w1[j] != expect && !v2w_dry(stream)) return V2W_E_ARG;
-        expect += (size_t)NCH * q->k[j] * 2048;
+        expect += (size_t)NCH * q->k[j] * V2W_FRAG_UNIT;
         if (p.w2[j] != expect && !v2w_dry(stream)) return V2W_E_ARG;
-        expect += (size_t)NCH * q->k[j] * 2048;
+        expect += (size_t)NCH * q->k[j] * V2W_FRAG_UNIT;
         p.ntot += 2 * NCH * q->k[j];
     }
     p.nto = (W - 2 * p.h2max) & ~3;

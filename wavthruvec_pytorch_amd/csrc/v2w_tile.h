@@ -82,3 +82,7 @@ struct MultiArgs {
 };
 
 }  // namespace
+
+// the pointer form of v2w_uni (v2w_common.h), through pin_s; beside the int form in the global namespace (declared inside the anonymous
+// namespace it would hide that one from every kernel there)
+template <typename T> __device__ __forceinline__ T* v2w_uni(T* v) { pin_s(v); return v; }

@@ -24,9 +24,6 @@
 
 namespace {
 
-typedef __bf16 b8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 struct WgBfArgs {
     const void* x; const float* x_a; const float* x_s;   // (B, Cin, Lq) fp32 or bf16, and its per-(b, ci) affine (or null)
     const void* dy;                                       // (B, Cout, Lq) fp32 or bf16
@@ -37,14 +34,6 @@ struct WgBfArgs {
     int hla, xc8, xtw;        // halo columns staged on the left (multiple of 8), 8-element groups staged per signal row, signal row stride in dwords (odd)
     float slope;
 };
-
-__device__ __forceinline__ unsigned int wg_pack(float lo, float hi) {
-    typedef __bf16 b2 __attribute__((ext_vector_type(2)));
-    b2 v; v[0] = (__bf16)lo; v[1] = (__bf16)hi;          // v_cvt_pk_bf16_f32: round to nearest even
-    return __builtin_bit_cast(unsigned int, v);
-}
-__device__ __forceinline__ float wg_lo(unsigned int w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float wg_hi(unsigned int w) { return __builtin_bit_cast(float, w & 0xffff0000u); }
 
 template <int MF> struct BfFrag;
 template <> struct BfFrag<32> {
@@ -171,7 +160,7 @@ wgrad_bf16_kernel(const WgBfArgs p) {
             if constexpr (BF) w = dyv[i];
             else {
                 const f32x4 v0 = dyv[2 * i], v1 = dyv[2 * i + 1];
-                w = u32x4{wg_pack(v0[0], v0[1]), wg_pack(v0[2], v0[3]), wg_pack(v1[0], v1[1]), wg_pack(v1[2], v1[3])};
+                w = u32x4{v2w_bf16x2(v0[0], v0[1]), v2w_bf16x2(v0[2], v0[3]), v2w_bf16x2(v1[0], v1[1]), v2w_bf16x2(v1[2], v1[3])};
             }
             *reinterpret_cast<u32x4*>(DYs + row * WGB_DYW + c8 * 8) = w;
         }
@@ -187,7 +176,7 @@ wgrad_bf16_kernel(const WgBfArgs p) {
                 float v[8];
                 if constexpr (BF) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) { v[2 * e] = wg_lo(xv[i][e]); v[2 * e + 1] = wg_hi(xv[i][e]); }
+                    for (int e = 0; e < 4; ++e) { v[2 * e] = v2w_bf16_lo(xv[i][e]); v[2 * e + 1] = v2w_bf16_hi(xv[i][e]); }
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { v[e] = xv[2 * i][e]; v[4 + e] = xv[2 * i + 1][e]; }
@@ -196,7 +185,7 @@ wgrad_bf16_kernel(const WgBfArgs p) {
                 for (int e = 0; e < 8; ++e) v[e] = in ? v2w_lrelu(fmaf(xa_cur, v[e], xs_cur), p.slope) : 0.f;
                 unsigned int* d = drow + c8 * 4;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) d[e] = wg_pack(v[2 * e], v[2 * e + 1]);
+                for (int e = 0; e < 4; ++e) d[e] = v2w_bf16x2(v[2 * e], v[2 * e + 1]);
             }
         }
         __syncthreads();
