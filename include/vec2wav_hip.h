@@ -591,6 +591,55 @@ int v2w_fold1(const float* dxu, float* dx, int B, int T, int H, int inner, int s
 int v2w_avgpool4_bwd(const float* dout, float* dx, int B, int L, void* stream);
 int v2w_cout1_wgrad(const float* x, const float* dz, float* dwf, int B, int C, int L, int k, int dil, int tap0, void* stream);
 
+/* ---- GAN training losses (additive in ABI v35; models.py:278-310 feature_loss / discriminator_loss / generator_loss and the mel term
+ * F.l1_loss of train.py:204): the loss values and the gradients that start the backward, forward and backward of a whole call in one
+ * launch each (the L1 forward: one streaming launch and one finishing launch).  Up to V2W_LOSS_MAX_ITEMS tensors (pairs) per call; the
+ * descriptors are HOST arrays, read before the call returns (as v2w_conv1d_fwd_multi reads its problems).
+ *
+ * A tensor is `rows` rows of `valid` floats, consecutive rows `pitch` floats apart; floats [valid, pitch) of a row are never read.
+ * pitch == valid or pitch == 0: dense, any length and any (4-byte) alignment.  Otherwise pitch % 4 == 0 and the base is 16-byte
+ * aligned - the form of the discriminators' feature maps ((B, C, roundup4(U)) buffers returned as [:, :, :U] views, their 4-D
+ * (b, C, U, inner) views and the leading-dim halves of a real-plus-generated batch), which are read in place.
+ *
+ * L1 (feature loss / mel term):
+ *   forward   term[i] = mean |a_i - b_i| (n floats, may be NULL), total[0] = scale * sum_i term[i] in list order (may be NULL).
+ *             Deterministic: workgroups are dealt to the pairs in proportion to their sizes by a plan that depends on the descriptors
+ *             only, each writes one fp64 partial to `scratch`, the finishing launch adds them in index order in fp64; no atomics.
+ *   backward  da_i = sgn(a_i - b_i) * ((scale * gout[0]) / numel_i), db_i = -da_i, written DENSE (rows x valid); either may be NULL
+ *             (a pair with both NULL is skipped).  sgn = (a > b) - (a < b); the coefficient is the correctly rounded fp32 quotient of
+ *             the fp32 product; gout is a DEVICE scalar, read by the kernel.  The forward ignores da / db.
+ *   v2w_l1_multi_plan (host only): starts[i] = first workgroup of pair i, starts[n] = workgroups of the streaming launch, which is
+ *             also the return value (> 0), at most V2W_L1_TARGET_WGS + n; every pair has at least one.  A pair counts
+ *             rows * ceil(valid / 4) units of four floats (both sides dense: ceil((rows * valid + s) / 4), s = floats of `a` past a
+ *             16-byte line); chunk = max(2048, ceil(sum of units / V2W_L1_TARGET_WGS)); pair i gets ceil(units_i / chunk) workgroups.
+ *   v2w_l1_multi_scratch_bytes (host only): bytes of `scratch` (8-byte aligned) the forward needs: 8 per workgroup.
+ * LSGAN terms (numel_i < 2^31, target 0 or 1):
+ *   forward   term[i] = mean (target_i - s_i)^2, total[0] = sum_i term[i] in list order, fp64 inside; one launch, no scratch.
+ *   backward  ds_i = 2 (s_i - target_i) * g_i / numel_i, dense; g_i = gout[0] + gterm[i], DEVICE pointers of which one may be NULL
+ *             (gterm: n floats, the gradients that arrived on the single terms); items with ds == NULL are skipped. */
+#define V2W_LOSS_MAX_ITEMS 64
+#define V2W_L1_TARGET_WGS  2048
+typedef struct {
+    const float* a; const float* b;
+    float* da; float* db;                  /* backward only */
+    int64_t rows;
+    int32_t valid, pitch_a, pitch_b, _pad;
+} v2w_l1_pair;
+typedef struct {
+    const float* s;
+    float* ds;                             /* backward only */
+    int64_t rows;
+    int32_t valid, pitch;
+    float target;
+    int32_t _pad;
+} v2w_lsgan_item;
+int       v2w_l1_multi_plan(const v2w_l1_pair* pairs, int n, int32_t* starts);
+long long v2w_l1_multi_scratch_bytes(const v2w_l1_pair* pairs, int n);
+int v2w_l1_mean_multi(const v2w_l1_pair* pairs, int n, float scale, float* term, float* total, void* scratch, void* stream);
+int v2w_l1_mean_multi_bwd(const v2w_l1_pair* pairs, int n, float scale, const float* gout, void* stream);
+int v2w_lsgan_multi(const v2w_lsgan_item* items, int n, float* term, float* total, void* stream);
+int v2w_lsgan_multi_bwd(const v2w_lsgan_item* items, int n, const float* gout, const float* gterm, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

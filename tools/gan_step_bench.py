@@ -139,7 +139,7 @@ def main():
         optim_d.step()
         t0 = tick('D step: backward + AdamW', t0)
         optim_g.zero_grad()
-        loss_mel = F.l1_loss(y_mel, y_g_hat_mel) * 45
+        loss_mel = (F.l1_loss if stock else HD.l1_mean_loss)(y_mel, y_g_hat_mel) * 45
         with (HD.frozen(mpd, msd) if freeze else contextlib.nullcontext()):
             y_df_hat_r, y_df_hat_g, fmap_f_r, fmap_f_g = mpd(y, y_g_hat)
             y_ds_hat_r, y_ds_hat_g, fmap_s_r, fmap_s_g = msd(y, y_g_hat)

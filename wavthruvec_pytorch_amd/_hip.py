@@ -108,6 +108,21 @@ class CondEvalArgs(C.Structure):
                 ('eps', C.c_float * V2W_MAX_STAGES)]
 
 
+class L1Pair(C.Structure):
+    """include/vec2wav_hip.h `v2w_l1_pair`: one (a, b) pair of the multi-tensor L1 loss; rows x valid floats, `pitch` floats between rows."""
+    _fields_ = [('a', _fp), ('b', _fp), ('da', _fp), ('db', _fp), ('rows', C.c_int64),
+                ('valid', C.c_int32), ('pitch_a', C.c_int32), ('pitch_b', C.c_int32), ('_pad', C.c_int32)]
+
+
+class LsganItem(C.Structure):
+    """include/vec2wav_hip.h `v2w_lsgan_item`: one score tensor of the LSGAN terms and its target (0 or 1)."""
+    _fields_ = [('s', _fp), ('ds', _fp), ('rows', C.c_int64), ('valid', C.c_int32), ('pitch', C.c_int32),
+                ('target', C.c_float), ('_pad', C.c_int32)]
+
+
+LOSS_MAX_ITEMS = 64
+L1_TARGET_WGS = 2048
+
 # name -> (restype, argtypes); must list every symbol include/vec2wav_hip.h declares
 SIGNATURES = {
     'v2w_abi_version': (C.c_int, []),
@@ -196,6 +211,13 @@ SIGNATURES = {
     'v2w_convt1d_fwd_len': (C.c_int, [C.POINTER(ConvT1dArgs), _fp, C.c_int, _fp]),
     'v2w_resblock2_stage_fwd_len': (C.c_int, [C.POINTER(StageArgs), _fp, C.c_int, _fp]),
     'v2w_conv_post_tanh_len': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, C.c_int, _fp]),
+    # GAN training losses: host descriptor arrays, read before the call returns
+    'v2w_l1_multi_plan': (C.c_int, [C.POINTER(L1Pair), C.c_int, C.POINTER(C.c_int32)]),
+    'v2w_l1_multi_scratch_bytes': (C.c_longlong, [C.POINTER(L1Pair), C.c_int]),
+    'v2w_l1_mean_multi': (C.c_int, [C.POINTER(L1Pair), C.c_int, C.c_float, _fp, _fp, _fp, _fp]),
+    'v2w_l1_mean_multi_bwd': (C.c_int, [C.POINTER(L1Pair), C.c_int, C.c_float, _fp, _fp]),
+    'v2w_lsgan_multi': (C.c_int, [C.POINTER(LsganItem), C.c_int, _fp, _fp, _fp]),
+    'v2w_lsgan_multi_bwd': (C.c_int, [C.POINTER(LsganItem), C.c_int, _fp, _fp, _fp]),
 }
 
 # entry points that LAUNCH (their last argument is the stream); the others are host-only queries.  schedule.Recorder tapes the former.

@@ -1,0 +1,337 @@
+// GAN training losses (reference models.py:278-310 feature_loss / discriminator_loss / generator_loss, train.py:204 the mel L1 term):
+// every map pair of a feature loss in ONE streaming launch (+ one finishing launch), every LSGAN term of a call in one launch, and
+// their backwards in one launch each.  The maps are read where the discriminators left them: `rows` rows of `valid` floats `pitch`
+// floats apart ([valid, pitch) is never read), so the [:, :, :U] views of the pitched feature-map buffers need no copy.
+//
+// Work split (host, v2w_l1_multi_plan): a pair is cut into UNITS of four floats - per row ceil(valid / 4) of them, the last one of a
+// row partial; a pair whose two sides are dense is one row of rows * valid floats whose units are cut at the 16-byte boundaries of
+// `a`.  Workgroups are dealt in proportion to the units (the element counts of one call span four orders of magnitude), at least one
+// per pair, about V2W_L1_TARGET_WGS in all: starts[i] is the first workgroup of pair i.  The plan depends on the descriptors only (not
+// on the device), every workgroup writes ONE fp64 partial and the finishing launch adds them in index order: the same call gives the
+// same bits.
+#include "v2w_common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kUnroll = 4;                       // units in flight per thread: 2 x 4 x 16 B of loads before the first use
+constexpr long long kMinChunk = kThreads * 8;    // units: no workgroup for less than 64 KB of reads unless the pair is smaller
+constexpr long long kMaxUnits = 1ll << 40;
+
+struct L1Item {
+    const float* a; const float* b; float* da; float* db;
+    long long shape;               // pa == 0 (one dense run): its floats; else rows << 32 | floats per row
+    int pa, pb;                    // row pitches in floats
+    __host__ __device__ bool flat() const { return pa == 0; }
+    __host__ __device__ int rows() const { return flat() ? 1 : (int)(shape >> 32); }
+    __host__ __device__ long long len() const { return flat() ? shape : (shape & 0xffffffffll); }      // floats per row
+};
+struct L1Args {
+    L1Item it[V2W_LOSS_MAX_ITEMS];
+    int starts[V2W_LOSS_MAX_ITEMS + 1];
+    int n;
+    float scale;
+    const float* gout;
+};
+static_assert(sizeof(L1Args) <= 3584, "kernel arguments travel by value: 4 KB with the hidden ones");
+
+struct LsItem { const float* s; float* ds; unsigned numel, valid, pitch; float target; };
+struct LsArgs {
+    LsItem it[V2W_LOSS_MAX_ITEMS];
+    int n;
+    const float* gout; const float* gterm;
+};
+
+__device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// elements [e0, e1) of the four floats at p (the others read as 0 and are never touched); one 16-byte load when all four are wanted
+// and p allows it
+__device__ __forceinline__ f32x4 load_unit(const float* p, int e0, int e1) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (e0 == 0 && e1 == 4 && aligned16(p)) return *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j >= e0 && j < e1) v[j] = p[j];
+    return v;
+}
+__device__ __forceinline__ void store_unit(float* p, f32x4 v, int e0, int e1) {
+    if (e0 == 0 && e1 == 4 && aligned16(p)) { *reinterpret_cast<f32x4*>(p) = v; return; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j >= e0 && j < e1) p[j] = v[j];
+}
+
+// BWD = false: part[workgroup] = sum |a - b| over the workgroup's units (fp64).
+// BWD = true:  da = sgn(a - b) * (scale * gout / numel), db = -da, dense (rows x len); sgn = (a > b) - (a < b).
+template <bool BWD>
+__global__ void __launch_bounds__(kThreads)
+l1_multi_kernel(const L1Args A, double* __restrict__ part) {
+    __shared__ double red[16];
+    const int wg = blockIdx.x;
+    int lo = 0, hi = A.n;
+    while (hi - lo > 1) {                                 // the pair of this workgroup: starts[lo] <= wg < starts[lo + 1]
+        const int mid = (lo + hi) >> 1;
+        if (A.starts[mid] <= wg) lo = mid; else hi = mid;
+    }
+    const L1Item& it = A.it[lo];
+    const float* a = it.a;
+    const float* b = it.b;
+    const long long len = it.len();
+    const bool flat = it.flat();
+    const int rows = it.rows();
+    const int shift = flat ? (int)((reinterpret_cast<uintptr_t>(a) >> 2) & 3) : 0;      // units of a flat pair start at a's 16-byte lines
+    const long long upr = (len + shift + 3) >> 2;                                       // units per row
+    const long long units = upr * rows;
+    const int nwg = A.starts[lo + 1] - A.starts[lo];
+    const long long chunk = (units + nwg - 1) / nwg;
+    const long long u0 = (long long)(wg - A.starts[lo]) * chunk;
+    const long long u1 = u0 + chunk < units ? u0 + chunk : units;
+    const unsigned cnt = u1 > u0 ? (unsigned)(u1 - u0) : 0u;
+    const long long r0 = flat ? 0 : u0 / upr;
+    const long long q0 = u0 - r0 * upr;
+    const unsigned upr32 = flat ? 1u : (unsigned)upr, q032 = flat ? 0u : (unsigned)q0;
+    a += r0 * it.pa - shift;                              // the first unit of row r0 (it may begin before the row: those floats are masked)
+    b += r0 * it.pb - shift;
+
+    float coef = 0.f;
+    float* da = nullptr;
+    float* db = nullptr;
+    if (BWD) {
+        const float numel = (float)(len * rows);
+        // (scale * gout) / numel, correctly rounded: the fp64 quotient of two floats rounds to the fp32 quotient
+        coef = (float)((double)(A.scale * A.gout[0]) / (double)numel);
+        da = it.da ? it.da + r0 * len - shift : nullptr;
+        db = it.db ? it.db + r0 * len - shift : nullptr;
+    }
+
+    double acc = 0.0;
+    for (unsigned t0 = threadIdx.x; t0 < cnt; t0 += kThreads * kUnroll) {
+        f32x4 va[kUnroll], vb[kUnroll];
+        long long oo[kUnroll];
+        int e0[kUnroll], e1[kUnroll];
+#pragma unroll
+        for (int k = 0; k < kUnroll; ++k) {
+            const unsigned t = t0 + k * kThreads;
+            long long p;             // position in its row of the unit's first float (negative: the floats before a flat pair's start)
+            size_t oa, ob;
+            if (flat) {
+                p = ((q0 + t) << 2) - shift;
+                oa = ob = ((size_t)q0 + t) << 2;
+                oo[k] = (long long)oa;
+            } else {
+                const unsigned tt = q032 + t, r = tt / upr32, q = tt - r * upr32;
+                p = (long long)q << 2;
+                oa = (size_t)r * it.pa + (q << 2);
+                ob = (size_t)r * it.pb + (q << 2);
+                oo[k] = (long long)r * len + (q << 2);
+            }
+            e0[k] = p < 0 ? (int)-p : 0;
+            e1[k] = len - p < 4 ? (int)(len - p) : 4;
+            if (t >= cnt) e0[k] = e1[k] = 0;
+            va[k] = load_unit(a + oa, e0[k], e1[k]);
+            vb[k] = load_unit(b + ob, e0[k], e1[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < kUnroll; ++k) {
+            if (!BWD) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc += (double)fabsf(va[k][j] - vb[k][j]);     // masked floats are 0 on both sides
+            } else {
+                f32x4 d, nd;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    d[j] = va[k][j] > vb[k][j] ? coef : (va[k][j] < vb[k][j] ? -coef : 0.f);
+                    nd[j] = -d[j];
+                }
+                if (da) store_unit(da + oo[k], d, e0[k], e1[k]);
+                if (db) store_unit(db + oo[k], nd, e0[k], e1[k]);
+            }
+        }
+    }
+    if (!BWD) {
+        const double s = v2w_block_sum(acc, red);
+        if (threadIdx.x == 0) part[wg] = s;
+    }
+}
+
+// term[i] = (sum of pair i's partials, in workgroup order) / numel_i;  total = scale * sum_i term[i], in list order; all in fp64
+__global__ void __launch_bounds__(kThreads)
+l1_finish_kernel(const L1Args A, const double* __restrict__ part, float* __restrict__ term, float* __restrict__ total) {
+    __shared__ double red[16];
+    double tot = 0.0;
+    for (int i = 0; i < A.n; ++i) {
+        double s = 0.0;
+        for (int k = A.starts[i] + threadIdx.x; k < A.starts[i + 1]; k += kThreads) s += part[k];
+        const double mean = v2w_block_sum(s, red) / (double)(A.it[i].len() * A.it[i].rows());
+        if (threadIdx.x == 0 && term) term[i] = (float)mean;
+        tot += mean;
+    }
+    if (threadIdx.x == 0 && total) total[0] = (float)((double)A.scale * tot);
+}
+
+// term[i] = mean (t_i - s_i)^2, total = sum_i term[i] (list order); one workgroup: the scores of a call are a few thousand floats
+__global__ void __launch_bounds__(1024)
+lsgan_multi_kernel(const LsArgs A, float* __restrict__ term, float* __restrict__ total) {
+    __shared__ double red[16];
+    double tot = 0.0;
+    for (int i = 0; i < A.n; ++i) {
+        const LsItem& it = A.it[i];
+        const double t = (double)it.target;
+        double acc = 0.0;
+        for (unsigned e = threadIdx.x; e < it.numel; e += 1024) {
+            const unsigned r = e / it.valid, j = e - r * it.valid;
+            const double d = t - (double)it.s[(size_t)r * it.pitch + j];
+            acc += d * d;
+        }
+        const double mean = v2w_block_sum(acc, red) / (double)it.numel;
+        if (threadIdx.x == 0 && term) term[i] = (float)mean;
+        tot += mean;
+    }
+    if (threadIdx.x == 0 && total) total[0] = (float)tot;
+}
+
+// ds_i = 2 (s_i - t_i) * g_i / numel_i, dense; g_i = gout[0] + gterm[i] (either may be absent); grid (blocks, items)
+__global__ void __launch_bounds__(kThreads)
+lsgan_multi_bwd_kernel(const LsArgs A) {
+    const int i = blockIdx.y;
+    const LsItem& it = A.it[i];
+    if (!it.ds) return;
+    const float g = (A.gout ? A.gout[0] : 0.f) + (A.gterm ? A.gterm[i] : 0.f);
+    const float c = g / (float)it.numel;
+    for (unsigned e = blockIdx.x * kThreads + threadIdx.x; e < it.numel; e += gridDim.x * kThreads) {
+        const unsigned r = e / it.valid, j = e - r * it.valid;
+        it.ds[e] = 2.f * (it.s[(size_t)r * it.pitch + j] - it.target) * c;
+    }
+}
+
+inline bool ptr16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool ptr4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
+// checks every descriptor, normalises it into the kernel's form and counts its units (four floats; see the head of this file)
+int l1_items(const v2w_l1_pair* pairs, int n, L1Item* items, long long* units) {
+    if (!pairs || n < 1 || n > V2W_LOSS_MAX_ITEMS) return V2W_E_ARG;
+    for (int i = 0; i < n; ++i) {
+        const v2w_l1_pair& p = pairs[i];
+        if (!p.a || !p.b || !ptr4(p.a) || !ptr4(p.b) || p.rows <= 0 || p.valid <= 0 || p.pitch_a < 0 || p.pitch_b < 0) return V2W_E_ARG;
+        const int pa = p.pitch_a ? p.pitch_a : p.valid, pb = p.pitch_b ? p.pitch_b : p.valid;
+        if (pa < p.valid || pb < p.valid) return V2W_E_ARG;
+        if (pa != p.valid && ((pa & 3) || !ptr16(p.a))) return V2W_E_ARG;       // pitched rows begin on 16-byte lines
+        if (pb != p.valid && ((pb & 3) || !ptr16(p.b))) return V2W_E_ARG;
+        if ((p.da && !ptr4(p.da)) || (p.db && !ptr4(p.db))) return V2W_E_ARG;
+        L1Item& it = items[i];
+        it.a = p.a; it.b = p.b; it.da = p.da; it.db = p.db;
+        if (p.rows == 1 || (pa == p.valid && pb == p.valid)) {
+            it.shape = (long long)p.rows * p.valid; it.pa = it.pb = 0;
+            const int shift = (int)((reinterpret_cast<uintptr_t>(p.a) >> 2) & 3);
+            units[i] = (it.shape + shift + 3) >> 2;
+        } else {
+            if (p.rows > 0x7fffffffll) return V2W_E_SHAPE;
+            it.shape = (p.rows << 32) | p.valid; it.pa = pa; it.pb = pb;
+            units[i] = p.rows * ((p.valid + 3) >> 2);
+        }
+        if (units[i] > kMaxUnits) return V2W_E_SHAPE;
+    }
+    return 0;
+}
+
+// starts[i] = first workgroup of pair i, starts[n] = workgroups of the launch (returned)
+int l1_plan(const long long* units, int n, int32_t* starts) {
+    long long total = 0;
+    for (int i = 0; i < n; ++i) total += units[i];
+    long long chunk = (total + V2W_L1_TARGET_WGS - 1) / V2W_L1_TARGET_WGS;
+    if (chunk < kMinChunk) chunk = kMinChunk;
+    int w = 0;
+    for (int i = 0; i < n; ++i) {
+        starts[i] = w;
+        const long long k = (units[i] + chunk - 1) / chunk;
+        w += k < 1 ? 1 : (int)k;
+    }
+    starts[n] = w;
+    return w;
+}
+
+int l1_args(const v2w_l1_pair* pairs, int n, float scale, const float* gout, L1Args* A) {
+    long long units[V2W_LOSS_MAX_ITEMS];
+    if (const int rc = l1_items(pairs, n, A->it, units)) return rc;
+    l1_plan(units, n, A->starts);
+    A->n = n; A->scale = scale; A->gout = gout;
+    return 0;
+}
+
+int ls_args(const v2w_lsgan_item* items, int n, bool bwd, LsArgs* A, unsigned* maxnumel) {
+    if (!items || n < 1 || n > V2W_LOSS_MAX_ITEMS) return V2W_E_ARG;
+    *maxnumel = 0;
+    for (int i = 0; i < n; ++i) {
+        const v2w_lsgan_item& p = items[i];
+        if (!p.s || !ptr4(p.s) || p.rows <= 0 || p.valid <= 0 || p.pitch < 0 || (p.pitch && p.pitch < p.valid)) return V2W_E_ARG;
+        if (p.target != 0.f && p.target != 1.f) return V2W_E_ARG;
+        if (bwd && p.ds && !ptr4(p.ds)) return V2W_E_ARG;
+        const long long numel = (long long)p.rows * p.valid;
+        if (numel > 0x7fffffffll) return V2W_E_SHAPE;
+        LsItem& it = A->it[i];
+        it.s = p.s; it.ds = p.ds; it.numel = (unsigned)numel; it.valid = (unsigned)p.valid;
+        it.pitch = (unsigned)(p.pitch ? p.pitch : p.valid); it.target = p.target;
+        if (it.numel > *maxnumel) *maxnumel = it.numel;
+    }
+    A->n = n; A->gout = nullptr; A->gterm = nullptr;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int v2w_l1_multi_plan(const v2w_l1_pair* pairs, int n, int32_t* starts) {
+    if (!starts) return V2W_E_ARG;
+    L1Item items[V2W_LOSS_MAX_ITEMS];
+    long long units[V2W_LOSS_MAX_ITEMS];
+    if (const int rc = l1_items(pairs, n, items, units)) return rc;
+    return l1_plan(units, n, starts);
+}
+
+extern "C" long long v2w_l1_multi_scratch_bytes(const v2w_l1_pair* pairs, int n) {
+    int32_t starts[V2W_LOSS_MAX_ITEMS + 1];
+    const int w = v2w_l1_multi_plan(pairs, n, starts);
+    return w < 0 ? (long long)w : (long long)w * (long long)sizeof(double);
+}
+
+extern "C" int v2w_l1_mean_multi(const v2w_l1_pair* pairs, int n, float scale, float* term, float* total, void* scratch, void* stream) {
+    if (!scratch || (!term && !total) || (reinterpret_cast<uintptr_t>(scratch) & 7)) return V2W_E_ARG;
+    L1Args A;
+    if (const int rc = l1_args(pairs, n, scale, nullptr, &A)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    double* part = static_cast<double*>(scratch);
+    V2W_LAUNCH(l1_multi_kernel<false>, dim3(A.starts[n]), dim3(kThreads), 0, st, A, part);
+    V2W_LAUNCH(l1_finish_kernel, dim3(1), dim3(kThreads), 0, st, A, part, term, total);
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_l1_mean_multi_bwd(const v2w_l1_pair* pairs, int n, float scale, const float* gout, void* stream) {
+    if (!gout) return V2W_E_ARG;
+    L1Args A;
+    if (const int rc = l1_args(pairs, n, scale, gout, &A)) return rc;
+    bool any = false;
+    for (int i = 0; i < n; ++i) any = any || A.it[i].da || A.it[i].db;
+    if (!any) return V2W_E_ARG;
+    V2W_LAUNCH(l1_multi_kernel<true>, dim3(A.starts[n]), dim3(kThreads), 0, (hipStream_t)stream, A, static_cast<double*>(nullptr));
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_lsgan_multi(const v2w_lsgan_item* items, int n, float* term, float* total, void* stream) {
+    if (!term && !total) return V2W_E_ARG;
+    LsArgs A;
+    unsigned maxnumel;
+    if (const int rc = ls_args(items, n, false, &A, &maxnumel)) return rc;
+    V2W_LAUNCH(lsgan_multi_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, A, term, total);
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_lsgan_multi_bwd(const v2w_lsgan_item* items, int n, const float* gout, const float* gterm, void* stream) {
+    if (!gout && !gterm) return V2W_E_ARG;
+    LsArgs A;
+    unsigned maxnumel;
+    if (const int rc = ls_args(items, n, true, &A, &maxnumel)) return rc;
+    A.gout = gout; A.gterm = gterm;
+    unsigned nbx = (maxnumel + kThreads - 1) / kThreads;
+    if (nbx > 256) nbx = 256;
+    V2W_LAUNCH(lsgan_multi_bwd_kernel, dim3(nbx, n), dim3(kThreads), 0, (hipStream_t)stream, A);
+    return v2w_launch_status();
+}

@@ -685,22 +685,106 @@ def set_precision(module, precision):
     return module
 
 
+class _L1MultiFn(torch.autograd.Function):
+    """scale * sum_i mean |a_i - b_i| over n map pairs (inputs: a_0 .. a_{n-1}, b_0 .. b_{n-1}) on the multi-tensor L1 kernels: the forward
+    is one streaming and one finishing launch for all pairs, the backward one launch that writes only the sides that ask for a gradient
+    and reads the incoming gradient on the device.  Like `_L1MeanFn` it saves nothing but the maps (alive anyway), which are read in place
+    - pitched views and batch halves included (hipops.loss_rows)."""
+
+    @staticmethod
+    def forward(ctx, scale, n, *maps):
+        ctx.scale, ctx.n = scale, n
+        ctx.save_for_backward(*maps)
+        return hipops.l1_mean_multi(list(zip(maps[:n], maps[n:])), scale)[1]
+
+    @staticmethod
+    @_hip.on_tensor_device
+    def backward(ctx, g):
+        maps, n = ctx.saved_tensors, ctx.n
+        need = ctx.needs_input_grad[2:]
+        da, db = hipops.l1_mean_multi_bwd(list(zip(maps[:n], maps[n:])), ctx.scale, g.contiguous(), need[:n], need[n:])
+        return (None, None, *da, *db)
+
+
+class _LsganFn(torch.autograd.Function):
+    """(sum_i mean (t_i - s_i)^2, the n terms) of n score tensors with targets t_i in {0, 1}: one launch forward, one backward (gradients
+    that arrive on the total and on single terms are added inside the kernel)."""
+
+    @staticmethod
+    def forward(ctx, targets, *scores):
+        ctx.targets = targets
+        ctx.save_for_backward(*scores)
+        ctx.set_materialize_grads(False)
+        terms, total = hipops.lsgan_multi(scores, targets)
+        return total, terms
+
+    @staticmethod
+    def backward(ctx, g_total, g_terms):
+        scores = ctx.saved_tensors
+        if g_total is None and g_terms is None:
+            return (None,) * (1 + len(scores))
+        with torch.cuda.device(scores[0].device):
+            ds = hipops.lsgan_multi_bwd(scores, ctx.targets, None if g_total is None else g_total.contiguous(),
+                                        None if g_terms is None else g_terms.contiguous(), ctx.needs_input_grad[1:])
+        return (None, *ds)
+
+
+def _any_cpu(tensors):
+    return any(not t.is_cuda for t in tensors)
+
+
+def _lsgan(scores, targets):
+    """(total, terms (n,)) of the LSGAN terms of GPU score tensors: one launch per hipops.LOSS_MAX_ITEMS tensors."""
+    cap = _hip.LOSS_MAX_ITEMS
+    outs = [_LsganFn.apply(tuple(targets[i:i + cap]), *scores[i:i + cap]) for i in range(0, len(scores), cap)]
+    if len(outs) == 1:
+        return outs[0]
+    return sum(t for t, _ in outs), torch.cat([x for _, x in outs])
+
+
+def l1_mean_loss(a, b):
+    """mean |a - b| (F.l1_loss with the default reduction: the mel term of train.py:204), differentiable in both arguments; GPU tensors run
+    on the multi-tensor L1 kernels as one pair."""
+    if _any_cpu((a, b)):
+        return F.l1_loss(a, b)
+    if a.shape != b.shape:
+        raise ValueError(f'l1_mean_loss: shapes differ: {tuple(a.shape)} and {tuple(b.shape)}')
+    return _L1MultiFn.apply(1.0, 1, a, b)
+
+
 def feature_loss(fmap_r, fmap_g):
-    """2 x the sum over every feature map of mean |real - generated| (models.py:278-284)."""
-    terms = [_L1MeanFn.apply(real, fake) for maps_r, maps_g in zip(fmap_r, fmap_g) for real, fake in zip(maps_r, maps_g)]
-    return 2 * sum(terms)
+    """2 x the sum over every feature map of mean |real - generated| (models.py:278-284).  GPU maps: all pairs of the call in one
+    autograd.Function (hipops.LOSS_MAX_ITEMS pairs per launch); CPU maps: the torch expressions."""
+    pairs = [(real, fake) for maps_r, maps_g in zip(fmap_r, fmap_g) for real, fake in zip(maps_r, maps_g)]
+    if not pairs or _any_cpu(t for p in pairs for t in p):
+        terms = [_L1MeanFn.apply(real, fake) for real, fake in pairs]
+        return 2 * sum(terms)
+    cap = _hip.LOSS_MAX_ITEMS
+    parts = [_L1MultiFn.apply(2.0, len(grp), *[r for r, _ in grp], *[f for _, f in grp])
+             for grp in (pairs[i:i + cap] for i in range(0, len(pairs), cap))]
+    return parts[0] if len(parts) == 1 else sum(parts)
 
 
 def discriminator_loss(disc_real_outputs, disc_generated_outputs):
     """LSGAN discriminator loss: sum over discriminators of mean (1 - D(y))^2 + mean D(y_hat)^2; also the per-discriminator
-    values as Python floats (models.py:287-299)."""
-    real_terms = [torch.mean((1 - score) ** 2) for score in disc_real_outputs]
-    fake_terms = [torch.mean(score ** 2) for score in disc_generated_outputs]
-    total = sum(r + f for r, f in zip(real_terms, fake_terms))
-    return total, [t.item() for t in real_terms], [t.item() for t in fake_terms]
+    values as Python floats (models.py:287-299).  GPU scores: one launch, and one device-to-host copy for all the floats."""
+    nr = min(len(disc_real_outputs), len(disc_generated_outputs))
+    scores = list(disc_real_outputs[:nr]) + list(disc_generated_outputs[:nr])
+    if not scores or _any_cpu(scores):
+        real_terms = [torch.mean((1 - score) ** 2) for score in disc_real_outputs]
+        fake_terms = [torch.mean(score ** 2) for score in disc_generated_outputs]
+        total = sum(r + f for r, f in zip(real_terms, fake_terms))
+        return total, [t.item() for t in real_terms], [t.item() for t in fake_terms]
+    total, terms = _lsgan(scores, (1.0,) * nr + (0.0,) * nr)
+    vals = terms.detach().tolist()
+    return total, vals[:nr], vals[nr:]
 
 
 def generator_loss(disc_outputs):
-    """LSGAN generator loss: sum over discriminators of mean (1 - D(y_hat))^2, and the terms (models.py:302-310)."""
-    terms = [torch.mean((1 - score) ** 2) for score in disc_outputs]
-    return sum(terms), terms
+    """LSGAN generator loss: sum over discriminators of mean (1 - D(y_hat))^2, and the terms (models.py:302-310).  GPU scores: one launch."""
+    scores = list(disc_outputs)
+    if not scores or _any_cpu(scores):
+        terms = [torch.mean((1 - score) ** 2) for score in disc_outputs]
+        return sum(terms), terms
+    total, terms = _lsgan(scores, (1.0,) * len(scores))
+    return total, list(terms.unbind(0))

@@ -997,3 +997,203 @@ def channel_sum(x):
     part = torch.empty((2 * Cc * _hip.V2W_BN_SPLITS,), device=x.device, dtype=torch.float64)
     bn_stats(x, stats, part)
     return stats[:Cc].float()
+
+
+# ---- GAN training losses (include/vec2wav_hip.h: v2w_l1_mean_multi / v2w_lsgan_multi and their backwards)
+def _dense_suffix(dims):
+    """How many trailing (size, stride) pairs form one contiguous run of floats."""
+    n, run = 0, 1
+    for size, stride in reversed(dims):
+        if stride != run:
+            break
+        run *= size
+        n += 1
+    return n
+
+
+def _dims(t):
+    return [(s, st) for s, st in zip(t.shape, t.stride()) if s != 1]
+
+
+def _rows_at(t, dims, k, aligned):
+    """(rows, valid, pitch) of `t` with its last k (non-unit) dims as one row, or None when the leading dims do not sit one pitch apart
+    (or, with `aligned`, pitched rows do not begin on 16-byte lines)."""
+    if k == len(dims):                                    # dense: one run; cut at the last dim only when it would not fit an int32
+        numel = t.numel()
+        if numel < 2 ** 31:
+            return 1, numel, numel
+        last = dims[-1][0]
+        return numel // last, last, last
+    if k == 0:
+        return None
+    valid = 1
+    for size, _ in dims[-k:]:
+        valid *= size
+    rows, pitch = 1, dims[-k - 1][1]
+    for i in range(len(dims) - k - 1, -1, -1):
+        if dims[i][1] != pitch * rows:
+            return None
+        rows *= dims[i][0]
+    if pitch < valid or valid >= 2 ** 31 or pitch >= 2 ** 31:
+        return None
+    if aligned and pitch != valid and (pitch % 4 or t.data_ptr() % 16):
+        return None
+    return rows, valid, pitch
+
+
+def loss_rows(t, like=None, aligned=True):
+    """The (rows, valid, pitch) descriptor of a tensor for the loss kernels - `rows` rows of `valid` contiguous floats, `pitch` floats
+    apart - straight from its strides, or None when it has no such form and must be made contiguous.  Dense tensors, last-dim slices
+    of pitched (B, C, P) buffers, their 4-D (b, C, U, inner) views and leading-dim slices of all of these qualify.  `like`: the other
+    tensor of an L1 pair (same shape): both are cut into the same rows.  `aligned`: pitched rows must start on 16-byte lines and
+    pitch % 4 == 0 (the L1 kernels' 16-byte loads; the LSGAN kernels read float by float)."""
+    if t.numel() == 0:
+        raise ValueError('loss of an empty tensor')
+    dims = _dims(t)
+    k = _dense_suffix(dims)
+    if like is not None:
+        if like.shape != t.shape:
+            raise ValueError(f'shapes differ: {tuple(t.shape)} and {tuple(like.shape)}')
+        k = min(k, _dense_suffix(_dims(like)))
+    return _rows_at(t, dims, k, aligned)
+
+
+def _loss_check(t, name):
+    if not t.is_cuda:
+        raise RuntimeError(f'{name} must live on a GPU: the HIP loss kernels have no CPU fallback')
+    if t.dtype != torch.float32:
+        raise TypeError(f'{name} must be torch.float32, got {t.dtype}')
+
+
+def _l1_pair_array(pairs):
+    """ctypes descriptors of the pairs and the tensors they point into (contiguous copies where a view has no row form)."""
+    n = len(pairs)
+    arr = (_hip.L1Pair * max(n, 1))()
+    keep = []
+    for i, (a, b) in enumerate(pairs):
+        _loss_check(a, 'a'); _loss_check(b, 'b')
+        if a.device != pairs[0][0].device or b.device != a.device:
+            raise RuntimeError('all tensors of one loss call must live on one device')
+        a, b = a.detach(), b.detach()
+        for _ in range(3):
+            fa, fb = loss_rows(a, b), loss_rows(b, a)
+            if fa is not None and fb is not None:
+                break
+            if fa is None:
+                a = a.contiguous()
+            if fb is None:
+                b = b.contiguous()
+        assert fa[:2] == fb[:2], (fa, fb)
+        keep += [a, b]
+        d = arr[i]
+        d.a, d.b, d.rows, d.valid, d.pitch_a, d.pitch_b = a.data_ptr(), b.data_ptr(), fa[0], fa[1], fa[2], fb[2]
+    return arr, keep
+
+
+def l1_plan(arr, n):
+    """(starts, workgroups) of v2w_l1_multi_plan for n descriptors."""
+    starts = (C.c_int32 * (n + 1))()
+    nwg = _hip.load().v2w_l1_multi_plan(arr, n, starts)
+    if nwg <= 0:
+        _hip.check(nwg or -1, 'v2w_l1_multi_plan')
+    return list(starts), nwg
+
+
+def l1_mean_multi(pairs, scale=1.0):
+    """pairs: [(a, b), ...] of equal-shaped fp32 GPU tensors (at most 64) -> (terms (n,), total ()): terms[i] = mean |a_i - b_i|,
+    total = scale * sum(terms); one streaming and one finishing launch, deterministic.  The views the discriminators return are read
+    in place (loss_rows)."""
+    n = len(pairs)
+    if n == 0:
+        raise ValueError('no pairs')
+    arr, keep = _l1_pair_array(pairs)
+    dev = keep[0].device
+    with torch.cuda.device(dev):
+        lib = _hip.load()
+        nbytes = lib.v2w_l1_multi_scratch_bytes(arr, n)
+        if nbytes <= 0:
+            _hip.check(int(nbytes) or -1, 'v2w_l1_multi_scratch_bytes')
+        scratch = torch.empty((nbytes // 8,), device=dev, dtype=torch.float64)
+        terms = torch.empty((n,), device=dev, dtype=torch.float32)
+        total = torch.empty((), device=dev, dtype=torch.float32)
+        _hip.check(lib.v2w_l1_mean_multi(arr, n, float(scale), terms.data_ptr(), total.data_ptr(), scratch.data_ptr(), _stream(keep[0])),
+                   'v2w_l1_mean_multi')
+    return terms, total
+
+
+def l1_mean_multi_bwd(pairs, scale, gout, need_a=None, need_b=None):
+    """Gradients of `gout * l1_mean_multi(pairs, scale)[1]`: ([da_i | None], [db_i | None]), dense, shaped like the inputs; one launch.
+    gout: a one-element fp32 GPU tensor, read by the kernel.  need_a / need_b: per pair, which sides to write (default: all)."""
+    n = len(pairs)
+    need_a = [True] * n if need_a is None else list(need_a)
+    need_b = [True] * n if need_b is None else list(need_b)
+    arr, keep = _l1_pair_array(pairs)
+    dev = keep[0].device
+    _loss_check(gout, 'gout')
+    if gout.numel() != 1:
+        raise ValueError('gout must hold one element')
+    da = [torch.empty(a.shape, device=dev, dtype=torch.float32) if w else None for (a, _), w in zip(pairs, need_a)]
+    db = [torch.empty(b.shape, device=dev, dtype=torch.float32) if w else None for (_, b), w in zip(pairs, need_b)]
+    for i in range(n):
+        arr[i].da, arr[i].db = _hip.ptr(da[i]), _hip.ptr(db[i])
+    if any(need_a) or any(need_b):
+        with torch.cuda.device(dev):
+            _hip.check(_hip.load().v2w_l1_mean_multi_bwd(arr, n, float(scale), gout.data_ptr(), _stream(keep[0])), 'v2w_l1_mean_multi_bwd')
+    return da, db
+
+
+def _lsgan_array(scores, targets):
+    n = len(scores)
+    if len(targets) != n:
+        raise ValueError('one target per score tensor')
+    arr = (_hip.LsganItem * max(n, 1))()
+    keep = []
+    for i, (s, t) in enumerate(zip(scores, targets)):
+        _loss_check(s, 'score')
+        if s.device != scores[0].device:
+            raise RuntimeError('all tensors of one loss call must live on one device')
+        s = s.detach()
+        form = loss_rows(s, aligned=False)
+        if form is None:
+            s = s.contiguous()
+            form = loss_rows(s, aligned=False)
+        keep.append(s)
+        d = arr[i]
+        d.s, d.rows, d.valid, d.pitch, d.target = s.data_ptr(), form[0], form[1], form[2], float(t)
+    return arr, keep
+
+
+def lsgan_multi(scores, targets):
+    """scores: fp32 GPU tensors (at most 64), targets: 0 / 1 each -> (terms (n,), total ()): terms[i] = mean (target_i - s_i)^2,
+    total = sum(terms); one launch."""
+    n = len(scores)
+    if n == 0:
+        raise ValueError('no scores')
+    arr, keep = _lsgan_array(scores, targets)
+    dev = keep[0].device
+    terms = torch.empty((n,), device=dev, dtype=torch.float32)
+    total = torch.empty((), device=dev, dtype=torch.float32)
+    with torch.cuda.device(dev):
+        _hip.check(_hip.load().v2w_lsgan_multi(arr, n, terms.data_ptr(), total.data_ptr(), _stream(keep[0])), 'v2w_lsgan_multi')
+    return terms, total
+
+
+def lsgan_multi_bwd(scores, targets, gout=None, gterms=None, need=None):
+    """Gradients of lsgan_multi: ds_i = 2 (s_i - target_i) * (gout + gterms[i]) / numel_i, dense, shaped like the scores; one launch.
+    gout (one element) / gterms (n): fp32 GPU tensors, read by the kernel; one of them may be None."""
+    n = len(scores)
+    need = [True] * n if need is None else list(need)
+    arr, keep = _lsgan_array(scores, targets)
+    dev = keep[0].device
+    for g, name, cnt in ((gout, 'gout', 1), (gterms, 'gterms', n)):
+        if g is not None:
+            _loss_check(g, name)
+            if g.numel() != cnt or not g.is_contiguous():
+                raise ValueError(f'{name} must hold {cnt} contiguous element(s)')
+    ds = [torch.empty(s.shape, device=dev, dtype=torch.float32) if w else None for s, w in zip(scores, need)]
+    for i in range(n):
+        arr[i].ds = _hip.ptr(ds[i])
+    if any(need):
+        with torch.cuda.device(dev):
+            _hip.check(_hip.load().v2w_lsgan_multi_bwd(arr, n, _hip.ptr(gout), _hip.ptr(gterms), _stream(keep[0])), 'v2w_lsgan_multi_bwd')
+    return ds
