@@ -1,14 +1,5 @@
 // extern "C" dispatch of the conv entry points declared in include/vec2wav_hip.h.
-#include "v2w_common.h"
-
-int v2w_conv1d_mfma(const v2w_conv1d_args* a, int n, hipStream_t stream, int* cfg_out, long long* ws_query = nullptr,
-                    const int32_t* len = nullptr, int len_mul = 1);
-int v2w_convt1d_mfma(const v2w_convt1d_args* a, hipStream_t stream, int* cfg_out, long long* ws_query = nullptr,
-                     const int32_t* len = nullptr, int len_mul = 1);
-int v2w_conv1d_split(const v2w_conv1d_args* a, int n, hipStream_t stream, bool bf16);
-int v2w_conv1d_direct(const v2w_conv1d_args* a, hipStream_t stream);
-int v2w_conv1d_wino(const v2w_conv1d_args* a, int n, hipStream_t stream, const int32_t* len = nullptr, int len_mul = 1);
-int v2w_convt1d_direct(const v2w_convt1d_args* a, hipStream_t stream);
+#include "v2w_internal.h"
 
 extern "C" int v2w_abi_version(void) { return V2W_ABI_VERSION; }
 extern "C" const char* v2w_build_arch(void) { return "gfx950"; }

@@ -37,7 +37,7 @@ static inline int v2w_launch_status() {
 static inline bool v2w_dry(hipStream_t s) { return s == V2W_DRY_STREAM; }
 
 // Name sink (include/vec2wav_hip.h, ABI v33): a "stream" with bit 0 set that is not the dry-run sentinel points at the caller's v2w_name_sink.
-// A call made with it goes as far as a real call - every launch site is V2W_LAUNCH, every attribute change V2W_MAX_LDS - and appends the
+// A call made with it goes as far as a real call - every launch site is V2W_LAUNCH, every attribute change v2w_max_lds() - and appends the
 // demangled name of each kernel it reaches instead of launching it.  The runtime maps the host stub to the kernel's symbol
 // (hipKernelNameRefByPtr: a table lookup, no device needed), so no launch site spells a name.
 static inline v2w_name_sink* v2w_sink(hipStream_t s) {
@@ -69,6 +69,33 @@ static inline void v2w_sink_add(v2w_name_sink* k, const void* host_fn) {
 // per-device state to remember it in); nothing to set for a name sink
 static inline hipError_t v2w_max_lds(const void* host_fn, int lds, hipStream_t s) {
     return v2w_sink(s) ? hipSuccess : hipFuncSetAttribute(host_fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+}
+
+// The launch of a kernel that may need more than 64 KB of dynamic LDS (160 KB per workgroup is the CU's all): V2W_E_SHAPE past that, the
+// attribute's error if it cannot be set, else the launch and its status.
+template <typename K, typename... A>
+static inline int v2w_launch_lds(K kern, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args) {
+    if (lds > 64 * 1024) {
+        if (lds > 160 * 1024) return V2W_E_SHAPE;
+        hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kern), (int)lds, stream);
+        if (e != hipSuccess) return (int)e;
+    }
+    V2W_LAUNCH(kern, grid, block, lds, stream, args...);
+    return v2w_launch_status();
+}
+
+static inline bool v2w_al16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }   // 16-byte aligned (or NULL)
+
+// start[0 .. nmax] of a launch that carries n <= nmax problems side by side: workgroups [start[q], start[q + 1]) belong to problem q, which
+// owns blocks[q] of them; the entries past start[n] hold a sentinel no workgroup id reaches (the kernels count the entries <= blockIdx.x).
+// Returns the grid.
+static inline int v2w_fill_starts(int* start, int nmax, const int* blocks, int n) {
+    int grid = 0;
+    for (int i = 0; i <= nmax; ++i) {
+        start[i] = i <= n ? grid : 0x7fffffff;
+        if (i < n) grid += blocks[i];
+    }
+    return grid;
 }
 
 // Compute units of the CURRENT device (the device the caller's stream belongs to: every entry point runs with it made current).

@@ -23,6 +23,7 @@
 // mode a stage of it was 128 cycles of MFMA issue in ~1300 cycles.
 #include <type_traits>
 #include "v2w_tile.h"
+#include "v2w_internal.h"
 
 namespace {
 
@@ -50,15 +51,12 @@ conv_bf16_kernel(const MultiArgs m) {
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_b[];   // 2 x [xrows][ROWB] signal tiles, then the float tables
 
-    int pq = 0;
-#pragma unroll
-    for (int i = 1; i < V2W_MAX_MULTI; ++i) pq += (int)blockIdx.x >= m.start[i] ? 1 : 0;
+    const int pq = tile_problem(m);
     const TileArgs p = pinned_tile_args(m.p[pq]);
     const int mtiles = p.Cout / MT;
     const int id = blockIdx.x - m.start[pq];
-    const int grp = id / (8 * mtiles), rem = id % (8 * mtiles);
-    const int mt = rem >> 3;
-    const int tile = grp * 8 + (rem & 7);
+    const TileId ti = tile_coords(mtiles, id);
+    const int mt = ti.mt, tile = ti.tile;
     if (tile >= p.ntiles) return;
     const int b = tile / p.ntl;
     const int n0 = (tile % p.ntl) * NT;
@@ -738,7 +736,7 @@ int launch_bf16(const TileArgs* ps, int nprob, hipStream_t stream, int32_t* cfg 
     static_assert(NI % 2 == 0, "the epilogue walks column blocks in pairs");
     MultiArgs m{};
     size_t lds = 0;
-    int grid = 0, epi = 0;
+    int blocks[V2W_MAX_MULTI], epi = 0;
     for (int i = 0; i < nprob; ++i) {
         TileArgs p = ps[i];
         if (p.Cout % MT != 0 || p.Cin % CK != 0) return V2W_E_SHAPE;
@@ -747,24 +745,21 @@ int launch_bf16(const TileArgs* ps, int nprob, hipStream_t stream, int32_t* cfg 
         p.ntl = (p.L + NT - 1) / NT;
         p.ntiles = p.B * p.ntl;
         p.xrows = (p.hla + NT + p.hr + 3) & ~3;
-        p.vec4 = (p.L % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.in) & 15) == 0);
+        p.vec4 = (p.L % 4 == 0) && v2w_al16(p.in);
         if (VEC && !p.vec4) return V2W_E_ARG;                  // (the dispatcher sends unaligned inputs to the VEC = false instantiation)
         const int nbuf = p.Cin / CK > 1 ? 2 : 1;
         int tab = nbuf * p.xrows * ROWB / 4;                        // float index of the tables, after the signal buffers ...
         if (tab < WM * WN * 32 * 64) tab = WM * WN * 32 * 64;              // ... and after the epilogue scratch that overlays them
         p.atab_off = tab;
-        auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        p.evec = p.L % 4 == 0 && al16(p.out) && al16(p.res) && al16(p.add0) && al16(p.add1) && al16(p.mask_src);
+        p.evec = p.L % 4 == 0 && v2w_al16(p.out) && v2w_al16(p.res) && v2w_al16(p.add0) && v2w_al16(p.add1) && v2w_al16(p.mask_src);
         const size_t l = ((size_t)tab + 5 * MT + 2 * p.Cin) * sizeof(float);
         if (l > lds) lds = l;
         if (p.mask_src) epi = 1;
         m.p[i] = p;
-        m.start[i] = grid;
-        grid += ((p.ntiles + 7) / 8) * 8 * (p.Cout / MT);
+        blocks[i] = tile_blocks(p.ntiles, p.Cout / MT);
     }
-    m.start[nprob] = grid;
-    for (int i = nprob + 1; i <= V2W_MAX_MULTI; ++i) m.start[i] = 0x7fffffff;
-    if (lds > 160 * 1024) return V2W_E_SHAPE;
+    const int grid = v2w_fill_starts(m.start, V2W_MAX_MULTI, blocks, nprob);
+    if (lds > 160 * 1024) return V2W_E_SHAPE;     // (here and not only in v2w_launch_lds: V2W_E_SHAPE comes before the io_bf16 codes and before a query's answer)
     const int io = m.p[0].io_bf16;
     for (int i = 1; i < nprob; ++i) if (m.p[i].io_bf16 != io) return V2W_E_ARG;      // one instantiation per launch
     if (io == 1 || (epi && io != 0)) return V2W_E_SHAPE;     // bf16 in with fp32 out does not occur on the path; the mask epilogue is fp32-only
@@ -777,12 +772,7 @@ int launch_bf16(const TileArgs* ps, int nprob, hipStream_t stream, int32_t* cfg 
               : io == 0 ? conv_bf16_kernel<MI, NI, WM, WN, NPF, 0, false, false, CK, VEC>
               : io == 2 ? conv_bf16_kernel<MI, NI, WM, WN, NPF, 0, false, true, CK, VEC>
                         : conv_bf16_kernel<MI, NI, WM, WN, NPF, 0, true, true, CK, VEC>;
-    if (lds > 64 * 1024) {
-        hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kern), (int)lds, stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    V2W_LAUNCH(kern, dim3(grid), dim3(NTHREADS), lds, stream, m);
-    return v2w_launch_status();
+    return v2w_launch_lds(kern, dim3(grid), dim3(NTHREADS), lds, stream, m);
 }
 
 // Virtual 3-tap (in general hl + hr + 1 tap) conv weights of a transposed conv, as bf16 fragments in the layout of pack_bf16_kernel:
@@ -808,10 +798,6 @@ pack_bf16_convt_kernel(const float* __restrict__ wf, b8* __restrict__ wps, int K
         wps[(((size_t)(mb * nch + ch) * KV + tv) * 2) * 64 + lane] = hi;
     }
 }
-
-}  // namespace
-int v2w_convt1d_bf16_res(const v2w_convt1d_args* a, int UP, int hl, int KV, hipStream_t stream, int* ntiles_out, int32_t* cfg);   // v2w_convt_bf16_res.hip
-namespace {
 
 struct ConvtGeom { int UP, hl, hr, KV; };
 static ConvtGeom convt_geom(int k, int u) {
@@ -844,8 +830,8 @@ int launch_bf16_convt(TileArgs p, hipStream_t stream, int* ntiles_out, int32_t* 
     p.ntl = (p.L + NT - 1) / NT;
     p.ntiles = p.B * p.ntl;
     p.xrows = (p.hla + NT + p.hr + 3) & ~3;
-    p.vec4 = (p.L % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.in) & 15) == 0);
-    p.evec = (p.L % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.out) & 15) == 0);
+    p.vec4 = (p.L % 4 == 0) && v2w_al16(p.in);
+    p.evec = (p.L % 4 == 0) && v2w_al16(p.out);
     const int nbuf = p.Cin / V2W_BF_CK > 1 ? 2 : 1;
     int tab = nbuf * p.xrows * V2W_BF_ROWB / 4;
     if (tab < WM * WN * 2048) tab = WM * WN * 2048;
@@ -859,17 +845,10 @@ int launch_bf16_convt(TileArgs p, hipStream_t stream, int* ntiles_out, int32_t* 
     if (ntiles_out) { *ntiles_out = p.ntiles; return 0; }
     MultiArgs m{};
     m.p[0] = p;
-    m.start[0] = 0;
-    const int grid = ((p.ntiles + 7) / 8) * 8 * (p.Cout / MT);
-    m.start[1] = grid;
-    for (int i = 2; i <= V2W_MAX_MULTI; ++i) m.start[i] = 0x7fffffff;
+    const int blocks = tile_blocks(p.ntiles, p.Cout / MT);
+    const int grid = v2w_fill_starts(m.start, V2W_MAX_MULTI, &blocks, 1);
     auto kern = p.io_bf16 ? conv_bf16_kernel<MI, NI, WM, WN, NPF, 2, true, true, V2W_BF_CK, VEC> : conv_bf16_kernel<MI, NI, WM, WN, NPF, 2, false, false, V2W_BF_CK, VEC>;
-    if (lds > 64 * 1024) {
-        hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kern), (int)lds, stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    V2W_LAUNCH(kern, dim3(grid), dim3(NTHREADS), lds, stream, m);
-    return v2w_launch_status();
+    return v2w_launch_lds(kern, dim3(grid), dim3(NTHREADS), lds, stream, m);
 }
 
 static int convt_bf16_dispatch(const v2w_convt1d_args* a, hipStream_t stream, int* ntiles_out, int32_t* cfg = nullptr) {
@@ -888,7 +867,7 @@ static int convt_bf16_dispatch(const v2w_convt1d_args* a, hipStream_t stream, in
     const int rows = p.Cout;
     // the stats tiling (rows of stats_part) depends on the tile width only: every configuration here is 256 or 512 positions wide, the
     // element-wise-staging fallback (unaligned input or a length that is not a multiple of 4) uses the widths of its aligned twin
-    const bool vec = (a->L % 4 == 0) && ((reinterpret_cast<uintptr_t>(a->in) & 15) == 0);
+    const bool vec = (a->L % 4 == 0) && v2w_al16(a->in);
     if (!vec) {     // (queries too: the answer comes from the instantiation that will launch, with every one of its checks)
         if (rows % 64 == 0 && !(rows % 128 == 0 && (long)a->B * ((a->L + 255) / 256) * (rows / 128) >= 512)) return launch_bf16_convt<1, 4, 2, 2, false>(p, stream, ntiles_out, cfg);
         if (rows % 128 == 0) return launch_bf16_convt<2, 4, 2, 2, false>(p, stream, ntiles_out, cfg);
@@ -934,11 +913,11 @@ int v2w_conv1d_bf16(const v2w_conv1d_args* a, int n, hipStream_t stream, int32_t
     }
     if (c32) {                           // one 32-row block x 256 positions per workgroup, aligned fp32 tensors only
         for (int i = 0; i < n; ++i)
-            if (a[i].L % 4 != 0 || (reinterpret_cast<uintptr_t>(a[i].in) & 15) != 0 || a[i].io_bf16 != 0) return V2W_E_SHAPE;
+            if (a[i].L % 4 != 0 || !v2w_al16(a[i].in) || a[i].io_bf16 != 0) return V2W_E_SHAPE;
         return launch_bf16<1, 2, 1, 4>(ps, n, stream, cfg);
     }
     for (int i = 0; i < n; ++i)          // unaligned input or L % 4 != 0: element-wise staging, one small-tile instantiation serves every shape
-        if (a[i].L % 4 != 0 || (reinterpret_cast<uintptr_t>(a[i].in) & 15) != 0) return launch_bf16<1, 2, 2, 2, V2W_BF_CK, false>(ps, n, stream, cfg);
+        if (a[i].L % 4 != 0 || !v2w_al16(a[i].in)) return launch_bf16<1, 2, 2, 2, V2W_BF_CK, false>(ps, n, stream, cfg);
     if (a->C_out % 128 == 0 && tiles >= 2 * 512) return launch_bf16<2, 4, 2, 2>(ps, n, stream, cfg);     // 128 x 256
     if (tiles >= 256 && a->C_in == 64 && a->io_bf16 == 3) return launch_bf16<1, 4, 2, 2, 64>(ps, n, stream, cfg);   // 64 x 256, bf16 tensors: the 64 input channels as ONE chunk
     // a deep layer (conv_pre: 768 / 1024 input channels x 7 taps) on a grid of one 64 x 256 tile per CU or less walks 24+ chunks behind a

@@ -415,14 +415,9 @@ int launch_res(const v2w_branch_convs_args* q, hipStream_t stream) {
     if (q->C % MT != 0) return V2W_E_SHAPE;
     const size_t lds = (size_t)(q->C / 32) * p.xrows * 64 + (size_t)(V2W_RS_MAXB * MT + 2 * q->C) * sizeof(float);
     if (2 * lds > 160 * 1024) return V2W_E_SHAPE;            // two workgroups per CU, or the structure does not pay
-    const int grid = ((p.ntiles + 7) / 8) * 8 * (q->C / MT);
+    const int grid = tile_blocks(p.ntiles, q->C / MT);
     auto kern = q->mode == 0 ? conv_bf16_res_kernel<MI, NI, WM, WN, 0> : conv_bf16_res_kernel<MI, NI, WM, WN, 1>;
-    if (lds > 64 * 1024) {
-        hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kern), (int)lds, stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    V2W_LAUNCH(kern, dim3(grid), dim3(NTH), lds, stream, p);
-    return v2w_launch_status();
+    return v2w_launch_lds(kern, dim3(grid), dim3(NTH), lds, stream, p);
 }
 
 }  // namespace

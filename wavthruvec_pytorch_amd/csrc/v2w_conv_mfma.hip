@@ -29,6 +29,7 @@
 //                64-lane fragments: lane&(MF-1) = row/col inside the MFMA tile, lane/MF = k index.
 #include <type_traits>
 #include "v2w_tile.h"
+#include "v2w_internal.h"
 #include "v2w_wino.h"
 
 #ifdef V2W_TIMELINE   // diagnostic build only (see v2w_common.h)
@@ -36,22 +37,6 @@ V2W_TL_SETTER(v2w_timeline_set_tile)
 #endif
 
 namespace {
-
-// Geometry of the LDS signal tile: [positions][RS floats], the CK channels of a row permuted so that the four k-steps a lane feeds
-// to one packed weight fragment (v2w_pack_mfma pairs k-step kk, lane half hk with channel 8g + 2kk + hk for the 32x32x2 MFMA and
-// 4kk + hk for 16x16x4) are 16 contiguous bytes.  RS is the smallest 16-byte-aligned stride that keeps the wave's ds_read_b128
-// (lane -> row, lane half -> slot quad) bank-conflict free.  Staging writes slot-adjacent channel PAIRS (c0, c0 + PAIR_DC).
-template <int MF, int CK> struct TileGeom {
-    static constexpr int RS = CK == 32 ? 36 : (MF == 32 ? 20 : 24);
-    static constexpr int PAIR_DC = MF == 32 ? 2 : 4;
-    __host__ __device__ static constexpr int slot(int c) {
-        return MF == 32 ? ((c & ~7) + 4 * (c & 1) + ((c & 7) >> 1)) : (4 * (c & 3) + (c >> 2));
-    }
-    // first channel of the pair that occupies slots 2P, 2P + 1
-    __host__ __device__ static constexpr int pair_c0(int P) {
-        return MF == 32 ? (8 * (P >> 2) + 4 * (P & 1) + ((P >> 1) & 1)) : (8 * (P & 1) + (P >> 1));
-    }
-};
 
 // EPI: which optional epilogue is compiled in.  0 = none (the generator's forward kernels).  1 = the backward-only leaky_relu-
 // derivative mask (+ out_slope): it costs 8 VGPRs (one occupancy step on the 128 x 128 tile, 5-12 % of a layer's time), so it is
@@ -82,8 +67,8 @@ conv_tile_kernel(const MultiArgs m) {
 
     extern __shared__ __attribute__((aligned(16))) float smem[];   // 2 x [xrows][RS] signal tiles, then the tables
 
-    // ---- which tile: ids that differ by a multiple of 8 tend to share an XCD (and its L2), so the M-tiles that
-    // re-read the same input tile are placed 8 apart (speed only, never correctness).
+    // ---- which tile (the tile map of v2w_tile.h; the problem lookup is spelled out here: through tile_problem() hipcc allocates the
+    // accumulators of the CK = 16 masked tile differently, with AGPR copies around its MFMA loop)
     int pq = 0;
 #pragma unroll
     for (int i = 1; i < V2W_MAX_MULTI; ++i) pq += (int)blockIdx.x >= m.start[i] ? 1 : 0;
@@ -92,13 +77,12 @@ conv_tile_kernel(const MultiArgs m) {
     int id = blockIdx.x - m.start[pq];
     int slice = 0;                            // split over C_in chunks (launch_tile): the grid repeats the tiles once per slice
     if (p.ksplit > 1) {
-        const int per = ((p.ntiles + 7) >> 3) * 8 * mtiles;
+        const int per = tile_blocks(p.ntiles, mtiles);
         slice = id / per;
         id -= slice * per;
     }
-    const int grp = id / (8 * mtiles), rem = id % (8 * mtiles);
-    const int mt = rem >> 3;
-    const int tile = grp * 8 + (rem & 7);
+    const TileId ti = tile_coords(mtiles, id);
+    const int mt = ti.mt, tile = ti.tile;
     if (tile >= p.ntiles) return;
     const int b = tile / p.ntl;
     const int n0 = (tile % p.ntl) * NT;   // first input-rate position of the tile
@@ -666,7 +650,7 @@ int launch_tile(const TileArgs* ps, int nprob, hipStream_t stream) {
     if (nprob < 1 || nprob > V2W_MAX_MULTI) return V2W_E_ARG;
     MultiArgs m{};
     size_t lds = 0;
-    int grid = 0;
+    int blocks[V2W_MAX_MULTI];
     for (int i = 0; i < nprob; ++i) {
         TileArgs p = ps[i];
         if (p.Cout % MT != 0 || p.Cin % CK != 0) return V2W_E_SHAPE;
@@ -682,12 +666,11 @@ int launch_tile(const TileArgs* ps, int nprob, hipStream_t stream) {
         p.xrows = (p.hla + NT + p.hr + 3) & ~3;
         p.xcols = p.xrows; p.xw = RS;
         if (p.in_stride < 1) p.in_stride = 1;
-        p.vec4 = (p.L % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.in) & 15) == 0) && p.in_stride == 1;
+        p.vec4 = (p.L % 4 == 0) && v2w_al16(p.in) && p.in_stride == 1;
         const int nbuf = p.Cin / CK > 1 ? 2 : 1;
         p.atab_off = nbuf * p.xrows * RS;
         // vector epilogue (conv only): float4 I/O along positions through a wave-private LDS scratch that overlays the signal buffers
-        auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        p.evec = U == 1 && p.L % 4 == 0 && al16(p.out) && al16(p.res) && al16(p.add0) && al16(p.add1) && al16(p.mask_src);
+        p.evec = U == 1 && p.L % 4 == 0 && v2w_al16(p.out) && v2w_al16(p.res) && v2w_al16(p.add0) && v2w_al16(p.add1) && v2w_al16(p.mask_src);
         if (U == 1 && p.atab_off < WM * WN * MF * MF * NI) p.atab_off = WM * WN * MF * MF * NI;   // room for the epilogue scratch
         size_t l = ((size_t)p.atab_off + 5 * MT + (p.in_a ? 2 * p.Cin : 0)) * sizeof(float);
         if (U == 1 && p.stats_part) {                 // row sums of a masked launch (bias gradients): vector epilogue only, [WN][MT] floats behind the tables
@@ -700,12 +683,9 @@ int launch_tile(const TileArgs* ps, int nprob, hipStream_t stream) {
         }
         if (l > lds) lds = l;
         m.p[i] = p;
-        m.start[i] = grid;
-        grid += ((p.ntiles + 7) / 8) * 8 * (p.Cout / MT);
+        blocks[i] = tile_blocks(p.ntiles, p.Cout / MT);
     }
-    for (int i = nprob; i <= V2W_MAX_MULTI; ++i) m.start[i] = i == nprob ? grid : 0x7fffffff;
-    m.start[nprob] = grid;
-    for (int i = nprob + 1; i <= V2W_MAX_MULTI; ++i) m.start[i] = 0x7fffffff;
+    int grid = v2w_fill_starts(m.start, V2W_MAX_MULTI, blocks, nprob);
     int epi = 0;
     for (int i = 0; i < nprob; ++i) {
         if (m.p[i].mask_src != nullptr) epi = 1;
@@ -722,14 +702,13 @@ int launch_tile(const TileArgs* ps, int nprob, hipStream_t stream) {
         // (a launch whose serial chain is short - fewer than 24 (chunk, tap) steps: the narrow upsamplers, 64-channel convs - gains less
         // from the split than the reduce launch behind it costs)
         while (s2 * 2 <= 8 && nch % (s2 * 2) == 0 && grid * s2 * 2 <= 512 && nch * m.p[0].K >= 24) s2 *= 2;
-        auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
         size_t floats = 0;
         bool ok = s2 > 1, vec = true;
         for (int i = 0; i < nprob && ok; ++i) {
             const TileArgs& p = m.p[i];
             const size_t n = (size_t)p.B * p.Cout * p.L * U;
             ok = !p.stats_part && p.CoutT == p.Cout && p.Cin / CK == nch;
-            vec = vec && (p.L * U) % 4 == 0 && al16(p.out) && al16(p.res) && al16(p.add0) && al16(p.add1);
+            vec = vec && (p.L * U) % 4 == 0 && v2w_al16(p.out) && v2w_al16(p.res) && v2w_al16(p.add0) && v2w_al16(p.add1);
             floats += n * s2;
         }
         if (m.p[0].ws_query) {                       // host-only query: bytes of caller scratch this launch would use
@@ -743,7 +722,6 @@ int launch_tile(const TileArgs* ps, int nprob, hipStream_t stream) {
                 red_vec = vec;
                 size_t off = 0;
                 long long f4 = 0;
-                grid = 0;
                 for (int i = 0; i < nprob; ++i) {
                     TileArgs& p = m.p[i];
                     const size_t n = (size_t)p.B * p.Cout * p.L * U;
@@ -754,10 +732,9 @@ int launch_tile(const TileArgs* ps, int nprob, hipStream_t stream) {
                     p.accumulate = 0; p.out_div = 0.f; p.ksplit = S;
                     p.evec = U == 1 && p.L % 4 == 0;
                     off += n * S;
-                    m.start[i] = grid;
-                    grid += ((p.ntiles + 7) / 8) * 8 * (p.Cout / MT) * S;
+                    blocks[i] *= S;
                 }
-                m.start[nprob] = grid;
+                grid = v2w_fill_starts(m.start, V2W_MAX_MULTI, blocks, nprob);
                 red.start[nprob] = f4;
                 red.n = nprob; red.S = S;
             }
@@ -766,35 +743,20 @@ int launch_tile(const TileArgs* ps, int nprob, hipStream_t stream) {
     if (m.p[0].ws_query) { *m.p[0].ws_query = 0; return 0; }
     bool vec = true, len = false;
     for (int i = 0; i < nprob; ++i) { vec = vec && m.p[i].vec4; len = len || m.p[i].len; }
-    if (len) {                                   // (every problem of the launch carries them: v2w_conv1d_mfma / v2w_convt1d_mfma)
-        if (epi != 0) return V2W_E_ARG;
-        auto kl = vec ? conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 3, true> : conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 3, false>;
-        if (lds > 64 * 1024) {
-            if (lds > 160 * 1024) return V2W_E_SHAPE;
-            hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kl), (int)lds, stream);
-            if (e != hipSuccess) return (int)e;
-        }
-        V2W_LAUNCH(kl, dim3(grid), dim3(NTHREADS), lds, stream, m);
-    } else {
-    auto kern = vec ? (epi == 1 ? conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 1, true>
-                       : (epi == 2 ? conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 2, true> : conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 0, true>))
-                    : (epi == 1 ? conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 1, false>
-                       : (epi == 2 ? conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 2, false> : conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 0, false>));
-    if (lds > 64 * 1024) {
-        if (lds > 160 * 1024) return V2W_E_SHAPE;
-        hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kern), (int)lds, stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    V2W_LAUNCH(kern, dim3(grid), dim3(NTHREADS), lds, stream, m);
-    }
-    if (S > 1) {
-        const int rc = v2w_launch_status();
-        if (rc != 0) return rc;
-        long long blocks = (red.start[nprob] + 255) / 256;
-        if (blocks > 2048) blocks = 2048;
-        if (red_vec) V2W_LAUNCH(splitk_reduce_kernel<true>, dim3((int)blocks), dim3(256), 0, stream, red);
-        else V2W_LAUNCH(splitk_reduce_kernel<false>, dim3((int)blocks), dim3(256), 0, stream, red);
-    }
+    if (len && epi != 0) return V2W_E_ARG;       // (lengths: every problem of the launch carries them - v2w_conv1d_mfma / v2w_convt1d_mfma)
+    const int e = len ? 3 : epi;
+    auto pick = [&](auto vec_c) {
+        constexpr bool V = decltype(vec_c)::value;
+        return e == 1 ? conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 1, V>
+             : e == 2 ? conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 2, V>
+             : e == 3 ? conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 3, V> : conv_tile_kernel<MF, U, MI, NI, WM, WN, CK, NPF, RING, 0, V>;
+    };
+    const int rc = v2w_launch_lds(vec ? pick(std::true_type{}) : pick(std::false_type{}), dim3(grid), dim3(NTHREADS), lds, stream, m);
+    if (rc != 0 || S == 1) return rc;
+    long long rblocks = (red.start[nprob] + 255) / 256;
+    if (rblocks > 2048) rblocks = 2048;
+    if (red_vec) V2W_LAUNCH(splitk_reduce_kernel<true>, dim3((int)rblocks), dim3(256), 0, stream, red);
+    else V2W_LAUNCH(splitk_reduce_kernel<false>, dim3((int)rblocks), dim3(256), 0, stream, red);
     return v2w_launch_status();
 }
 
@@ -961,39 +923,32 @@ static LayerCfg v2w_layer_cfg(int c_in, int c_out, int u) {
     return c;
 }
 
-extern "C" int v2w_pack_mfma(const float* wf, float* wp, int k, int c_in, int c_out, int u, void* stream) {
+// One body for the three packers: n matrices [k][c_in][c_out] back to back -> n packed streams back to back, one launch.
+static int pack_mfma(const float* wf, float* wp, int k, int c_in, int c_out, int u, int n, int tflip, void* stream) {
     if (!wf || !wp || k <= 0 || c_in <= 0 || c_out <= 0 || u <= 0) return V2W_E_ARG;
     const LayerCfg cfg = v2w_layer_cfg(c_in, c_out, u);
     if (!cfg.mf) return V2W_E_SHAPE;
     const size_t total = (size_t)k * c_in * c_out;
     int grid = (int)((total + 255) / 256); if (grid > 4096) grid = 4096;
-    V2W_LAUNCH(pack_mfma_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, wf, wp, k, c_in, c_out, cfg.mf, cfg.ck, u);
+    V2W_LAUNCH(pack_mfma_kernel, dim3(grid, n), dim3(256), 0, (hipStream_t)stream, wf, wp, k, c_in, c_out, cfg.mf, cfg.ck, u, tflip);
     return v2w_launch_status();
+}
+
+extern "C" int v2w_pack_mfma(const float* wf, float* wp, int k, int c_in, int c_out, int u, void* stream) {
+    return pack_mfma(wf, wp, k, c_in, c_out, u, 1, 0, stream);
 }
 
 // The fragment stream of a conv layer's INPUT-GRADIENT convolution straight from the layer's own wf [k][C][D] (C = its C_in, D = its C_out):
 // the stream v2w_pack_mfma(v2w_wf_transpose_flip(wf), k, D, C, 1) would give, without the transposed copy.  c_in / c_out are the
 // gradient convolution's (c_in = D, c_out = C).
 extern "C" int v2w_pack_mfma_dgrad(const float* wf, float* wp, int k, int c_in, int c_out, void* stream) {
-    if (!wf || !wp || k <= 0 || c_in <= 0 || c_out <= 0) return V2W_E_ARG;
-    const LayerCfg cfg = v2w_layer_cfg(c_in, c_out, 1);
-    if (!cfg.mf) return V2W_E_SHAPE;
-    const size_t total = (size_t)k * c_in * c_out;
-    int grid = (int)((total + 255) / 256); if (grid > 4096) grid = 4096;
-    V2W_LAUNCH(pack_mfma_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, wf, wp, k, c_in, c_out, cfg.mf, cfg.ck, 1, 1);
-    return v2w_launch_status();
+    return pack_mfma(wf, wp, k, c_in, c_out, 1, 1, 1, stream);
 }
 
-// n matrices [k][c_in][c_out] back to back -> n packed streams back to back, one launch (the groups of a grouped conv)
+// the groups of a grouped conv
 extern "C" int v2w_pack_mfma_batch(const float* wf, float* wp, int k, int c_in, int c_out, int u, int n, void* stream) {
     if (n <= 0 || n > 65535) return V2W_E_ARG;
-    if (!wf || !wp || k <= 0 || c_in <= 0 || c_out <= 0 || u <= 0) return V2W_E_ARG;
-    const LayerCfg cfg = v2w_layer_cfg(c_in, c_out, u);
-    if (!cfg.mf) return V2W_E_SHAPE;
-    const size_t total = (size_t)k * c_in * c_out;
-    int grid = (int)((total + 255) / 256); if (grid > 4096) grid = 4096;
-    V2W_LAUNCH(pack_mfma_kernel, dim3(grid, n), dim3(256), 0, (hipStream_t)stream, wf, wp, k, c_in, c_out, cfg.mf, cfg.ck, u);
-    return v2w_launch_status();
+    return pack_mfma(wf, wp, k, c_in, c_out, u, n, 0, stream);
 }
 
 // Called by v2w_api.hip.  Returns V2W_E_SHAPE when no tile configuration fits (caller falls back to the direct kernel).

@@ -13,7 +13,7 @@
 // three MFMAs: (slope w) . x  +  hi((1 - slope) w) . relu(x)  +  lo((1 - slope) w) . relu(x).  The weights of the dominant term are split
 // into two bf16 (16 mantissa bits together), so the product stays at the precision of the bf16 activations; the slope-scaled term is 1 % of
 // the sum and takes one bf16.
-#include "v2w_common.h"
+#include "v2w_internal.h"
 
 namespace {
 

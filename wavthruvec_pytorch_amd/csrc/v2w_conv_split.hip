@@ -19,6 +19,7 @@
 //              global -> LDS by LDS-DMA (v2w_lds_dma16: no registers), two stages ahead of its use.
 // Sync       : one workgroup barrier per tap; the async copies are fenced with explicit s_waitcnt vmcnt (see the loop).
 #include "v2w_tile.h"
+#include "v2w_internal.h"
 
 
 namespace {
@@ -59,15 +60,12 @@ conv_split_kernel(const MultiArgs m) {
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
-    int pq = 0;
-#pragma unroll
-    for (int i = 1; i < V2W_MAX_MULTI; ++i) pq += (int)blockIdx.x >= m.start[i] ? 1 : 0;
+    const int pq = tile_problem(m);
     const TileArgs& p = m.p[pq];
     const int mtiles = p.Cout / MT;
     const int id = blockIdx.x - m.start[pq];
-    const int grp = id / (8 * mtiles), rem = id % (8 * mtiles);
-    const int mt = rem >> 3;
-    const int tile = grp * 8 + (rem & 7);
+    const TileId ti = tile_coords(mtiles, id);
+    const int mt = ti.mt, tile = ti.tile;
     if (tile >= p.ntiles) return;
     const int b = tile / p.ntl;
     const int n0 = (tile % p.ntl) * NT;
@@ -465,7 +463,7 @@ int launch_split(const TileArgs* ps, int nprob, hipStream_t stream, bool bf) {
     if (nprob < 1 || nprob > V2W_MAX_MULTI) return V2W_E_ARG;
     MultiArgs m{};
     size_t lds = 0;
-    int grid = 0;
+    int blocks[V2W_MAX_MULTI];
     for (int i = 0; i < nprob; ++i) {
         TileArgs p = ps[i];
         if (p.Cout % MT != 0 || p.Cin % CK != 0 || !p.wps || !p.winv) return V2W_E_SHAPE;
@@ -477,9 +475,8 @@ int launch_split(const TileArgs* ps, int nprob, hipStream_t stream, bool bf) {
         p.xcols = (p.hla + NT + p.hr + 3) & ~3;
         p.xw = 0;
         if (p.in_stride < 1) p.in_stride = 1;
-        auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-        p.vec4 = (p.L % 4 == 0) && p.L >= 4 && al16(p.in) && p.in_stride == 1;
-        p.evec = (p.L % 4 == 0) && al16(p.out) && al16(p.res) && al16(p.add0) && al16(p.add1) && al16(p.mask_src);
+        p.vec4 = (p.L % 4 == 0) && p.L >= 4 && v2w_al16(p.in) && p.in_stride == 1;
+        p.evec = (p.L % 4 == 0) && v2w_al16(p.out) && v2w_al16(p.res) && v2w_al16(p.add0) && v2w_al16(p.add1) && v2w_al16(p.mask_src);
         const size_t rawb = ((size_t)CK * (p.xcols / 4) * 16 + 1023) & ~(size_t)1023;
         size_t l = (size_t)2 * p.xcols * V2W_SPLIT_ROWB + (size_t)V2W_SPLIT_NAB * (MT / 32) * V2W_FRAG_UNIT + rawb;
         const size_t tl = ((size_t)4 * 32 * RS + 5 * MT) * sizeof(float);   // epilogue: transpose tiles + constants overlay the stage buffers
@@ -488,11 +485,9 @@ int launch_split(const TileArgs* ps, int nprob, hipStream_t stream, bool bf) {
         l += (p.in_a ? (size_t)2 * p.Cin : 0) * sizeof(float);
         if (l > lds) lds = l;
         m.p[i] = p;
-        m.start[i] = grid;
-        grid += ((p.ntiles + 7) / 8) * 8 * (p.Cout / MT);
+        blocks[i] = tile_blocks(p.ntiles, p.Cout / MT);
     }
-    m.start[nprob] = grid;
-    for (int i = nprob + 1; i <= V2W_MAX_MULTI; ++i) m.start[i] = 0x7fffffff;
+    const int grid = v2w_fill_starts(m.start, V2W_MAX_MULTI, blocks, nprob);
     // every problem of the launch shares one etab/atab offset (the largest), so that the kernel reads it from its own args
     bool vec = true;                                               // one staging flavour per launch: float4 only if every problem allows it
     for (int i = 0; i < nprob; ++i) vec = vec && m.p[i].vec4;
@@ -500,13 +495,7 @@ int launch_split(const TileArgs* ps, int nprob, hipStream_t stream, bool bf) {
     if (bf && HM != V2W_SPLIT_HMAX) return V2W_E_SHAPE;             // (the wide-halo form exists for the split-f16 operands only)
     auto kern = bf ? (vec ? conv_split_kernel<MI, NI, WM, WN, true, true> : conv_split_kernel<MI, NI, WM, WN, false, true>)
                    : (vec ? conv_split_kernel<MI, NI, WM, WN, true, false, HM> : conv_split_kernel<MI, NI, WM, WN, false, false, HM>);
-    if (lds > 160 * 1024) return V2W_E_SHAPE;
-    if (lds > 64 * 1024) {
-        hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kern), (int)lds, stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    V2W_LAUNCH(kern, dim3(grid), dim3(NTHREADS), lds, stream, m);
-    return v2w_launch_status();
+    return v2w_launch_lds(kern, dim3(grid), dim3(NTHREADS), lds, stream, m);
 }
 
 // ---- weight preparation: max |w| of the layer -> power-of-two scale -> (hi, lo) half fragments in consumption order
@@ -743,8 +732,6 @@ extern "C" int v2w_pack_bf16(const float* wf, void* wps, float* sc, int k, int c
     V2W_LAUNCH(pack_bf16_kernel, dim3(g2), dim3(256), 0, (hipStream_t)stream, wf, reinterpret_cast<b8*>(wps), sc, k, c_in, c_out);
     return v2w_launch_status();
 }
-
-int v2w_conv1d_bf16(const v2w_conv1d_args* a, int n, hipStream_t stream, int32_t* cfg);   // v2w_conv_bf16.hip
 
 // Called by v2w_api.hip for algo == V2W_ALGO_SPLIT (bf = false) and V2W_ALGO_BF16 (bf = true).  n problems sharing B, C_in, C_out, L in one launch.
 int v2w_conv1d_split(const v2w_conv1d_args* a, int n, hipStream_t stream, bool bf) {

@@ -6,7 +6,9 @@
 // layer triple).  Every coefficient is 0, +-1 or 1/2, folded into the weights by the packers; the input side is x_j -+ x_j'.
 //
 // GEMM view per workgroup: M = MT output channels, N = NTP output PAIRS (2 NTP positions), K = C_in x terms, four accumulator sets.
-// The staging is conv_tile_kernel's (v2w_conv_mfma.hip): the activated signal (CondBN affine + leaky_relu applied once) in the LDS tile
+// The staging is a copy of conv_tile_kernel's (v2w_conv_mfma.hip; the LDS tile geometry, TileGeom, is shared through v2w_tile.h - hipcc
+// allocates other register counts for either kernel when item / prefetch / commit / stage_scalar, the weight ring or the prologue tables
+// come from one shared definition, so each kernel keeps its own): the activated signal (CondBN affine + leaky_relu applied once) in the LDS tile
 // Xs[positions][36 floats], position-major, channels permuted so that a lane's four k-steps are one ds_read_b128; double-buffered over
 // chunks of 32 input channels.  Unlike there the next chunk is loaded and written after the MFMA phase (its registers would cost the third
 // wave per SIMD; the other workgroups on the CU cover the latency).
@@ -20,16 +22,15 @@
 // Epilogue: the output transform in registers, then bias [+ res_a*res + res_s] [+ add0 (+ add1) | + out] [/ out_div] per element
 // in conv_tile_kernel's order; second outputs of a pair at or past L are not stored.  Fixed summation order, no atomics.
 #include "v2w_tile.h"
+#include "v2w_internal.h"
 #include "v2w_wino.h"
 
 namespace {
 
 constexpr int WCK = 32;                 // channels per chunk
-constexpr int WRS = 36;                 // floats per LDS row (TileGeom<32, 32>::RS)
+typedef TileGeom<32, WCK> WG;           // the LDS signal tile of conv_tile_kernel's 32-channel chunks (v2w_tile.h)
 constexpr int WGPC = 4;                 // A fragments (units of 4 k-steps) per chunk and term
 constexpr int WHMAX = 32;               // staging slots cover 2 NTP + 2 WHMAX rows
-__host__ __device__ constexpr int wslot(int c) { return (c & ~7) + 4 * (c & 1) + ((c & 7) >> 1); }
-__host__ __device__ constexpr int wpair_c0(int P) { return 8 * (P >> 2) + 4 * (P & 1) + ((P >> 1) & 1); }
 __host__ __device__ inline int wino_tpos(int P, int d) { const int q = P / d; return 2 * d * q + (P - q * d); }
 
 // LEN: per-item valid lengths, as in conv_tile_body (v2w_conv_mfma.hip): inputs at and past Lb = min(L, len[b] * len_mul) select 0, a tile
@@ -46,15 +47,12 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
-    int pq = 0;
-#pragma unroll
-    for (int i = 1; i < V2W_MAX_MULTI; ++i) pq += (int)blockIdx.x >= m.start[i] ? 1 : 0;
+    const int pq = tile_problem(m);
     const TileArgs& p = m.p[pq];
     const int mtiles = p.Cout / MT;
     const int id = blockIdx.x - m.start[pq];
-    const int grp = id / (8 * mtiles), rem = id % (8 * mtiles);
-    const int mt = rem >> 3;
-    const int tile = grp * 8 + (rem & 7);
+    const TileId ti = tile_coords(mtiles, id);
+    const int mt = ti.mt, tile = ti.tile;
     if (tile >= p.ntiles) return;
     const int b = tile / p.ntl;
     const int P0 = (tile % p.ntl) * NTP;     // first output pair of the tile
@@ -78,7 +76,7 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
     const float slope = p.slope;
     const int nch = p.Cin / WCK;
     const int pos0 = (wino_tpos(P0, d) - p.hl) & ~3;     // position of LDS row 0 (floor to a float4)
-    const int bufsz = p.xrows * WRS;
+    const int bufsz = p.xrows * WG::RS;
     float* const etab = smem + p.atab_off;   // bias, res_a, res_s [MT] each
     float* const atab = etab + 3 * MT;       // folded CondBN affine of this batch item: a[Cin] then s[Cin]
 
@@ -106,7 +104,7 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
         const int P = 2 * pg + ((idx >> 3) & 1);
         row = quad * 4;
         in_img = quad < nq && P < WCK / 2;
-        c0 = wpair_c0(in_img ? P : 0);
+        c0 = WG::pair_c0(in_img ? P : 0);
         const int pos = pos0 + row;
         in_seq = in_img && pos >= 0 && pos < L;
     };
@@ -134,14 +132,14 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
                 a0 = atab[ci0 + c0]; s0 = atab[p.Cin + ci0 + c0];
                 a1 = atab[ci0 + c0 + 2]; s1 = atab[p.Cin + ci0 + c0 + 2];
             }
-            float* dst = Xs + row * WRS + wslot(c0);
+            float* dst = Xs + row * WG::RS + WG::slot(c0);
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 f32x2 v = {0.f, 0.f};        // padding stays exactly 0 (it pads the ACTIVATED signal)
                 if (in_seq && (!LEN || pos0 + row + e < Lb)) {      // (LEN: per element - Lb need not be a multiple of 4)
                     v[0] = v2w_lrelu(fmaf(a0, pf[s][0][e], s0), slope); v[1] = v2w_lrelu(fmaf(a1, pf[s][1][e], s1), slope);
                 }
-                *reinterpret_cast<f32x2*>(dst + e * WRS) = v;
+                *reinterpret_cast<f32x2*>(dst + e * WG::RS) = v;
             }
         }
     };
@@ -151,12 +149,12 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
             const float* src = p.in + (size_t)ch * L;
             const float av = p.in_a ? p.in_a[ch] : 1.f;
             const float sv = p.in_s ? p.in_s[ch] : 0.f;
-            float* dst = Xs + wslot(c);
+            float* dst = Xs + WG::slot(c);
             for (int j = lane; j < p.xrows; j += 64) {
                 const int l = pos0 + j;
                 float v = 0.f;
                 if (l >= 0 && l < Lb) v = v2w_lrelu(fmaf(av, src[l], sv), slope);
-                dst[j * WRS] = v;
+                dst[j * WG::RS] = v;
             }
         }
     };
@@ -236,8 +234,8 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
 
     const int P = P0 + wn0 + lr;                   // this lane's output pair
     const int t0 = wino_tpos(P, d);                // ... and its first output position
-    const int lbase = (t0 - p.hl - pos0) * WRS + 4 * hk;   // x of tap 0 for output t0, unit 0
-    const int dstep = d * WRS;
+    const int lbase = (t0 - p.hl - pos0) * WG::RS + 4 * hk;   // x of tap 0 for output t0, unit 0
+    const int dstep = d * WG::RS;
     typedef std::integral_constant<int, 3> S3;
     typedef std::integral_constant<int, 2> S2;
     typedef std::integral_constant<int, 1> S1;
@@ -305,7 +303,7 @@ int launch_wino(const TileArgs* ps, int nprob, hipStream_t stream) {
     static_assert(NTHREADS * NPF < 8 * 8192, "item index range of the magic division");
     MultiArgs m{};
     size_t lds = 0;
-    int grid = 0;
+    int blocks[V2W_MAX_MULTI];
     bool vec = true;
     for (int i = 0; i < nprob; ++i) {
         TileArgs p = ps[i];
@@ -323,28 +321,20 @@ int launch_wino(const TileArgs* ps, int nprob, hipStream_t stream) {
         }
         p.xrows = (rows + 3) & ~3;
         if (p.xrows > 2 * NTP + 2 * WHMAX) return V2W_E_SHAPE;
-        p.vec4 = (p.L % 4 == 0) && ((reinterpret_cast<uintptr_t>(p.in) & 15) == 0);
+        p.vec4 = (p.L % 4 == 0) && v2w_al16(p.in);
         vec = vec && p.vec4;
         const int nbuf = p.Cin / WCK > 1 ? 2 : 1;
-        p.atab_off = nbuf * p.xrows * WRS;
+        p.atab_off = nbuf * p.xrows * WG::RS;
         const size_t l = ((size_t)p.atab_off + 3 * MT + (p.in_a ? 2 * p.Cin : 0)) * sizeof(float);
         if (l > lds) lds = l;
         m.p[i] = p;
-        m.start[i] = grid;
-        grid += ((p.ntiles + 7) / 8) * 8 * (p.Cout / MT);
+        blocks[i] = tile_blocks(p.ntiles, p.Cout / MT);
     }
-    m.start[nprob] = grid;
-    for (int i = nprob + 1; i <= V2W_MAX_MULTI; ++i) m.start[i] = 0x7fffffff;
-    if (lds > 160 * 1024) return V2W_E_SHAPE;
+    const int grid = v2w_fill_starts(m.start, V2W_MAX_MULTI, blocks, nprob);
     const bool lens = m.p[0].len != nullptr;      // (all problems of the launch or none: v2w_conv1d_wino)
     auto kern = lens ? (vec ? conv_wino_len_kernel<MI, WN, NPF, true> : conv_wino_len_kernel<MI, WN, NPF, false>)
                     : (vec ? conv_wino_kernel<MI, WN, NPF, true> : conv_wino_kernel<MI, WN, NPF, false>);
-    if (lds > 64 * 1024) {
-        hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kern), (int)lds, stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    V2W_LAUNCH(kern, dim3(grid), dim3(NTHREADS), lds, stream, m);
-    return v2w_launch_status();
+    return v2w_launch_lds(kern, dim3(grid), dim3(NTHREADS), lds, stream, m);
 }
 
 // wpw float index o = (((mb * nch + ch) * nfr + fi) * 64 + lane) * 4 + j, nfr = wino_terms(k) * 4, fragment fi = (segment, unit gg, term)

@@ -23,6 +23,7 @@
 //     bias; the epilogue passes 32 positions at a time through a wave-private scratch [32 channels][5 x 32 outputs] (over the dead tile).
 #include <type_traits>
 #include "v2w_tile.h"
+#include "v2w_internal.h"
 
 namespace {
 
@@ -443,14 +444,9 @@ int launch_ct(CtArgs p, hipStream_t stream, int* ntiles_out, int32_t* cfg) {
     if (lds * (WGS > 2 ? 2 : WGS) > 160 * 1024) return V2W_E_SHAPE;
     if (cfg) { const int32_t c[10] = {MI, NI, WM, WN, UP, 102 /* = this kernel */, 1, 1, 32, U}; for (int i = 0; i < 10; ++i) cfg[i] = c[i]; }
     if (ntiles_out) { *ntiles_out = p.ntiles; return 0; }
-    const int grid = ((p.ntiles + 7) / 8) * 8 * ((p.CoutR * UP) / MT);
+    const int grid = tile_blocks(p.ntiles, (p.CoutR * UP) / MT);
     auto kern = convt_bf16_res_kernel<MI, NI, WM, WN, UP, U>;
-    if (lds > 64 * 1024) {
-        hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kern), (int)lds, stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    V2W_LAUNCH(kern, dim3(grid), dim3(NTH), lds, stream, p);
-    return v2w_launch_status();
+    return v2w_launch_lds(kern, dim3(grid), dim3(NTH), lds, stream, p);
 }
 
 }  // namespace

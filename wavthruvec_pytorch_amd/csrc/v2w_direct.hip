@@ -1,7 +1,7 @@
 // Scalar-FMA kernels: the any-shape path of the conv entry points (V2W_ALGO_DIRECT) and the fused tail
 // leaky_relu -> conv_post -> tanh (models.py:143-145).  One thread per output sample, lanes along the
 // frame axis so every global access is coalesced.
-#include "v2w_common.h"
+#include "v2w_internal.h"
 
 namespace {
 
@@ -405,9 +405,6 @@ extern "C" int v2w_conv_post_tanh_len(const float* in, const float* wf, const fl
     else V2W_LAUNCH((conv_post_tanh_len_kernel<15>), grid, dim3(256), lds, s, in, wf, bias, out, B, C_in, L, k, slope, len, len_mul);
     return v2w_launch_status();
 }
-
-int v2w_conv_post_tanh_bf16_mfma(const unsigned short* in, const float* wf, const float* bias, float* out,
-                                 int B, int C_in, int L, int k, float slope, hipStream_t stream);      // v2w_conv_post_bf16.hip
 
 extern "C" int v2w_conv_post_tanh_bf16in(const void* x_bf16, const float* wf, const float* bias, float* out,
                                          int B, int C_in, int L, int k, float slope, void* stream) {

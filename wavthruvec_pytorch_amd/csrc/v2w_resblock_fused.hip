@@ -293,7 +293,7 @@ int launch_pair(const v2w_pair_args* a, int n, hipStream_t stream) {
     constexpr int W = MF * NI * WN;
     PairMulti m{};
     size_t lds = 0;
-    int grid = 0;
+    int blocks[V2W_PAIR_MULTI];
     for (int i = 0; i < n; ++i) {
         const v2w_pair_args& q = a[i];
         PairArgs p{};
@@ -320,19 +320,11 @@ int launch_pair(const v2w_pair_args* a, int n, hipStream_t stream) {
         const size_t l = ((size_t)p.eoff + 2 * MF) * sizeof(float);
         if (l > lds) lds = l;
         m.p[i] = p;
-        m.start[i] = grid;
-        grid += p.ntiles;
+        blocks[i] = p.ntiles;
     }
-    m.start[n] = grid;
-    for (int i = n + 1; i <= V2W_PAIR_MULTI; ++i) m.start[i] = 0x7fffffff;
+    const int grid = v2w_fill_starts(m.start, V2W_PAIR_MULTI, blocks, n);
     auto kern = resblock_pair_kernel<MF, NI, WN>;
-    if (lds > 64 * 1024) {
-        if (lds > 160 * 1024) return V2W_E_SHAPE;
-        hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kern), (int)lds, stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    V2W_LAUNCH(kern, dim3(grid), dim3(64 * WN), lds, stream, m);
-    return v2w_launch_status();
+    return v2w_launch_lds(kern, dim3(grid), dim3(64 * WN), lds, stream, m);
 }
 
 
@@ -918,12 +910,7 @@ int launch_stage(const v2w_stage_args* q, hipStream_t stream, const int32_t* len
     auto kern = bwd ? resblock2_stage_kernel<MF, NI, WN, false, true>
                     : (len ? (post ? resblock2_stage_kernel<MF, NI, WN, (MF == 16), false, true> : resblock2_stage_kernel<MF, NI, WN, false, false, true>)
                               : (post ? resblock2_stage_kernel<MF, NI, WN, (MF == 16)> : resblock2_stage_kernel<MF, NI, WN, false>));
-    if (lds > 64 * 1024) {
-        hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kern), (int)lds, stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    V2W_LAUNCH(kern, dim3(q->B * p.ntl), dim3(64 * WN), lds, stream, p);
-    return v2w_launch_status();
+    return v2w_launch_lds(kern, dim3(q->B * p.ntl), dim3(64 * WN), lds, stream, p);
 }
 
 }  // namespace

@@ -12,7 +12,7 @@
 //   * C = 16 uses the 32-row MFMA with the packed fragments' rows 16-31 zero (the pipe is idle most of the time anyway).
 // Weights: the bf16 fragments of v2w_pack_bf16 / v2w_split_pack_batch, [16-channel k-step][tap][2 KiB, first KiB used].
 #include <type_traits>
-#include "v2w_common.h"
+#include "v2w_internal.h"
 
 namespace {
 
@@ -400,8 +400,7 @@ int launch_stage_bf16(const v2w_stage_split_args* q, hipStream_t stream) {
     p.xrows = (p.xoff + W + 2 * p.h1max + 3) & ~3;
     if (p.xrows < p.h2max) return V2W_E_SHAPE;
     p.ntl = (q->L + p.nto - 1) / p.nto;
-    auto al16 = [](const void* x) { return (reinterpret_cast<uintptr_t>(x) & 15) == 0; };
-    p.vec4 = (q->L % 4 == 0) && al16(q->in) && al16(q->out);
+    p.vec4 = (q->L % 4 == 0) && v2w_al16(q->in) && v2w_al16(q->out);
     int kmax = 0;
     for (int j = 0; j < q->nk; ++j) if (q->k[j] > kmax) kmax = q->k[j];
     size_t lds = (size_t)(p.xrows + W + p.h2max) * ROWB + (2 * V2W_SB_MAXB + 2) * C * sizeof(float) + (size_t)kmax * (C / 16) * 1024;
@@ -411,12 +410,7 @@ int launch_stage_bf16(const v2w_stage_split_args* q, hipStream_t stream) {
     if (q->io_bf16 != 0 && q->io_bf16 != 3) return V2W_E_ARG;
     if (v2w_dry(stream)) return 0;
     auto kern = q->io_bf16 ? stage_bf16_kernel<C, true> : stage_bf16_kernel<C, false>;
-    if (lds > 64 * 1024) {
-        hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kern), (int)lds, stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    V2W_LAUNCH(kern, dim3(q->B * p.ntl), dim3(256), lds, stream, p);
-    return v2w_launch_status();
+    return v2w_launch_lds(kern, dim3(q->B * p.ntl), dim3(256), lds, stream, p);
 }
 
 }  // namespace
@@ -424,11 +418,6 @@ int launch_stage_bf16(const v2w_stage_split_args* q, hipStream_t stream) {
 #ifdef V2W_TIMELINE
 V2W_TL_SETTER(v2w_timeline_set_stage_bf16)
 #endif
-
-int v2w_resblock2_stage_bf16_wide(const v2w_stage_split_args* a, hipStream_t stream, int* up_tiles_out = nullptr);   // v2w_stage_bf16_wide.hip
-int v2w_resblock2_stage_bf16_n16(const v2w_stage_split_args* a, hipStream_t stream);    // v2w_stage_bf16_n16.hip
-int v2w_resblock1_pairs_bf16_n16(const v2w_stage_split_args* a, hipStream_t stream);    // v2w_stage_bf16_n16.hip
-int v2w_resblock2_stage_bf16_n32s(const v2w_stage_split_args* a, hipStream_t stream, int* up_tiles_out);   // v2w_stage_bf16_n32s.hip
 
 // Called by v2w_resblock2_stage_split_fwd when a->bf16 is set.  V2W_E_SHAPE: the caller falls back to the split stage kernel.
 int v2w_resblock2_stage_bf16(const v2w_stage_split_args* a, hipStream_t stream, int* up_tiles_out) {

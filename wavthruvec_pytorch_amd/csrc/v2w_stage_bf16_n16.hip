@@ -18,6 +18,7 @@
 #include <type_traits>
 #include <utility>
 #include "v2w_tile.h"
+#include "v2w_internal.h"
 
 namespace {
 
@@ -665,8 +666,6 @@ V2W_TL_SETTER(v2w_timeline_set_n16)
 #endif
 
 #define V2W_N16_WN 4
-
-int v2w_resblock2_stage_bf16_n16s(const v2w_stage_split_args* a, hipStream_t stream);     // v2w_stage_bf16_n16s.hip: the streaming form, stage + tail
 
 // Called by v2w_resblock2_stage_bf16 (v2w_stage_bf16.hip) for C = 16 on bf16 tensors.  V2W_E_SHAPE: not the reference's block set / not
 // aligned - the caller runs its own kernels.

@@ -26,6 +26,7 @@
 #include <type_traits>
 #include <utility>
 #include "v2w_tile.h"
+#include "v2w_internal.h"
 
 namespace {
 

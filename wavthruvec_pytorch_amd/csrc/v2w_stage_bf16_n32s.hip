@@ -21,6 +21,7 @@
 #include <type_traits>
 #include <utility>
 #include "v2w_tile.h"
+#include "v2w_internal.h"
 
 namespace {
 

@@ -17,6 +17,7 @@
 //   * weights: the fragments of v2w_pack_bf16 / v2w_split_pack_batch from L2 through a four-slot register ring, three k-steps ahead.
 #include <type_traits>
 #include "v2w_tile.h"
+#include "v2w_internal.h"
 
 namespace {
 

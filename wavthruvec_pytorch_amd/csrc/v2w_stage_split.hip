@@ -17,7 +17,7 @@
 //   Weights: the (hi, lo) fragment stream of v2w_pack_split (row block 0: [chunk C/16][tap K][hi | lo][64 lanes][16 B]; for C = 16
 //          the 16 output rows are zero-padded to the 32 rows of the MFMA: these stages are latency-, not MFMA-bound),
 //          read straight from L2 into registers through a 4-slot ring: no weight barrier at all, two barriers per branch.
-#include "v2w_common.h"
+#include "v2w_internal.h"
 #include <type_traits>
 
 namespace {
@@ -367,17 +367,10 @@ int launch_stage_split(const v2w_stage_split_args* q, hipStream_t stream) {
     if (lds > 160 * 1024) return V2W_E_SHAPE;
     if (v2w_dry(stream)) return 0;
     auto kern = q->bf16 ? stage_split_kernel<NCH, NI, WN, true> : stage_split_kernel<NCH, NI, WN, false>;
-    if (lds > 64 * 1024) {
-        hipError_t e = v2w_max_lds(reinterpret_cast<const void*>(kern), (int)lds, stream);
-        if (e != hipSuccess) return (int)e;
-    }
-    V2W_LAUNCH(kern, dim3(q->B * p.ntl), dim3(64 * WN), lds, stream, p);
-    return v2w_launch_status();
+    return v2w_launch_lds(kern, dim3(q->B * p.ntl), dim3(64 * WN), lds, stream, p);
 }
 
 }  // namespace
-
-int v2w_resblock2_stage_bf16(const v2w_stage_split_args* a, hipStream_t stream, int* up_tiles_out = nullptr);   // v2w_stage_bf16.hip
 
 static int stage_split_dispatch(const v2w_stage_split_args* a, void* stream, int* up_tiles_out) {
     if (!a || (!a->in && !a->rb1) || (!a->out && !a->post_out && !a->up_out && !a->rb1) || a->nk < 1 || a->nk > V2W_SS_MAXB) return V2W_E_ARG;

@@ -1,5 +1,6 @@
-// Arguments of the tile kernels (f32 MFMA: v2w_conv_mfma.hip, split-f16 MFMA: v2w_conv_split.hip).  Host code fills
-// TileArgs from the C-ABI structs; several problems of identical tile configuration travel in one MultiArgs.
+// Arguments of the tile kernels (f32 MFMA: v2w_conv_mfma.hip, v2w_conv_wino.hip; split-f16 / bf16 MFMA: v2w_conv_split.hip, v2w_conv_bf16.hip)
+// and the device code they share: the multi-problem tile map and the geometry of the f32 kernels' LDS signal tile.
+// Host code fills TileArgs from the C-ABI structs; several problems of identical tile configuration travel in one MultiArgs.
 #pragma once
 #include "v2w_common.h"
 
@@ -79,6 +80,43 @@ __device__ __forceinline__ TileArgs pinned_tile_args(const TileArgs& g) {
 struct MultiArgs {
     TileArgs p[V2W_MAX_MULTI];
     int start[V2W_MAX_MULTI + 1];
+};
+
+// ---- the multi-problem tile map, one definition for the four tile kernels (conv_tile_kernel, conv_wino_body, conv_bf16_kernel,
+// conv_split_kernel) and their launchers.  Host: problem q owns tile_blocks(ntiles, C_out / MT) workgroups from start[q] on
+// (v2w_fill_starts, v2w_common.h).  Device: tile_problem() finds q (conv_tile_kernel spells that loop out, see there), tile_coords() places workgroup `id` of the problem.  Ids that
+// differ by a multiple of 8 tend to share an XCD (and its L2), so the M-tiles that re-read the same input tile are placed 8 apart
+// (speed only, never correctness); the position tiles are therefore padded to whole groups of 8 and the padding workgroups return.
+__host__ __device__ constexpr int tile_blocks(int ntiles, int mtiles) { return ((ntiles + 7) >> 3) * 8 * mtiles; }
+__device__ __forceinline__ int tile_problem(const MultiArgs& m) {
+    int pq = 0;
+#pragma unroll
+    for (int i = 1; i < V2W_MAX_MULTI; ++i) pq += (int)blockIdx.x >= m.start[i] ? 1 : 0;
+    return pq;
+}
+// M-tile and position tile of the problem; a tile >= ntiles is padding (the workgroup returns), else item = tile / ntl
+struct TileId { int mt, tile; };
+// mtiles = C_out / MT; id = the workgroup's index inside its problem (conv_tile_kernel: inside its C_in slice)
+__device__ __forceinline__ TileId tile_coords(int mtiles, int id) {
+    const int grp = id / (8 * mtiles), rem = id % (8 * mtiles);
+    return TileId{rem >> 3, grp * 8 + (rem & 7)};
+}
+
+// ---- the f32 tile kernels (conv_tile_kernel: v2w_conv_mfma.hip, conv_wino_body: v2w_conv_wino.hip) share their LDS signal tile.
+// Geometry of the LDS signal tile: [positions][RS floats], the CK channels of a row permuted so that the four k-steps a lane feeds
+// to one packed weight fragment (v2w_pack_mfma pairs k-step kk, lane half hk with channel 8g + 2kk + hk for the 32x32x2 MFMA and
+// 4kk + hk for 16x16x4) are 16 contiguous bytes.  RS is the smallest 16-byte-aligned stride that keeps the wave's ds_read_b128
+// (lane -> row, lane half -> slot quad) bank-conflict free.  Staging writes slot-adjacent channel PAIRS (c0, c0 + PAIR_DC).
+template <int MF, int CK> struct TileGeom {
+    static constexpr int RS = CK == 32 ? 36 : (MF == 32 ? 20 : 24);
+    static constexpr int PAIR_DC = MF == 32 ? 2 : 4;
+    __host__ __device__ static constexpr int slot(int c) {
+        return MF == 32 ? ((c & ~7) + 4 * (c & 1) + ((c & 7) >> 1)) : (4 * (c & 3) + (c >> 2));
+    }
+    // first channel of the pair that occupies slots 2P, 2P + 1
+    __host__ __device__ static constexpr int pair_c0(int P) {
+        return MF == 32 ? (8 * (P >> 2) + 4 * (P & 1) + ((P >> 1) & 1)) : (8 * (P & 1) + (P >> 1));
+    }
 };
 
 }  // namespace
