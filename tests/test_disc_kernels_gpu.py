@@ -20,6 +20,7 @@ import torch
 
 from tests import disc_cases as K
 from tests import disc_ref as R
+from wavthruvec_pytorch_amd import hipops
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +32,7 @@ def env():
     assert torch.cuda.is_available(), 'GPU tests need a MI355X'
     from wavthruvec_pytorch_amd import _hip
     dev = torch.device('cuda:0')
-    return dev, _hip, _hip.load(), torch.cuda.current_stream(dev).cuda_stream
+    return dev, _hip, _hip.load(), torch.cuda.current_stream(dev).cuda_stream       # (lib, stream: the entry points hipops does not wrap)
 
 
 def _f32(seed, *shape):
@@ -63,7 +64,7 @@ def test_phase_split(env, c):
     xd = R.pitched(x, ip, SENT).to(dev)
     n = B * s * Cc * op
     buf = _nan(dev, off + n + 4)
-    _hip.check(lib.v2w_phase_split(xd.data_ptr(), buf.data_ptr() + 4 * off, B, Cc, Cg, L, inner, s, c['ipitch'], c['opitch'], st), 'v2w_phase_split')
+    hipops.phase_split(xd, L=L, inner=inner, s=s, cg=Cg, out=buf[off:off + n].view(B, s * Cc, op))     # the pitches: those of xd and of the view
     got = buf.cpu()
     assert torch.equal(got[off:off + n].view(B, s * Cc, op), R.pitched(R.phase_split(x, Cg, s), op))
     assert torch.isnan(got[:off]).all() and torch.isnan(got[off + n:]).all()
@@ -82,7 +83,7 @@ def test_phase_merge(env, c):
     assert torch.equal(out.cpu(), R.pitched(want, op, SENT))            # the pitch tail keeps its sentinel
     # and it inverts v2w_phase_split on the valid part: split(merge(xs)) is xs with the positions past L zeroed
     back = _nan(dev, B, s * Cc, ip)
-    _hip.check(lib.v2w_phase_split(out.data_ptr(), back.data_ptr(), B, Cc, Cg, L, inner, s, op, ip, st), 'v2w_phase_split')
+    hipops.phase_split(out, L=L, inner=inner, s=s, cg=Cg, out=back)
     assert torch.equal(back.cpu(), R.pitched(R.phase_split(want, Cg, s), ip))
     assert torch.equal(R.phase_merge(R.unpitched(back.cpu(), Uq, inner), Cg, s, L), want)
 
@@ -95,7 +96,7 @@ def test_unfold1(env, c):
     x = _f32(3, B, T)
     xd = x.to(dev)
     out = _nan(dev, B, rows, P)
-    _hip.check(lib.v2w_unfold1(xd.data_ptr(), out.data_ptr(), B, T, H, inner, s, k, pad, rows, P, st), 'v2w_unfold1')
+    hipops.unfold1(xd, H=H, inner=inner, s=s, k=k, pad=pad, rows=rows, out=out)
     got = out.cpu()
     assert torch.equal(got, R.pitched(R.unfold1(x, H, inner, s, k, pad, rows), P))
     assert torch.equal(got[:, k:], torch.zeros(B, rows - k, P))
@@ -110,7 +111,7 @@ def test_fold1(env, c):
     dxu = _f32(4, B, rows, Uq, inner)                                   # rows k .. 15 are not the kernel's to read
     dxud = R.pitched(dxu, P, SENT).to(dev)
     dx = _nan(dev, B, T)
-    _hip.check(lib.v2w_fold1(dxud.data_ptr(), dx.data_ptr(), B, T, H, inner, s, k, pad, rows, P, st), 'v2w_fold1')
+    hipops.fold1(dxud, T=T, H=H, inner=inner, s=s, k=k, pad=pad, out=dx)
     want, S = R.fold1(dxu, T, H, inner, s, k, pad)
     _report('fold1 ' + c['id'], dx=R.worst_ratio(dx.cpu(), want, R.sum_bound(2 * k, S)))
     if H * inner > T:                                                   # the samples the pad reflects carry more than their own taps
@@ -125,7 +126,7 @@ def test_unfold_taps(env, c):
     x = _f32(5, B, Cc, L, inner)
     xd = R.pitched(x, ip, SENT).to(dev)
     out = _nan(dev, B, k * Cc, op)
-    _hip.check(lib.v2w_unfold_taps(xd.data_ptr(), out.data_ptr(), B, Cc, L, inner, s, k, pad, ip, op, st), 'v2w_unfold_taps')
+    hipops.unfold_taps(xd, L=L, inner=inner, s=s, k=k, pad=pad, out=out)
     assert torch.equal(out.cpu(), R.pitched(R.unfold_taps(x, s, k, pad), op))
 
 
@@ -135,7 +136,7 @@ def test_zero_tail(env, c):
     rows, pitch, valid = c['rows'], c['pitch'], c['valid']
     x = _f32(6, rows + 1, pitch)                                        # one row more than the call owns
     xd = x.to(dev)
-    _hip.check(lib.v2w_zero_tail(xd.data_ptr(), rows, pitch, valid, st), 'v2w_zero_tail')
+    hipops.zero_tail(xd[:rows], valid=valid)
     want = torch.cat((R.zero_tail(x[:rows], valid), x[rows:]))
     assert torch.equal(xd.cpu(), want)
 
@@ -148,8 +149,8 @@ def test_avgpool4_and_backward(env, c):
     x, g = _f32(7, B, L), _f32(8, B, Lo)
     xd, gd = x.to(dev), g.to(dev)
     out, dx = _nan(dev, B, Lo), _nan(dev, B, L)
-    _hip.check(lib.v2w_avgpool4(xd.data_ptr(), out.data_ptr(), B, L, st), 'v2w_avgpool4')
-    _hip.check(lib.v2w_avgpool4_bwd(gd.data_ptr(), dx.data_ptr(), B, L, st), 'v2w_avgpool4_bwd')
+    hipops.avgpool4(xd, out=out)
+    hipops.avgpool4_bwd(gd, L=L, out=dx)
     want, _ = R.avgpool4(x)
     wdx, _ = R.avgpool4_bwd(g, L)
     e, eb = (out.cpu().double() - want).abs().max().item(), (dx.cpu().double() - wdx).abs().max().item()
@@ -195,8 +196,7 @@ def test_disc_dz(env, c):
     fd, gd, dd = f.to(dev), None if g is None else g.to(dev), None if d is None else d.to(dev)
 
     def call(dz, rs):
-        _hip.check(lib.v2w_disc_dz(fd.data_ptr(), _hip.ptr(gd), _hip.ptr(dd), dz.data_ptr(), _hip.ptr(rs), rows, pitch, valid, c['slope'], st),
-                   'v2w_disc_dz')
+        hipops.disc_dz(fd, gd, dd, valid=valid, slope=c['slope'], out=dz, rowsum=rs)
 
     _check_dz(env, 'dz ' + c['id'], c, rows, pitch, valid, f, g, d, None if d is None else d[:, :valid], call)
 
@@ -214,8 +214,7 @@ def test_disc_dz_merge(env, c):
     d_valid = R.dz_merge_d(dxs, Cg, s, L).reshape(rows, valid)
 
     def call(dz, rs):
-        _hip.check(lib.v2w_disc_dz_merge(fd.data_ptr(), _hip.ptr(gd), dxsd.data_ptr(), dz.data_ptr(), _hip.ptr(rs), B, Cc, Cg, L, inner, s,
-                                         dpitch, pitch, c['slope'], st), 'v2w_disc_dz_merge')
+        hipops.disc_dz_merge(fd, gd, dxsd, cg=Cg, L=L, inner=inner, s=s, slope=c['slope'], out=dz, rowsum=rs)
 
     _check_dz(env, 'dz_merge ' + c['id'], c, rows, pitch, valid, f, g, None, d_valid, call)
 
@@ -227,7 +226,7 @@ def test_rowsum_reduce(env, c):
     rs = _f32(15, B, Cc) * 100
     rsd = rs.to(dev)
     db = _nan(dev, Cc + 4)
-    _hip.check(lib.v2w_rowsum_reduce(rsd.data_ptr(), db.data_ptr(), B, Cc, st), 'v2w_rowsum_reduce')
+    hipops.rowsum_reduce(rsd, out=db[:Cc])
     got = db.cpu()
     assert torch.equal(got[:Cc], torch.from_numpy(R.rowsum_reduce_f32(rs.numpy()))) and torch.isnan(got[Cc:]).all()
 
@@ -239,7 +238,7 @@ def test_cout1_wgrad(env, c):
     x, dz = _f32(16, B, Cc, L), _f32(17, B, 1, L)
     xd, dzd = x.to(dev), dz.to(dev)
     dwf = _nan(dev, k, Cc, 1)
-    _hip.check(lib.v2w_cout1_wgrad(xd.data_ptr(), dzd.data_ptr(), dwf.data_ptr(), B, Cc, L, k, dil, tap0, st), 'v2w_cout1_wgrad')
+    hipops.cout1_wgrad(xd, dzd, k=k, dil=dil, tap0=tap0, out=dwf)
     _, _, want, S = R.conv_grads(x, torch.zeros(k, Cc, 1), dz, dil, tap0)
     _report('cout1_wgrad ' + c['id'], dwf=R.worst_ratio(dwf.cpu(), want, R.sum_bound(c['chain'], S)))
 
@@ -256,19 +255,8 @@ def _conv_data(c, seed):
 
 
 def _run_conv(x, w4, bias, out, c, tap0, out_slope, algo, packs):
-    """One launch for G = 1, the groups four per launch otherwise (what discriminators.py does); x (B, G*ci, L), w4 [G][k][ci][co] on the GPU."""
-    from wavthruvec_pytorch_amd import hipops
-    G, k, ci, co = w4.shape
-    probs = []
-    for g in range(G):
-        kw = dict(k=k, dil=c['dil'], slope=1.0, out_slope=out_slope, pad_left=tap0 * c['dil'], algo=algo, group=(g, ci, co) if G > 1 else None)
-        kw['wps' if algo == hipops.ALGO_SPLIT else 'wp'] = packs[g]
-        probs.append((x, w4[g], None if bias is None else bias[g * co:(g + 1) * co], out, kw))
-    if G == 1:
-        hipops.conv1d(*probs[0][:4], **probs[0][4])
-    else:
-        for i in range(0, G, 4):
-            hipops.conv1d_multi(probs[i:i + 4])
+    """The launches discriminators.py makes for a conv (hipops.conv1d_groups); x (B, G*ci, L), w4 [G][k][ci][co] on the GPU."""
+    hipops.conv1d_groups(x, w4, bias, out, packs, dil=c['dil'], pad_left=tap0 * c['dil'], out_slope=out_slope, algo=algo)
     torch.cuda.synchronize()
     return out
 
@@ -280,7 +268,6 @@ def _ref_device(c, dev):
 
 @_cases(K.CONV)
 def test_conv_forms_f32_mfma(env, c):
-    from wavthruvec_pytorch_amd import hipops
     dev = env[0]
     B, G, cig, cog, L, k, dil, tap0 = (c[n] for n in ('B', 'G', 'cig', 'cog', 'L', 'k', 'dil', 'tap0'))
     x, w4, bias, dy = _conv_data(c, 20)
@@ -302,7 +289,6 @@ def test_conv_forms_f32_mfma(env, c):
 def test_conv_forms_split_f16(env, c):
     """The project's bar for the split-f16 products (test_conv1d_split_f16): no worse than twice the f32 kernel's error plus 1e-6, both
     against fp64.  A shape the split kernel has no tile for is declined with V2W_E_SHAPE."""
-    from wavthruvec_pytorch_amd import hipops
     dev, _hip = env[0], env[1]
     B, G, cig, cog, L, k, dil, tap0 = (c[n] for n in ('B', 'G', 'cig', 'cog', 'L', 'k', 'dil', 'tap0'))
     x, w4, bias, dy = _conv_data(c, 30)
@@ -365,8 +351,7 @@ def test_wgrad_groups(env, c):
     got = []
     for _ in range(2):
         slab, dw = _nan(dev, G * ns * k * ci * co), _nan(dev, G, k, ci, co)
-        _hip.check(lib.v2w_wgrad_groups(xd.data_ptr(), dyd.data_ptr(), dw.data_ptr(), slab.data_ptr(), B, ci, co, Lq, k, dil, tap0, G, st),
-                   'v2w_wgrad_groups')
+        hipops.wgrad_groups(xd, dyd, groups=G, k=k, dil=dil, tap0=tap0, out=dw, slab=slab)
         got.append(dw.cpu())
     assert torch.equal(got[0], got[1])
     ratios = {}

@@ -171,6 +171,41 @@ def test_mpd_unfolded_tap_form(dev, monkeypatch):
             assert a.shape == b.shape and (a - b.cpu()).abs().max().item() <= TOL
 
 
+def test_declined_split_input_gradient_packs_nothing(dev, monkeypatch):
+    """precision 'f16x3', one DiscriminatorP(3) in train mode at B = 1, T = 640: the split-f16 kernel takes the forward of the first two-tap
+    layer (3 x 32 stacked channels -> 128) and declines its transposed problem (tests/disc_cases.py `split_twotap_zero_third`: dgrad_rc =
+    E_SHAPE), which runs on the exact kernel.  In either of two forward + backward runs on the same input the `pack_split` calls are the
+    forward's split weights (train mode refolds on every call) and the transposed ones of the layers that do not decline - none for the
+    layer that does - and the two runs give bit-equal gradients."""
+    from tests import disc_cases as K
+    from wavthruvec_pytorch_amd import _hip, hipops
+    from wavthruvec_pytorch_amd.discriminators import DiscriminatorP, set_precision
+    case = next(c for c in K.SPLIT if c['id'] == 'split_twotap_zero_third')
+    assert case['dgrad_rc'] == _hip.E_SHAPE
+    torch.manual_seed(31)
+    d = set_precision(DiscriminatorP(3).to(dev), 'f16x3').train()
+    y = synthetic.make_audio_pair(1, 640, seed=7)[1].to(dev)
+    packs = []                                                       # wf.shape of every pack_split call
+    orig = hipops.pack_split
+    monkeypatch.setattr(hipops, 'pack_split', lambda wf, *a, **kw: (packs.append(tuple(wf.shape)), orig(wf, *a, **kw))[1])
+    runs = []
+    for _ in range(2):
+        del packs[:]
+        d.zero_grad(set_to_none=True)
+        x = y.clone().requires_grad_(True)
+        score, fmap = d(x)
+        nfwd = len(packs)
+        (score.sum() + sum((f * f).mean() for f in fmap)).backward()
+        took = _split_layers(d)                                      # the layers whose forward ran (and stayed) on the split kernel
+        declines = [l for l in took if (l.stride * l.c_in, l.c_out) == (case['cig'], case['cog'])]
+        assert len(took) == nfwd == 4 and len(declines) == 1
+        assert (case['k'], case['cog'], case['cig']) not in packs[nfwd:]         # [taps][C_out][stacked C_in] of its transposed weights
+        assert len(packs) == nfwd + len(took) - len(declines)
+        runs.append((x.grad.clone(), [p.grad.clone() for p in d.parameters()]))
+    (gx1, gp1), (gx2, gp2) = runs
+    assert torch.equal(gx1, gx2) and all(torch.equal(a, b) for a, b in zip(gp1, gp2))
+
+
 @pytest.mark.parametrize('kind', ['mpd', 'msd'])
 def test_discriminator_weights_follow_the_optimizer(dev, kind):
     """The folded / packed kernel weights are cached per parameter version: after `optimizer.step()` (train.py:199) the next forward

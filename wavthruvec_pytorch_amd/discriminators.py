@@ -6,7 +6,7 @@ shapes (weight_norm: bias / weight_g / weight_v with Conv2d (k, 1) shapes for th
 the first scale discriminator: bias / weight_orig / weight_u / weight_v) - so `do_%08d` checkpoints load.
 
 Differentiable: each discriminator call is one `autograd.Function` (`_DiscFn`) whose backward runs on the same C ABI (input
-gradients on the forward conv kernel with transposed tap-flipped weights, weight gradients on `v2w_wgrad_slice`, weight-norm
+gradients on the forward conv kernel with transposed tap-flipped weights, weight gradients on `v2w_wgrad_groups`, weight-norm
 backward on `v2w_wn_bwd`), so both optimisation steps of train.py:188-215 work.  No PyTorch/CPU fallback: the convolutions run on
 the f32 MFMA tile kernel through the C ABI as stride-1 problems (csrc/v2w_disc.hip explains the mapping):
   stride-s layers  -> `v2w_phase_split` + a conv over the s stacked phases (ceil(k/s)-ish taps),
@@ -18,14 +18,18 @@ the f32 MFMA tile kernel through the C ABI as stride-1 problems (csrc/v2w_disc.h
                       `[:, :, :length]` views: same shapes and values as the reference, strided when length % 4 != 0.
 Weight preparation (weight-norm fold on the HIP kernel; spectral-norm power iteration, tap re-indexing for the stride / group
 forms with torch index ops on the weight tensors) is cached per parameter version.
+
+How the file is laid out: a `_DiscConv` decides its stride-1 form once, in `__init__` (`form`, `cs`, `kp`, `Q`); its
+`kernel_weights()` returns a `_Weights` record (forward weights, the optional split-f16 set, input-gradient weights built on first
+use); `_conv_split_or_exact` is the one place a conv is launched with the split-f16 fallback; `_DiscFn.backward` walks the layers
+top down through `_dz_and_bias_grad`, `_weight_grad` and `_input_grad`.  Every kernel is reached through `hipops`.
 """
 from __future__ import annotations
 
 import math
 import os
-from typing import List
-
 import threading
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -35,8 +39,69 @@ from . import _hip, hipops
 from .synthetic import DISC_P_LAYERS, DISC_P_POST, DISC_S_LAYERS, DISC_S_POST
 
 LRELU_SLOPE = 0.1   # models.py:9
-_WGRAD_GROUPED = os.environ.get('V2W_DISC_WGRAD_GROUPS', '1') == '1'   # all groups of a layer in one wgrad launch (grid.z)
 _UNFOLD_ROWS = 16   # C_in = 1 layers: the k shifted copies padded to the MFMA kernel's smallest channel block
+
+# the stride-1 form a layer's conv runs in:
+_FIRST = 'first'    # C_in = 1: the k taps as 16 rows of a 1-tap conv (v2w_unfold1)
+_TAPS = 'taps'      # optional (V2W_DISC_UNFOLD=1): the taps of a short strided conv as k * C_in channels of a 1-tap conv (v2w_unfold_taps)
+_PHASES = 'phases'  # stride s > 1: the s phases of the input stacked along the channels (v2w_phase_split), ceil(k / s)-ish taps
+_PLAIN = 'plain'    # stride 1: the input itself, its pitch tail zeroed (v2w_zero_tail)
+
+
+def _mfma_packs(w4):
+    """Per group the packed MFMA stream of w4 [G][k][C_in][C_out], or None where the tile kernel has no configuration for the shape."""
+    G, _k, ci, co = w4.shape
+    if ci % 16 == 0 and (co % 32 == 0 or co == 16):
+        return list(hipops.pack_mfma_batch(w4).unbind(0))
+    return [None] * G
+
+
+class _Weights:
+    """One layer's weights in kernel form, per group of its stride-1 conv (`_DiscConv.kernel_weights` builds it; the y and y_hat calls
+    of one step share it):
+      w4 [G][kp][cs / G][C_out / G], wp    the forward conv and its packed MFMA streams (`_mfma_packs`)
+      ws4 [G][kps][..][..], wps            the same conv for the split-f16 kernel (precision 'f16x3'), or None: not eligible, or declined
+      transposed(), transposed_split()     the input-gradient conv's weights in both forms, built on first use."""
+    __slots__ = ('w4', 'wp', 'ws4', 'wps', 'wT4', 'wTp', 'wTs4', 'wTs')
+
+    def __init__(self, w4, split):
+        self.w4, self.wp = w4, _mfma_packs(w4)
+        self.ws4 = self.wps = self.wT4 = self.wTp = self.wTs4 = self.wTs = None
+        if split:
+            # (hi, lo) f16 fragments + scale record of the forward conv, per group.  The kernel pipelines over an odd tap count: the
+            # two-tap phase-stacked layers (k = 5, stride 3) get a zero third tap behind the others (same pad_left; 1.5 x the MFMAs at 2.2 x the rate)
+            self.ws4 = w4 if w4.shape[1] % 2 == 1 else torch.cat([w4, torch.zeros_like(w4[:, :1])], 1)
+            self.wps = [hipops.pack_split(self.ws4[g]) for g in range(w4.shape[0])]
+
+    def __contains__(self, name):
+        """`'wps' in rec`: the record carries that form at this point."""
+        return getattr(self, name, None) is not None
+
+    def split(self):
+        """(ws4, wps) or None."""
+        return None if self.wps is None else (self.ws4, self.wps)
+
+    def transposed(self):
+        """(wT4 [G][kp][C_out / G][cs / G] with the taps reversed, its packed MFMA streams)."""
+        if self.wT4 is None:
+            self.wT4 = self.w4.flip(1).transpose(2, 3).contiguous()
+            self.wTp = _mfma_packs(self.wT4)
+        return self.wT4, self.wTp
+
+    def transposed_split(self, allowed):
+        """(wTs4 [G][kps][C_out / G][cs / G] - the zero pad tap comes first - and its pack_split pairs), or None: the layer has no split set, the
+        split kernel does not serve the transposed shape, or (`allowed` False) it has declined this problem before."""
+        if self.wTs is None and self.wps is not None and allowed and hipops.split_supported(self.w4.shape[3], self.w4.shape[2]):
+            self.wTs4 = self.ws4.flip(1).transpose(2, 3).contiguous()
+            self.wTs = [hipops.pack_split(self.wTs4[g]) for g in range(self.wTs4.shape[0])]
+        return None if self.wTs is None else (self.wTs4, self.wTs)
+
+    def forget_split(self, transposed):
+        """The split kernel declined the forward conv (or, `transposed`, the input-gradient conv): exact from here on."""
+        if transposed:
+            self.wTs4 = self.wTs = None
+        else:
+            self.ws4 = self.wps = None
 
 
 class _DiscConv(nn.Module):
@@ -64,6 +129,7 @@ class _DiscConv(nn.Module):
         self._last_sn = None
         self._jmap = None
         self._wpad = None
+        self._no_split_dgrad = None     # (C_out / G, cs / G, pitch) of the input-gradient conv the split-f16 kernel declined last
         # 'f32' (exact) or 'f16x3': the forward and input-gradient convs of the layers the split-f16 kernel serves - dense, stride 1, an odd
         # tap count: the 1024 -> 1024 five-tap convs that are 54 % of a period discriminator's and 30 % of a scale discriminator's FLOPs -
         # run as f16 hi + lo operands (three MFMAs per product, fp32 accumulate: ~1e-6 of the fp32 result); weight gradients stay exact.
@@ -73,10 +139,34 @@ class _DiscConv(nn.Module):
         # 1-tap conv (exact MAC count, no halo).  Measured equal to the phase-stacked default (40.6 vs 40.4 ms per MPD forward):
         # one tap per staged chunk makes the kernel staging-bound, which cancels the 6/5 tap-slot saving.
         self.unfolded = c_in > 1 and stride > 1 and groups == 1 and k <= 8 and os.environ.get('V2W_DISC_UNFOLD', '0') == '1'
+        # the stride-1 form: `cs` stacked input channels, `kp` taps of which `Q` sit left of the output position.  With j - P = s*q + r, tap j
+        # of the strided conv is tap q + Q on phase r of the stacked one
+        if c_in == 1:
+            self.form, self.cs = _FIRST, _UNFOLD_ROWS
+        elif self.unfolded:
+            self.form, self.cs = _TAPS, k * c_in
+        elif stride > 1:
+            self.form, self.cs = _PHASES, stride * c_in
+        else:
+            self.form, self.cs = _PLAIN, c_in
+        self.Q, self.kp = 0, 1
+        if self.form in (_PHASES, _PLAIN):
+            self.Q = -(-padding // stride)
+            self.kp = self.Q + (k - 1 - padding) // stride + 1
 
     def extra_repr(self):
         return f'{self.c_in}, {self.c_out}, k={self.k}, stride={self.stride}, groups={self.groups}, ' \
                f'{"spectral_norm" if self.spectral else "weight_norm"}'
+
+    def rows_out(self, rows_in):
+        """Output rows of the strided conv on `rows_in` input rows."""
+        if self.form == _PHASES:
+            return -(-rows_in // self.stride)
+        return (rows_in + 2 * self.padding - self.k) // self.stride + 1 if self.form in (_FIRST, _TAPS) else rows_in
+
+    def dil(self, inner):
+        """Dilation of the stride-1 conv on feature maps of `inner` columns per row."""
+        return 1 if self.kp == 1 else inner
 
     # -- weights in kernel form --------------------------------------------------------------------------------------
     def _folded(self, out=None):
@@ -96,9 +186,9 @@ class _DiscConv(nn.Module):
     def invalidate_weight_cache(self):
         self._cache = None
 
-    def kernel_weights(self):
-        """Per-group stride-1 weights: dict(wf=[G] of [k'][s * C_in/G][C_out/G], wp=[G] packed or None, kp, pad_left_taps).
-        With j - P = s*q + r:  wf'[q + Q][r * cig + c][o] = wf[s*q + r + P][c][o]  (0 where the tap does not exist)."""
+    def kernel_weights(self) -> _Weights:
+        """The `_Weights` of the current parameters.  Phase-stacked / plain form, with j - P = s*q + r:
+        w4[g][q + Q][r * cig + c][o] = wf[s*q + r + P][c][g * cog + o]  (0 where the tap does not exist)."""
         params = list(self.parameters()) + list(self.buffers())
         key = tuple((p.data_ptr(), p._version) for p in params)
         # train mode refolds every call, as the reference's weight-norm / spectral-norm hooks do (and as the generator does): a
@@ -114,62 +204,47 @@ class _DiscConv(nn.Module):
             return self._pair_rec[1]
         k, s, P, G = self.k, self.stride, self.padding, self.groups
         cig, cog = self.c_in // G, self.c_out // G
-        stacked = not self.unfolded and self.c_in > 1
+        stacked = self.form in (_PHASES, _PLAIN)
         dev = self.bias.device
         if stacked and (self._wpad is None or self._wpad.device != dev):
             # constants of the re-indexing, built once: the tap map j[q][r] (k = "no such tap" -> the zero row of wpad)
-            self._Q = -(-P // s)
-            self._kp = self._Q + (k - 1 - P) // s + 1
-            q = torch.arange(self._kp, device=dev).view(self._kp, 1) - self._Q
+            q = torch.arange(self.kp, device=dev).view(self.kp, 1) - self.Q
             r = torch.arange(s, device=dev).view(1, s)
             j = s * q + r + P
             self._jmap = torch.where((j >= 0) & (j < k), j, torch.full_like(j, k)).reshape(-1)
             self._wpad = torch.zeros((k + 1, cig, self.c_out), device=dev)
         wf = self._folded(self._wpad[:k] if stacked else None)            # [k][cig][co]
-        if self.unfolded:                                    # rows (j, c): the taps become channels of a 1-tap conv
-            groups, kp, Q = [wf.reshape(1, k * cig, self.c_out)], 1, 0
-        elif self.c_in == 1:                                 # unfolded: rows = taps
+        if self.form == _TAPS:                               # rows (j, c): the taps become channels of a 1-tap conv
+            w4 = torch.stack([wf.reshape(1, k * cig, self.c_out)], 0)
+        elif self.form == _FIRST:                            # rows = taps
             w2 = torch.zeros((1, _UNFOLD_ROWS, self.c_out), device=dev)
             w2[0, :k] = wf[:, 0, :]
-            groups, kp, Q = [w2], 1, 0
+            w4 = torch.stack([w2], 0)
         else:
-            kp, Q, wpad = self._kp, self._Q, self._wpad
-            w5 = wpad[self._jmap].reshape(kp, s * cig, G, cog)             # rows (r, c), columns (g, o)
-            groups = w5.permute(2, 0, 1, 3).contiguous()                   # [G][kp][s * cig][cog]
-        if not torch.is_tensor(groups):
-            groups = torch.stack(groups, 0)
-        packable = groups.shape[2] % 16 == 0 and (groups.shape[3] % 32 == 0 or groups.shape[3] == 16)
-        rec = dict(w4=groups, wf=list(groups.unbind(0)), kp=kp, Q=Q,
-                   wp=list(hipops.pack_mfma_batch(groups).unbind(0)) if packable else [None] * groups.shape[0])
-        if self.split_eligible(kp, groups.shape[2], groups.shape[3]):
-            # (hi, lo) f16 fragments + scale record of the forward conv, per group.  The kernel pipelines over an odd tap count: the
-            # two-tap phase-stacked layers (k = 5, stride 3) get a zero third tap behind the others (same pad_left; 1.5 x the MFMAs at 2.2 x the rate)
-            ws = groups if kp % 2 == 1 else torch.cat([groups, torch.zeros_like(groups[:, :1])], 1)
-            rec['ws4'], rec['kps'] = ws, ws.shape[1]
-            rec['wps'] = [hipops.pack_split(ws[g]) for g in range(ws.shape[0])]
+            w5 = self._wpad[self._jmap].reshape(self.kp, s * cig, G, cog)  # rows (r, c), columns (g, o)
+            w4 = w5.permute(2, 0, 1, 3).contiguous()                       # [G][kp][s * cig][cog]
+        rec = _Weights(w4, split=self.split_eligible(w4.shape[2], w4.shape[3]))
         self._cache = (key, rec)
         if _PAIR.on and not self.spectral:
             self._pair_rec = (key, rec)
         return rec
 
-    def split_eligible(self, kp, cigp, cog):
+    def split_eligible(self, cigp, cog):
         """The split-f16 kernel serves this layer's stride-1 form: `cigp` stacked input channels and `cog` output channels per group."""
-        return (self.precision == 'f16x3' and not self.unfolded and self.c_in > 1 and kp >= 2
-                and hipops.split_supported(cigp, cog))
+        return (self.precision == 'f16x3' and self.form in (_PHASES, _PLAIN) and self.kp >= 2 and hipops.split_supported(cigp, cog))
 
     def param_grads(self, db, dws, sn):
         """Gradients of this layer's parameters (parameters() order) from the bias gradient and the per-group weight gradients
-        of the stacked stride-1 form, dws[g] [k'][s * C_in/G][C_out/G] (the inverse of `kernel_weights`' re-indexing)."""
+        of the stride-1 form, dws[g] [kp][cs / G][C_out / G] (the inverse of `kernel_weights`' re-indexing)."""
         k, s, G = self.k, self.stride, self.groups
         co, cig = self.c_out, self.c_in // G
         dev = db.device
-        if self.c_in == 1:
+        if self.form == _FIRST:
             dwf = dws[0][0, :k, :].reshape(k, 1, co)
-        elif self.unfolded:
+        elif self.form == _TAPS:
             dwf = dws[0].reshape(k, cig, co)
         else:
-            kp = dws[0].shape[0]
-            d5 = torch.stack(dws, 2).reshape(kp * s, cig, co)            # rows (q, r), then c; columns (g, o)
+            d5 = torch.stack(dws, 2).reshape(self.kp * s, cig, co)       # rows (q, r), then c; columns (g, o)
             dwf = torch.zeros((k + 1, cig, co), device=dev).index_add_(0, self._jmap, d5)[:k]
         dwf = dwf.contiguous()
         if not self.spectral:
@@ -190,100 +265,70 @@ def _check_cuda(*xs):
             raise RuntimeError('the discriminators run on the MI355X HIP path only (no CPU fallback)')
 
 
-def _pitch(n):
-    """Row pitch of a feature-map buffer: the MFMA kernel's float4 staging wants rows that are multiples of 4 floats."""
-    return (n + 3) // 4 * 4
-
-
-def _stream(x):
-    return torch.cuda.current_stream(x.device).cuda_stream
-
-
 def _stacked_input(layer: _DiscConv, x, L_in, inner):
-    """The stride-1 form's input of a layer: x (B, C_in, pitch) activated feature-map buffer (valid [:L_in * inner]) ->
-    (xs (B, C_in', P), U): phases stacked (stride > 1), taps unfolded (optional) or x itself with its tail zeroed (stride 1)."""
-    B, pin = x.shape[0], x.shape[2]
-    s, G = layer.stride, layer.groups
-    lib, st = _hip.load(), _stream(x)
-    if s > 1 and layer.unfolded:
-        U = (L_in + 2 * layer.padding - layer.k) // s + 1
-        P = _pitch(U * inner)
-        xs = torch.empty((B, layer.k * layer.c_in, P), device=x.device)
-        _hip.check(lib.v2w_unfold_taps(x.data_ptr(), xs.data_ptr(), B, layer.c_in, L_in, inner, s, layer.k, layer.padding, pin, P, st),
-                   'v2w_unfold_taps')
-    elif s > 1:
-        U = -(-L_in // s)
-        P = _pitch(U * inner)
-        xs = torch.empty((B, s * layer.c_in, P), device=x.device)
-        _hip.check(lib.v2w_phase_split(x.data_ptr(), xs.data_ptr(), B, layer.c_in, layer.c_in // G, L_in, inner, s, pin, P, st),
-                   'v2w_phase_split')
+    """The stride-1 form's input of a layer above the first: x (B, C_in, pitch) activated feature-map buffer (valid [:L_in * inner]) ->
+    xs (B, layer.cs, roundup4(layer.rows_out(L_in) * inner)): phases stacked, taps unfolded, or x itself with its tail zeroed."""
+    if layer.form == _TAPS:
+        return hipops.unfold_taps(x, L=L_in, inner=inner, s=layer.stride, k=layer.k, pad=layer.padding)
+    if layer.form == _PHASES:
+        return hipops.phase_split(x, L=L_in, inner=inner, s=layer.stride, cg=layer.c_in // layer.groups)
+    return hipops.zero_tail(x, valid=L_in * inner)
+
+
+def _unfold_first(layer: _DiscConv, x, H, inner):
+    """The first layer's stride-1 input: x (B, 1, T) -> (B, 16, roundup4(layer.rows_out(H) * inner))."""
+    if layer.rows_out(H) < 1:
+        raise RuntimeError('discriminator input is shorter than the first kernel')
+    return hipops.unfold1(x, H=H, inner=inner, s=layer.stride, k=layer.k, pad=layer.padding, rows=_UNFOLD_ROWS)
+
+
+def _conv_split_or_exact(layer: _DiscConv, rec: _Weights, x, bias, out, inner, out_slope, dgrad):
+    """The layer's stride-1 conv x (B, cs, P) -> out (B, C_out, P), or (`dgrad`) its input-gradient conv x = dz (B, C_out, P) -> out
+    (B, cs, P) on the transposed, tap-flipped weights.  On the split-f16 kernel where the record has that form; a problem that
+    kernel declines (V2W_E_SHAPE: a halo beyond its staging slots, another channel count per group) runs on the exact fp32 kernel, which
+    overwrites whatever groups the declined launches wrote, and the record forgets the split weights: no re-pack, no retry.  A declined
+    input-gradient problem is also remembered ON THE LAYER - records are rebuilt whenever a parameter version moves, i.e. after every
+    optimizer step - so that later steps do not even pack for it."""
+    dil = layer.dil(inner)
+    if dgrad:
+        exact = rec.transposed()
+        declined = (layer.c_out // layer.groups, layer.cs // layer.groups, x.shape[2])
+        split = rec.transposed_split(allowed=layer._no_split_dgrad != declined)
     else:
-        U, xs = L_in, x
-        _hip.check(lib.v2w_zero_tail(x.data_ptr(), B * layer.c_in, pin, L_in * inner, st), 'v2w_zero_tail')
-    return xs, U
+        exact, split = (rec.w4, rec.wp), rec.split()
+
+    def run(w4, packs, algo):
+        taps_left = w4.shape[1] - 1 - layer.Q if dgrad else layer.Q
+        hipops.conv1d_groups(x, w4, bias, out, packs, dil=dil, pad_left=taps_left * dil, out_slope=out_slope, algo=algo)
+
+    if split is not None:
+        try:
+            return run(*split, hipops.ALGO_SPLIT)
+        except _hip.HipLibraryError as e:
+            if e.code != _hip.E_SHAPE:
+                raise
+        rec.forget_split(dgrad)
+        if dgrad:
+            layer._no_split_dgrad = declined
+    run(*exact, hipops.ALGO_AUTO)
 
 
-def _conv_layer(layer: _DiscConv, rec, x, L_in, inner, out_slope, keep=None):
+def _conv_layer(layer: _DiscConv, rec, x, L_in, inner, out_slope):
     """x (B, C_in, pitch(L_in * inner)) -> (out buffer (B, C_out, pitch(U * inner)), U), U = L_out of the strided conv.  The convs
     run at L = pitch: the tail columns are ordinary positions to the kernel, hold zeros on the input side (phase_split / unfold
     fill them; `v2w_zero_tail` before a stride-1 layer reads a conv output directly) and are never part of the returned views."""
-    B = x.shape[0]
-    G = layer.groups
-    xs, U = _stacked_input(layer, x, L_in, inner)
-    if keep is not None:
-        keep.append(xs)
-    out = torch.empty((B, layer.c_out, xs.shape[2]), device=x.device)
-    cig, cog = xs.shape[1] // G, layer.c_out // G
-    kw = dict(k=rec['kp'], dil=1 if rec['kp'] == 1 else inner, slope=1.0, pad_left=rec['Q'] * inner, out_slope=out_slope)
-    bias = layer.bias.detach()
-
-    def problems(split):
-        if split:       # precision = 'f16x3': the split-f16 kernel on the (zero-padded to an odd tap count) stacked weights
-            kws = dict(kw, k=rec['kps'], algo=hipops.ALGO_SPLIT)
-            return [(xs, rec['ws4'][g], bias[g * cog:(g + 1) * cog], out,
-                     dict(kws, wps=rec['wps'][g], group=(g, cig, cog) if G > 1 else None)) for g in range(G)]
-        return [(xs, rec['wf'][g], bias[g * cog:(g + 1) * cog], out, dict(kw, wp=rec['wp'][g], group=(g, cig, cog) if G > 1 else None))
-                for g in range(G)]
-
-    def run(probs):
-        if G == 1:
-            x0, w0, b0, o0, k0 = probs[0]
-            hipops.conv1d(x0, w0, b0, o0, **k0)
-        else:
-            for i in range(0, G, 4):
-                hipops.conv1d_multi(probs[i:i + 4])
-
-    if 'wps' in rec:
-        try:
-            run(problems(True))
-            return out, U
-        except _hip.HipLibraryError as e:       # a shape the split kernel declines (a halo beyond its staging slots): exact from here on
-            if e.code != _hip.E_SHAPE:
-                raise
-            for key in ('wps', 'ws4', 'kps'):
-                rec.pop(key, None)
-    run(problems(False))
-    return out, U
+    xs = _stacked_input(layer, x, L_in, inner)
+    out = torch.empty((x.shape[0], layer.c_out, xs.shape[2]), device=x.device)
+    _conv_split_or_exact(layer, rec, xs, layer.bias.detach(), out, inner, out_slope, dgrad=False)
+    return out, layer.rows_out(L_in)
 
 
-def _unfold_first(layer: _DiscConv, x, T, H, inner):
-    B = x.shape[0]
-    U = (H + 2 * layer.padding - layer.k) // layer.stride + 1
-    if U < 1:
-        raise RuntimeError('discriminator input is shorter than the first kernel')
-    P = _pitch(U * inner)
-    xu = torch.empty((B, _UNFOLD_ROWS, P), device=x.device)
-    _hip.check(_hip.load().v2w_unfold1(x.data_ptr(), xu.data_ptr(), B, T, H, inner, layer.stride, layer.k, layer.padding, _UNFOLD_ROWS,
-                                       P, _stream(x)), 'v2w_unfold1')
-    return xu, U
-
-
-def _first_layer(layer: _DiscConv, rec, x, T, H, inner):
+def _first_layer(layer: _DiscConv, rec, x, H, inner):
     """C_in = 1: x (B, 1, T) -> activated buffer (B, C_out, pitch(U * inner)) through the unfolded 1-tap form."""
-    xu, U = _unfold_first(layer, x, T, H, inner)
+    xu = _unfold_first(layer, x, H, inner)
     out = torch.empty((x.shape[0], layer.c_out, xu.shape[2]), device=x.device)
-    hipops.conv1d(xu, rec['wf'][0], layer.bias.detach(), out, k=1, dil=1, slope=1.0, wp=rec['wp'][0], out_slope=LRELU_SLOPE)
-    return out, U
+    hipops.conv1d(xu, rec.w4[0], layer.bias.detach(), out, k=1, dil=1, slope=1.0, wp=rec.wp[0], out_slope=LRELU_SLOPE)
+    return out, layer.rows_out(H)
 
 
 class _DiscBase(nn.Module):
@@ -295,21 +340,18 @@ class _DiscBase(nn.Module):
     def _geometry(self, t):
         raise NotImplementedError
 
-    def _run(self, x, keep=False):
+    def _run(self, x):
         """x (B, 1, T) -> state for the views / the backward: per layer (buffer (B, C, pitch), rows U) + the weights used."""
         b, c, t = x.shape
         inner, H = self._geometry(t)
         layers = self._layers()
         recs = [l.kernel_weights() for l in layers]             # (spectral norm: the power iteration of this call happens here)
         sn = [l._last_sn for l in layers]
-        bufs = []
-        xss = [None] if keep else None                           # stacked inputs kept for the weight gradients (288 GB of HBM)
-        f, U = _first_layer(layers[0], recs[0], x, t, H, inner)
-        bufs.append((f, U))
+        bufs = [_first_layer(layers[0], recs[0], x, H, inner)]
         for i in range(1, len(layers)):
-            f, U = _conv_layer(layers[i], recs[i], f, U, inner, LRELU_SLOPE if i + 1 < len(layers) else 0.0, xss)
-            bufs.append((f, U))
-        return dict(bufs=bufs, recs=recs, sn=sn, inner=inner, H=H, T=t, xss=xss)
+            f, U = bufs[-1]
+            bufs.append(_conv_layer(layers[i], recs[i], f, U, inner, LRELU_SLOPE if i + 1 < len(layers) else 0.0))
+        return dict(bufs=bufs, recs=recs, sn=sn, inner=inner, H=H, T=t)
 
     def _views(self, st, b):
         inner = st['inner']
@@ -330,6 +372,48 @@ class _DiscBase(nn.Module):
         return torch.flatten(fmap[-1], 1, -1), fmap
 
 
+# ---- the backward of one layer, in the order it runs: dz and the bias gradient, the weight gradient, the input gradient
+class _Down(NamedTuple):
+    """What a layer's backward hands to the layer below: the gradient wrt that layer's activated map, as the pitched buffer `d`
+    (s == 1), or still in the phase-stacked form (B, s * C, pitch) of a stride-s layer with `cg` channels per group - un-stacked
+    inside the next disc_dz."""
+    d: torch.Tensor
+    cg: int
+    s: int
+
+
+def _dz_and_bias_grad(f, U, inner, g, down: Optional[_Down], slope, need_db):
+    """f (B, C, P): a layer's activated map (U rows of `inner` columns valid), g: the gradient that arrived on its returned view (dense)
+    or None, down: the one from the layer above or None -> (dz (B, C, P), the gradient wrt the conv's output; db (C,) or None)."""
+    B, Cc, P = f.shape
+    dz = torch.empty((B, Cc, P), device=f.device)
+    rowsum = torch.empty((B, Cc), device=f.device) if need_db else None      # bias gradient partials from the same pass
+    if down is not None and down.s > 1:
+        hipops.disc_dz_merge(f, g, down.d, cg=down.cg, L=U, inner=inner, s=down.s, slope=slope, out=dz, rowsum=rowsum)
+    else:
+        hipops.disc_dz(f, g, None if down is None else down.d, valid=U * inner, slope=slope, out=dz, rowsum=rowsum)
+    return dz, (hipops.rowsum_reduce(rowsum) if need_db else None)
+
+
+def _weight_grad(layer: _DiscConv, xs, dz, inner):
+    """xs (B, cs, P): the layer's stride-1 input, dz (B, C_out, P) -> the weight gradient in the stride-1 form, per group:
+    [G] of [kp][cs / G][C_out / G] (`_DiscConv.param_grads` takes it back to the reference's parameters)."""
+    assert xs.shape[1] == layer.cs and xs.shape[2] == dz.shape[2]
+    if layer.c_out == 1:
+        return [hipops.cout1_wgrad(xs, dz, k=layer.kp, dil=layer.dil(inner), tap0=layer.Q)]
+    return list(hipops.wgrad_groups(xs, dz, groups=layer.groups, k=layer.kp, dil=layer.dil(inner), tap0=layer.Q).unbind(0))
+
+
+def _input_grad(layer: _DiscConv, rec: _Weights, dz, inner) -> _Down:
+    """dz (B, C_out, P) -> the gradient wrt the layer's stride-1 input (B, cs, P) - the forward conv kernel with the transposed,
+    tap-flipped weights - as what flows to the layer below (the first layer: to `fold1`)."""
+    if layer.form == _TAPS:
+        raise NotImplementedError('backward of the unfolded-tap form (V2W_DISC_UNFOLD=1) is not built')
+    dxs = torch.empty((dz.shape[0], layer.cs, dz.shape[2]), device=dz.device)
+    _conv_split_or_exact(layer, rec, dz, None, dxs, inner, 0.0, dgrad=True)
+    return _Down(dxs, layer.c_in // layer.groups, layer.stride if layer.form == _PHASES else 1)
+
+
 class _DiscFn(torch.autograd.Function):
     """One discriminator call under autograd: forward = `_DiscBase._run`, backward below (the D step and the G step of
     train.py:188-215 both differentiate through it).  Inputs: x and every parameter in `_layers()` order."""
@@ -337,7 +421,7 @@ class _DiscFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, disc, x, *params):
         xd = x.detach().contiguous().float()
-        st = disc._run(xd, keep=False)        # (the phase-stacked layer inputs are rebuilt in the backward from the maps below them: -11 GB)
+        st = disc._run(xd)        # (the stride-1 layer inputs are rebuilt in the backward from the maps below them: -11 GB)
         views = tuple(disc._views(st, xd.shape[0]))
         # the maps go through save_for_backward, not a ctx attribute: autograd then releases them when the backward has run (unless
         # retain_graph) - as a plain attribute they lived as long as ANY tensor downstream of this call (train.py keeps `loss_disc_*` and the
@@ -353,137 +437,35 @@ class _DiscFn(torch.autograd.Function):
     @staticmethod
     @_hip.on_tensor_device
     def backward(ctx, *gouts):
-        disc = ctx.disc
         x, *maps = ctx.saved_tensors
-        st = dict(ctx.st, bufs=list(zip(maps, ctx.rows)))
-        del maps
-        lib, stream = _hip.load(), _stream(x)
-        layers = disc._layers()
+        st, rows = ctx.st, ctx.rows
+        layers = ctx.disc._layers()
         inner, H, T = st['inner'], st['H'], st['T']
-        B, dev = x.shape[0], x.device
         n = len(layers)
-        grads = [None] * n           # per layer: tuple of parameter gradients in parameters() order
-        dnext, dx = None, None       # gradient wrt the activated map of layer l arriving from layer l + 1: a pitched buffer, or
-        merge = None                 # the phase-stacked input gradient of a strided layer + its geometry (merged inside disc_dz)
+        grads = [None] * n           # per layer: its parameter gradients in parameters() order
+        down, dx = None, None        # what flows into layer l from layer l + 1; the gradient wrt the audio
         for l in reversed(range(n)):
-            layer, rec = layers[l], st['recs'][l]
-            f, U = st['bufs'][l]
-            P, valid, C = f.shape[2], st['bufs'][l][1] * inner, layer.c_out
-            g = gouts[l]
-            if g is None and dnext is None and merge is None:
+            layer, rec, g = layers[l], st['recs'][l], gouts[l]
+            if g is None and down is None:
                 continue                                     # nothing flows through this layer (nor, so far, below it)
             if g is not None:
                 g = g.contiguous().float()
-            dz = torch.empty((B, C, P), device=dev)
-            slope = LRELU_SLOPE if l + 1 < n else 1.0
-            rowsum = torch.empty((B * C,), device=dev) if ctx.need_dw else None     # bias gradient partials from the same pass
-            if merge is not None:
-                dxs_up, cg_up, s_up = merge
-                _hip.check(lib.v2w_disc_dz_merge(f.data_ptr(), _hip.ptr(g), dxs_up.data_ptr(), dz.data_ptr(), _hip.ptr(rowsum), B, C, cg_up, U,
-                                                 inner, s_up, dxs_up.shape[2], P, slope, stream), 'v2w_disc_dz_merge')
-            else:
-                _hip.check(lib.v2w_disc_dz(f.data_ptr(), _hip.ptr(g), _hip.ptr(dnext), dz.data_ptr(), _hip.ptr(rowsum), B * C, P, valid, slope,
-                                           stream), 'v2w_disc_dz')
-            dnext, merge = None, None
-            db = None
-            if ctx.need_dw:
-                db = torch.empty((C,), device=dev)
-                _hip.check(lib.v2w_rowsum_reduce(rowsum.data_ptr(), db.data_ptr(), B, C, stream), 'v2w_rowsum_reduce')
-            # the layer's stride-1 input (the phases of the map below stacked along the channels; the 16-row unfold of the first layer): rebuilt
-            # here, one streaming pass, and only when a weight gradient reads it - the forward keeps the feature maps alone
-            G = layer.groups
-            if l == 0:
-                xs_c = _UNFOLD_ROWS
-            else:
-                xs_c = layer.c_in * (layer.stride if layer.stride > 1 and not layer.unfolded else (layer.k if layer.stride > 1 else 1))
-            xs = None
-            if ctx.need_dw:
-                if st['xss'] is not None and l > 0:
-                    xs = st['xss'][l]
-                elif l == 0:
-                    xs = _unfold_first(layer, x, T, H, inner)[0]
-                else:
-                    xs = _stacked_input(layer, st['bufs'][l - 1][0], st['bufs'][l - 1][1], inner)[0]
-                assert xs.shape[1] == xs_c and xs.shape[2] == P
-            cigp, cog = xs_c // G, C // G
-            kp, Q = rec['kp'], rec['Q']
-            dil = 1 if kp == 1 else inner
-            # ---- weight gradient in the stacked form, then back to the reference's (C_out, C_in / groups, k)
+            dz, db = _dz_and_bias_grad(maps[l], rows[l], inner, g, down, LRELU_SLOPE if l + 1 < n else 1.0, ctx.need_dw)
+            down = None
             if ctx.need_dw:                   # (frozen discriminators - `frozen()` around the G step - skip all of this)
-                if C == 1:
-                    dwp = torch.empty((kp, xs_c, 1), device=dev)
-                    _hip.check(lib.v2w_cout1_wgrad(xs.data_ptr(), dz.data_ptr(), dwp.data_ptr(), B, xs_c, P, kp, dil, Q, stream),
-                               'v2w_cout1_wgrad')
-                    dws = [dwp]
-                else:
-                    ns = lib.v2w_wgrad_slabs(B, cigp, cog, P)
-                    if ns == 0:
-                        raise _hip.HipLibraryError(f'v2w_wgrad_slice: no configuration for C_in={cigp}, C_out={cog}')
-                    dwg = torch.empty((G, kp, cigp, cog), device=dev)
-                    if _WGRAD_GROUPED:
-                        slab = torch.empty((G * lib.v2w_wgrad_group_slabs(B, cigp, cog, P, G) * kp * cigp * cog,), device=dev)
-                        _hip.check(lib.v2w_wgrad_groups(xs.data_ptr(), dz.data_ptr(), dwg.data_ptr(), slab.data_ptr(), B, cigp, cog, P, kp, dil,
-                                                        Q, G, stream), 'v2w_wgrad_groups')
-                    else:
-                        slab = torch.empty((ns * kp * cigp * cog,), device=dev)
-                        for gi in range(G):
-                            _hip.check(lib.v2w_wgrad_slice(xs.data_ptr() + gi * cigp * P * 4, dz.data_ptr() + gi * cog * P * 4,
-                                                           dwg[gi].data_ptr(), slab.data_ptr(), B, cigp, cog, P, kp, dil, Q, xs_c, C,
-                                                           stream), 'v2w_wgrad_slice')
-                    dws = list(dwg.unbind(0))
-                grads[l] = layer.param_grads(db, dws, st['sn'][l])
-            # ---- input gradient: the forward conv kernel with the transposed, tap-flipped weights
-            if l > 0 or ctx.need_dx:
-                dxs = torch.empty((B, xs_c, P), device=dev)
-                if 'wT' not in rec:                                            # shared by the y / y_hat calls of one step
-                    packable = cog % 16 == 0 and (cigp % 32 == 0 or cigp == 16)
-                    wT4 = rec['w4'].flip(1).transpose(2, 3).contiguous()        # [G][kp][cog][cigp], taps reversed
-                    rec['wT'] = list(wT4.unbind(0))
-                    rec['wTp'] = list(hipops.pack_mfma_batch(wT4).unbind(0)) if packable else [None] * G
-                if 'wps' in rec and 'wTs' not in rec and hipops.split_supported(cog, cigp) and getattr(layer, '_no_split_dgrad', None) != (cog, cigp, P):
-                    # the same layer's input-gradient conv in split-f16 form: transposed, tap-reversed (the zero pad tap comes first)
-                    wTs4 = rec['ws4'].flip(1).transpose(2, 3).contiguous()       # [G][kps][cog][cigp]
-                    rec['wTs4'], rec['wTs'] = wTs4, [hipops.pack_split(wTs4[gi]) for gi in range(G)]
-                if 'wTs' in rec:
-                    kps = rec['kps']
-                    probs = [(dz, rec['wTs4'][gi], None, dxs, dict(k=kps, dil=dil, slope=1.0, pad_left=(kps - 1 - Q) * dil, algo=hipops.ALGO_SPLIT,
-                                                                   wps=rec['wTs'][gi], group=(gi, cog, cigp) if G > 1 else None)) for gi in range(G)]
-                    try:
-                        if G == 1:
-                            hipops.conv1d(dz, probs[0][1], None, dxs, **probs[0][4])
-                        else:
-                            for i in range(0, G, 4):
-                                hipops.conv1d_multi(probs[i:i + 4])
-                    except _hip.HipLibraryError as e:
-                        # the split-f16 kernel took the forward but declines the TRANSPOSED problem (another halo, another channel count per
-                        # group): the exact fp32 input-gradient conv below - for this step and, remembered ON THE LAYER (`rec` is rebuilt whenever
-                        # a parameter version moves, i.e. after every optimizer step), for every later one: no re-pack, no retry.  The exact conv
-                        # overwrites whatever groups the declined launches wrote.
-                        if e.code != _hip.E_SHAPE:
-                            raise
-                        layer._no_split_dgrad = (cog, cigp, P)
-                        for key in ('wTs', 'wTs4'):
-                            rec.pop(key, None)
-                if 'wTs' not in rec:
-                    probs = [(dz, rec['wT'][gi], None, dxs, dict(k=kp, dil=dil, slope=1.0, pad_left=(kp - 1 - Q) * dil, wp=rec['wTp'][gi],
-                                                                 group=(gi, cog, cigp) if G > 1 else None)) for gi in range(G)]
-                    for i in range(0, G, 4):
-                        hipops.conv1d_multi(probs[i:i + 4])
-                if l == 0:
-                    dx = torch.empty((B, 1, T), device=dev)
-                    _hip.check(lib.v2w_fold1(dxs.data_ptr(), dx.data_ptr(), B, T, H, inner, layer.stride, layer.k, layer.padding,
-                                             _UNFOLD_ROWS, P, stream), 'v2w_fold1')
-                elif layer.stride > 1 and not layer.unfolded:
-                    merge = (dxs, layer.c_in // G, layer.stride)           # un-stacked by the next iteration's disc_dz
-                elif layer.stride > 1:
-                    raise NotImplementedError('backward of the unfolded-tap form (V2W_DISC_UNFOLD=1) is not built')
-                else:
-                    dnext = dxs
+                # the layer's stride-1 input: rebuilt here, one streaming pass, and only when a weight gradient reads it - the forward
+                # keeps the feature maps alone
+                xs = _unfold_first(layer, x, H, inner) if l == 0 else _stacked_input(layer, maps[l - 1], rows[l - 1], inner)
+                grads[l] = layer.param_grads(db, _weight_grad(layer, xs, dz, inner), st['sn'][l])
+            if l > 0:
+                down = _input_grad(layer, rec, dz, inner)
+            elif ctx.need_dx:
+                dx = hipops.fold1(_input_grad(layer, rec, dz, inner).d, T=T, H=H, inner=inner, s=layer.stride, k=layer.k, pad=layer.padding)
         flat = []
         for l in range(n):
             npar = len(list(layers[l].parameters()))
             flat.extend(grads[l] if grads[l] is not None else [None] * npar)
-        return (None, dx if ctx.need_dx else None, *flat)
+        return (None, dx, *flat)
 
 
 class DiscriminatorP(_DiscBase):
@@ -580,27 +562,16 @@ class DiscriminatorS(_DiscBase):
         return 1, t
 
 
-def _avg_pool_fwd(x):
-    B, C, L = x.shape
-    out = torch.empty((B, C, L // 2 + 1), device=x.device)
-    _hip.check(_hip.load().v2w_avgpool4(x.data_ptr(), out.data_ptr(), B * C, L, _stream(x)), 'v2w_avgpool4')
-    return out
-
-
 class _AvgPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        ctx.shape = x.shape
-        return _avg_pool_fwd(x.detach().contiguous().float())
+        ctx.L = x.shape[2]
+        return hipops.avgpool4(x.detach().contiguous().float())
 
     @staticmethod
     @_hip.on_tensor_device
     def backward(ctx, g):
-        B, C, L = ctx.shape
-        g = g.contiguous().float()
-        dx = torch.empty((B, C, L), device=g.device)
-        _hip.check(_hip.load().v2w_avgpool4_bwd(g.data_ptr(), dx.data_ptr(), B * C, L, _stream(g)), 'v2w_avgpool4_bwd')
-        return dx
+        return hipops.avgpool4_bwd(g.contiguous().float(), L=ctx.L)
 
 
 @_hip.on_tensor_device
@@ -610,7 +581,7 @@ def avg_pool(x):
     if torch.is_grad_enabled() and x.requires_grad:
         return _AvgPoolFn.apply(x)
     with torch.no_grad():
-        return _avg_pool_fwd(x.detach().contiguous().float())
+        return hipops.avgpool4(x.detach().contiguous().float())
 
 
 class _MeanPool(nn.Module):

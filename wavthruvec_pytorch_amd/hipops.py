@@ -913,8 +913,7 @@ def convt1d_dgrad(dy, wf, out, *, k, u, mask=None, mask_slope=1.0, algo=ALGO_AUT
     # ran at less than half the forward's rate)
     dyp = None
     if algo == ALGO_AUTO and L % 4 == 0 and conv_tile_config(B, co, out.shape[1], L, 3) is not None:
-        dyp = torch.empty((B, u * co, L), device=dy.device, dtype=torch.float32)
-        _hip.check(_hip.load().v2w_phase_split(dy.data_ptr(), dyp.data_ptr(), B, co, co, L * u, 1, u, 0, 0, _stream(dy)), 'v2w_phase_split')
+        dyp = phase_split(dy, L=L * u, inner=1, s=u)                    # (B, u * C_out, L)
     for r in range(u):
         t0, c = (r + pad) % u, (r + pad) // u
         nt = (k - t0 + u - 1) // u
@@ -997,6 +996,188 @@ def channel_sum(x):
     part = torch.empty((2 * Cc * _hip.V2W_BN_SPLITS,), device=x.device, dtype=torch.float64)
     bn_stats(x, stats, part)
     return stats[:Cc].float()
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# discriminator path (csrc/v2w_disc.hip).  Feature maps are (B, C, pitch) buffers of which [:, :, :L * inner] is valid (L rows of `inner`
+# columns: inner = the period of a period discriminator, 1 otherwise); B, the channel counts and every pitch come from the tensors.
+def _pitch4(n):
+    return (n + 3) // 4 * 4
+
+
+def _out(out, shape, like, name, pitched=False):
+    """`out`, checked, or a new fp32 tensor of `shape` on `like`'s device.  pitched: the caller's `out` chooses its own row pitch (the last
+    dimension; the library checks that the valid part fits)."""
+    if out is None:
+        return torch.empty(shape, device=like.device, dtype=torch.float32)
+    _chk(out, name)
+    n = len(shape) - 1 if pitched else len(shape)
+    if out.dim() != len(shape) or tuple(out.shape[:n]) != tuple(shape[:n]):
+        raise ValueError(f'{name}: expected {tuple(shape)}{" (any row pitch)" if pitched else ""}, got {tuple(out.shape)}')
+    return out
+
+
+def phase_split(x, *, L, inner, s, cg=None, out=None):
+    """x (B, C, ipitch) -> out (B, s * C, opitch), default opitch = roundup4(ceil(L / s) * inner): the s phases of the L rows stacked along the
+    channels, group by group (cg channels per group, default C), zero past L."""
+    _chk(x, 'x')
+    B, Cc, ip = x.shape
+    out = _out(out, (B, s * Cc, _pitch4(-(-L // s) * inner)), x, 'out', pitched=True)
+    _hip.check(_hip.load().v2w_phase_split(x.data_ptr(), out.data_ptr(), B, Cc, Cc if cg is None else cg, L, inner, s, ip, out.shape[2], _stream(x)),
+               'v2w_phase_split')
+    return out
+
+
+def unfold_taps(x, *, L, inner, s, k, pad, out=None):
+    """x (B, C, ipitch) -> out (B, k * C, opitch), default opitch = roundup4(U * inner), U = (L + 2 pad - k) / s + 1: tap j of a k-tap
+    stride-s conv as channels j * C .. of a 1-tap conv."""
+    _chk(x, 'x')
+    B, Cc, ip = x.shape
+    out = _out(out, (B, k * Cc, _pitch4(((L + 2 * pad - k) // s + 1) * inner)), x, 'out', pitched=True)
+    _hip.check(_hip.load().v2w_unfold_taps(x.data_ptr(), out.data_ptr(), B, Cc, L, inner, s, k, pad, ip, out.shape[2], _stream(x)), 'v2w_unfold_taps')
+    return out
+
+
+def zero_tail(x, *, valid):
+    """x (..., pitch), in place: [valid, pitch) of every row becomes 0.  Returns x."""
+    _chk(x, 'x')
+    pitch = x.shape[-1]
+    _hip.check(_hip.load().v2w_zero_tail(x.data_ptr(), x.numel() // pitch, pitch, valid, _stream(x)), 'v2w_zero_tail')
+    return x
+
+
+def unfold1(x, *, H, inner, s, k, pad, rows, out=None):
+    """x (B, 1, T) or (B, T), read as H rows of `inner` columns (reflect-padded on the right to H * inner) -> out (B, rows, opitch), default
+    opitch = roundup4(U * inner), U = (H + 2 pad - k) / s + 1: row j is tap j of the k-tap stride-s conv, rows k .. are 0."""
+    _chk(x, 'x')
+    B, T = x.shape[0], x.shape[-1]
+    out = _out(out, (B, rows, _pitch4(((H + 2 * pad - k) // s + 1) * inner)), x, 'out', pitched=True)
+    _hip.check(_hip.load().v2w_unfold1(x.data_ptr(), out.data_ptr(), B, T, H, inner, s, k, pad, rows, out.shape[2], _stream(x)), 'v2w_unfold1')
+    return out
+
+
+def fold1(dxu, *, T, H, inner, s, k, pad, out=None):
+    """Backward of unfold1: dxu (B, rows, ipitch) -> dx (B, 1, T), the reflected tail folded back."""
+    _chk(dxu, 'dxu')
+    B, rows, ip = dxu.shape
+    if out is None:
+        out = torch.empty((B, 1, T), device=dxu.device, dtype=torch.float32)
+    _chk(out, 'out')
+    if out.numel() != B * T:
+        raise ValueError(f'out: expected {B} x {T} elements, got {tuple(out.shape)}')
+    _hip.check(_hip.load().v2w_fold1(dxu.data_ptr(), out.data_ptr(), B, T, H, inner, s, k, pad, rows, ip, _stream(dxu)), 'v2w_fold1')
+    return out
+
+
+def disc_dz(f, g, d, *, valid, slope, out=None, rowsum=None):
+    """dz = (g + d) * lrelu'(f) on [:valid] of every row, 0 behind: f (..., pitch) the activated feature map, g its dense gradient (rows x
+    valid) or None, d a pitched gradient like f or None.  rowsum (optional, at least one float per row) receives the sum of each dz row."""
+    _chk(f, 'f'); _chk(g, 'g'); _chk(d, 'd'); _chk(rowsum, 'rowsum')
+    pitch = f.shape[-1]
+    rows = f.numel() // pitch
+    out = _out(out, tuple(f.shape), f, 'out')
+    if (g is not None and g.numel() != rows * valid) or (d is not None and d.shape != f.shape) or out.shape != f.shape \
+            or (rowsum is not None and rowsum.numel() < rows):
+        raise ValueError('disc_dz: g must hold rows x valid elements, d and out must be shaped like f, rowsum must hold a float per row')
+    _hip.check(_hip.load().v2w_disc_dz(f.data_ptr(), _hip.ptr(g), _hip.ptr(d), out.data_ptr(), _hip.ptr(rowsum), rows, pitch, valid, slope,
+                                       _stream(f)), 'v2w_disc_dz')
+    return out
+
+
+def disc_dz_merge(f, g, dxs, *, cg, L, inner, s, slope, out=None, rowsum=None):
+    """disc_dz with d given as dxs (B, s * C, dpitch), the phase-stacked input gradient of the stride-s layer above (cg channels per group):
+    f (B, C, pitch) (or its B * C rows), valid = L * inner."""
+    _chk(f, 'f'); _chk(g, 'g'); _chk(dxs, 'dxs'); _chk(rowsum, 'rowsum')
+    B, sC, dp = dxs.shape
+    Cc, pitch = sC // s, f.shape[-1]
+    out = _out(out, tuple(f.shape), f, 'out')
+    if sC % s or f.numel() != B * Cc * pitch or out.shape != f.shape or (g is not None and g.numel() != B * Cc * L * inner) \
+            or (rowsum is not None and rowsum.numel() < B * Cc):
+        raise ValueError('disc_dz_merge: f and out must hold B x C rows for dxs (B, s * C, dpitch), g their valid parts, rowsum a float per row')
+    _hip.check(_hip.load().v2w_disc_dz_merge(f.data_ptr(), _hip.ptr(g), dxs.data_ptr(), out.data_ptr(), _hip.ptr(rowsum), B, Cc, cg, L, inner, s,
+                                             dp, pitch, slope, _stream(f)), 'v2w_disc_dz_merge')
+    return out
+
+
+def rowsum_reduce(rowsum, out=None):
+    """rowsum (B, C) (the row sums of disc_dz) -> the bias gradient db (C,): the sum over the batch items, fp64, in fixed order."""
+    _chk(rowsum, 'rowsum')
+    B, Cc = rowsum.shape
+    out = _out(out, (Cc,), rowsum, 'out')
+    _hip.check(_hip.load().v2w_rowsum_reduce(rowsum.data_ptr(), out.data_ptr(), B, Cc, _stream(rowsum)), 'v2w_rowsum_reduce')
+    return out
+
+
+def cout1_wgrad(x, dz, *, k, dil, tap0, out=None):
+    """Weight gradient dwf [k][C][1] of a C_out = 1 conv with taps at (t - tap0) * dil: x (B, C, L), dz (B, 1, L)."""
+    _chk(x, 'x'); _chk(dz, 'dz')
+    B, Cc, L = x.shape
+    if tuple(dz.shape) != (B, 1, L):
+        raise ValueError(f'dz: expected {(B, 1, L)}, got {tuple(dz.shape)}')
+    out = _out(out, (k, Cc, 1), x, 'out')
+    _hip.check(_hip.load().v2w_cout1_wgrad(x.data_ptr(), dz.data_ptr(), out.data_ptr(), B, Cc, L, k, dil, tap0, _stream(x)), 'v2w_cout1_wgrad')
+    return out
+
+
+def wgrad_groups(x, dy, *, groups, k, dil, tap0, out=None, slab=None):
+    """Weight gradients dwf [G][k][C_in / G][C_out / G] of every group of a grouped Conv1d (taps at (t - tap0) * dil) in one launch per tap
+    group: x (B, C_in, Lq), dy (B, C_out, Lq).  slab: the scratch of the position splits (allocated here when None)."""
+    _chk(x, 'x'); _chk(dy, 'dy')
+    B, ci, Lq = x.shape
+    co = dy.shape[1]
+    if dy.shape[0] != B or dy.shape[2] != Lq or ci % groups or co % groups:
+        raise ValueError(f'wgrad_groups: x {tuple(x.shape)} and dy {tuple(dy.shape)} do not form {groups} groups of one batch and length')
+    ci, co = ci // groups, co // groups
+    lib = _hip.load()
+    if lib.v2w_wgrad_slabs(B, ci, co, Lq) == 0:
+        raise _hip.HipLibraryError(f'v2w_wgrad_groups: no configuration for C_in={ci}, C_out={co}')
+    out = _out(out, (groups, k, ci, co), x, 'out')
+    n = groups * lib.v2w_wgrad_group_slabs(B, ci, co, Lq, groups) * k * ci * co
+    if slab is None:
+        slab = torch.empty((n,), device=x.device, dtype=torch.float32)
+    _chk(slab, 'slab')
+    if slab.numel() < n:
+        raise ValueError(f'slab: {n} floats needed, got {slab.numel()}')
+    _hip.check(lib.v2w_wgrad_groups(x.data_ptr(), dy.data_ptr(), out.data_ptr(), slab.data_ptr(), B, ci, co, Lq, k, dil, tap0, groups, _stream(x)),
+               'v2w_wgrad_groups')
+    return out
+
+
+def avgpool4(x, out=None):
+    """AvgPool1d(4, 2, padding=2) along the last axis: x (..., L) -> out (..., L / 2 + 1)."""
+    _chk(x, 'x')
+    L = x.shape[-1]
+    out = _out(out, tuple(x.shape[:-1]) + (L // 2 + 1,), x, 'out')
+    _hip.check(_hip.load().v2w_avgpool4(x.data_ptr(), out.data_ptr(), x.numel() // L, L, _stream(x)), 'v2w_avgpool4')
+    return out
+
+
+def avgpool4_bwd(g, *, L, out=None):
+    """Backward of avgpool4: g (..., L / 2 + 1) -> dx (..., L)."""
+    _chk(g, 'g')
+    if g.shape[-1] != L // 2 + 1:
+        raise ValueError(f'g: expected rows of {L // 2 + 1}, got {tuple(g.shape)}')
+    out = _out(out, tuple(g.shape[:-1]) + (L,), g, 'out')
+    _hip.check(_hip.load().v2w_avgpool4_bwd(g.data_ptr(), out.data_ptr(), g.numel() // g.shape[-1], L, _stream(g)), 'v2w_avgpool4_bwd')
+    return out
+
+
+def conv1d_groups(x, w4, bias, out, packs, *, dil, pad_left, out_slope=0.0, algo=ALGO_AUTO):
+    """A grouped stride-1 conv as one problem per group on channel slices: x (B, G * C_in, L), w4 [G][k][C_in][C_out], bias (G * C_out,) or
+    None, out (B, G * C_out, L); packs[g]: group g's pack_mfma stream (or None) - with algo = ALGO_SPLIT its pack_split pair.  One launch
+    when G == 1, otherwise the groups four per launch."""
+    G, k, ci, co = w4.shape
+    probs = []
+    for g in range(G):
+        kw = dict(k=k, dil=dil, slope=1.0, pad_left=pad_left, out_slope=out_slope, algo=algo, group=(g, ci, co) if G > 1 else None)
+        kw['wps' if algo == ALGO_SPLIT else 'wp'] = packs[g]
+        probs.append((x, w4[g], None if bias is None else bias[g * co:(g + 1) * co], out, kw))
+    if G == 1:
+        conv1d(*probs[0][:4], **probs[0][4])
+    else:
+        for i in range(0, G, 4):
+            conv1d_multi(probs[i:i + 4])
+    return out
 
 
 # ---- GAN training losses (include/vec2wav_hip.h: v2w_l1_mean_multi / v2w_lsgan_multi and their backwards)
