@@ -640,6 +640,56 @@ int v2w_l1_mean_multi_bwd(const v2w_l1_pair* pairs, int n, float scale, const fl
 int v2w_lsgan_multi(const v2w_lsgan_item* items, int n, float* term, float* total, void* stream);
 int v2w_lsgan_multi_bwd(const v2w_lsgan_item* items, int n, const float* gout, const float* gterm, void* stream);
 
+/* ---- AdamW (additive in ABI v35; torch.optim.AdamW as train.py:96-99 constructs it and train.py:198,215 steps it: decoupled weight
+ * decay, no amsgrad, no maximize): the step of up to V2W_ADAMW_MAX_ITEMS parameter tensors in ONE launch that reads p, g, m, v and
+ * writes p, m, v once (28 bytes per parameter).  The descriptors and the hyperparameters are HOST memory, read before the call returns.
+ * p, g, m (exp_avg), v (exp_avg_sq): `numel` dense fp32 each, 4-byte aligned; items whose four pointers share their 16-byte phase take
+ * 16-byte accesses, the others float-by-float ones.  Every element of p, m and v is written exactly once and nothing else is written;
+ * no atomics, no scratch, no library state.  The kernel never sees the step count t: the caller passes bias_corr1 = 1 - beta1^t and
+ * bias_corr2_sqrt = sqrt(1 - beta2^t), each computed in double and rounded once to fp32 (no device step tensor, no host sync).
+ *
+ * Arithmetic.  Launch constants, each computed on the host in double from the fp32 fields and rounded ONCE to fp32:
+ *     decay = 1 - lr * weight_decay,  omb1 = 1 - beta1,  omb2 = 1 - beta2,  rbc2 = 1 / bias_corr2_sqrt,  step = lr / bias_corr1
+ * Per element, every line ONE correctly rounded fp32 operation (fma = fused multiply-add, one rounding), in this order:
+ *     pd  = p * decay
+ *     d   = g - m
+ *     m'  = fma(omb1, d, m)                       3 roundings on m': omb1, d, m'
+ *     gg  = g * g
+ *     tg  = omb2 * gg
+ *     v'  = fma(beta2, v, tg)                     4 roundings on v': omb2, gg, tg, v'
+ *     den = fma(sqrt(v'), rbc2, eps)              sqrt correctly rounded
+ *     q   = m' / den                              correctly rounded
+ *     p'  = fma(-step, q, pd)                    15 roundings on p': decay, pd, the 3 of m', the 4 of v', sqrt, rbc2, den, step, q, p'
+ * which is p <- p (1 - lr wd);  m <- m + (1 - b1)(g - m);  v <- b2 v + (1 - b2) g g;  p <- p - (lr / bias_corr1) m / (sqrt(v) / bias_corr2_sqrt
+ * + eps), torch's order.  Against that formula evaluated exactly from the same fp32 inputs, with u = 2^-24:
+ *     |m' - exact| <= 3u (|m| + |g|),   |v' - exact| <= 4u (|v| + g g),   |p' - exact| <= 15u (|p| + step (|m| + |g|) / den)
+ * to first order (|m'| <= |m| + |g|; v' and den are sums of non-negative terms, so their relative errors add up).
+ *
+ * V2W_E_ARG: items or h NULL; n < 1 or n > V2W_ADAMW_MAX_ITEMS; a NULL or not 4-byte aligned pointer; numel <= 0; a beta outside [0, 1);
+ * eps < 0, lr < 0, bias_corr1 <= 0 or bias_corr2_sqrt <= 0 (or a NaN among them); p, m or v of one item overlapping each other.
+ * V2W_E_SHAPE: numel > 2^42 (more than 2^40 units).
+ * V2W_ADAMW_MAX_ITEMS: the table travels by value in the kernel arguments, which hold 4 KB with the hidden ones (3584 bytes are the
+ * library's own limit, as for the loss kernels): 80 * 40 (items) + 81 * 4 (starts) + 28 (constants) + 4 (n) = 3556 bytes.
+ * The plan, v2w_adamw_multi_plan (host only; it reads the items like the launch does): starts[i] = first workgroup of tensor i, starts[n] =
+ *     workgroups of the launch, also the return value (> 0), at most V2W_ADAMW_TARGET_WGS + n; every tensor has at least one.  A tensor counts
+ *     ceil((numel + s) / 4) units of four floats, s = floats of p past a 16-byte line when g, m and v have the same phase, else 0;
+ *     chunk = max(2048, ceil(sum of units / V2W_ADAMW_TARGET_WGS)); tensor i gets ceil(units_i / chunk) workgroups of 256 threads. */
+#define V2W_ADAMW_MAX_ITEMS  80
+#define V2W_ADAMW_TARGET_WGS 2048
+typedef struct {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    int64_t numel;
+} v2w_adamw_item;
+typedef struct {
+    float lr, beta1, beta2, eps, weight_decay, bias_corr1, bias_corr2_sqrt;
+    int32_t _pad;
+} v2w_adamw_hyper;
+int v2w_adamw_multi_plan(const v2w_adamw_item* items, int n, int32_t* starts);
+int v2w_adamw_multi(const v2w_adamw_item* items, int n, const v2w_adamw_hyper* h, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,8 +2,9 @@
 """One full vec2wav GAN training iteration as vec2wav/train.py:160-215 runs it - generator forward, mel of the generated audio,
 discriminator step (MPD + MSD on y and y_g_hat.detach(), backward, AdamW), generator step (MPD + MSD again, feature / LSGAN /
 L1-mel losses, backward through the discriminators, the mel and the generator, AdamW) - entirely on the HIP path.
-argv: B T steps [stock] [frozen]   ('stock': the discriminators as stock torch.nn conv stacks (MIOpen + torch autograd) for comparison;
-'frozen': `with discriminators.frozen(mpd, msd)` around the G step's discriminator forwards - same trajectory, no wasted D gradients)"""
+argv: B T steps [stock] [frozen] [optim=hip|optim=torch]   ('stock': the discriminators as stock torch.nn conv stacks (MIOpen + torch autograd) for comparison;
+'frozen': `with discriminators.frozen(mpd, msd)` around the G step's discriminator forwards - same trajectory, no wasted D gradients;
+'optim=hip': both optimizers are wavthruvec_pytorch_amd.AdamW, the library's multi-tensor kernel - the default 'optim=torch' is torch.optim.AdamW)"""
 import contextlib
 import os
 import sys
@@ -14,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
-from wavthruvec_pytorch_amd import Generator, synthetic  # noqa: E402
+from wavthruvec_pytorch_amd import AdamW, Generator, synthetic  # noqa: E402
 from wavthruvec_pytorch_amd.mel import mel_spectrogram  # noqa: E402
 from wavthruvec_pytorch_amd import discriminators as HD  # noqa: E402
 
@@ -100,8 +101,20 @@ def main():
         if f16x3:
             HD.set_precision(mpd, 'f16x3'); HD.set_precision(msd, 'f16x3')
             g.precision = 'f16x3'
-    optim_g = torch.optim.AdamW(g.parameters(), 2e-4, betas=(0.8, 0.99))
-    optim_d = torch.optim.AdamW(list(mpd.parameters()) + list(msd.parameters()), 2e-4, betas=(0.8, 0.99))
+    hipopt = 'optim=hip' in sys.argv[4:]   # optim=hip: wavthruvec_pytorch_amd.AdamW (the library's multi-tensor kernel); optim=torch (default): torch's
+    Opt = AdamW if hipopt else torch.optim.AdamW
+    optim_g = Opt(g.parameters(), 2e-4, betas=(0.8, 0.99))
+    optim_d = Opt(list(mpd.parameters()) + list(msd.parameters()), 2e-4, betas=(0.8, 0.99))
+    opt_events = {'optim_d.step()': [], 'optim_g.step()': []}
+
+    def timed_step(opt, name, timed):
+        if not timed:
+            return opt.step()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        opt.step()
+        b.record()
+        opt_events[name].append((a, b))
     inp = synthetic.make_inputs(h, B, T, seed=1, device=dev)
     y = torch.tanh(torch.randn(B, 1, T * 320, device=dev)) * 0.5
     margs = (h.n_fft, h.num_mels, h.sampling_rate, h.hop_size, h.win_size, h.fmin, h.fmax_for_loss)
@@ -136,7 +149,7 @@ def main():
         loss_disc_s, _, _ = HD.discriminator_loss(y_ds_hat_r, y_ds_hat_g)
         t0 = tick('D step: forwards', t0)
         (loss_disc_s + loss_disc_f).backward()
-        optim_d.step()
+        timed_step(optim_d, 'optim_d.step()', it >= 2)
         t0 = tick('D step: backward + AdamW', t0)
         optim_g.zero_grad()
         loss_mel = (F.l1_loss if stock else HD.l1_mean_loss)(y_mel, y_g_hat_mel) * 45
@@ -147,7 +160,7 @@ def main():
             + HD.feature_loss(fmap_f_r, fmap_f_g) + loss_mel
         t0 = tick('G step: discriminator forwards + losses', t0)
         loss_gen_all.backward()
-        optim_g.step()
+        timed_step(optim_g, 'optim_g.step()', it >= 2)
         t0 = tick('G step: backward (D, mel, G) + AdamW', t0)
     torch.cuda.synchronize()
     if os.environ.get('V2W_CPROFILE'):
@@ -175,6 +188,8 @@ def main():
           f'({B * T * 320 / dt / 1e6:.2f} M samples/s trained), loss_gen {loss_gen_all.item():.4f}')
     for k, v in times.items():
         print(f'    {k:45s} {v / steps * 1e3:8.1f} ms   peak {peaks[k] / 2 ** 30:6.1f} GiB, live at its end {live[k] / 2 ** 30:6.1f} GiB')
+    for k, evs in opt_events.items():
+        print(f'    {k + " [" + ("hip" if hipopt else "torch") + "], events":45s} {sum(a.elapsed_time(b) for a, b in evs) / len(evs):8.3f} ms')
     print(f'    peak device memory (torch allocator)          {max(peaks.values()) / 2 ** 30:8.1f} GiB')
 
 

@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Forward + backward time of the generator at cfg2 (the generator half of a vec2wav/train.py step).
-argv: B T steps precision loss   (loss 'sum' = a weighted sum of the waveform; 'mel' = train.py:172-174,204's
-F.l1_loss(y_mel, mel_spectrogram(y_g_hat)) * 45 through the HIP mel_spectrogram and its backward)."""
+argv: B T steps precision loss optimizer   (loss 'sum' = a weighted sum of the waveform; 'mel' = train.py:172-174,204's
+F.l1_loss(y_mel, mel_spectrogram(y_g_hat)) * 45 through the HIP mel_spectrogram and its backward; optimizer 'torch' (default) =
+torch.optim.AdamW, 'hip' = wavthruvec_pytorch_amd.AdamW, the library's multi-tensor kernel)."""
 import os
 import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
-from wavthruvec_pytorch_amd import Generator, synthetic  # noqa: E402
+from wavthruvec_pytorch_amd import AdamW, Generator, synthetic  # noqa: E402
 from wavthruvec_pytorch_amd.mel import mel_spectrogram  # noqa: E402
 
 
@@ -22,7 +23,11 @@ def main():
     g.load_state_dict(synthetic.make_state_dict(h, seed=0))
     g = g.to(dev).train()
     g.precision = sys.argv[4] if len(sys.argv) > 4 else 'f32'
-    opt = torch.optim.AdamW(g.parameters(), 2e-4, betas=(0.8, 0.99))
+    opt_kind = sys.argv[6] if len(sys.argv) > 6 else 'torch'
+    if opt_kind not in ('torch', 'hip'):
+        raise SystemExit(f"optimizer must be 'torch' or 'hip', got {opt_kind!r}")
+    opt = (AdamW if opt_kind == 'hip' else torch.optim.AdamW)(g.parameters(), 2e-4, betas=(0.8, 0.99))
+    ev = []                       # (start, end) events around every timed opt.step()
     inp = synthetic.make_inputs(h, B, T, seed=1, device=dev)
     dy = torch.randn(B, 1, T * 320, device=dev)
     loss_kind = sys.argv[5] if len(sys.argv) > 5 else 'sum'
@@ -37,9 +42,15 @@ def main():
             (torch.nn.functional.l1_loss(y_mel, mel_spectrogram(y.squeeze(1), *margs)) * 45).backward()
         else:
             (y * dy).sum().backward()
+        if it >= 2:
+            ev.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+            ev[-1][0].record()
         opt.step()
+        if it >= 2:
+            ev[-1][1].record()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
+    d_opt = sum(a.elapsed_time(b) for a, b in ev) / len(ev)
     with torch.no_grad():
         g(*inp)          # (the first no-grad forward after training steps allocates its own workspace and plans: not part of the figure)
         torch.cuda.synchronize(); t1 = time.perf_counter()
@@ -48,7 +59,7 @@ def main():
         torch.cuda.synchronize()
         df = (time.perf_counter() - t1) / steps
     print(f'B={B} T={T} loss={loss_kind} {g.precision}: forward+backward+AdamW {dt * 1e3:.2f} ms/step ; inference-schedule forward {df * 1e3:.2f} ms ; '
-          f'{B * T * 320 / dt / 1e6:.1f} M samples/s trained')
+          f'{B * T * 320 / dt / 1e6:.1f} M samples/s trained ; optimizer {opt_kind}: step() {d_opt:.3f} ms (events)')
 
 
 if __name__ == '__main__':

@@ -123,6 +123,21 @@ class LsganItem(C.Structure):
 LOSS_MAX_ITEMS = 64
 L1_TARGET_WGS = 2048
 
+
+class AdamWItem(C.Structure):
+    """include/vec2wav_hip.h `v2w_adamw_item`: one parameter tensor of the multi-tensor AdamW step, its gradient and its two moments."""
+    _fields_ = [('p', _fp), ('g', _fp), ('m', _fp), ('v', _fp), ('numel', C.c_int64)]
+
+
+class AdamWHyper(C.Structure):
+    """include/vec2wav_hip.h `v2w_adamw_hyper`: the hyperparameters of one launch; the bias corrections carry the step count."""
+    _fields_ = [('lr', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float), ('eps', C.c_float), ('weight_decay', C.c_float),
+                ('bias_corr1', C.c_float), ('bias_corr2_sqrt', C.c_float), ('_pad', C.c_int32)]
+
+
+ADAMW_MAX_ITEMS = 80
+ADAMW_TARGET_WGS = 2048
+
 # name -> (restype, argtypes); must list every symbol include/vec2wav_hip.h declares
 SIGNATURES = {
     'v2w_abi_version': (C.c_int, []),
@@ -218,6 +233,9 @@ SIGNATURES = {
     'v2w_l1_mean_multi_bwd': (C.c_int, [C.POINTER(L1Pair), C.c_int, C.c_float, _fp, _fp]),
     'v2w_lsgan_multi': (C.c_int, [C.POINTER(LsganItem), C.c_int, _fp, _fp, _fp]),
     'v2w_lsgan_multi_bwd': (C.c_int, [C.POINTER(LsganItem), C.c_int, _fp, _fp, _fp]),
+    # AdamW: host descriptor array and hyperparameters, read before the call returns
+    'v2w_adamw_multi_plan': (C.c_int, [C.POINTER(AdamWItem), C.c_int, C.POINTER(C.c_int32)]),
+    'v2w_adamw_multi': (C.c_int, [C.POINTER(AdamWItem), C.c_int, C.POINTER(AdamWHyper), _fp]),
 }
 
 # entry points that LAUNCH (their last argument is the stream); the others are host-only queries.  schedule.Recorder tapes the former.

@@ -1,0 +1,196 @@
+// AdamW (torch.optim.AdamW as the reference calls it, train.py:96-99,198,215: decoupled weight decay, no amsgrad, no maximize): the step of
+// up to V2W_ADAMW_MAX_ITEMS parameter tensors in ONE streaming launch.  One pass reads p, g, m, v and writes p, m, v (28 bytes per
+// parameter); the arithmetic, its order and its fp32 roundings are stated in include/vec2wav_hip.h.
+//
+// Work split (host, v2w_adamw_multi_plan; the shape of v2w_l1_multi_plan): a tensor is cut into UNITS of four floats.  When the four
+// pointers of an item share their 16-byte phase (s floats past a 16-byte line) the units are cut at the 16-byte lines - the first and the
+// last one partial - and every whole unit is one 16-byte load / store per lane and tensor; otherwise the units start at element 0 and the
+// item takes float-by-float accesses, chosen by a branch that is uniform over the workgroup.  Workgroups are dealt in proportion to the
+// units (the parameter sizes of one call span six orders of magnitude), at least one per tensor, about V2W_ADAMW_TARGET_WGS in all:
+// starts[i] is the first workgroup of tensor i, found from blockIdx.x by a search every lane makes alike.  The plan depends on the
+// descriptors only.  Every element of p, m and v is written exactly once, nothing else is written; no atomics, no LDS, no scratch.
+#include "v2w_common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kUnroll = 2;                       // units in flight per thread: 2 x 4 tensors x 16 B of loads before the first use
+constexpr long long kMinChunk = kThreads * 8;    // units: no workgroup for less than 4 x 32 KB of reads unless the tensor is smaller
+constexpr long long kMaxUnits = 1ll << 40;
+
+// the launch's constants, each derived from the v2w_adamw_hyper in double and rounded ONCE to fp32 (host)
+struct Coef { float decay, omb1, beta2, omb2, rbc2, eps, step; };
+
+struct AdamWArgs {
+    v2w_adamw_item it[V2W_ADAMW_MAX_ITEMS];
+    int starts[V2W_ADAMW_MAX_ITEMS + 1];
+    Coef c;
+    int n;
+};
+static_assert(sizeof(v2w_adamw_item) == 40 && sizeof(v2w_adamw_hyper) == 32, "include/vec2wav_hip.h states these sizes");
+static_assert(sizeof(AdamWArgs) <= 3584, "kernel arguments travel by value: 4 KB with the hidden ones");
+
+__host__ __device__ inline int phase16(const void* p) { return (int)((reinterpret_cast<uintptr_t>(p) >> 2) & 3); }
+__host__ __device__ inline bool same_phase(const v2w_adamw_item& it) {
+    const int ph = phase16(it.p);
+    return phase16(it.g) == ph && phase16(it.m) == ph && phase16(it.v) == ph;
+}
+__host__ __device__ inline long long item_units(const v2w_adamw_item& it) {
+    return (it.numel + (same_phase(it) ? phase16(it.p) : 0) + 3) >> 2;
+}
+
+// elements [e0, e1) of the four floats at q (the others read as 0 and are never touched); one 16-byte access when all four are wanted
+// and the item's pointers allow it (`vec`: q is then on a 16-byte line)
+__device__ __forceinline__ f32x4 load_unit(const float* q, int e0, int e1, bool vec) {
+    f32x4 x = {0.f, 0.f, 0.f, 0.f};
+    if (vec && e0 == 0 && e1 == 4) return *reinterpret_cast<const f32x4*>(q);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j >= e0 && j < e1) x[j] = q[j];
+    return x;
+}
+__device__ __forceinline__ void store_unit(float* q, f32x4 x, int e0, int e1, bool vec) {
+    if (vec && e0 == 0 && e1 == 4) { *reinterpret_cast<f32x4*>(q) = x; return; }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (j >= e0 && j < e1) q[j] = x[j];
+}
+
+__global__ void __launch_bounds__(kThreads)
+adamw_multi_kernel(const AdamWArgs A) {
+    const int wg = blockIdx.x;
+    int lo = 0, hi = A.n;
+    while (hi - lo > 1) {                                 // the tensor of this workgroup: starts[lo] <= wg < starts[lo + 1]
+        const int mid = (lo + hi) >> 1;
+        if (A.starts[mid] <= wg) lo = mid; else hi = mid;
+    }
+    const v2w_adamw_item& it = A.it[lo];
+    const long long numel = it.numel;
+    const bool vec = same_phase(it);
+    const int shift = vec ? phase16(it.p) : 0;
+    const long long units = (numel + shift + 3) >> 2;
+    const int nwg = A.starts[lo + 1] - A.starts[lo];
+    const long long chunk = (units + nwg - 1) / nwg;
+    const long long u0 = (long long)(wg - A.starts[lo]) * chunk;
+    const long long u1 = u0 + chunk < units ? u0 + chunk : units;
+    const unsigned cnt = u1 > u0 ? (unsigned)(u1 - u0) : 0u;
+    // unit u holds elements [4u - shift, 4u - shift + 4) of the tensor; the floats before element 0 and past numel are masked
+    const long long base = (u0 << 2) - shift;
+    float* p = it.p + base;
+    const float* g = it.g + base;
+    float* m = it.m + base;
+    float* v = it.v + base;
+    const Coef c = A.c;
+
+    for (unsigned t0 = threadIdx.x; t0 < cnt; t0 += kThreads * kUnroll) {
+        f32x4 xp[kUnroll], xg[kUnroll], xm[kUnroll], xv[kUnroll];
+        size_t off[kUnroll];
+        int e0[kUnroll], e1[kUnroll];
+#pragma unroll
+        for (int k = 0; k < kUnroll; ++k) {
+            const unsigned t = t0 + k * kThreads;
+            off[k] = (size_t)t << 2;
+            const long long pos = base + (long long)off[k];           // element index of the unit's first float
+            e0[k] = pos < 0 ? (int)-pos : 0;
+            e1[k] = numel - pos < 4 ? (int)(numel - pos) : 4;
+            if (t >= cnt) e0[k] = e1[k] = 0;
+            xp[k] = load_unit(p + off[k], e0[k], e1[k], vec);
+            xg[k] = load_unit(g + off[k], e0[k], e1[k], vec);
+            xm[k] = load_unit(m + off[k], e0[k], e1[k], vec);
+            xv[k] = load_unit(v + off[k], e0[k], e1[k], vec);
+        }
+#pragma unroll
+        for (int k = 0; k < kUnroll; ++k) {
+            f32x4 np, nm, nv;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {                              // include/vec2wav_hip.h: one fp32 rounding per line
+                const float pd = __fmul_rn(xp[k][j], c.decay);
+                const float d = __fsub_rn(xg[k][j], xm[k][j]);
+                nm[j] = __fmaf_rn(c.omb1, d, xm[k][j]);
+                const float gg = __fmul_rn(xg[k][j], xg[k][j]);
+                const float tg = __fmul_rn(c.omb2, gg);
+                nv[j] = __fmaf_rn(c.beta2, xv[k][j], tg);
+                const float den = __fmaf_rn(__fsqrt_rn(nv[j]), c.rbc2, c.eps);
+                const float q = __fdiv_rn(nm[j], den);
+                np[j] = __fmaf_rn(-c.step, q, pd);
+            }
+            store_unit(p + off[k], np, e0[k], e1[k], vec);
+            store_unit(m + off[k], nm, e0[k], e1[k], vec);
+            store_unit(v + off[k], nv, e0[k], e1[k], vec);
+        }
+    }
+}
+
+inline bool ptr4(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+inline bool overlap(const void* a, const void* b, long long numel) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b), bytes = (uintptr_t)numel * 4;
+    return x < y ? y - x < bytes : x - y < bytes;
+}
+
+// checks every descriptor and counts its units (four floats; see the head of this file)
+int adamw_items(const v2w_adamw_item* items, int n, long long* units) {
+    if (!items || n < 1 || n > V2W_ADAMW_MAX_ITEMS) return V2W_E_ARG;
+    for (int i = 0; i < n; ++i) {
+        const v2w_adamw_item& it = items[i];
+        if (!ptr4(it.p) || !ptr4(it.g) || !ptr4(it.m) || !ptr4(it.v) || it.numel <= 0) return V2W_E_ARG;
+        if (it.numel > (kMaxUnits << 2)) return V2W_E_SHAPE;
+        units[i] = item_units(it);
+        if (units[i] > kMaxUnits) return V2W_E_SHAPE;
+        if (overlap(it.p, it.m, it.numel) || overlap(it.p, it.v, it.numel) || overlap(it.m, it.v, it.numel)) return V2W_E_ARG;
+    }
+    return 0;
+}
+
+// starts[i] = first workgroup of tensor i, starts[n] = workgroups of the launch (returned)
+int adamw_plan(const long long* units, int n, int32_t* starts) {
+    long long total = 0;
+    for (int i = 0; i < n; ++i) total += units[i];
+    long long chunk = (total + V2W_ADAMW_TARGET_WGS - 1) / V2W_ADAMW_TARGET_WGS;
+    if (chunk < kMinChunk) chunk = kMinChunk;
+    int w = 0;
+    for (int i = 0; i < n; ++i) {
+        starts[i] = w;
+        const long long k = (units[i] + chunk - 1) / chunk;
+        w += k < 1 ? 1 : (int)k;
+    }
+    starts[n] = w;
+    return w;
+}
+
+// the comparisons are written so that a NaN is refused
+int adamw_coef(const v2w_adamw_hyper* h, Coef* c) {
+    if (!h) return V2W_E_ARG;
+    if (!(h->beta1 >= 0.f && h->beta1 < 1.f) || !(h->beta2 >= 0.f && h->beta2 < 1.f)) return V2W_E_ARG;
+    if (!(h->eps >= 0.f) || !(h->lr >= 0.f) || !(h->bias_corr1 > 0.f) || !(h->bias_corr2_sqrt > 0.f)) return V2W_E_ARG;
+    c->decay = (float)(1.0 - (double)h->lr * (double)h->weight_decay);
+    c->omb1 = (float)(1.0 - (double)h->beta1);
+    c->beta2 = h->beta2;
+    c->omb2 = (float)(1.0 - (double)h->beta2);
+    c->rbc2 = (float)(1.0 / (double)h->bias_corr2_sqrt);
+    c->eps = h->eps;
+    c->step = (float)((double)h->lr / (double)h->bias_corr1);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int v2w_adamw_multi_plan(const v2w_adamw_item* items, int n, int32_t* starts) {
+    if (!starts) return V2W_E_ARG;
+    long long units[V2W_ADAMW_MAX_ITEMS];
+    if (const int rc = adamw_items(items, n, units)) return rc;
+    return adamw_plan(units, n, starts);
+}
+
+extern "C" int v2w_adamw_multi(const v2w_adamw_item* items, int n, const v2w_adamw_hyper* h, void* stream) {
+    AdamWArgs A;
+    long long units[V2W_ADAMW_MAX_ITEMS];
+    if (const int rc = adamw_items(items, n, units)) return rc;
+    if (const int rc = adamw_coef(h, &A.c)) return rc;
+    for (int i = 0; i < n; ++i) A.it[i] = items[i];
+    adamw_plan(units, n, A.starts);
+    A.n = n;
+    hipStream_t st = (hipStream_t)stream;
+    if (v2w_dry(st)) return 0;
+    V2W_LAUNCH(adamw_multi_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A);
+    return v2w_launch_status();
+}

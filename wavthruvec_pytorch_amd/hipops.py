@@ -1378,3 +1378,63 @@ def lsgan_multi_bwd(scores, targets, gout=None, gterms=None, need=None):
         with torch.cuda.device(dev):
             _hip.check(_hip.load().v2w_lsgan_multi_bwd(arr, n, _hip.ptr(gout), _hip.ptr(gterms), _stream(keep[0])), 'v2w_lsgan_multi_bwd')
     return ds
+
+
+# ---- AdamW (include/vec2wav_hip.h: v2w_adamw_multi)
+def adamw_plan(arr, n):
+    """(starts, workgroups) of v2w_adamw_multi_plan for n descriptors."""
+    starts = (C.c_int32 * (n + 1))()
+    nwg = _hip.load().v2w_adamw_multi_plan(arr, n, starts)
+    if nwg <= 0:
+        _hip.check(nwg or -1, 'v2w_adamw_multi_plan')
+    return list(starts), nwg
+
+
+def adamw_hyper(*, lr, betas, eps, weight_decay, step):
+    """The v2w_adamw_hyper of step number `step` (>= 1): the bias corrections are computed in double and rounded once to fp32."""
+    step = int(step)
+    if step < 1:
+        raise ValueError(f'step must be >= 1, got {step}')
+    b1, b2 = float(betas[0]), float(betas[1])
+    return _hip.AdamWHyper(float(lr), b1, b2, float(eps), float(weight_decay), 1.0 - b1 ** step, (1.0 - b2 ** step) ** 0.5, 0)
+
+
+def adamw_multi(params, grads, exp_avgs, exp_avg_sqs, *, lr, betas, eps, weight_decay, step):
+    """One AdamW step (decoupled weight decay, no amsgrad) of every tensor of the lists, in place on params / exp_avgs / exp_avg_sqs:
+    ceil(n / ADAMW_MAX_ITEMS) launches on the current stream.  `step` is the number of THIS step (1 for the first).  fp32 GPU tensors on
+    one device; params and moments must be contiguous (they are written in place), a non-contiguous gradient is copied.  Returns the
+    number of launches.  The parameters' version counters are NOT bumped (the kernels write through raw pointers): optim.AdamW does."""
+    n = len(params)
+    if not (n == len(grads) == len(exp_avgs) == len(exp_avg_sqs)):
+        raise ValueError('params, grads, exp_avgs and exp_avg_sqs must have one entry per tensor')
+    if n == 0:
+        return 0
+    hyper = adamw_hyper(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, step=step)
+    dev = params[0].device
+    arr = (_hip.AdamWItem * n)()
+    keep = []
+    for i, (p, g, m, v) in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs)):
+        p, g, m, v = p.detach(), g.detach(), m.detach(), v.detach()
+        if g.is_cuda and g.dtype == torch.float32 and not g.is_contiguous():
+            g = g.contiguous()
+        for t, name in ((p, 'param'), (g, 'grad'), (m, 'exp_avg'), (v, 'exp_avg_sq')):
+            _chk(t, f'{name}[{i}]')
+            if t.device != dev:
+                raise RuntimeError('all tensors of one adamw_multi call must live on one device')
+            if t.numel() != p.numel():
+                raise ValueError(f'{name}[{i}] has {t.numel()} elements, its parameter {p.numel()}')
+        if p.numel() == 0:
+            raise ValueError(f'param[{i}] is empty')
+        keep += [p, g, m, v]
+        d = arr[i]
+        d.p, d.g, d.m, d.v, d.numel = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+    launches = 0
+    with torch.cuda.device(dev):
+        lib = _hip.load()
+        stream = _stream(keep[0])
+        for i0 in range(0, n, _hip.ADAMW_MAX_ITEMS):
+            k = min(_hip.ADAMW_MAX_ITEMS, n - i0)
+            chunk = C.cast(C.byref(arr, i0 * C.sizeof(_hip.AdamWItem)), C.POINTER(_hip.AdamWItem))
+            _hip.check(lib.v2w_adamw_multi(chunk, k, C.byref(hyper), stream), 'v2w_adamw_multi')
+            launches += 1
+    return launches
