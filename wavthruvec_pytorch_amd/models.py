@@ -80,15 +80,37 @@ class ConvTranspose1d(_WNConvBase):
     transposed = True
 
 
-def _fold_one(m, device):
+def _lrelu_conv(m, src, res=None):
+    """conv_m(lrelu(src)) + bias [+ res] with the weights folded now -> (the output, the folded weights)."""
     v, g = (m.weight_v.detach(), m.weight_g.detach()) if m.weight_normed else (m.weight.detach(), None)
     wf = hipops.fold_conv_weight(v, g)
-    return wf, hipops.pack_mfma(wf)
+    out = torch.empty_like(src)
+    hipops.conv1d(src, wf, m.bias.detach(), out, k=m.kernel_size, dil=m.dilation, slope=LRELU_SLOPE, res=res, wp=hipops.pack_mfma(wf))
+    return out, wf
+
+
+def _resblock_steps(rb, x, pairs, keep=False):
+    """The pair loop of a standalone residual block: x = x + conv_b(lrelu(conv_a(lrelu(x))))  or  x = x + conv_a(lrelu(x))  per pair.
+    Returns (out, steps): with `keep`, every pair as the backward.PairStep its backward reads."""
+    from .backward import PairStep
+    name = {id(m): n for n, m in rb.named_modules()}
+    cur, steps = x.detach().contiguous().float(), []
+    for ca, cb in pairs:
+        u = wfb = None
+        if cb is None:
+            out, wfa = _lrelu_conv(ca, cur, res=cur)
+        else:
+            u, wfa = _lrelu_conv(ca, cur)
+            out, wfb = _lrelu_conv(cb, u, res=cur)
+        if keep:
+            steps.append(PairStep(cur, None, u, ca, name[id(ca)], wfa, cb, name.get(id(cb)), wfb))
+        cur = out
+    return cur, steps
 
 
 def _resblock_forward(rb, x, pairs):
     """Standalone residual block (the reference's are callable: models.py:37-44, 65-70): x (B, C, L) fp32 on the GPU.
-    pairs: [(conv_a, conv_b | None)]: x = x + conv_b(lrelu(conv_a(lrelu(x))))  or  x = x + conv_a(lrelu(x))."""
+    pairs: [(conv_a, conv_b | None)] as in _resblock_steps."""
     if not x.is_cuda:
         raise RuntimeError('ResBlock (HIP): GPU tensors only; there is no CPU fallback')
     if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in rb.parameters())):
@@ -96,20 +118,7 @@ def _resblock_forward(rb, x, pairs):
         names, params = zip(*rb.named_parameters())
         return ResBlockFunction.apply(rb, pairs, names, x, *params)
     with torch.no_grad():
-        cur = x.detach().contiguous().float()
-        for ca, cb in pairs:
-            wfa, wpa = _fold_one(ca, cur.device)
-            if cb is None:
-                out = torch.empty_like(cur)
-                hipops.conv1d(cur, wfa, ca.bias.detach(), out, k=ca.kernel_size, dil=ca.dilation, slope=LRELU_SLOPE, res=cur, wp=wpa)
-            else:
-                t = torch.empty_like(cur)
-                hipops.conv1d(cur, wfa, ca.bias.detach(), t, k=ca.kernel_size, dil=ca.dilation, slope=LRELU_SLOPE, wp=wpa)
-                wfb, wpb = _fold_one(cb, cur.device)
-                out = torch.empty_like(cur)
-                hipops.conv1d(t, wfb, cb.bias.detach(), out, k=cb.kernel_size, dil=cb.dilation, slope=LRELU_SLOPE, res=cur, wp=wpb)
-            cur = out
-        return cur
+        return _resblock_steps(rb, x, pairs)[0]
 
 
 class ResBlock1(nn.Module):
