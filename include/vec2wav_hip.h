@@ -264,6 +264,16 @@ typedef struct {
 } v2w_stage_args;
 int v2w_resblock2_stage_fwd(const v2w_stage_args* a, void* stream);
 int v2w_resblock2_stage_bwd_rows(const v2w_stage_args* a);
+/* Winograd F(2,3) form of the plain forward for C == 32 (no tail, no gradient form): the same section with 4 / 10 / 15 MFMA terms
+ * per output pair for k = 3 / 7 / 11 instead of 6 / 14 / 22.  HERE wp1[j] / wp2[j] are the v2w_pack_wino streams of the layers (v2w_fold_desc::wpw
+ * writes them in the batched fold).  Every k odd and >= 3, every dil1 == 1, dil2 such that the pairs of a 256-position window cover its kept
+ * outputs (1, 2, 3, ...; the standard set (3,1,3), (7,1,3), (11,1,3) is the measured case).  Results equal v2w_resblock2_stage_fwd up to Winograd
+ * rounding; fixed summation order, run-to-run bit-identical.  V2W_E_SHAPE otherwise (the caller then uses v2w_resblock2_stage_fwd with the
+ * v2w_pack_mfma streams).  v2w_resblock2_stage_wino_tile: outputs a tile keeps, i.e. the positions between tile starts (0: shape not taken). */
+int v2w_resblock2_stage_wino_fwd(const v2w_stage_args* a, void* stream);
+int v2w_resblock2_stage_wino_tile(const v2w_stage_args* a);
+/* ... with per-item valid lengths, as v2w_resblock2_stage_fwd_len: bit-identical to v2w_resblock2_stage_wino_fwd when every length is L */
+int v2w_resblock2_stage_wino_fwd_len(const v2w_stage_args* a, const int32_t* len, int len_mul, void* stream);
 /* The same section for an 8-channel stage (the sixth stage of a x640 generator, upsample_rates (5,4,4,2,2,2); ABI v27), fp32 on the
  * vector ALU: C == 8, odd kernel sizes, halos <= 32, nk <= 4.  HERE wp1[j] / wp2[j] are the FOLDED weights [k][C][C] of
  * v2w_wn_fold_conv (there is no fragment stream for 8 channels).  V2W_E_SHAPE otherwise. */

@@ -187,6 +187,9 @@ SIGNATURES = {
     'v2w_resblock_pair_fwd': (C.c_int, [C.POINTER(PairArgs), C.c_int, _fp]),
     'v2w_resblock2_stage_bwd_rows': (C.c_int, [C.POINTER(StageArgs)]),
     'v2w_resblock2_stage_fwd': (C.c_int, [C.POINTER(StageArgs), _fp]),
+    'v2w_resblock2_stage_wino_fwd': (C.c_int, [C.POINTER(StageArgs), _fp]),
+    'v2w_resblock2_stage_wino_tile': (C.c_int, [C.POINTER(StageArgs)]),
+    'v2w_resblock2_stage_wino_fwd_len': (C.c_int, [C.POINTER(StageArgs), _fp, C.c_int, _fp]),
     'v2w_resblock2_stage_small_fwd': (C.c_int, [C.POINTER(StageArgs), _fp]),
     'v2w_branch_convs_bf16_fwd': (C.c_int, [C.POINTER(BranchConvsArgs), _fp]),
     'v2w_convt1d_fwd': (C.c_int, [C.POINTER(ConvT1dArgs), _fp]),

@@ -15,6 +15,7 @@
 //   Weights: the same packed A-fragment streams the per-layer kernel uses (v2w_pack_mfma, single chunk), read straight
 //   from L2 through a two-deep register ping-pong.
 #include "v2w_common.h"
+#include "v2w_wino.h"
 
 #ifdef V2W_TIMELINE   // diagnostic build only (see v2w_common.h)
 V2W_TL_SETTER(v2w_timeline_set)
@@ -913,6 +914,375 @@ int launch_stage(const v2w_stage_args* q, hipStream_t stream, const int32_t* len
     return v2w_launch_lds(kern, dim3(q->B * p.ntl), dim3(64 * WN), lds, stream, p);
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// Winograd F(2,3) form of the 32-channel stage kernel (the forward without the tail; no gradient form).  The same section on the
+// same tiles - x staged once, lrelu(x) / lrelu(t1_j) position-major in LDS, the branch sum in registers - but both conv phases go in
+// output PAIRS (t, t + dil) through the four accumulator classes of v2w_wino.h: 4 / 10 / 15 MFMA terms per pair for k = 3 / 7 / 11
+// instead of 6 / 14 / 22.  Weights: the v2w_pack_wino stream of each layer (one row block, one chunk), consumption order
+// [segment][unit][term], through the same 4-deep register ring.
+//   Lane column lr of wave w owns pair P = 32 w + lr in BOTH phases, but a pair is another set of positions in each: conv1 (dil 1) pairs
+//   window columns (2P, 2P + 1) - the lane's HOME columns, where raw x, t1_j and the branch sum live in registers - conv2 (dil d2) pairs
+//   (q, q + d2), q = 2 d2 (P / d2) + P % d2.  conv2's result therefore goes home through the T1 tile, dead once conv2_j has read it:
+//   two more LDS barriers per branch, and r_j = t1_j + (conv2_j + b2_j) is formed and summed exactly as in the direct kernel.
+//   With d2 = 3 the 128 pairs of a 256-column window cover columns 0 .. 251 and 252, 253, 255, 256: the kept outputs [h2max, h2max + nto)
+//   all lie below 2 d2 (128 / d2) = 252; the last pair's taps reach one row past the direct kernel's pad (the T1 tile has `trows` rows).
+//   A pair whose other output is discarded still reads rows only that output needs (x0 / the last x): those meet the classes M0 / M3 of
+//   the discarded output alone, so a kept output never sees an unstaged row.
+struct StageConvWino {
+    typedef Frag<32> F;
+    typedef F::acc_t acc_t;
+    static constexpr int RING = 4, GPC = 4, RS = StageGeom<32>::RS;
+    f32x4 ar[RING];        // weight fragments, RING - 1 in flight
+    int fidx;              // fragments of the running stream requested so far
+
+    static __device__ __forceinline__ float sub(float v, float w) { float t; asm("v_sub_f32 %0, %1, %2" : "=v"(t) : "v"(v), "v"(w)); return t; }
+
+    __device__ __forceinline__ void start(const f32x4* w, int lane) {
+#pragma unroll
+        for (int g = 0; g + 1 < RING; ++g) ar[g] = w[(size_t)g * 64 + lane];
+    }
+    // One segment of NTAP taps: `x` = this lane's float4 of x0, unit 0 (rows `dstep` floats apart, units 8 floats).  The operand rows are
+    // read where they are used: the other wave of the SIMD covers the LDS latency (a register double buffer that requested them one unit
+    // ahead spilled and ran the kernel 9 % slower at B = 32 x T = 256).  Every segment consumes NTERM * 4 fragments, a
+    // multiple of the ring: each starts at ring slot 0.
+    template <int NTAP>
+    __device__ __forceinline__ void segment(acc_t (&acc)[4], const f32x4* wa, const f32x4* wnext, int nfrag, int lane,
+                                            const float* x, int dstep) {
+        constexpr int NX = NTAP + 1, NTERM = wino_seg_terms(NTAP);
+#pragma unroll
+        for (int gg = 0; gg < GPC; ++gg) {
+            f32x4 xr[NX];
+#pragma unroll
+            for (int j = 0; j < NX; ++j) xr[j] = *reinterpret_cast<const f32x4*>(x + j * dstep + 8 * gg);
+            f32x4 u[NTERM];
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                if constexpr (NTAP == 3) {
+                    u[0][kk] = sub(xr[0][kk], xr[2][kk]); u[1][kk] = v2w_add(xr[1][kk], xr[2][kk]);
+                    u[2][kk] = sub(xr[2][kk], xr[1][kk]); u[3][kk] = sub(xr[1][kk], xr[3][kk]);
+                } else if constexpr (NTAP == 2) {
+                    u[0][kk] = sub(xr[0][kk], xr[1][kk]); u[1][kk] = xr[1][kk]; u[2][kk] = sub(xr[1][kk], xr[2][kk]);
+                } else {
+                    u[0][kk] = xr[0][kk]; u[1][kk] = xr[1][kk];
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);      // the input transform stays AHEAD of this unit's MFMAs
+#pragma unroll
+            for (int t = 0; t < NTERM; ++t) {
+                const int cls = NTAP == 3 ? t : (NTAP == 2 ? (t == 2 ? 3 : t) : (t == 1 ? 3 : 0));    // accumulator class of the term
+                const int slot = (gg * NTERM + t) % RING;
+                const int f = fidx++;                                               // uniform: the stream select stays scalar
+                const f32x4* wsrc = f < nfrag ? wa + (size_t)f * 64 : wnext + (size_t)(f - nfrag) * 64;
+                ar[(slot + RING - 1) % RING] = wsrc[lane];
+                __builtin_amdgcn_sched_barrier(0);  // one request per fragment consumed, in order: the ring stays RING - 1 fragments ahead
+#pragma unroll
+                for (int kk = 0; kk < 4; ++kk) acc[cls] = F::mfma(ar[slot][kk], u[t][kk], acc[cls]);
+            }
+        }
+    }
+    // the whole phase: zeroes the four classes, K taps from `x0` (this lane's float4 of tap 0 of the pair's first output, unit 0)
+    __device__ __forceinline__ void run(acc_t (&acc)[4], const f32x4* wa, const f32x4* wnext, int K, int lane, const float* x0, int dstep) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int e = 0; e < F::NREG; ++e) acc[c][e] = 0.f;
+        const int nfrag = wino_terms(K) * GPC;
+        fidx = RING - 1;
+        const float* x = x0;
+        int s = 0;
+        for (; s + 3 <= K; s += 3, x += 3 * dstep) segment<3>(acc, wa, wnext, nfrag, lane, x, dstep);
+        if (K - s == 2) segment<2>(acc, wa, wnext, nfrag, lane, x, dstep);
+        else if (K - s == 1) segment<1>(acc, wa, wnext, nfrag, lane, x, dstep);
+    }
+};
+
+// a position row of the 32-channel tiles <-> this lane's 16 accumulator rows (channel F::row(e, hk)): see row_get / row_put of the direct kernel
+__device__ __forceinline__ void stage32_row_get(const float* row, int hk, float (&v)[16]) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x2 a = *reinterpret_cast<const f32x2*>(row + 8 * g + 2 * hk);
+        const f32x2 c = *reinterpret_cast<const f32x2*>(row + 8 * g + 2 * hk + 4);
+        v[4 * g] = a[0]; v[4 * g + 2] = a[1]; v[4 * g + 1] = c[0]; v[4 * g + 3] = c[1];
+    }
+}
+__device__ __forceinline__ void stage32_row_put(float* row, int hk, const float (&v)[16]) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        *reinterpret_cast<f32x2*>(row + 8 * g + 2 * hk) = f32x2{v[4 * g], v[4 * g + 2]};
+        *reinterpret_cast<f32x2*>(row + 8 * g + 2 * hk + 4) = f32x2{v[4 * g + 1], v[4 * g + 3]};
+    }
+}
+__device__ __forceinline__ void stage32_bias_rows(const float* tab, int hk, float (&v)[16]) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const f32x4 q = *reinterpret_cast<const f32x4*>(tab + 8 * g + 4 * hk);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[4 * g + r] = q[r];
+    }
+}
+__host__ __device__ inline int stage_wino_tpos(int P, int d) { const int q = P / d; return 2 * d * q + (P - q * d); }
+
+// LEN: per-item valid lengths as in the direct kernel - x and t1_j select 0 at and past Lb = min(L, len[b] * len_mul), a tile whose outputs
+// all lie past it returns at once; LEN = false compiles to the code without lengths.
+template <int WN, bool LEN>
+__global__ void __launch_bounds__(64 * WN, 2)
+resblock2_stage_wino_kernel(const StageArgs p, const int trows) {
+    typedef Frag<32> F;
+    typedef F::acc_t acc_t;
+    typedef StageGeom<32> G;
+    constexpr int NTHREADS = 64 * WN;
+    constexpr int C = 32;
+    constexpr int W = 64 * WN;              // positions each conv phase computes: 32 pairs per wave
+    constexpr int RS = G::RS;
+    constexpr int NR = F::NREG;
+
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int tile = blockIdx.x;
+    const int b = tile / p.ntl;
+    const int n0 = (tile % p.ntl) * p.nadv;          // first valid output position of the tile (multiple of 4)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lr = lane & 31, hk = lane >> 5;
+    const int L = p.L;
+    const float slope = p.slope;
+    float* const Xa = smem;                          // [xrows][RS]  lrelu(x), exactly 0 outside the sequence
+    float* const Ta = smem + p.xrows * RS;           // [trows][RS]  raw x of the window, then per branch lrelu(t1_j), then conv2_j + b2_j on its way home
+    float* const etab = Ta + trows * RS;             // bias1[nk][C], bias2[nk][C]
+    const int pos0 = n0 - p.h2max - p.h1max - p.xoff;   // position of X row 0
+    const int xc0 = p.xoff + p.h1max;                // X row of window column 0 (position n0 - h2max)
+    const int Lb = LEN ? min(L, p.len[b] * p.len_mul) : L;     // end of this item's sequence (LEN; else the tensor's)
+    if constexpr (LEN) {
+        if (n0 >= Lb) return;                        // every output of the tile lies past the item's end
+    }
+    for (int i = tid; i < p.nk * C; i += NTHREADS) {
+        const int j = i / C, c = i - j * C;
+        etab[i] = p.bias1[j] ? p.bias1[j][c] : 0.f;
+        etab[V2W_STAGE_MAXB * C + i] = p.bias2[j] ? p.bias2[j][c] : 0.f;
+    }
+
+    // ---- stage x = a*in + s: the direct kernel's staging (4 slot-adjacent channels x 4 positions per item, all loads issued first)
+    constexpr int NCQ = C / 4;
+    auto quad_ch = [&](int cq, int i) { return 8 * (cq >> 1) + (cq & 1) + 2 * i; };
+    if (p.vec4) {
+        constexpr int NPF = (NCQ * ((W + 2 * G::HMAX + 8) / 4) + NTHREADS - 1) / NTHREADS;
+        const int xr4 = p.xrows >> 2;
+        f32x4 g[NPF][4];
+        float av[NPF][4], sv[NPF][4];
+#pragma unroll
+        for (int s = 0; s < NPF; ++s) {
+            const int idx = tid + s * NTHREADS;
+            const int cq = idx % NCQ, pq = idx / NCQ;
+            const int pos = pos0 + pq * 4;
+            const bool ok = pq < xr4 && pos >= 0 && pos < L;      // L % 4 == 0, pos % 4 == 0: whole float4 inside
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                g[s][i] = f32x4{0.f, 0.f, 0.f, 0.f}; av[s][i] = 1.f; sv[s][i] = 0.f;
+                if (ok) {
+                    const int ch = b * C + quad_ch(cq, i);
+                    g[s][i] = *reinterpret_cast<const f32x4*>(p.in + (size_t)ch * L + pos);
+                    if (p.in_a) { av[s][i] = p.in_a[ch]; sv[s][i] = p.in_s[ch]; }
+                }
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < NPF; ++s) {
+            const int idx = tid + s * NTHREADS;
+            const int cq = idx % NCQ, pq = idx / NCQ;
+            if (pq >= xr4) continue;
+            const int r0 = pq * 4;
+            const bool ok = pos0 + r0 >= 0 && pos0 + r0 < L;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                f32x4 raw, act;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    raw[i] = ok && (!LEN || pos0 + r0 + e < Lb) ? fmaf(av[s][i], g[s][i][e], sv[s][i]) : 0.f;
+                    act[i] = v2w_lrelu(raw[i], slope);
+                }
+                const int r = r0 + e;
+                *reinterpret_cast<f32x4*>(Xa + r * RS + 4 * cq) = act;
+                if (r >= xc0 && r < xc0 + W) *reinterpret_cast<f32x4*>(Ta + (r - xc0) * RS + 4 * cq) = raw;
+            }
+        }
+    } else {                                    // any L / alignment: one element at a time
+        for (int i = tid; i < C * p.xrows; i += NTHREADS) {
+            const int c = i / p.xrows, r = i - c * p.xrows, pos = pos0 + r;
+            float raw = 0.f;
+            if (pos >= 0 && pos < Lb) {
+                const int ch = b * C + c;
+                raw = fmaf(p.in_a ? p.in_a[ch] : 1.f, p.in[(size_t)ch * L + pos], p.in_s ? p.in_s[ch] : 0.f);
+            }
+            Xa[r * RS + G::slot(c)] = v2w_lrelu(raw, slope);
+            if (r >= xc0 && r < xc0 + W) Ta[(r - xc0) * RS + G::slot(c)] = raw;
+        }
+    }
+
+    StageConvWino sc;
+    sc.start(reinterpret_cast<const f32x4*>(p.wp1[0]), lane);
+    __syncthreads();
+
+    const int P = wave * 32 + lr;             // this lane's pair in both phases
+    const int hc = 2 * P;                     // its home columns hc, hc + 1 (conv1's pair); column col <-> position n0 - h2max + col
+    float xres[2][NR];                        // raw x at the home columns: the residual of conv1 in every branch
+    bool in_seq[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        stage32_row_get(Ta + (hc + h) * RS, hk, xres[h]);
+        const int pos = n0 - p.h2max + hc + h;
+        in_seq[h] = pos >= 0 && pos < Lb;     // conv2 zero-pads t1 outside the sequence (LEN: the item's)
+    }
+
+    acc_t acc[4];
+    float t1r[2][NR], oacc[2][NR];
+    for (int jb = 0; jb < p.nk; ++jb) {
+        const int K = p.K[jb], d2 = p.d2[jb];
+        const int h1 = (K - 1) / 2, h2 = d2 * (K - 1) / 2;
+        const f32x4* w1 = reinterpret_cast<const f32x4*>(p.wp1[jb]);
+        const f32x4* w2 = reinterpret_cast<const f32x4*>(p.wp2[jb]);
+        const f32x4* wafter = jb + 1 < p.nk ? reinterpret_cast<const f32x4*>(p.wp1[jb + 1]) : w2;   // last: a harmless re-read
+
+        // ---- conv1_j (dilation 1) on the pairs (2P, 2P + 1) ; t1_j = x + (conv + b1), 0 outside the sequence
+        float brow[NR];
+        sc.run(acc, w1, w2, K, lane, Xa + (xc0 + hc - h1) * RS + 4 * hk, RS);
+        stage32_bias_rows(etab + jb * C, hk, brow);
+#pragma unroll
+        for (int e = 0; e < NR; ++e) {
+            const float y0 = (acc[0][e] + acc[1][e]) + acc[2][e], y1 = (acc[1][e] - acc[2][e]) - acc[3][e];
+            t1r[0][e] = in_seq[0] ? (y0 + brow[e]) + xres[0][e] : 0.f;
+            t1r[1][e] = in_seq[1] ? (y1 + brow[e]) + xres[1][e] : 0.f;
+        }
+        v2w_lds_barrier();                    // everyone is done reading Ta (raw x at jb == 0, the previous branch's conv2 results after)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            float a[NR];
+#pragma unroll
+            for (int e = 0; e < NR; ++e) a[e] = v2w_lrelu(t1r[h][e], slope);
+            stage32_row_put(Ta + (hc + h) * RS, hk, a);
+        }
+        v2w_lds_barrier();
+
+        // ---- conv2_j on the pairs (q, q + d2) ; its results + b2 go home through the T1 tile
+        const int q0 = stage_wino_tpos(P, d2);
+        sc.run(acc, w2, wafter, K, lane, Ta + (q0 - h2) * RS + 4 * hk, d2 * RS);
+        stage32_bias_rows(etab + V2W_STAGE_MAXB * C + jb * C, hk, brow);
+        float c2[2][NR];
+#pragma unroll
+        for (int e = 0; e < NR; ++e) {
+            c2[0][e] = ((acc[0][e] + acc[1][e]) + acc[2][e]) + brow[e];
+            c2[1][e] = ((acc[1][e] - acc[2][e]) - acc[3][e]) + brow[e];
+        }
+        v2w_lds_barrier();                    // every wave is done reading lrelu(t1_j)
+        if (q0 < W) stage32_row_put(Ta + q0 * RS, hk, c2[0]);
+        if (q0 + d2 < W) stage32_row_put(Ta + (q0 + d2) * RS, hk, c2[1]);
+        v2w_lds_barrier();
+        // r_j = t1_j + (conv2 + b2) ; branch sum in the reference's order.  (Columns no pair wrote - past 2 d2 (W / 2 / d2) - hold stale
+        // values: they lie outside the kept outputs.)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            stage32_row_get(Ta + (hc + h) * RS, hk, c2[h]);
+#pragma unroll
+            for (int e = 0; e < NR; ++e) {
+                const float r = c2[h][e] + t1r[h][e];
+                oacc[h][e] = jb == 0 ? r : oacc[h][e] + r;
+            }
+        }
+    }
+
+    // ---- store: the direct kernel's - through an LDS scratch [C][W + 4] over the T1 tile, float4s along positions
+    __syncthreads();                          // every wave is done reading T1
+    {
+        constexpr int SRS = W + 4;
+        float* const scr = Ta;
+        const int soff = (p.h2max + 3) & ~3;          // scratch column of window column h2max: 16-byte aligned
+        const float dinv = p.out_div != 0.f ? 1.f / p.out_div : 1.f;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int scol = hc + h - p.h2max + soff;
+#pragma unroll
+            for (int e = 0; e < NR; ++e) scr[F::row(e, hk) * SRS + scol] = oacc[h][e];
+        }
+        __syncthreads();
+        const int nq = p.nto >> 2;
+        const unsigned magic = (unsigned)(((1ull << 32) + nq - 1) / nq);
+        for (int idx = tid; idx < C * nq; idx += NTHREADS) {
+            const int row = (int)__umulhi((unsigned)idx, magic), q = idx - row * nq;
+            const int pos = n0 + 4 * q;
+            if (pos >= L) continue;
+            f32x4 v = *reinterpret_cast<const f32x4*>(scr + row * SRS + soff + 4 * q);
+            if (p.out_div != 0.f) {
+#pragma unroll
+                for (int x = 0; x < 4; ++x) v[x] = v2w_div_by(v[x], p.out_div, dinv);
+            }
+            float* dst = p.out + ((size_t)b * C + row) * L + pos;
+            if (p.vec4) {
+                *reinterpret_cast<f32x4*>(dst) = v;              // L % 4 == 0: whole float4 inside
+            } else {
+#pragma unroll
+                for (int x = 0; x < 4; ++x)
+                    if (pos + x < L) dst[x] = v[x];
+            }
+        }
+    }
+}
+
+// The launcher's geometry; *nto_out (optional) = kept outputs per tile.  A dry stream stops in front of the launch.
+template <int WN>
+int launch_stage_wino(const v2w_stage_args* q, hipStream_t stream, int* nto_out, const int32_t* len, int len_mul) {
+    typedef StageGeom<32> G;
+    constexpr int W = 64 * WN, NP = W / 2;
+    StageArgs p{};
+    p.in = q->in; p.in_a = q->in_a; p.in_s = q->in_s; p.out = q->out;
+    p.nk = q->nk; p.B = q->B; p.L = q->L; p.slope = q->slope; p.out_div = q->out_div;
+    for (int j = 0; j < q->nk; ++j) {
+        p.wp1[j] = q->wp1[j]; p.bias1[j] = q->bias1[j]; p.wp2[j] = q->wp2[j]; p.bias2[j] = q->bias2[j];
+        p.K[j] = q->k[j]; p.d1[j] = q->dil1[j]; p.d2[j] = q->dil2[j];
+        if (wino_terms(q->k[j]) == 0 || q->dil1[j] != 1) return V2W_E_SHAPE;     // odd k >= 3; conv1's pairs are the home columns
+        const int h1 = (q->k[j] - 1) / 2, h2 = q->dil2[j] * (q->k[j] - 1) / 2;
+        if (h1 > p.h1max) p.h1max = h1;
+        if (h2 > p.h2max) p.h2max = h2;
+    }
+    p.nto = (W - 2 * p.h2max) & ~3;
+    if (p.nto < W / 2 || p.h1max > G::HMAX) return V2W_E_SHAPE;
+    p.nadv = p.nto; p.hout = 0;
+    int trows = W + p.h2max;
+    for (int j = 0; j < q->nk; ++j) {
+        const int d2 = q->dil2[j], h2 = d2 * (q->k[j] - 1) / 2;
+        if (p.h2max + p.nto > 2 * d2 * (NP / d2)) return V2W_E_SHAPE;             // conv2_j's pairs must cover every kept output
+        const int last = stage_wino_tpos(NP - 1, d2) + d2 + h2 + 1;              // rows the last pair's taps reach
+        if (last > trows) trows = last;
+    }
+    const int hsum = p.h1max + p.h2max;
+    p.xoff = ((hsum + 3) & ~3) - hsum;
+    p.xrows = (p.xoff + W + 2 * p.h1max + 3) & ~3;
+    if (p.xrows < p.h2max) return V2W_E_SHAPE;
+    if (32 * (W + 4) > trows * G::RS) return V2W_E_SHAPE;     // the store scratch [C][W + 4] overlays the T1 tile
+    p.ntl = (q->L + p.nadv - 1) / p.nadv;
+    p.vec4 = (q->L % 4 == 0) && v2w_al16(q->in) && v2w_al16(q->out) && v2w_al16(q->in_a) && v2w_al16(q->in_s);
+    const size_t lds = ((size_t)(p.xrows + trows) * G::RS + 2 * V2W_STAGE_MAXB * 32) * sizeof(float);
+    if (lds > 80 * 1024) return V2W_E_SHAPE;                  // two workgroups per CU
+    if (nto_out) *nto_out = p.nto;
+    if (v2w_dry(stream)) return 0;
+    p.len = len; p.len_mul = len_mul;
+    auto kern = len ? resblock2_stage_wino_kernel<WN, true> : resblock2_stage_wino_kernel<WN, false>;
+    return v2w_launch_lds(kern, dim3(q->B * p.ntl), dim3(64 * WN), lds, stream, p, trows);
+}
+
+static int stage_wino_check(const v2w_stage_args* a) {
+    if (!a || a->nk < 1 || a->nk > V2W_STAGE_MAXB || a->B <= 0 || a->C <= 0 || a->L <= 0) return V2W_E_ARG;
+    for (int j = 0; j < a->nk; ++j)
+        if (a->k[j] <= 0 || a->dil1[j] <= 0 || a->dil2[j] <= 0) return V2W_E_ARG;
+    if (a->C != 32 || a->post_out || a->bwd_mask2) return V2W_E_SHAPE;      // the plain forward of the 32-channel stage only
+    return 0;
+}
+// windows of 256 positions, or of 128 for the latency sizes: the direct kernel's rule (stage_fwd)
+static int stage_wino_launch(const v2w_stage_args* a, hipStream_t st, int* nto_out, const int32_t* len = nullptr, int len_mul = 1) {
+    int h2max = 0;
+    for (int j = 0; j < a->nk; ++j) { const int h2 = a->dil2[j] * (a->k[j] - 1) / 2; if (h2 > h2max) h2max = h2; }
+    const int nto = (256 - 2 * h2max) & ~3;
+    const bool small = nto > 0 && (long long)a->B * ((a->L + nto - 1) / nto) < 224 && 128 - 2 * h2max >= 64;
+    return small ? launch_stage_wino<2>(a, st, nto_out, len, len_mul) : launch_stage_wino<4>(a, st, nto_out, len, len_mul);
+}
 }  // namespace
 
 extern "C" int v2w_resblock_pair_fwd(const v2w_pair_args* a, int n, void* stream) {
@@ -974,4 +1344,27 @@ extern "C" int v2w_resblock2_stage_fwd(const v2w_stage_args* a, void* stream) { 
 extern "C" int v2w_resblock2_stage_fwd_len(const v2w_stage_args* a, const int32_t* len, int len_mul, void* stream) {
     if (!len || len_mul < 1 || (a && a->bwd_mask2)) return V2W_E_ARG;
     return stage_fwd(a, stream, len, len_mul);
+}
+
+// Winograd F(2,3) form of the plain 32-channel forward (include/vec2wav_hip.h): wp1 / wp2 are v2w_pack_wino streams.
+static int stage_wino_fwd(const v2w_stage_args* a, void* stream, const int32_t* len, int len_mul) {
+    const int rc = stage_wino_check(a);
+    if (rc) return rc;
+    if (!a->in || !a->out || (a->in_a == nullptr) != (a->in_s == nullptr)) return V2W_E_ARG;
+    for (int j = 0; j < a->nk; ++j)
+        if (!a->wp1[j] || !a->wp2[j]) return V2W_E_ARG;
+    return stage_wino_launch(a, (hipStream_t)stream, nullptr, len, len_mul);
+}
+extern "C" int v2w_resblock2_stage_wino_fwd(const v2w_stage_args* a, void* stream) { return stage_wino_fwd(a, stream, nullptr, 1); }
+// ... with per-item valid lengths (as v2w_resblock2_stage_fwd_len)
+extern "C" int v2w_resblock2_stage_wino_fwd_len(const v2w_stage_args* a, const int32_t* len, int len_mul, void* stream) {
+    if (!len || len_mul < 1) return V2W_E_ARG;
+    return stage_wino_fwd(a, stream, len, len_mul);
+}
+
+// Kept outputs per tile of that launch (a tile starts every so many positions; 0: shape not taken).  Host only.
+extern "C" int v2w_resblock2_stage_wino_tile(const v2w_stage_args* a) {
+    int nto = 0;
+    if (stage_wino_check(a) != 0 || stage_wino_launch(a, V2W_DRY_STREAM, &nto) != 0) return 0;
+    return nto;
 }

@@ -59,6 +59,16 @@ class DirectStreams:
         pass
 
 
+STAGE_WINO_BLOCKS = [(3, 1, 3), (7, 1, 3), (11, 1, 3)]     # (kernel size, dilation 1, dilation 2) of the reference's ResBlock2 triple
+
+
+def stage_wino_selected(wino_stage, precision, algo, C, blocks) -> bool:
+    """Does the fused stage kernel run in its Winograd F(2,3) form (hipops.resblock2_stage_wino)?  Exact fp32 on the MFMA path, the
+    32-channel stage, the standard block set - the one shape that form was measured on; everything else keeps the direct-form kernel.
+    Read by the planner (rb2_stage_f32) and by the fold (Generator._wino_stage_layers: which layers get a Winograd stream)."""
+    return bool(wino_stage) and precision == 'f32' and algo != hipops.ALGO_DIRECT and C == 32 and list(blocks) == STAGE_WINO_BLOCKS
+
+
 def _branches(rbs, names, wps):
     return [dict(wps1=wps[nm + '.convs.0'], b1=rb.convs[0].bias.detach(), wps2=wps[nm + '.convs.1'], b2=rb.convs[1].bias.detach(),
                  k=rb.kernel_size, dil1=rb.convs[0].dilation, dil2=rb.convs[1].dilation) for nm, rb in zip(names, rbs)]
@@ -469,8 +479,15 @@ class ForwardPlanner:
         g = self.g
         if self.st or not (self.C in self.fuse_stage and self.all_wp):
             return False
-        branches = self._f32_branches(self.wp, 'wp1', 'wp2')
         lk = self.lkw(self.lmul * g.ups[i].stride)
+        wpw = g._fold_key.get('wpw_stage', {})
+        if (all(f'{nm}.convs.{c}' in wpw for nm in self.names for c in (0, 1)) and stage_wino_selected(
+                g.wino_stage, g.precision, self.algo, self.C, [(rb.kernel_size, rb.convs[0].dilation, rb.convs[1].dilation) for rb in self.rbs])):
+            # the Winograd F(2,3) form (its streams come from the same fold); a launch it declines runs on the direct form below
+            if self.timed(self.stage_tag(), hipops.resblock2_stage_wino, self.xr, self.aff, self._f32_branches(wpw, 'wpw1', 'wpw2'), self.xs,
+                          slope=LRELU_SLOPE, out_div=float(self.nk), **lk):
+                return True
+        branches = self._f32_branches(self.wp, 'wp1', 'wp2')
         kp = g.conv_post.kernel_size
         if g.fuse_post and i == self.ns - 1 and self.C == 16 and kp <= 9 and kp % 2 == 1 and g.conv_post.in_channels == 16:
             y = torch.empty((self.B, 1, self.Lo), device=self.dev, dtype=torch.float32)

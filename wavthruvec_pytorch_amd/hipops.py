@@ -830,6 +830,40 @@ def resblock2_stage(x, in_affine, branches, out, *, slope, out_div, post=None, b
     return True
 
 
+def resblock2_stage_wino(x, in_affine, branches, out, *, slope, out_div, lengths=None, len_mul=1):
+    """Winograd F(2,3) form of `resblock2_stage` for the plain forward of a 32-channel stage (v2w_resblock2_stage_wino_fwd).  `branches`:
+    list of dicts(wpw1, b1, wpw2, b2, k, dil1, dil2) with the pack_wino streams of the layers.  Returns False (nothing launched) when the
+    shape is not taken."""
+    B, Cc, L = x.shape
+    a = _hip.StageArgs()
+    a.in_ = x.data_ptr()
+    a.in_a, a.in_s = (in_affine[0].data_ptr(), in_affine[1].data_ptr()) if in_affine is not None else (None, None)
+    for j, br in enumerate(branches):
+        a.wp1[j] = br['wpw1'].data_ptr(); a.bias1[j] = _hip.ptr(br['b1'])
+        a.wp2[j] = br['wpw2'].data_ptr(); a.bias2[j] = _hip.ptr(br['b2'])
+        a.k[j], a.dil1[j], a.dil2[j] = br['k'], br['dil1'], br['dil2']
+    a.out = out.data_ptr()
+    a.nk, a.B, a.C, a.L = len(branches), B, Cc, L
+    a.slope = slope; a.out_div = out_div
+    if lengths is not None:     # per-item valid lengths (see _len_ptr; v2w_resblock2_stage_wino_fwd_len)
+        rc = _hip.load().v2w_resblock2_stage_wino_fwd_len(C.byref(a), _len_ptr(lengths, len_mul), int(len_mul), _stream(x))
+    else:
+        rc = _hip.load().v2w_resblock2_stage_wino_fwd(C.byref(a), _stream(x))
+    if rc == -2:
+        return False
+    _hip.check(rc, 'v2w_resblock2_stage_wino_fwd')
+    return True
+
+
+def resblock2_stage_wino_tile(B, Cc, L, ks, dil1s, dil2s) -> int:
+    """Outputs one tile of `resblock2_stage_wino` keeps (tiles start that many positions apart; 0: shape not taken).  Host only."""
+    a = _hip.StageArgs()
+    a.nk, a.B, a.C, a.L = len(ks), B, Cc, L
+    for j in range(len(ks)):
+        a.k[j], a.dil1[j], a.dil2[j] = ks[j], dil1s[j], dil2s[j]
+    return _hip.load().v2w_resblock2_stage_wino_tile(C.byref(a))
+
+
 def resblock2_stage_bwd_rows(B, Cc, L, ks, dil1s, dil2s) -> int:
     """Rows of [C][2] floats per branch the input-gradient form of `resblock2_stage` writes into its `rowsums` buffers (0: shape not taken).
     dil1s / dil2s as handed to the kernel (conv2's dilations first)."""

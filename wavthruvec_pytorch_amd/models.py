@@ -223,6 +223,7 @@ class Generator(nn.Module):
                                               # the stage's output never leaves the chip, one launch less per stage
         self.fuse_bn_finalize = True          # train mode: a stage's statistics reduction and its finalisation as one launch (v2w_bn_reduce_finalize) where nothing is all-reduced in between
         self.wino = True                      # precision 'f32': conv_pre and the wide residual convs (but the 64-channel dilation-3 ones) on the Winograd F(2,3) kernel
+        self.wino_stage = True                # precision 'f32': the fused 32-channel stage kernel in its Winograd F(2,3) form (standard block set; forward_plan.stage_wino_selected)
                                               # (hipops.ALGO_WINO: 4 / 10 / 15 instead of 6 / 14 / 22 products per output pair for k = 3 / 7 / 11),
                                               # weights transformed by the batched fold; a launch the kernel declines runs on the direct-form tile
         self.merge_waits = True               # bf16 storage: one wait per side stream and call, earlier steps of the stream count as met (forward_plan.need)
@@ -408,13 +409,15 @@ class Generator(nn.Module):
             ps = (m.weight_v, m.weight_g) if m.weight_normed else (m.weight,)
             vers.append(tuple((p.data_ptr(), p._version) for p in ps))
         wino = self.wino and self.precision == 'f32' and self.algo != hipops.ALGO_DIRECT
-        state = (tuple(vers), self.algo, str(device), need_wf, bf16_only, wino)
+        stage_names = self._wino_stage_layers()
+        state = (tuple(vers), self.algo, str(device), need_wf, bf16_only, wino, bool(stage_names))
         force = (self.training and self.always_refold) or need_wf
         if not force and self._fold_key.get('state') == state:
             return self._fold_key['wf'], self._fold_key['wp']
         wf, wp, batch = {}, {}, []
         wpd = {}        # need_wf: fragment streams of the input-gradient convs of the C -> C residual convs (backward.py), from the same pass
         wpw = {}        # wino: the Winograd F(2,3) streams of the layers that kernel serves (forward_plan.ck), from the same pass
+        wpw_stage = {}  # wino_stage: the same streams for the six layers of the 32-channel stage (the fused stage kernel's Winograd form)
         for name, m in layers:
             if bf16_only and name != 'conv_post':      # bf16 activation storage: every other layer runs on its bf16 fragments (_split_weights):
                 wf[name], wp[name] = None, None        # no fp32 fold / fragment stream is read, none is built
@@ -430,6 +433,8 @@ class Generator(nn.Module):
             if (mfma_ok and wino and not m.transposed and hipops.wino_terms(m.kernel_size) and m.in_channels % 32 == 0 and m.in_channels >= 64
                     and m.out_channels % 64 == 0 and (m.out_channels >= 128 or m.dilation == 1)):
                 wpwb = wpw[name] = self._wbuf('wpw.' + name, (hipops.wino_terms(m.kernel_size) * m.in_channels * m.out_channels,), device=device)
+            if mfma_ok and name in stage_names:
+                wpwb = wpw_stage[name] = self._wbuf('wpw.' + name, (hipops.wino_terms(m.kernel_size) * m.in_channels * m.out_channels,), device=device)
             if mfma_ok and need_wf:     # a forward that will be back-propagated: dgrad / wgrad also read the plain layout - written by the
                 # same batched fold (was: three launches per layer, ~100 host-bound launches and 1.6 ms in front of every training forward)
                 n_el = m.kernel_size * m.in_channels * m.out_channels
@@ -459,8 +464,21 @@ class Generator(nn.Module):
                 plan.key = key
                 self._fold_key['plan'] = plan
             plan.run()
-        self._fold_key.update(state=state, wf=wf, wp=wp, wpd=wpd, wpw=wpw, vers=tuple(vers), gen=self._fold_key.get('gen', 0) + 1)
+        self._fold_key.update(state=state, wf=wf, wp=wp, wpd=wpd, wpw=wpw, wpw_stage=wpw_stage, vers=tuple(vers), gen=self._fold_key.get('gen', 0) + 1)
         return wf, wp
+
+    def _wino_stage_layers(self):
+        """Names of the conv layers that get a Winograd stream for the fused 32-channel stage kernel: both convs of every block of a stage
+        the planner runs in that form (forward_plan.stage_wino_selected) - none with `wino_stage` off."""
+        from .forward_plan import stage_wino_selected
+        names, nk = set(), self.num_kernels
+        for i, up in enumerate(self.ups):
+            rbs = [self.resblocks[i * nk + j] for j in range(nk)]
+            if all(isinstance(rb, ResBlock2) for rb in rbs) and stage_wino_selected(
+                    self.wino_stage, self.precision, self.algo, up.out_channels,
+                    [(rb.kernel_size, rb.convs[0].dilation, rb.convs[1].dilation) for rb in rbs]):
+                names.update(f'resblocks.{i * nk + j}.convs.{c}' for j in range(nk) for c in (0, 1))
+        return names
 
     def _split_weights(self, device, all_ups=False, ups_stream=None, mark=None, between=None):
         """precision == 'f16x3': (hi, lo) half-precision fragments + scale record of every Conv1d layer the split kernel
@@ -672,7 +690,7 @@ class Generator(nn.Module):
         ptrs = tuple(p.data_ptr() for p in self.parameters()) + tuple(b.data_ptr() for b in self.buffers())
         return (tuple(x.shape), str(x.device), torch.cuda.current_stream(x.device).cuda_stream, self.training, self.precision, self.algo, self.bf16_storage, tuple(self.fuse_stage), tuple(self.fuse_pairs),
                 self.fuse_wide, self.fuse_wide_stage, self.fuse_up, self.fuse_post, self.fuse_bn_finalize, self.cond_stream, self.merge_waits, self.split_min_channels,
-                self.always_refold, self.wino, ptrs)
+                self.always_refold, self.wino, self.wino_stage, ptrs)
 
     def _forward_hip(self, x, spk, nz, save, lens=None):
         """One forward through the C ABI.  `save` (a dict) asks for the back-propagatable form (forward_plan.py).  A no-grad forward is PLANNED
