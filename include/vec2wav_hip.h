@@ -700,6 +700,79 @@ typedef struct {
 int v2w_adamw_multi_plan(const v2w_adamw_item* items, int n, int32_t* starts);
 int v2w_adamw_multi(const v2w_adamw_item* items, int n, const v2w_adamw_hyper* h, void* stream);
 
+/* ---- Spectral norm of conv weights (additive in ABI v35; legacy torch.nn.utils.spectral_norm as models.py:219-258 applies it to the first
+ * DiscriminatorS: one power iteration per training forward, W / sigma): up to V2W_SN_MAX_LAYERS weight matrices per call, the step in 4
+ * launches (2 without the iteration), its backward in 2, whatever the number of layers.  Nothing is allocated, no state is kept.
+ *
+ * A layer is W = weight_orig (C_out, C_in / groups, k) contiguous - R = c_out rows of N = c_in * k floats; a Conv2d (.., k, 1) weight has the
+ * same memory - with u (R) and v (N).  The descriptors live in DEVICE memory for the launches; the plan fills their offsets on the HOST copy
+ * first.  Per call the caller hands over a workspace `ws` (16-byte aligned, v2w_sn_grids::ws_bytes; contents meaningless between calls, the
+ * step and the backward may share it) and a KEEP slab `keep` (16-byte aligned, v2w_sn_grids::keep_bytes) that receives, at float offset
+ * keep_off of each layer: sigma (one float, three unused), the u of this call (R floats, padded to a multiple of 4), the v of this call (N
+ * floats, padded likewise).  The slab is what the backward of THIS call reads: a later step overwrites u and v in place, not the slab.
+ *
+ *   v2w_sn_plan (host only)  checks every descriptor, fills blk_t / blk_r / blk_s / ws_off / keep_off and *g; returns ws_bytes (> 0).
+ *       V2W_E_ARG: descs or g NULL; n < 1 or n > V2W_SN_MAX_LAYERS; c_out, c_in or k <= 0; w, u, v or wf NULL or not 4-byte aligned.
+ *       V2W_E_SHAPE: R * N >= 2^31.
+ *       Work split, with nb = ceil(R / 64): the W^T u launch gives the layer nb * ceil(N / 256) workgroups (64 rows x 256 columns each), the
+ *       W v launch ceil(R / 4) (one wave per row), the relayout launches ceil(R / 64) * ceil(N / 64) tiles; ws holds per layer
+ *       max(nb * N + R, tiles) floats rounded up to 4: nb partial rows of W^T u then t = W v (step), one partial per tile (backward).
+ *   v2w_sn_step   training != 0:  a = W^T u;  v <- a / max(||a||, 1e-12);  t = W v;  u <- t / max(||t||, 1e-12);  sigma = sum_o u[o] t[o]
+ *                 (sigma REUSES the t = W v that the u update formed - no third matrix-vector product - with the new, rounded u);
+ *                 wf[j][c][o] = w[o][c][j] / sigma, the layout of v2w_wn_fold_conv.  u and v are overwritten in place.
+ *                 training == 0: no iteration, u and v are not written; t = W v and sigma = sum_o u[o] t[o] from the stored vectors; wf as above.
+ *                 Either way sigma and the u, v the call used go to the keep slab.
+ *   v2w_sn_bwd    dw[o][c][j] = dwf[j][c][o] / sigma - (sum(dwf . w) / sigma^2) u[o] v[c k + j]  with sigma, u, v from the keep slab (u, v
+ *                 are constants of the forward, as under torch.no_grad in the reference's hook).  dwf[i] / dw[i]: HOST arrays of n device
+ *                 pointers, read before the call returns; dwf[i] is [k][c_in][c_out] like wf, dw[i] is shaped like w; a layer with both
+ *                 NULL is skipped.  V2W_E_ARG: one of a pair NULL, all pairs NULL, a pointer not 4-byte aligned.
+ *   Both launching calls: V2W_E_ARG for a NULL descs_dev / g / keep / ws, n out of range or != g->n, ws or keep not 16-byte aligned,
+ *   ws_bytes < g->ws_bytes.
+ *
+ * Memory access: rows are read with 16-byte loads when N % 4 == 0 and the base pointer is 16-byte aligned (the "vector path"), else with
+ * coalesced 4-byte loads; wf and dwf are always accessed along C_out, 4 bytes per lane, 256 consecutive bytes per wave.
+ * Determinism: no atomics; sums across workgroups go through ws and are added in index order; a layer's results are the same bits
+ * whatever else shares the launch.
+ *
+ * Arithmetic: every operation below is ONE correctly rounded fp32 operation (fma = fused multiply-add); "chain of m" = m of them applied one
+ * after the other to one accumulator that starts at 0; a "wave sum" is 6 additions (butterfly over 64 lanes), a "block sum" of W waves a
+ * wave sum and then W additions in wave order.  The number in brackets is the roundings on the path to one output entry.
+ *   a[j]    one partial per band of 64 rows: an fma chain of 16 (every 4th row of the band) in each of 4 waves, 3 additions to combine the
+ *           waves; then nb - 1 additions over the bands in index order                                              [16 + 3 + nb - 1]
+ *   q       = sum_j a[j]^2: per thread an fma chain of ceil(N / 1024), block sum of 16 waves                         [ceil(N / 1024) + 22]
+ *   dn      = max(sqrt(q), 1e-12)                                                                                    [1]
+ *   v[j]    = a[j] / dn                                                                                              [1]
+ *   t[o]    vector path: 4 fma chains of ceil(N / 256) per lane, 2 additions (x + y) + (z + w), wave sum             [ceil(N / 256) + 8]
+ *           scalar path: one fma chain of ceil(N / 64) per lane, wave sum                                            [ceil(N / 64) + 6]
+ *   p       = sum_o t[o]^2: per thread an fma chain of ceil(R / 256), block sum of 4 waves                           [ceil(R / 256) + 10]
+ *   du      = max(sqrt(p), 1e-12)                                                                                    [1]
+ *   u[o]    = t[o] / du                                                                                              [1]
+ *   sigma   = sum_o u[o] t[o]: as p                                                                                  [ceil(R / 256) + 10]
+ *   wf      = w / sigma                                                                                              [1]
+ *   dot     = sum dwf w: per 64 x 64 tile an fma chain of 16 per thread and a block sum of 4 waves; then over the layer's tiles per thread
+ *             a chain of ceil(tiles / 256) additions and a block sum of 4 waves                                      [26 + ceil(tiles / 256) + 10]
+ *   s2      = sigma sigma;  coef = dot / s2;  g = dwf / sigma;  uv = u[o] v[c];  dw = fma(-coef, uv, g)              [1 each]
+ * tests/sn_ref.py restates this in fp64 and turns the counts into per-entry bounds. */
+#define V2W_SN_MAX_LAYERS 64
+typedef struct {
+    const float* w;
+    float* u;
+    float* v;
+    float* wf;
+    int32_t c_out, c_in, k;          /* c_in: input channels per group */
+    int32_t blk_t, blk_r, blk_s;     /* filled by v2w_sn_plan: the layer's first workgroup in the three grid shapes */
+    int64_t ws_off, keep_off;        /* filled by v2w_sn_plan: float offsets of the layer in ws and in keep */
+} v2w_sn_desc;                       /* 72 bytes */
+typedef struct {
+    int32_t n, grid_t, grid_r, grid_s;
+    int64_t ws_bytes, keep_bytes;
+} v2w_sn_grids;                      /* 32 bytes; HOST memory, filled by v2w_sn_plan, read by the launching calls before they return */
+long long v2w_sn_plan(v2w_sn_desc* descs, int n, v2w_sn_grids* g);
+int v2w_sn_step(const v2w_sn_desc* descs_dev, int n, int training, const v2w_sn_grids* g, float* keep, void* ws, long long ws_bytes,
+                void* stream);
+int v2w_sn_bwd(const v2w_sn_desc* descs_dev, int n, const v2w_sn_grids* g, const float* keep, const float* const* dwf, float* const* dw,
+               void* ws, long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,9 +2,10 @@
 """One full vec2wav GAN training iteration as vec2wav/train.py:160-215 runs it - generator forward, mel of the generated audio,
 discriminator step (MPD + MSD on y and y_g_hat.detach(), backward, AdamW), generator step (MPD + MSD again, feature / LSGAN /
 L1-mel losses, backward through the discriminators, the mel and the generator, AdamW) - entirely on the HIP path.
-argv: B T steps [stock] [frozen] [optim=hip|optim=torch]   ('stock': the discriminators as stock torch.nn conv stacks (MIOpen + torch autograd) for comparison;
+argv: B T steps [stock] [frozen] [optim=hip|optim=torch] [sn=torch]   ('stock': the discriminators as stock torch.nn conv stacks (MIOpen + torch autograd) for comparison;
 'frozen': `with discriminators.frozen(mpd, msd)` around the G step's discriminator forwards - same trajectory, no wasted D gradients;
-'optim=hip': both optimizers are wavthruvec_pytorch_amd.AdamW, the library's multi-tensor kernel - the default 'optim=torch' is torch.optim.AdamW)"""
+'sn=torch': discriminators.NATIVE_SN = False - the spectral norm of the first scale discriminator on torch's mv / normalize / dot / outer, the
+behaviour before the v2w_sn_* entry points; 'optim=hip': both optimizers are wavthruvec_pytorch_amd.AdamW, the library's multi-tensor kernel - the default 'optim=torch' is torch.optim.AdamW)"""
 import contextlib
 import os
 import sys
@@ -81,6 +82,8 @@ def main():
         HD.BATCH_PAIRS = True
     if 'nopairs' in sys.argv[4:]:
         HD.BATCH_PAIRS = False
+    if 'sn=torch' in sys.argv[4:]:
+        HD.NATIVE_SN = False
     f16x3 = 'f16x3' in sys.argv[4:]        # the dense five-tap 1024 -> 1024 discriminator convs (forward + input gradient) and the generator's
     #                                        forward / input-gradient convs as f16 hi + lo operands; every weight gradient exact
     dev = torch.device('cuda:0')

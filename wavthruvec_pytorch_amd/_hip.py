@@ -138,6 +138,20 @@ class AdamWHyper(C.Structure):
 ADAMW_MAX_ITEMS = 80
 ADAMW_TARGET_WGS = 2048
 
+
+class SnDesc(C.Structure):
+    """include/vec2wav_hip.h `v2w_sn_desc`: one spectral-normed conv weight (R = c_out rows of N = c_in * k floats), its u, v and folded output."""
+    _fields_ = [('w', _fp), ('u', _fp), ('v', _fp), ('wf', _fp), ('c_out', C.c_int32), ('c_in', C.c_int32), ('k', C.c_int32),
+                ('blk_t', C.c_int32), ('blk_r', C.c_int32), ('blk_s', C.c_int32), ('ws_off', C.c_int64), ('keep_off', C.c_int64)]
+
+
+class SnGrids(C.Structure):
+    """include/vec2wav_hip.h `v2w_sn_grids`: what v2w_sn_plan hands the launching calls (host memory)."""
+    _fields_ = [('n', C.c_int32), ('grid_t', C.c_int32), ('grid_r', C.c_int32), ('grid_s', C.c_int32), ('ws_bytes', C.c_int64), ('keep_bytes', C.c_int64)]
+
+
+SN_MAX_LAYERS = 64
+
 # name -> (restype, argtypes); must list every symbol include/vec2wav_hip.h declares
 SIGNATURES = {
     'v2w_abi_version': (C.c_int, []),
@@ -239,6 +253,10 @@ SIGNATURES = {
     # AdamW: host descriptor array and hyperparameters, read before the call returns
     'v2w_adamw_multi_plan': (C.c_int, [C.POINTER(AdamWItem), C.c_int, C.POINTER(C.c_int32)]),
     'v2w_adamw_multi': (C.c_int, [C.POINTER(AdamWItem), C.c_int, C.POINTER(AdamWHyper), _fp]),
+    # spectral norm: DEVICE descriptors (planned on the host copy), host grids and host pointer arrays, read before the call returns
+    'v2w_sn_plan': (C.c_longlong, [C.POINTER(SnDesc), C.c_int, C.POINTER(SnGrids)]),
+    'v2w_sn_step': (C.c_int, [_fp, C.c_int, C.c_int, C.POINTER(SnGrids), _fp, _fp, C.c_longlong, _fp]),
+    'v2w_sn_bwd': (C.c_int, [_fp, C.c_int, C.POINTER(SnGrids), _fp, C.POINTER(_fp), C.POINTER(_fp), _fp, C.c_longlong, _fp]),
 }
 
 # entry points that LAUNCH (their last argument is the stream); the others are host-only queries.  schedule.Recorder tapes the former.

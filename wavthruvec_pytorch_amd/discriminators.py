@@ -16,8 +16,9 @@ the f32 MFMA tile kernel through the C ABI as stride-1 problems (csrc/v2w_disc.h
   leaky_relu       -> the conv epilogue (`out_slope`): feature maps are stored activated, as the reference returns them,
   row pitch        -> feature maps live in (B, C, roundup4(length)) buffers (the kernel's float4 staging) and are returned as
                       `[:, :, :length]` views: same shapes and values as the reference, strided when length % 4 != 0.
-Weight preparation (weight-norm fold on the HIP kernel; spectral-norm power iteration, tap re-indexing for the stride / group
-forms with torch index ops on the weight tensors) is cached per parameter version.
+Weight preparation (weight-norm fold on the HIP kernel; the spectral-norm power iteration, sigma and W / sigma of all layers of a call in
+one `hipops.sn_step` - `NATIVE_SN`; tap re-indexing for the stride / group forms with torch index ops on the weight tensors) is cached
+per parameter version.
 
 How the file is laid out: a `_DiscConv` decides its stride-1 form once, in `__init__` (`form`, `cs`, `kp`, `Q`); its
 `kernel_weights()` returns a `_Weights` record (forward weights, the optional split-f16 set, input-gradient weights built on first
@@ -127,6 +128,8 @@ class _DiscConv(nn.Module):
         self._cache = None
         self._pair_rec = None
         self._last_sn = None
+        self._sn_ready = None           # (wf, _SnKept) of a spectral layer that `_sn_prepare` has stepped for the coming kernel_weights()
+        self._wf_sn = None
         self._jmap = None
         self._wpad = None
         self._no_split_dgrad = None     # (C_out / G, cs / G, pitch) of the input-gradient conv the split-f16 kernel declined last
@@ -174,6 +177,12 @@ class _DiscConv(nn.Module):
         co, cig, k = self.c_out, self.c_in // self.groups, self.k
         if not self.spectral:
             return hipops.fold_conv_weight(self.weight_v.detach().reshape(co, cig, k), self.weight_g.detach().reshape(co, 1, 1), out=out)
+        if NATIVE_SN:          # stepped with the discriminator's other layers (`_sn_prepare`), or - a layer used on its own - here, n = 1
+            if self._sn_ready is None:
+                _sn_prepare([self])
+            (wf, self._last_sn), self._sn_ready = self._sn_ready, None
+            assert out is None or wf.data_ptr() == out.data_ptr()
+            return wf
         w = self.weight_orig.detach()
         wm = w.reshape(co, -1)
         if self.training:      # legacy torch.nn.utils.spectral_norm: v <- norm(W^T u), u <- norm(W v), in place, per forward
@@ -186,11 +195,36 @@ class _DiscConv(nn.Module):
     def invalidate_weight_cache(self):
         self._cache = None
 
+    def _key(self):
+        return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
+
+    def _reindex_constants(self):
+        """Constants of the stacked forms' re-indexing, built once per device: the tap map j[q][r] (k = "no such tap" -> the zero row of wpad)."""
+        dev = self.bias.device
+        if self._wpad is None or self._wpad.device != dev:
+            q = torch.arange(self.kp, device=dev).view(self.kp, 1) - self.Q
+            r = torch.arange(self.stride, device=dev).view(1, self.stride)
+            j = self.stride * q + r + self.padding
+            self._jmap = torch.where((j >= 0) & (j < self.k), j, torch.full_like(j, self.k)).reshape(-1)
+            self._wpad = torch.zeros((self.k + 1, self.c_in // self.groups, self.c_out), device=dev)
+
+    def _sn_tensors(self):
+        """(weight_orig as (C_out, C_in / groups, k), u, v, wf) of a spectral layer for hipops.sn_step: wf is where `kernel_weights` reads the
+        folded weight - the first k rows of wpad for the stacked forms, a buffer of the layer's own otherwise."""
+        co, cig, k = self.c_out, self.c_in // self.groups, self.k
+        if self.form in (_PHASES, _PLAIN):
+            self._reindex_constants()
+            wf = self._wpad[:k]
+        else:
+            if self._wf_sn is None or self._wf_sn.device != self.bias.device:
+                self._wf_sn = torch.empty((k, cig, co), device=self.bias.device)
+            wf = self._wf_sn
+        return self.weight_orig.detach().reshape(co, cig, k), self.weight_u, self.weight_v, wf
+
     def kernel_weights(self) -> _Weights:
         """The `_Weights` of the current parameters.  Phase-stacked / plain form, with j - P = s*q + r:
         w4[g][q + Q][r * cig + c][o] = wf[s*q + r + P][c][g * cog + o]  (0 where the tap does not exist)."""
-        params = list(self.parameters()) + list(self.buffers())
-        key = tuple((p.data_ptr(), p._version) for p in params)
+        key = self._key()
         # train mode refolds every call, as the reference's weight-norm / spectral-norm hooks do (and as the generator does): a
         # `.data` mutation (EMA swap, re-initialisation) bumps neither the pointer nor the version counter, so the cache is an
         # eval-mode optimisation only (`invalidate_weight_cache()` after a `.data` edit in eval mode)
@@ -206,13 +240,8 @@ class _DiscConv(nn.Module):
         cig, cog = self.c_in // G, self.c_out // G
         stacked = self.form in (_PHASES, _PLAIN)
         dev = self.bias.device
-        if stacked and (self._wpad is None or self._wpad.device != dev):
-            # constants of the re-indexing, built once: the tap map j[q][r] (k = "no such tap" -> the zero row of wpad)
-            q = torch.arange(self.kp, device=dev).view(self.kp, 1) - self.Q
-            r = torch.arange(s, device=dev).view(1, s)
-            j = s * q + r + P
-            self._jmap = torch.where((j >= 0) & (j < k), j, torch.full_like(j, k)).reshape(-1)
-            self._wpad = torch.zeros((k + 1, cig, self.c_out), device=dev)
+        if stacked:
+            self._reindex_constants()
         wf = self._folded(self._wpad[:k] if stacked else None)            # [k][cig][co]
         if self.form == _TAPS:                               # rows (j, c): the taps become channels of a 1-tap conv
             w4 = torch.stack([wf.reshape(1, k * cig, self.c_out)], 0)
@@ -233,12 +262,12 @@ class _DiscConv(nn.Module):
         """The split-f16 kernel serves this layer's stride-1 form: `cigp` stacked input channels and `cog` output channels per group."""
         return (self.precision == 'f16x3' and self.form in (_PHASES, _PLAIN) and self.kp >= 2 and hipops.split_supported(cigp, cog))
 
-    def param_grads(self, db, dws, sn):
-        """Gradients of this layer's parameters (parameters() order) from the bias gradient and the per-group weight gradients
-        of the stride-1 form, dws[g] [kp][cs / G][C_out / G] (the inverse of `kernel_weights`' re-indexing)."""
+    def folded_grad(self, dws):
+        """dwf [k][C_in / groups][C_out], the gradient wrt the folded weight, from the per-group weight gradients of the stride-1 form,
+        dws[g] [kp][cs / G][C_out / G] (the inverse of `kernel_weights`' re-indexing)."""
         k, s, G = self.k, self.stride, self.groups
         co, cig = self.c_out, self.c_in // G
-        dev = db.device
+        dev = dws[0].device
         if self.form == _FIRST:
             dwf = dws[0][0, :k, :].reshape(k, 1, co)
         elif self.form == _TAPS:
@@ -246,17 +275,55 @@ class _DiscConv(nn.Module):
         else:
             d5 = torch.stack(dws, 2).reshape(self.kp * s, cig, co)       # rows (q, r), then c; columns (g, o)
             dwf = torch.zeros((k + 1, cig, co), device=dev).index_add_(0, self._jmap, d5)[:k]
-        dwf = dwf.contiguous()
+        return dwf.contiguous()
+
+    def param_grads(self, db, dws, sn):
+        """Gradients of this layer's parameters (parameters() order) from the bias gradient and the per-group weight gradients of the
+        stride-1 form."""
+        co, cig, k = self.c_out, self.c_in // self.groups, self.k
+        dwf = self.folded_grad(dws)
         if not self.spectral:
             v, g = self.weight_v.detach(), self.weight_g.detach()
             dv, dg = hipops.wn_backward(dwf, v.reshape(co, cig, k), g.reshape(co, 1, 1), False)
             return [db, dg.reshape(g.shape), dv.reshape(v.shape)]
         # W = weight_orig / sigma, sigma = u^T W v with u, v constants (the power iteration runs under no_grad)
-        sigma, u, vv = sn
         w = self.weight_orig.detach()
+        if isinstance(sn, _SnKept):        # one layer of the step's set (the discriminator's backward hands all of them over at once)
+            dwfs = [None] * sn.plan.n
+            dwfs[sn.index] = dwf
+            return [db, hipops.sn_backward(sn.plan, sn.keep, dwfs)[sn.index].reshape(w.shape)]
+        sigma, u, vv = sn
         dW = dwf.permute(2, 1, 0).reshape(w.shape)
         dot = (dW * w).sum() / (sigma * sigma)
         return [db, dW / sigma - dot * torch.outer(u, vv).reshape(w.shape)]
+
+
+class _SnKept(NamedTuple):
+    """What one native spectral-norm step leaves for its backward: the layer set's plan, the call's keep slab (sigma, u, v of every layer as
+    the forward used them - the next call overwrites the buffers before this call's backward runs) and the layer's index in the set."""
+    plan: 'hipops.SnPlan'
+    keep: torch.Tensor
+    index: int
+
+    def values(self):
+        """(sigma, u, v) of the layer, views of the slab."""
+        return self.plan.keep_views(self.keep, self.index)
+
+
+def _sn_prepare(layers):
+    """NATIVE_SN: the spectral layers among `layers` whose `kernel_weights()` is about to fold (train mode: every call, with one power iteration,
+    as the legacy hook; eval mode: only when the cached record is stale, and without one) take their step in ONE hipops.sn_step per mode;
+    each finds its folded weight and its `_SnKept` in `_sn_ready`."""
+    todo = [l for l in layers if l.spectral and (l.training or l._cache is None or l._cache[0] != l._key())]
+    for training in (True, False):
+        grp = [l for l in todo if l.training == training]
+        if not grp:
+            continue
+        _check_cuda(*[l.bias for l in grp])
+        tensors = [l._sn_tensors() for l in grp]
+        plan, keep = hipops.sn_step(tensors, training)
+        for i, (l, t) in enumerate(zip(grp, tensors)):
+            l._sn_ready = (t[3], _SnKept(plan, keep, i))
 
 
 def _check_cuda(*xs):
@@ -345,7 +412,9 @@ class _DiscBase(nn.Module):
         b, c, t = x.shape
         inner, H = self._geometry(t)
         layers = self._layers()
-        recs = [l.kernel_weights() for l in layers]             # (spectral norm: the power iteration of this call happens here)
+        if NATIVE_SN:
+            _sn_prepare(layers)                                 # spectral norm: the power iteration of this call, all layers in one step
+        recs = [l.kernel_weights() for l in layers]             # (NATIVE_SN off: the power iteration of this call happens here)
         sn = [l._last_sn for l in layers]
         bufs = [_first_layer(layers[0], recs[0], x, H, inner)]
         for i in range(1, len(layers)):
@@ -444,6 +513,7 @@ class _DiscFn(torch.autograd.Function):
         n = len(layers)
         grads = [None] * n           # per layer: its parameter gradients in parameters() order
         down, dx = None, None        # what flows into layer l from layer l + 1; the gradient wrt the audio
+        sn_todo = []                 # (l, db, dwf, _SnKept) of the natively spectral-normed layers: their backward is one call, after the loop
         for l in reversed(range(n)):
             layer, rec, g = layers[l], st['recs'][l], gouts[l]
             if g is None and down is None:
@@ -456,11 +526,25 @@ class _DiscFn(torch.autograd.Function):
                 # the layer's stride-1 input: rebuilt here, one streaming pass, and only when a weight gradient reads it - the forward
                 # keeps the feature maps alone
                 xs = _unfold_first(layer, x, H, inner) if l == 0 else _stacked_input(layer, maps[l - 1], rows[l - 1], inner)
-                grads[l] = layer.param_grads(db, _weight_grad(layer, xs, dz, inner), st['sn'][l])
+                dws = _weight_grad(layer, xs, dz, inner)
+                if isinstance(st['sn'][l], _SnKept):
+                    sn_todo.append((l, db, layer.folded_grad(dws), st['sn'][l]))
+                else:
+                    grads[l] = layer.param_grads(db, dws, st['sn'][l])
             if l > 0:
                 down = _input_grad(layer, rec, dz, inner)
             elif ctx.need_dx:
                 dx = hipops.fold1(_input_grad(layer, rec, dz, inner).d, T=T, H=H, inner=inner, s=layer.stride, k=layer.k, pad=layer.padding)
+        while sn_todo:               # the layers that shared a step share its backward
+            kept = sn_todo[0][3]
+            grp = [e for e in sn_todo if e[3].keep is kept.keep]
+            sn_todo = [e for e in sn_todo if e[3].keep is not kept.keep]
+            dwfs = [None] * kept.plan.n
+            for _l, _db, dwf, sk in grp:
+                dwfs[sk.index] = dwf
+            dw = hipops.sn_backward(kept.plan, kept.keep, dwfs)
+            for l, db, _dwf, sk in grp:
+                grads[l] = [db, dw[sk.index].reshape(layers[l].weight_orig.shape)]
         flat = []
         for l in range(n):
             npar = len(list(layers[l].parameters()))
@@ -508,6 +592,10 @@ _PAIR = _PairState()
 # 'auto': up to _BATCH_PAIRS_MAX_SAMPLES input samples per half (above, the autograd slices of the split feature maps cost more than the launches).
 BATCH_PAIRS = 'auto'
 _BATCH_PAIRS_MAX_SAMPLES = 1 << 20
+# The spectral-norm arithmetic of the first scale discriminator on the C ABI (hipops.sn_step / sn_backward: all layers of a call in four
+# launches, their backward in two).  False: the torch lines of `_DiscConv._folded` / `param_grads` (mv, normalize, dot, outer), kept as the
+# benchmark's A/B partner and the tests' second implementation.  Either way u, v advance once per call and spectral layers are never pair-shared.
+NATIVE_SN = True
 
 
 def _batch_pair(d, y, y_hat):

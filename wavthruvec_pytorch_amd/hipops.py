@@ -1214,6 +1214,94 @@ def conv1d_groups(x, w4, bias, out, packs, *, dil, pad_left, out_slope=0.0, algo
     return out
 
 
+# ---- spectral norm of the first scale discriminator's conv weights (include/vec2wav_hip.h: v2w_sn_plan / v2w_sn_step / v2w_sn_bwd)
+class SnPlan:
+    """The planned descriptor table of one layer set - layers: (w (C_out, C_in / groups, k[, 1]), u (C_out,), v (C_in / groups * k,),
+    wf [k][C_in / groups][C_out]) - on the device, its grids and its workspace.  `keep_views(keep, i)` -> (sigma, u, v) of layer i in a
+    keep slab of a step."""
+
+    def __init__(self, layers):
+        n = len(layers)
+        if not 1 <= n <= _hip.SN_MAX_LAYERS:
+            raise ValueError(f'sn: 1 .. {_hip.SN_MAX_LAYERS} layers per call, got {n}')
+        descs = (_hip.SnDesc * n)()
+        self.shapes = []
+        for d, (w, u, v, wf) in zip(descs, layers):
+            _chk(w, 'w'); _chk(u, 'u'); _chk(v, 'v'); _chk(wf, 'wf')
+            co, ci, k = w.shape[:3]
+            if w.numel() != co * ci * k or u.numel() != co or v.numel() != ci * k or tuple(wf.shape) != (k, ci, co):
+                raise ValueError(f'sn: w {tuple(w.shape)}, u {tuple(u.shape)}, v {tuple(v.shape)}, wf {tuple(wf.shape)} do not belong together')
+            d.w, d.u, d.v, d.wf = w.data_ptr(), u.data_ptr(), v.data_ptr(), wf.data_ptr()
+            d.c_out, d.c_in, d.k = co, ci, k
+            self.shapes.append((co, ci, k))
+        self.grids = _hip.SnGrids()
+        rc = _hip.load().v2w_sn_plan(descs, n, C.byref(self.grids))
+        _hip.check(0 if rc > 0 else int(rc or -1), 'v2w_sn_plan')
+        dev = layers[0][0].device
+        self.n, self.device = n, dev
+        self.keep_off = [int(d.keep_off) for d in descs]
+        self.keep_floats = self.grids.keep_bytes // 4
+        self.descs_dev = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8).to(dev)
+        self.ws = torch.empty((self.grids.ws_bytes // 4,), device=dev, dtype=torch.float32)
+        self.tensors = [tuple(l) for l in layers]       # what the descriptors point at stays alive with the plan
+
+    def keep_views(self, keep, i):
+        co, ci, k = self.shapes[i]
+        o = self.keep_off[i]
+        ou, ov = o + 4, o + 4 + (co + 3) // 4 * 4
+        return keep[o], keep[ou:ou + co], keep[ov:ov + ci * k]
+
+
+_SN_PLANS = {}
+
+
+def sn_plan(layers) -> SnPlan:
+    """The cached SnPlan of this layer set (keyed by the tensors' addresses and shapes)."""
+    if not layers:
+        raise ValueError('sn: no layers')
+    for l in layers:
+        for t, name in zip(l, ('w', 'u', 'v', 'wf')):
+            _chk(t, name)
+    key = tuple((t.data_ptr(), tuple(t.shape)) for l in layers for t in l) + (str(layers[0][0].device),)
+    plan = _SN_PLANS.get(key)
+    if plan is None:
+        plan = _SN_PLANS[key] = SnPlan(layers)
+    return plan
+
+
+def sn_step(layers, training):
+    """One spectral-norm step of every layer (w, u, v, wf) in one v2w_sn_step: with `training` v <- norm(W^T u), u <- norm(W v) in place;
+    sigma = u . W v; wf = W / sigma in the fold layout.  -> (plan, keep): keep is this call's slab of (sigma, u, v) per layer
+    (`plan.keep_views(keep, i)`), which `sn_backward` reads."""
+    plan = sn_plan(layers)
+    keep = torch.empty((plan.keep_floats,), device=plan.device, dtype=torch.float32)
+    _hip.check(_hip.load().v2w_sn_step(plan.descs_dev.data_ptr(), plan.n, int(bool(training)), C.byref(plan.grids), keep.data_ptr(),
+                                       plan.ws.data_ptr(), plan.grids.ws_bytes, _stream(keep)), 'v2w_sn_step')
+    return plan, keep
+
+
+def sn_backward(plan: SnPlan, keep, dwfs, outs=None):
+    """dwfs[i]: the gradient wrt layer i's folded weight [k][C_in / groups][C_out], or None -> dw[i] shaped (C_out, C_in / groups, k)
+    (None where dwfs[i] is): dwf / sigma - (sum(dwf . w) / sigma^2) u v^T, one v2w_sn_bwd for all of them."""
+    if len(dwfs) != plan.n:
+        raise ValueError(f'sn_backward: {plan.n} layers planned, {len(dwfs)} gradients given')
+    _chk(keep, 'keep')
+    pd, po = (_hip._fp * plan.n)(), (_hip._fp * plan.n)()
+    dws = [None] * plan.n
+    for i, g in enumerate(dwfs):
+        if g is None:
+            continue
+        co, ci, k = plan.shapes[i]
+        _chk(g, 'dwf')
+        if tuple(g.shape) != (k, ci, co):
+            raise ValueError(f'sn_backward: dwf[{i}] must be {(k, ci, co)}, got {tuple(g.shape)}')
+        dws[i] = _out(None if outs is None else outs[i], (co, ci, k), g, 'dw')
+        pd[i], po[i] = g.data_ptr(), dws[i].data_ptr()
+    _hip.check(_hip.load().v2w_sn_bwd(plan.descs_dev.data_ptr(), plan.n, C.byref(plan.grids), keep.data_ptr(), pd, po,
+                                      plan.ws.data_ptr(), plan.grids.ws_bytes, _stream(keep)), 'v2w_sn_bwd')
+    return dws
+
+
 # ---- GAN training losses (include/vec2wav_hip.h: v2w_l1_mean_multi / v2w_lsgan_multi and their backwards)
 def _dense_suffix(dims):
     """How many trailing (size, stride) pairs form one contiguous run of floats."""
