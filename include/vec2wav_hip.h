@@ -547,6 +547,23 @@ int v2w_mel_finish(const float* spec, const float* basis, float* out, int B, int
 int v2w_mel_finish_bwd(const float* spec, const float* basis, const float* basisT, const float* gout, float* dspec,
                        int B, int Cs, int FP, int F, int nb, int n_mels, void* stream);
 int v2w_mel_phases_bwd(const float* dxp, float* dy, int B, int L, int hop, int pad, int FP, void* stream);
+/* The two ends for a batch of unequal lengths (additive; forward only; `len` / len_mul as under "Batches of unequal lengths" above: item b
+ * holds Lb = min(len[b] * len_mul, L) samples, whatever y[b, Lb:] holds - NaN, Inf, stale workspace - reaches no stored value, the grids do
+ * not depend on the values).  With n_fft = 2 * pad + hop (a multiple of hop) and k = n_fft / hop, item b has
+ *   F_b = (Lb + 2 * pad - n_fft) / hop + 1 frames if Lb > pad (reflect padding needs more than pad samples) and Lb + 2 * pad >= n_fft, else 0.
+ *   v2w_mel_phases_len: xp[b][p][f] = ypad_b[f * hop + p], ypad_b = y[b, :Lb] reflected about ITS ends (index 0 and index Lb - 1): the bits
+ *                       of a B = 1 v2w_mel_phases call on y[b, :Lb] over that call's roundup4(F_b + k - 1) columns; exactly 0 in the columns
+ *                       past them (no frame of the item reads those) and past Lb + 2 * pad; all 0 for an item with F_b = 0.  No load
+ *                       address is at or past Lb within row b.
+ *   v2w_mel_finish_len: (takes no L: F_b is clamped to F = the frames of L) frames f < F_b as v2w_mel_finish computes them (same operations in the same order); frames F_b <= f < F store
+ *                       exactly 0.0 - the zero padding of a padded target mel (dataset.py:194-218), not log(1e-5).  A workgroup (16 frames)
+ *                       whose frames all lie at or past F_b stores its zeros without reading spec.
+ * The DFT conv between them is v2w_conv1d_fwd on the whole xp as before: an item's F_b + k - 1 columns are no integer multiple of len[b],
+ * so v2w_conv1d_fwd_len does not apply and no tile is skipped.  V2W_E_ARG as the plain calls, and for len == NULL, len_mul < 1,
+ * (2 * pad) % hop != 0 (phases) or n_fft % hop != 0 / n_fft < hop / n_fft - hop odd (finish). */
+int v2w_mel_phases_len(const float* y, float* xp, int B, int L, int hop, int pad, int FP, const int32_t* len, int len_mul, void* stream);
+int v2w_mel_finish_len(const float* spec, const float* basis, float* out, int B, int Cs, int FP, int F, int nb, int n_mels,
+                       const int32_t* len, int len_mul, int hop, int n_fft, void* stream);
 
 /* ---- MPD / MSD discriminator forwards (models.py:158-275): the memory-bound ends; the convolutions run
  * through v2w_conv1d_fwd (in_ct / out_ct for groups, out_slope for the activated feature maps, dil = period for the (k, 1) Conv2d).
@@ -649,6 +666,25 @@ int v2w_l1_mean_multi(const v2w_l1_pair* pairs, int n, float scale, float* term,
 int v2w_l1_mean_multi_bwd(const v2w_l1_pair* pairs, int n, float scale, const float* gout, void* stream);
 int v2w_lsgan_multi(const v2w_lsgan_item* items, int n, float* term, float* total, void* stream);
 int v2w_lsgan_multi_bwd(const v2w_lsgan_item* items, int n, const float* gout, const float* gterm, void* stream);
+/* Masked mel L1 of a batch of unequal lengths (additive; forward only - the validation loop of train.py:246-289, batched): a, b (B, C, F)
+ * dense fp32; `len` a DEVICE array of B int32, len_mul >= 1 as under "Batches of unequal lengths": item b counts its first
+ * F_b = min(frames(len[b] * len_mul), F) frames, frames(n) as v2w_mel_finish_len states it with pad = (n_fft - hop) / 2.
+ *   per_item[b] = (sum of |a - b| over the C x F_b valid elements) / (C * F_b), 0 for F_b = 0      (B floats, may be NULL)
+ *   total[0]    = (sum over b of those sums) / (C * sum_b F_b), 0 when no item has a frame         (may be NULL)
+ * Elements at or past F_b are selected away (never multiplied by a mask): NaN or Inf there reaches nothing.
+ * Work split: an item is ceil(C * F / 4) units of four floats - 16-byte loads when F % 4 == 0 and both pointers are 16-byte aligned, else
+ * element loads - shared out over G = v2w_l1_masked_plan(C, F) = clamp(ceil(units / 1024), 1, 256) workgroups, grid (G, B): it depends on
+ * the shape only.  Workgroup (g, b) writes ONE fp64 partial to ws[b * G + g] (ws: B * G doubles, 8-byte aligned); a finishing launch adds
+ * an item's G partials in index order and the items' sums in a fixed order: no atomics, the same call gives the same bits, and an item's
+ * value depends on no other item.
+ * Roundings on the way to one value: [1] fp32 for each a - b (the absolute value is exact); every sum is fp64 - per thread at most
+ * 4 * ceil(units / (256 G)) additions in a chain, [6 + 4] in the workgroup's reduction, [G] over the partials (total: + [ceil(B / 256) +
+ * 6 + 4] over the items), [1] the fp64 quotient, then [1] fp32 for the stored value.
+ * V2W_E_ARG: a NULL a / b / len / ws, per_item and total both NULL, len_mul < 1, hop < 1, n_fft < hop, n_fft % hop != 0, n_fft - hop odd, a pointer not
+ * 4-byte (ws: 8-byte) aligned; V2W_E_SHAPE: C * F >= 2^31 - 3 or B > 65535. */
+int v2w_l1_masked_plan(int C, int F);        /* host only: G > 0, or a V2W_E_* code */
+int v2w_l1_masked(const float* a, const float* b, int B, int C, int F, const int32_t* len, int len_mul, int hop, int n_fft,
+                  float* per_item, float* total, void* ws, void* stream);
 
 /* ---- AdamW (additive in ABI v35; torch.optim.AdamW as train.py:96-99 constructs it and train.py:198,215 steps it: decoupled weight
  * decay, no amsgrad, no maximize): the step of up to V2W_ADAMW_MAX_ITEMS parameter tensors in ONE launch that reads p, g, m, v and

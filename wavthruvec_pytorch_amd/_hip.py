@@ -243,6 +243,11 @@ SIGNATURES = {
     'v2w_convt1d_fwd_len': (C.c_int, [C.POINTER(ConvT1dArgs), _fp, C.c_int, _fp]),
     'v2w_resblock2_stage_fwd_len': (C.c_int, [C.POINTER(StageArgs), _fp, C.c_int, _fp]),
     'v2w_conv_post_tanh_len': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, C.c_int, _fp]),
+    # mel_spectrogram and the mel L1 of a batch of unequal lengths (forward only)
+    'v2w_mel_phases_len': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp]),
+    'v2w_mel_finish_len': (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp]),
+    'v2w_l1_masked_plan': (C.c_int, [C.c_int, C.c_int]),
+    'v2w_l1_masked': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp]),
     # GAN training losses: host descriptor arrays, read before the call returns
     'v2w_l1_multi_plan': (C.c_int, [C.POINTER(L1Pair), C.c_int, C.POINTER(C.c_int32)]),
     'v2w_l1_multi_scratch_bytes': (C.c_longlong, [C.POINTER(L1Pair), C.c_int]),

@@ -204,6 +204,95 @@ lsgan_multi_bwd_kernel(const LsArgs A) {
     }
 }
 
+// ---- masked mel L1 of a batch of unequal lengths (v2w_l1_masked): a, b (B, C, F) dense; item b counts its first Fb frames.  An item is
+// ceil(C * F / 4) units of four floats, shared out over the gridDim.x workgroups of its grid row; workgroup (g, b) writes part[b * G + g].
+constexpr int kMaskedUnitsPerWg = kThreads * kUnroll;
+constexpr int kMaskedMaxWgs = 256;
+
+__device__ __forceinline__ int masked_frames(const int32_t* __restrict__ len, int b, int len_mul, int hop, int n_fft, int F) {
+    const int pad = (n_fft - hop) / 2;
+    const long long n = (long long)len[b] * len_mul;
+    if (n <= pad || n + 2 * pad < n_fft) return 0;           // reflect padding needs more than pad samples; one frame needs n_fft padded ones
+    const long long fr = (n + 2 * pad - n_fft) / hop + 1;
+    return fr < F ? (int)fr : F;
+}
+
+// VEC: F % 4 == 0 and both pointers 16-byte aligned - a unit lies in one row and is one 16-byte load per side.  A masked element is
+// selected away (its load, where a unit straddles Fb, is discarded): nothing at or past Fb reaches the sum.
+template <bool VEC>
+__global__ void __launch_bounds__(kThreads)
+l1_masked_kernel(const float* __restrict__ a, const float* __restrict__ b, const int32_t* __restrict__ len, int len_mul, int hop, int n_fft,
+                 int C, int F, double* __restrict__ part) {
+    __shared__ double red[16];
+    const int item = blockIdx.y, G = gridDim.x;
+    const int Fb = masked_frames(len, item, len_mul, hop, n_fft, F);
+    const int n = C * F;
+    const int units = (n + 3) >> 2;
+    const int chunk = (units + G - 1) / G;
+    const int u0 = blockIdx.x * chunk;
+    const int u1 = u0 + chunk < units ? u0 + chunk : units;
+    const float* ai = a + (size_t)item * n;
+    const float* bi = b + (size_t)item * n;
+    double acc = 0.0;
+    if (Fb > 0) {
+        for (int t0 = u0 + threadIdx.x; t0 < u1; t0 += kThreads * kUnroll) {
+            f32x4 va[kUnroll], vb[kUnroll];
+            int col[kUnroll][4];                              // column of each of the unit's floats; F: masked or not there
+#pragma unroll
+            for (int k = 0; k < kUnroll; ++k) {
+                const int u = t0 + k * kThreads;
+                va[k] = vb[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) col[k][j] = F;
+                if (u >= u1) continue;
+                const int e = u << 2;
+                if (VEC) {
+                    const int c = e % F;
+                    if (c < Fb) {
+                        va[k] = *reinterpret_cast<const f32x4*>(ai + e);
+                        vb[k] = *reinterpret_cast<const f32x4*>(bi + e);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) col[k][j] = c + j;
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int c = (e + j) % F;
+                        if (e + j < n && c < Fb) { va[k][j] = ai[e + j]; vb[k][j] = bi[e + j]; col[k][j] = c; }
+                    }
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kUnroll; ++k)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc += col[k][j] < Fb ? (double)fabsf(va[k][j] - vb[k][j]) : 0.0;
+        }
+    }
+    const double s = v2w_block_sum(acc, red);
+    if (threadIdx.x == 0) part[(size_t)item * G + blockIdx.x] = s;
+}
+
+// per_item[b] = (the item's G partials, added in index order) / (C * Fb); total = (the items' sums) / (C * sum Fb): one workgroup, thread t
+// takes the items t, t + 256, ...; the sums over the items go through the fixed-order block reduction
+__global__ void __launch_bounds__(kThreads)
+l1_masked_finish_kernel(const double* __restrict__ part, const int32_t* __restrict__ len, int len_mul, int hop, int n_fft,
+                        int B, int C, int F, int G, float* __restrict__ per_item, float* __restrict__ total) {
+    __shared__ double red[16];
+    double tot = 0.0, cnt = 0.0;
+    for (int b = threadIdx.x; b < B; b += kThreads) {
+        const int Fb = masked_frames(len, b, len_mul, hop, n_fft, F);
+        double s = 0.0;
+        for (int g = 0; g < G; ++g) s += part[(size_t)b * G + g];
+        const double ne = (double)C * (double)Fb;
+        if (per_item) per_item[b] = Fb > 0 ? (float)(s / ne) : 0.f;
+        tot += s;                                             // (an item without frames wrote zeros)
+        cnt += ne;
+    }
+    tot = v2w_block_sum(tot, red);
+    cnt = v2w_block_sum(cnt, red);
+    if (threadIdx.x == 0 && total) total[0] = cnt > 0.0 ? (float)(tot / cnt) : 0.f;
+}
+
 inline bool ptr16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool ptr4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
@@ -312,6 +401,32 @@ extern "C" int v2w_l1_mean_multi_bwd(const v2w_l1_pair* pairs, int n, float scal
     for (int i = 0; i < n; ++i) any = any || A.it[i].da || A.it[i].db;
     if (!any) return V2W_E_ARG;
     V2W_LAUNCH(l1_multi_kernel<true>, dim3(A.starts[n]), dim3(kThreads), 0, (hipStream_t)stream, A, static_cast<double*>(nullptr));
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_l1_masked_plan(int C, int F) {
+    if (C <= 0 || F <= 0) return V2W_E_ARG;
+    const long long n = (long long)C * F;
+    if (n > 0x7fffffffll - 3) return V2W_E_SHAPE;
+    const long long g = ((n + 3) / 4 + kMaskedUnitsPerWg - 1) / kMaskedUnitsPerWg;
+    return g < 1 ? 1 : (g > kMaskedMaxWgs ? kMaskedMaxWgs : (int)g);
+}
+
+extern "C" int v2w_l1_masked(const float* a, const float* b, int B, int C, int F, const int32_t* len, int len_mul, int hop, int n_fft,
+                             float* per_item, float* total, void* ws, void* stream) {
+    if (!a || !b || !len || !ws || (!per_item && !total) || B <= 0 || len_mul < 1 || hop < 1 || n_fft < hop || n_fft % hop || (n_fft - hop) % 2)
+        return V2W_E_ARG;
+    if (!ptr4(a) || !ptr4(b) || (reinterpret_cast<uintptr_t>(ws) & 7)) return V2W_E_ARG;
+    const int G = v2w_l1_masked_plan(C, F);
+    if (G < 0) return G;
+    if (B > 65535) return V2W_E_SHAPE;                        // (grid.y)
+    hipStream_t st = (hipStream_t)stream;
+    double* part = static_cast<double*>(ws);
+    if (F % 4 == 0 && ptr16(a) && ptr16(b))
+        V2W_LAUNCH(l1_masked_kernel<true>, dim3(G, B), dim3(kThreads), 0, st, a, b, len, len_mul, hop, n_fft, C, F, part);
+    else
+        V2W_LAUNCH(l1_masked_kernel<false>, dim3(G, B), dim3(kThreads), 0, st, a, b, len, len_mul, hop, n_fft, C, F, part);
+    V2W_LAUNCH(l1_masked_finish_kernel, dim3(1), dim3(kThreads), 0, st, part, len, len_mul, hop, n_fft, B, C, F, G, per_item, total);
     return v2w_launch_status();
 }
 

@@ -122,6 +122,86 @@ mel_phase_bwd_kernel(const float* __restrict__ dxp, float* __restrict__ dy, int 
     }
 }
 
+// ---- batches of unequal lengths (forward only): item b holds Lb = min(len[b] * len_mul, L) samples
+__device__ __forceinline__ int mel_item_samples(const int32_t* __restrict__ len, int b, int len_mul, int L) {
+    const long long n = (long long)len[b] * len_mul;
+    return n < 0 ? 0 : (n > L ? L : (int)n);
+}
+// frames of an item of Lb samples: reflect padding needs Lb > pad, one frame needs Lb + 2 pad >= n_fft
+__device__ __forceinline__ int mel_item_frames(int Lb, int hop, int pad, int n_fft) {
+    return (Lb > pad && Lb + 2 * pad >= n_fft) ? (Lb + 2 * pad - n_fft) / hop + 1 : 0;
+}
+
+// mel_phase_kernel with the reflection about the item's own last sample; 0 from column roundup4(F_b + k - 1) on (the FP of the item's own
+// B = 1 call; no frame of the item reads further) and past the padded item.  Every load index s satisfies 0 <= s < Lb.
+__global__ void __launch_bounds__(256)
+mel_phase_len_kernel(const float* __restrict__ y, float* __restrict__ xp, const int32_t* __restrict__ len, int len_mul,
+                     int L, int hop, int pad, int FP) {
+    const int b = blockIdx.y;
+    const int Lb = mel_item_samples(len, b, len_mul, L);
+    const int n_fft = 2 * pad + hop;
+    const int Fb = mel_item_frames(Lb, hop, pad, n_fft);
+    const int Lp = Fb > 0 ? Lb + 2 * pad : 0;
+    const int FPb = Fb > 0 ? (Fb + n_fft / hop - 1 + 3) / 4 * 4 : 0;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < hop * FP; idx += gridDim.x * 256) {
+        const int p = idx / FP, f = idx - p * FP;
+        const int i = f * hop + p;
+        float v = 0.f;
+        if (f < FPb && i < Lp) {
+            int s = i - pad;
+            s = s < 0 ? -s : (s >= Lb ? 2 * (Lb - 1) - s : s);   // -s <= pad < Lb;  2(Lb-1) - s >= Lb - 1 - pad >= 0
+            v = y[(size_t)b * L + s];
+        }
+        xp[((size_t)b * hop + p) * FP + f] = v;
+    }
+}
+
+// mel_finish_kernel for the first Fb frames of item b (the same operations in the same order); 0.0 in the frames [Fb, F)
+__global__ void __launch_bounds__(256)
+mel_finish_len_kernel(const float* __restrict__ spec, const float* __restrict__ basis, float* __restrict__ out,
+                      const int32_t* __restrict__ len, int len_mul, int hop, int n_fft,
+                      int Cs, int FP, int F, int nb, int n_mels) {
+    extern __shared__ float mag[];                     // [nb][V2W_MEL_FT]
+    const int b = blockIdx.y, f0 = blockIdx.x * V2W_MEL_FT;
+    const int pad = (n_fft - hop) / 2;
+    const long long n = (long long)len[b] * len_mul;
+    const long long nmax = (long long)F * hop + n_fft;                      // (more samples than F frames need)
+    int Fb = mel_item_frames((int)(n < 0 ? 0 : (n > nmax ? nmax : n)), hop, pad, n_fft);
+    Fb = Fb < F ? Fb : F;
+    if (f0 >= Fb) {                                    // (uniform over the workgroup) nothing of the item here: zeros, spec unread
+        for (int idx = threadIdx.x; idx < n_mels * V2W_MEL_FT; idx += 256) {
+            const int m = idx / V2W_MEL_FT, f = f0 + idx % V2W_MEL_FT;
+            if (f < F) out[((size_t)b * n_mels + m) * F + f] = 0.f;
+        }
+        return;
+    }
+    const float* sb = spec + (size_t)b * Cs * FP;
+    for (int idx = threadIdx.x; idx < nb * V2W_MEL_FT; idx += 256) {
+        const int c = idx / V2W_MEL_FT, ff = idx - c * V2W_MEL_FT;
+        const int f = f0 + ff;
+        float m = 0.f;
+        if (f < Fb) {
+            const float re = sb[(size_t)c * FP + f], im = sb[(size_t)(nb + c) * FP + f];
+            m = sqrtf(re * re + im * im + 1e-9f);
+        }
+        mag[idx] = m;
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < n_mels * V2W_MEL_FT; idx += 256) {
+        const int m = idx / V2W_MEL_FT, ff = idx - m * V2W_MEL_FT;
+        const int f = f0 + ff;
+        if (f >= F) continue;
+        float v = 0.f;
+        if (f < Fb) {
+            const float* br = basis + (size_t)m * nb;
+            float acc = 0.f;
+            for (int c = 0; c < nb; ++c) acc = fmaf(br[c], mag[c * V2W_MEL_FT + ff], acc);
+            v = logf(fmaxf(acc, 1e-5f));
+        }
+        out[((size_t)b * n_mels + m) * F + f] = v;
+    }
+}
+
 }  // namespace
 
 // y (B, L) -> xp (B, hop, FP); FP >= F + n_fft/hop - 1 frames columns (F = number of STFT frames), pad = (n_fft - hop)/2.
@@ -143,6 +223,26 @@ extern "C" int v2w_mel_finish(const float* spec, const float* basis, float* out,
     return v2w_launch_status();
 }
 
+// The two ends with per-item lengths (include/vec2wav_hip.h): len a device array of B int32, item b holds min(len[b] * len_mul, L) samples.
+extern "C" int v2w_mel_phases_len(const float* y, float* xp, int B, int L, int hop, int pad, int FP, const int32_t* len, int len_mul,
+                                  void* stream) {
+    if (!y || !xp || !len || len_mul < 1 || B <= 0 || L <= 1 || hop <= 0 || pad < 0 || pad >= L || FP <= 0 || (2 * pad) % hop) return V2W_E_ARG;
+    if ((long long)hop * FP > 0x7fffffffll) return V2W_E_SHAPE;
+    int gx = (hop * FP + 255) / 256; if (gx > 1024) gx = 1024;
+    V2W_LAUNCH(mel_phase_len_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, y, xp, len, len_mul, L, hop, pad, FP);
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_mel_finish_len(const float* spec, const float* basis, float* out, int B, int Cs, int FP, int F, int nb, int n_mels,
+                                  const int32_t* len, int len_mul, int hop, int n_fft, void* stream) {
+    if (!spec || !basis || !out || B <= 0 || F <= 0 || FP < F || nb <= 0 || Cs < 2 * nb || n_mels <= 0) return V2W_E_ARG;
+    if (!len || len_mul < 1 || hop < 1 || n_fft < hop || n_fft % hop || (n_fft - hop) % 2) return V2W_E_ARG;
+    const size_t lds = (size_t)nb * V2W_MEL_FT * sizeof(float);
+    if (lds > 64 * 1024) return V2W_E_SHAPE;
+    V2W_LAUNCH(mel_finish_len_kernel, dim3((F + V2W_MEL_FT - 1) / V2W_MEL_FT, B), dim3(256), lds, (hipStream_t)stream,
+                       spec, basis, out, len, len_mul, hop, n_fft, Cs, FP, F, nb, n_mels);
+    return v2w_launch_status();
+}
 
 // Backward of v2w_mel_finish: gout (B, n_mels, F) -> dspec (B, Cs, FP), which the caller zero-fills (pad rows / frames stay 0).
 // basisT (nb, n_mels) is the transposed filterbank.
