@@ -736,6 +736,58 @@ typedef struct {
 int v2w_adamw_multi_plan(const v2w_adamw_item* items, int n, int32_t* starts);
 int v2w_adamw_multi(const v2w_adamw_item* items, int n, const v2w_adamw_hyper* h, void* stream);
 
+/* ---- Global-norm gradient clipping and the non-finite guard (additive in ABI v35; torch.nn.utils.clip_grad_norm_ with norm_type 2, and
+ * an AdamW step that takes the clip coefficient from DEVICE memory): one streaming launch over up to V2W_ADAMW_MAX_ITEMS gradient
+ * tensors, one finishing launch, and the coefficient consumed by the step's kernel - no gradient is rewritten, the host reads nothing.
+ * The descriptors are the AdamW ones, HOST memory read before the call returns, and so is the work split: v2w_adamw_multi_plan's units,
+ * chunk and starts[], 16-byte accesses for an item whose pointers share their 16-byte phase and float-by-float ones otherwise.  For the
+ * two entries that touch g only (sumsq, scale) the plan is taken of the item with p = m = v = g: the phase is g's own, every item takes
+ * 16-byte accesses, and p, m, v are neither read nor checked.  No atomics, no library state; every value below that leaves a kernel
+ * leaves it through an ordinary vector store.
+ *
+ *   v2w_grad_sumsq_partials (host only)  the workgroups W of the sumsq launch for these items (> 0) = the floats it writes: the return
+ *       value of v2w_adamw_multi_plan for the items with p = m = v = g.
+ *   v2w_grad_sumsq_multi  partials[w] = sum of g^2 over the chunk of workgroup w, for w in [0, W); nothing else is written.  A list of
+ *       more than V2W_ADAMW_MAX_ITEMS tensors is several calls into consecutive ranges of one caller-owned buffer.
+ *       Order (fixed: the same call gives the same bits): thread t of 256 takes the units t, t + 256, ... of the chunk in that order
+ *       and the four floats of a unit in index order, acc = fma(x, x, acc) from acc = 0 (masked floats enter as 0): a chain of
+ *       T = 4 * ceil(chunk_i / 256) roundings at most, chunk_i = ceil(units_i / workgroups_i) <= the plan's chunk; then the block sum
+ *       of 4 waves (v2w_sn's: a butterfly of 6 additions over the 64 lanes, then the waves' sums in wave order), 6 + 4 roundings.
+ *   v2w_grad_norm_finish  one workgroup; thread t adds the partials [t * c, (t + 1) * c), c = ceil(n_partials / 256), in index order in
+ *       fp64, the 256 sums go through the same block sum in fp64: S.  Thread 0 writes
+ *         out[0] = (float)sqrt(S)                                     the total L2 norm
+ *         out[1] = (float)min(1, max_norm / (sqrt(S) + 1e-6))         the clip coefficient, in fp64 and rounded once (torch's formula: 1 for
+ *                                                                     max_norm = +inf and a finite norm; NaN passes through the min)
+ *         out[2] = 1.0 when (float)sqrt(S) is finite, else 0.0
+ *         out[3] = out[3] + (1 - out[2])                              a running count of non-finite norms: read, incremented, written back.
+ *       `out` is the caller's (4 floats, 4-byte aligned; the count starts from whatever the caller put there).
+ *   v2w_scale_multi       g[e] = g[e] * coef[0] for every element, ONE fp32 multiplication each, the coefficient read from DEVICE memory
+ *       by the kernel: a coefficient of exactly 1.0 leaves every bit as it was (no branch on it anywhere).
+ *   v2w_adamw_multi_clipped  v2w_adamw_multi with g replaced by g' = g * clip[1] (ONE fp32 multiplication, ahead of the list of operations
+ *       above; g itself is only read).  clip: the 4 floats v2w_grad_norm_finish wrote, DEVICE memory read by the kernel.  With
+ *       skip_nonfinite != 0 and clip[2] == 0 every workgroup returns before its first load: p, m and v keep their bits.  With
+ *       clip[1] == 1.0 the step's bits are v2w_adamw_multi's.  The same kernel body as v2w_adamw_multi, compiled a second time.
+ *
+ * Bounds, u = 2^-24, to first order, against the exact value from the same fp32 inputs.
+ *   Sum of squares: every term is >= 0, so the relative errors of a chain add up: |partial - exact| <= (T + 10) u * exact, and the fp64
+ *       sum S inherits it (its own roundings are 2^-29 of u each).  The norm is a square root - half the relative error - and one
+ *       rounding to fp32:   |out[0] - exact norm| <= ((T + 10) / 2 + 1) u * norm.   At the generator's parameter list (chunk 2048, T = 32)
+ *       that is 22 u.  The coefficient, where it is below 1, has the norm's relative error and its own rounding: (T + 10) / 2 + 2.
+ *       A square overflows fp32 for |g| > 1.8e19: such a gradient reads as a non-finite norm.
+ *   Clipped step, against the AdamW formula evaluated exactly at g clip[1]: one more rounding on g' wherever g enters -
+ *       4 roundings on m' (was 3), 6 on v' (was 4: g' enters twice), 18 on p' (was 15), on the same magnitudes taken at g':
+ *       |m' - exact| <= 4u (|m| + |g'|),   |v' - exact| <= 6u (|v| + g' g'),   |p' - exact| <= 18u (|p| + step (|m| + |g'|) / den)
+ *   tests/clip_ref.py restates both in fp64.
+ *
+ * V2W_E_ARG: items NULL; n < 1 or n > V2W_ADAMW_MAX_ITEMS; numel <= 0; g (sumsq, scale) or any of p, g, m, v (clipped step: every check of
+ * v2w_adamw_multi) NULL or not 4-byte aligned; partials, coef, clip or out NULL or not 4-byte aligned; n_partials < 1; max_norm negative
+ * or NaN.  V2W_E_SHAPE: numel > 2^42. */
+int v2w_grad_sumsq_partials(const v2w_adamw_item* items, int n);
+int v2w_grad_sumsq_multi(const v2w_adamw_item* items, int n, float* partials, void* stream);
+int v2w_grad_norm_finish(const float* partials, int n_partials, float max_norm, float* out, void* stream);
+int v2w_scale_multi(const v2w_adamw_item* items, int n, const float* coef, void* stream);
+int v2w_adamw_multi_clipped(const v2w_adamw_item* items, int n, const v2w_adamw_hyper* h, const float* clip, int skip_nonfinite, void* stream);
+
 /* ---- Spectral norm of conv weights (additive in ABI v35; legacy torch.nn.utils.spectral_norm as models.py:219-258 applies it to the first
  * DiscriminatorS: one power iteration per training forward, W / sigma): up to V2W_SN_MAX_LAYERS weight matrices per call, the step in 4
  * launches (2 without the iteration), its backward in 2, whatever the number of layers.  Nothing is allocated, no state is kept.

@@ -2,10 +2,12 @@
 """One full vec2wav GAN training iteration as vec2wav/train.py:160-215 runs it - generator forward, mel of the generated audio,
 discriminator step (MPD + MSD on y and y_g_hat.detach(), backward, AdamW), generator step (MPD + MSD again, feature / LSGAN /
 L1-mel losses, backward through the discriminators, the mel and the generator, AdamW) - entirely on the HIP path.
-argv: B T steps [stock] [frozen] [optim=hip|optim=torch] [sn=torch]   ('stock': the discriminators as stock torch.nn conv stacks (MIOpen + torch autograd) for comparison;
+argv: B T steps [stock] [frozen] [optim=hip|optim=torch] [clip|torchclip] [sn=torch]   ('stock': the discriminators as stock torch.nn conv stacks (MIOpen + torch autograd) for comparison;
 'frozen': `with discriminators.frozen(mpd, msd)` around the G step's discriminator forwards - same trajectory, no wasted D gradients;
 'sn=torch': discriminators.NATIVE_SN = False - the spectral norm of the first scale discriminator on torch's mv / normalize / dot / outer, the
-behaviour before the v2w_sn_* entry points; 'optim=hip': both optimizers are wavthruvec_pytorch_amd.AdamW, the library's multi-tensor kernel - the default 'optim=torch' is torch.optim.AdamW)"""
+behaviour before the v2w_sn_* entry points; 'optim=hip': both optimizers are wavthruvec_pytorch_amd.AdamW, the library's multi-tensor kernel - the default 'optim=torch' is torch.optim.AdamW;
+'clip' (with optim=hip): both are AdamW(max_grad_norm=1000.0), the global-norm clip inside the step; 'torchclip': torch.nn.utils.clip_grad_norm_(parameters, 1000.0)
+ahead of each plain step, inside its timed events; default: no clipping)"""
 import contextlib
 import os
 import sys
@@ -106,16 +108,25 @@ def main():
             g.precision = 'f16x3'
     hipopt = 'optim=hip' in sys.argv[4:]   # optim=hip: wavthruvec_pytorch_amd.AdamW (the library's multi-tensor kernel); optim=torch (default): torch's
     Opt = AdamW if hipopt else torch.optim.AdamW
-    optim_g = Opt(g.parameters(), 2e-4, betas=(0.8, 0.99))
-    optim_d = Opt(list(mpd.parameters()) + list(msd.parameters()), 2e-4, betas=(0.8, 0.99))
+    clip, torchclip = 'clip' in sys.argv[4:], 'torchclip' in sys.argv[4:]
+    if clip and not hipopt:
+        raise SystemExit("'clip' needs optim=hip")
+    okw = dict(max_grad_norm=1000.0) if clip else {}
+    optim_g = Opt(g.parameters(), 2e-4, betas=(0.8, 0.99), **okw)
+    optim_d = Opt(list(mpd.parameters()) + list(msd.parameters()), 2e-4, betas=(0.8, 0.99), **okw)
     opt_events = {'optim_d.step()': [], 'optim_g.step()': []}
+
+    def step(opt):
+        if torchclip:
+            torch.nn.utils.clip_grad_norm_([p for grp in opt.param_groups for p in grp['params']], 1000.0)
+        opt.step()
 
     def timed_step(opt, name, timed):
         if not timed:
-            return opt.step()
+            return step(opt)
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        opt.step()
+        step(opt)
         b.record()
         opt_events[name].append((a, b))
     inp = synthetic.make_inputs(h, B, T, seed=1, device=dev)

@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Forward + backward time of the generator at cfg2 (the generator half of a vec2wav/train.py step).
-argv: B T steps precision loss optimizer   (loss 'sum' = a weighted sum of the waveform; 'mel' = train.py:172-174,204's
+argv: B T steps precision loss optimizer [clip|torchclip]   (loss 'sum' = a weighted sum of the waveform; 'mel' = train.py:172-174,204's
 F.l1_loss(y_mel, mel_spectrogram(y_g_hat)) * 45 through the HIP mel_spectrogram and its backward; optimizer 'torch' (default) =
-torch.optim.AdamW, 'hip' = wavthruvec_pytorch_amd.AdamW, the library's multi-tensor kernel)."""
+torch.optim.AdamW, 'hip' = wavthruvec_pytorch_amd.AdamW, the library's multi-tensor kernel; 'clip' (with 'hip' only) =
+AdamW(max_grad_norm=1000.0), the global-norm clip inside the step; 'torchclip' = torch.nn.utils.clip_grad_norm_(parameters, 1000.0) ahead
+of the plain step of the chosen optimizer, inside the timed events; default: no clipping)."""
 import os
 import sys
 import time
@@ -26,7 +28,12 @@ def main():
     opt_kind = sys.argv[6] if len(sys.argv) > 6 else 'torch'
     if opt_kind not in ('torch', 'hip'):
         raise SystemExit(f"optimizer must be 'torch' or 'hip', got {opt_kind!r}")
-    opt = (AdamW if opt_kind == 'hip' else torch.optim.AdamW)(g.parameters(), 2e-4, betas=(0.8, 0.99))
+    clip_kind = sys.argv[7] if len(sys.argv) > 7 else ''
+    if clip_kind not in ('', 'clip', 'torchclip') or (clip_kind == 'clip' and opt_kind != 'hip'):
+        raise SystemExit(f"the seventh argument is 'clip' (optimizer 'hip' only) or 'torchclip', got {clip_kind!r} with optimizer {opt_kind!r}")
+    opt = (AdamW if opt_kind == 'hip' else torch.optim.AdamW)(g.parameters(), 2e-4, betas=(0.8, 0.99),
+                                                              **(dict(max_grad_norm=1000.0) if clip_kind == 'clip' else {}))
+    params = list(g.parameters())
     ev = []                       # (start, end) events around every timed opt.step()
     inp = synthetic.make_inputs(h, B, T, seed=1, device=dev)
     dy = torch.randn(B, 1, T * 320, device=dev)
@@ -45,6 +52,8 @@ def main():
         if it >= 2:
             ev.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
             ev[-1][0].record()
+        if clip_kind == 'torchclip':
+            torch.nn.utils.clip_grad_norm_(params, 1000.0)
         opt.step()
         if it >= 2:
             ev[-1][1].record()
@@ -58,8 +67,9 @@ def main():
             g(*inp)
         torch.cuda.synchronize()
         df = (time.perf_counter() - t1) / steps
+    opt_label = opt_kind + (' + ' + clip_kind if clip_kind else '')
     print(f'B={B} T={T} loss={loss_kind} {g.precision}: forward+backward+AdamW {dt * 1e3:.2f} ms/step ; inference-schedule forward {df * 1e3:.2f} ms ; '
-          f'{B * T * 320 / dt / 1e6:.1f} M samples/s trained ; optimizer {opt_kind}: step() {d_opt:.3f} ms (events)')
+          f'{B * T * 320 / dt / 1e6:.1f} M samples/s trained ; optimizer {opt_label}: step() {d_opt:.3f} ms (events)')
 
 
 if __name__ == '__main__':

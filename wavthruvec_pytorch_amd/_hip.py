@@ -258,6 +258,12 @@ SIGNATURES = {
     # AdamW: host descriptor array and hyperparameters, read before the call returns
     'v2w_adamw_multi_plan': (C.c_int, [C.POINTER(AdamWItem), C.c_int, C.POINTER(C.c_int32)]),
     'v2w_adamw_multi': (C.c_int, [C.POINTER(AdamWItem), C.c_int, C.POINTER(AdamWHyper), _fp]),
+    # global-norm clipping and the non-finite guard: the AdamW descriptors; partials / out / coef / clip are DEVICE memory
+    'v2w_grad_sumsq_partials': (C.c_int, [C.POINTER(AdamWItem), C.c_int]),
+    'v2w_grad_sumsq_multi': (C.c_int, [C.POINTER(AdamWItem), C.c_int, _fp, _fp]),
+    'v2w_grad_norm_finish': (C.c_int, [_fp, C.c_int, C.c_float, _fp, _fp]),
+    'v2w_scale_multi': (C.c_int, [C.POINTER(AdamWItem), C.c_int, _fp, _fp]),
+    'v2w_adamw_multi_clipped': (C.c_int, [C.POINTER(AdamWItem), C.c_int, C.POINTER(AdamWHyper), _fp, C.c_int, _fp]),
     # spectral norm: DEVICE descriptors (planned on the host copy), host grids and host pointer arrays, read before the call returns
     'v2w_sn_plan': (C.c_longlong, [C.POINTER(SnDesc), C.c_int, C.POINTER(SnGrids)]),
     'v2w_sn_step': (C.c_int, [_fp, C.c_int, C.c_int, C.POINTER(SnGrids), _fp, _fp, C.c_longlong, _fp]),

@@ -9,6 +9,11 @@
 // units (the parameter sizes of one call span six orders of magnitude), at least one per tensor, about V2W_ADAMW_TARGET_WGS in all:
 // starts[i] is the first workgroup of tensor i, found from blockIdx.x by a search every lane makes alike.  The plan depends on the
 // descriptors only.  Every element of p, m and v is written exactly once, nothing else is written; no atomics, no LDS, no scratch.
+//
+// Global-norm clipping and the non-finite guard (include/vec2wav_hip.h, v2w_grad_sumsq_multi and its neighbours) ride on the same table and
+// plan: grad_sumsq_kernel writes one fp32 sum of squares per workgroup (fixed order, no atomics), grad_norm_finish_kernel adds them in fp64
+// and leaves norm, clip coefficient, finite flag and a running count in four floats of the caller's, grad_scale_kernel is g *= coef[0], and
+// adamw_multi_clipped_kernel is the step's body compiled with g * clip[1] for g - the coefficient never visits the host.
 #include "v2w_common.h"
 
 namespace {
@@ -56,33 +61,56 @@ __device__ __forceinline__ void store_unit(float* q, f32x4 x, int e0, int e1, bo
         if (j >= e0 && j < e1) q[j] = x[j];
 }
 
-__global__ void __launch_bounds__(kThreads)
-adamw_multi_kernel(const AdamWArgs A) {
-    const int wg = blockIdx.x;
+// the chunk of workgroup wg: its tensor, and units [u0, u0 + cnt) of it
+struct Span {
+    int item;
+    long long numel, base;      // base: element index of the first float of unit u0 (negative inside a partial first unit)
+    unsigned cnt;
+    bool vec;
+};
+__device__ __forceinline__ Span find_span(const AdamWArgs& A, int wg) {
     int lo = 0, hi = A.n;
     while (hi - lo > 1) {                                 // the tensor of this workgroup: starts[lo] <= wg < starts[lo + 1]
         const int mid = (lo + hi) >> 1;
         if (A.starts[mid] <= wg) lo = mid; else hi = mid;
     }
     const v2w_adamw_item& it = A.it[lo];
-    const long long numel = it.numel;
-    const bool vec = same_phase(it);
-    const int shift = vec ? phase16(it.p) : 0;
-    const long long units = (numel + shift + 3) >> 2;
+    Span s;
+    s.item = lo;
+    s.numel = it.numel;
+    s.vec = same_phase(it);
+    const int shift = s.vec ? phase16(it.p) : 0;
+    const long long units = (s.numel + shift + 3) >> 2;
     const int nwg = A.starts[lo + 1] - A.starts[lo];
     const long long chunk = (units + nwg - 1) / nwg;
     const long long u0 = (long long)(wg - A.starts[lo]) * chunk;
     const long long u1 = u0 + chunk < units ? u0 + chunk : units;
-    const unsigned cnt = u1 > u0 ? (unsigned)(u1 - u0) : 0u;
+    s.cnt = u1 > u0 ? (unsigned)(u1 - u0) : 0u;
     // unit u holds elements [4u - shift, 4u - shift + 4) of the tensor; the floats before element 0 and past numel are masked
-    const long long base = (u0 << 2) - shift;
-    float* p = it.p + base;
-    const float* g = it.g + base;
-    float* m = it.m + base;
-    float* v = it.v + base;
+    s.base = (u0 << 2) - shift;
+    return s;
+}
+// the floats [e0, e1) of unit t of the span that belong to the tensor (none for t >= cnt)
+__device__ __forceinline__ void unit_mask(const Span& s, unsigned t, size_t off, int& e0, int& e1) {
+    const long long pos = s.base + (long long)off;                    // element index of the unit's first float
+    e0 = pos < 0 ? (int)-pos : 0;
+    e1 = s.numel - pos < 4 ? (int)(s.numel - pos) : 4;
+    if (t >= s.cnt) e0 = e1 = 0;
+}
+
+// CLIP: the step on g * coef (include/vec2wav_hip.h, v2w_adamw_multi_clipped); otherwise coef is not looked at
+template <bool CLIP>
+__device__ __forceinline__ void adamw_body(const AdamWArgs& A, float coef) {
+    const Span s = find_span(A, blockIdx.x);
+    const v2w_adamw_item& it = A.it[s.item];
+    const bool vec = s.vec;
+    float* p = it.p + s.base;
+    const float* g = it.g + s.base;
+    float* m = it.m + s.base;
+    float* v = it.v + s.base;
     const Coef c = A.c;
 
-    for (unsigned t0 = threadIdx.x; t0 < cnt; t0 += kThreads * kUnroll) {
+    for (unsigned t0 = threadIdx.x; t0 < s.cnt; t0 += kThreads * kUnroll) {
         f32x4 xp[kUnroll], xg[kUnroll], xm[kUnroll], xv[kUnroll];
         size_t off[kUnroll];
         int e0[kUnroll], e1[kUnroll];
@@ -90,10 +118,7 @@ adamw_multi_kernel(const AdamWArgs A) {
         for (int k = 0; k < kUnroll; ++k) {
             const unsigned t = t0 + k * kThreads;
             off[k] = (size_t)t << 2;
-            const long long pos = base + (long long)off[k];           // element index of the unit's first float
-            e0[k] = pos < 0 ? (int)-pos : 0;
-            e1[k] = numel - pos < 4 ? (int)(numel - pos) : 4;
-            if (t >= cnt) e0[k] = e1[k] = 0;
+            unit_mask(s, t, off[k], e0[k], e1[k]);
             xp[k] = load_unit(p + off[k], e0[k], e1[k], vec);
             xg[k] = load_unit(g + off[k], e0[k], e1[k], vec);
             xm[k] = load_unit(m + off[k], e0[k], e1[k], vec);
@@ -104,10 +129,11 @@ adamw_multi_kernel(const AdamWArgs A) {
             f32x4 np, nm, nv;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {                              // include/vec2wav_hip.h: one fp32 rounding per line
+                const float gj = CLIP ? __fmul_rn(xg[k][j], coef) : xg[k][j];
                 const float pd = __fmul_rn(xp[k][j], c.decay);
-                const float d = __fsub_rn(xg[k][j], xm[k][j]);
+                const float d = __fsub_rn(gj, xm[k][j]);
                 nm[j] = __fmaf_rn(c.omb1, d, xm[k][j]);
-                const float gg = __fmul_rn(xg[k][j], xg[k][j]);
+                const float gg = __fmul_rn(gj, gj);
                 const float tg = __fmul_rn(c.omb2, gg);
                 nv[j] = __fmaf_rn(c.beta2, xv[k][j], tg);
                 const float den = __fmaf_rn(__fsqrt_rn(nv[j]), c.rbc2, c.eps);
@@ -118,6 +144,92 @@ adamw_multi_kernel(const AdamWArgs A) {
             store_unit(m + off[k], nm, e0[k], e1[k], vec);
             store_unit(v + off[k], nv, e0[k], e1[k], vec);
         }
+    }
+}
+
+__global__ void __launch_bounds__(kThreads)
+adamw_multi_kernel(const AdamWArgs A) { adamw_body<false>(A, 1.f); }
+
+// clip: the four floats of v2w_grad_norm_finish; a skipped step returns before the first load (the branch is uniform over the launch)
+__global__ void __launch_bounds__(kThreads)
+adamw_multi_clipped_kernel(const AdamWArgs A, const float* __restrict__ clip, int skip_nonfinite) {
+    if (skip_nonfinite && clip[2] == 0.f) return;
+    adamw_body<true>(A, clip[1]);
+}
+
+// partials[wg] = sum of g^2 over the workgroup's chunk: per thread one fma chain over its units in order, then the fixed block sum.
+// The items arrive with p = m = v = g: every span takes the 16-byte path.
+__global__ void __launch_bounds__(kThreads)
+grad_sumsq_kernel(const AdamWArgs A, float* __restrict__ partials) {
+    __shared__ float red[16];
+    const Span s = find_span(A, blockIdx.x);
+    const float* g = A.it[s.item].g + s.base;
+    float acc = 0.f;
+    for (unsigned t0 = threadIdx.x; t0 < s.cnt; t0 += kThreads * kUnroll) {
+        f32x4 x[kUnroll];
+#pragma unroll
+        for (int k = 0; k < kUnroll; ++k) {
+            const unsigned t = t0 + k * kThreads;
+            const size_t off = (size_t)t << 2;
+            int e0, e1;
+            unit_mask(s, t, off, e0, e1);
+            x[k] = load_unit(g + off, e0, e1, s.vec);
+        }
+#pragma unroll
+        for (int k = 0; k < kUnroll; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc = __fmaf_rn(x[k][j], x[k][j], acc);
+    }
+    const float sum = v2w_block_sum(acc, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = sum;
+}
+
+// g *= coef[0], every element once
+__global__ void __launch_bounds__(kThreads)
+grad_scale_kernel(const AdamWArgs A, const float* __restrict__ coef) {
+    const Span s = find_span(A, blockIdx.x);
+    float* g = const_cast<float*>(A.it[s.item].g) + s.base;
+    const float c = coef[0];
+    for (unsigned t0 = threadIdx.x; t0 < s.cnt; t0 += kThreads * kUnroll) {
+        f32x4 x[kUnroll];
+        size_t off[kUnroll];
+        int e0[kUnroll], e1[kUnroll];
+#pragma unroll
+        for (int k = 0; k < kUnroll; ++k) {
+            const unsigned t = t0 + k * kThreads;
+            off[k] = (size_t)t << 2;
+            unit_mask(s, t, off[k], e0[k], e1[k]);
+            x[k] = load_unit(g + off[k], e0[k], e1[k], s.vec);
+        }
+#pragma unroll
+        for (int k = 0; k < kUnroll; ++k) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) x[k][j] = __fmul_rn(x[k][j], c);
+            store_unit(g + off[k], x[k], e0[k], e1[k], s.vec);
+        }
+    }
+}
+
+// include/vec2wav_hip.h, v2w_grad_norm_finish: thread t adds its run of partials in index order, the 256 sums take the fixed block sum
+__global__ void __launch_bounds__(kThreads)
+grad_norm_finish_kernel(const float* __restrict__ partials, int n, float max_norm, float* out) {
+    __shared__ double red[16];
+    const int per = (n + kThreads - 1) / kThreads;
+    const int k0 = threadIdx.x * per, k1 = k0 + per < n ? k0 + per : n;
+    double acc = 0.0;
+    for (int k = k0; k < k1; ++k) acc += (double)partials[k];
+    const double S = v2w_block_sum(acc, red);
+    if (threadIdx.x == 0) {
+        const double nrm = sqrt(S);
+        const float nf = (float)nrm;
+        double c = (double)max_norm / (nrm + 1e-6);
+        c = c > 1.0 ? 1.0 : c;                                         // a NaN stays one, as under torch.clamp
+        const float fin = __builtin_isfinite(nf) ? 1.f : 0.f;
+        const float count = out[3];
+        out[0] = nf;
+        out[1] = (float)c;
+        out[2] = fin;
+        out[3] = count + (1.f - fin);
     }
 }
 
@@ -172,6 +284,25 @@ int adamw_coef(const v2w_adamw_hyper* h, Coef* c) {
     return 0;
 }
 
+// the table of the launches that touch g only: every item with p = m = v = g (the plan then counts g's own phase and every span takes
+// 16-byte accesses); only g and numel of the caller's items are looked at
+int grad_args(const v2w_adamw_item* items, int n, AdamWArgs* A) {
+    if (!items || n < 1 || n > V2W_ADAMW_MAX_ITEMS) return V2W_E_ARG;
+    long long units[V2W_ADAMW_MAX_ITEMS];
+    for (int i = 0; i < n; ++i) {
+        if (!ptr4(items[i].g) || items[i].numel <= 0) return V2W_E_ARG;
+        if (items[i].numel > (kMaxUnits << 2)) return V2W_E_SHAPE;
+        float* g = const_cast<float*>(items[i].g);
+        A->it[i] = v2w_adamw_item{g, g, g, g, items[i].numel};
+        units[i] = item_units(A->it[i]);
+        if (units[i] > kMaxUnits) return V2W_E_SHAPE;
+    }
+    adamw_plan(units, n, A->starts);
+    A->c = Coef{};
+    A->n = n;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int v2w_adamw_multi_plan(const v2w_adamw_item* items, int n, int32_t* starts) {
@@ -192,5 +323,55 @@ extern "C" int v2w_adamw_multi(const v2w_adamw_item* items, int n, const v2w_ada
     hipStream_t st = (hipStream_t)stream;
     if (v2w_dry(st)) return 0;
     V2W_LAUNCH(adamw_multi_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A);
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_adamw_multi_clipped(const v2w_adamw_item* items, int n, const v2w_adamw_hyper* h, const float* clip, int skip_nonfinite,
+                                       void* stream) {
+    AdamWArgs A;
+    long long units[V2W_ADAMW_MAX_ITEMS];
+    if (const int rc = adamw_items(items, n, units)) return rc;
+    if (const int rc = adamw_coef(h, &A.c)) return rc;
+    if (!ptr4(clip)) return V2W_E_ARG;
+    for (int i = 0; i < n; ++i) A.it[i] = items[i];
+    adamw_plan(units, n, A.starts);
+    A.n = n;
+    hipStream_t st = (hipStream_t)stream;
+    if (v2w_dry(st)) return 0;
+    V2W_LAUNCH(adamw_multi_clipped_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A, clip, skip_nonfinite);
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_grad_sumsq_partials(const v2w_adamw_item* items, int n) {
+    AdamWArgs A;
+    if (const int rc = grad_args(items, n, &A)) return rc;
+    return A.starts[n];
+}
+
+extern "C" int v2w_grad_sumsq_multi(const v2w_adamw_item* items, int n, float* partials, void* stream) {
+    AdamWArgs A;
+    if (const int rc = grad_args(items, n, &A)) return rc;
+    if (!ptr4(partials)) return V2W_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (v2w_dry(st)) return 0;
+    V2W_LAUNCH(grad_sumsq_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A, partials);
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_grad_norm_finish(const float* partials, int n_partials, float max_norm, float* out, void* stream) {
+    if (!ptr4(partials) || !ptr4(out) || n_partials < 1 || !(max_norm >= 0.f)) return V2W_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (v2w_dry(st)) return 0;
+    V2W_LAUNCH(grad_norm_finish_kernel, dim3(1), dim3(kThreads), 0, st, partials, n_partials, max_norm, out);
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_scale_multi(const v2w_adamw_item* items, int n, const float* coef, void* stream) {
+    AdamWArgs A;
+    if (const int rc = grad_args(items, n, &A)) return rc;
+    if (!ptr4(coef)) return V2W_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (v2w_dry(st)) return 0;
+    V2W_LAUNCH(grad_scale_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A, coef);
     return v2w_launch_status();
 }

@@ -1521,17 +1521,11 @@ def adamw_hyper(*, lr, betas, eps, weight_decay, step):
     return _hip.AdamWHyper(float(lr), b1, b2, float(eps), float(weight_decay), 1.0 - b1 ** step, (1.0 - b2 ** step) ** 0.5, 0)
 
 
-def adamw_multi(params, grads, exp_avgs, exp_avg_sqs, *, lr, betas, eps, weight_decay, step):
-    """One AdamW step (decoupled weight decay, no amsgrad) of every tensor of the lists, in place on params / exp_avgs / exp_avg_sqs:
-    ceil(n / ADAMW_MAX_ITEMS) launches on the current stream.  `step` is the number of THIS step (1 for the first).  fp32 GPU tensors on
-    one device; params and moments must be contiguous (they are written in place), a non-contiguous gradient is copied.  Returns the
-    number of launches.  The parameters' version counters are NOT bumped (the kernels write through raw pointers): optim.AdamW does."""
+def _adamw_array(params, grads, exp_avgs, exp_avg_sqs):
+    """(descriptors, the tensors they point into) of one AdamW call; fp32 GPU tensors on one device, a non-contiguous gradient is copied."""
     n = len(params)
     if not (n == len(grads) == len(exp_avgs) == len(exp_avg_sqs)):
         raise ValueError('params, grads, exp_avgs and exp_avg_sqs must have one entry per tensor')
-    if n == 0:
-        return 0
-    hyper = adamw_hyper(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, step=step)
     dev = params[0].device
     arr = (_hip.AdamWItem * n)()
     keep = []
@@ -1550,13 +1544,162 @@ def adamw_multi(params, grads, exp_avgs, exp_avg_sqs, *, lr, betas, eps, weight_
         keep += [p, g, m, v]
         d = arr[i]
         d.p, d.g, d.m, d.v, d.numel = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+    return arr, keep
+
+
+def _item_chunks(arr, n):
+    """(pointer to the first descriptor, count) of every run of at most ADAMW_MAX_ITEMS descriptors."""
+    for i0 in range(0, n, _hip.ADAMW_MAX_ITEMS):
+        yield C.cast(C.byref(arr, i0 * C.sizeof(_hip.AdamWItem)), C.POINTER(_hip.AdamWItem)), min(_hip.ADAMW_MAX_ITEMS, n - i0)
+
+
+def adamw_multi(params, grads, exp_avgs, exp_avg_sqs, *, lr, betas, eps, weight_decay, step):
+    """One AdamW step (decoupled weight decay, no amsgrad) of every tensor of the lists, in place on params / exp_avgs / exp_avg_sqs:
+    ceil(n / ADAMW_MAX_ITEMS) launches on the current stream.  `step` is the number of THIS step (1 for the first).  fp32 GPU tensors on
+    one device; params and moments must be contiguous (they are written in place), a non-contiguous gradient is copied.  Returns the
+    number of launches.  The parameters' version counters are NOT bumped (the kernels write through raw pointers): optim.AdamW does."""
+    n = len(params)
+    if not (n == len(grads) == len(exp_avgs) == len(exp_avg_sqs)):
+        raise ValueError('params, grads, exp_avgs and exp_avg_sqs must have one entry per tensor')
+    if n == 0:
+        return 0
+    hyper = adamw_hyper(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, step=step)
+    arr, keep = _adamw_array(params, grads, exp_avgs, exp_avg_sqs)
     launches = 0
-    with torch.cuda.device(dev):
+    with torch.cuda.device(keep[0].device):
         lib = _hip.load()
         stream = _stream(keep[0])
-        for i0 in range(0, n, _hip.ADAMW_MAX_ITEMS):
-            k = min(_hip.ADAMW_MAX_ITEMS, n - i0)
-            chunk = C.cast(C.byref(arr, i0 * C.sizeof(_hip.AdamWItem)), C.POINTER(_hip.AdamWItem))
+        for chunk, k in _item_chunks(arr, n):
             _hip.check(lib.v2w_adamw_multi(chunk, k, C.byref(hyper), stream), 'v2w_adamw_multi')
+            launches += 1
+    return launches
+
+
+# ---- global-norm clipping and the non-finite guard (include/vec2wav_hip.h: v2w_grad_sumsq_multi and its neighbours)
+def _clip_buffer(t, name, floats):
+    _chk(t, name)
+    if t.numel() < floats:
+        raise ValueError(f'{name} must hold {floats} floats, got {t.numel()}')
+
+
+def _grad_array(grads, in_place=False):
+    """(descriptors with g and numel set, the tensors they point into); fp32 GPU tensors on one device.  A non-contiguous gradient is
+    copied for reading; one that is to be written in place is refused."""
+    n = len(grads)
+    arr = (_hip.AdamWItem * max(n, 1))()
+    keep = []
+    for i, g in enumerate(grads):
+        g = g.detach()
+        if g.is_cuda and g.dtype == torch.float32 and not g.is_contiguous():
+            if in_place:
+                raise ValueError(f'grad[{i}] is not contiguous: it cannot be scaled in place')
+            g = g.contiguous()
+        _chk(g, f'grad[{i}]')
+        if g.device != grads[0].device:
+            raise RuntimeError('all gradients of one call must live on one device')
+        if g.numel() == 0:
+            raise ValueError(f'grad[{i}] is empty')
+        keep.append(g)
+        arr[i].g, arr[i].numel = g.data_ptr(), g.numel()
+    return arr, keep
+
+
+def _sumsq_partials(arr, n):
+    lib = _hip.load()
+    total = 0
+    for chunk, k in _item_chunks(arr, n):
+        w = lib.v2w_grad_sumsq_partials(chunk, k)
+        if w <= 0:
+            _hip.check(w or -1, 'v2w_grad_sumsq_partials')
+        total += w
+    return total
+
+
+def grad_sumsq_partials(grads):
+    """The floats grad_sumsq_multi writes for these gradients: the workgroups of its launches (host only)."""
+    if len(grads) == 0:
+        return 0
+    arr, _keep = _grad_array(grads)
+    return _sumsq_partials(arr, len(grads))
+
+
+def grad_sumsq_multi(grads, partials=None):
+    """Per-workgroup sums of squares of every gradient of the list: ceil(n / ADAMW_MAX_ITEMS) launches into consecutive ranges of
+    `partials` (fp32, GPU; allocated when None, otherwise it must hold grad_sumsq_partials(grads) floats - the rest of it is left
+    alone).  Returns (partials, count); deterministic, no atomics."""
+    n = len(grads)
+    if n == 0:
+        raise ValueError('no gradients')
+    arr, keep = _grad_array(grads)
+    dev = keep[0].device
+    with torch.cuda.device(dev):
+        lib = _hip.load()
+        count = _sumsq_partials(arr, n)
+        if partials is None:
+            partials = torch.empty((count,), device=dev, dtype=torch.float32)
+        _clip_buffer(partials, 'partials', count)
+        if partials.device != dev:
+            raise RuntimeError('partials must live on the gradients\' device')
+        stream = _stream(keep[0])
+        at = 0
+        for chunk, k in _item_chunks(arr, n):
+            _hip.check(lib.v2w_grad_sumsq_multi(chunk, k, partials.data_ptr() + 4 * at, stream), 'v2w_grad_sumsq_multi')
+            at += lib.v2w_grad_sumsq_partials(chunk, k)
+    return partials, count
+
+
+def grad_norm_finish(partials, count, max_norm, out=None):
+    """out[0] = the L2 norm the first `count` partials add up to, out[1] = min(1, max_norm / (norm + 1e-6)), out[2] = 1.0 when the norm
+    is finite else 0.0, out[3] += 1 - out[2]; one launch of one workgroup, nothing is read back.  `out`: 4 fp32 on the GPU (zeros when
+    None).  max_norm = inf gives the norm alone (coefficient 1)."""
+    count = int(count)
+    _clip_buffer(partials, 'partials', max(count, 1))
+    with torch.cuda.device(partials.device):
+        if out is None:
+            out = torch.zeros((4,), device=partials.device, dtype=torch.float32)
+        _clip_buffer(out, 'out', 4)
+        _hip.check(_hip.load().v2w_grad_norm_finish(partials.data_ptr(), count, float(max_norm), out.data_ptr(), _stream(partials)),
+                   'v2w_grad_norm_finish')
+    return out
+
+
+def scale_multi(grads, coef):
+    """g *= coef[0] in place for every gradient of the list, the coefficient read from GPU memory by the kernel (`coef`: fp32, at least
+    one element - e.g. grad_norm_finish(...)[1:]); ceil(n / ADAMW_MAX_ITEMS) launches.  A coefficient of exactly 1.0 changes no bit."""
+    n = len(grads)
+    if n == 0:
+        return 0
+    arr, keep = _grad_array(grads, in_place=True)
+    _clip_buffer(coef, 'coef', 1)
+    launches = 0
+    with torch.cuda.device(keep[0].device):
+        lib = _hip.load()
+        stream = _stream(keep[0])
+        for chunk, k in _item_chunks(arr, n):
+            _hip.check(lib.v2w_scale_multi(chunk, k, coef.data_ptr(), stream), 'v2w_scale_multi')
+            launches += 1
+    return launches
+
+
+def adamw_multi_clipped(params, grads, exp_avgs, exp_avg_sqs, clip, *, skip_nonfinite=False, lr, betas, eps, weight_decay, step):
+    """adamw_multi on g * clip[1], `clip` the four floats of grad_norm_finish on the GPU, read by the kernel: the gradients are not
+    written, the host reads nothing.  With skip_nonfinite and clip[2] == 0 (a non-finite norm) the launches write nothing."""
+    n = len(params)
+    if not (n == len(grads) == len(exp_avgs) == len(exp_avg_sqs)):
+        raise ValueError('params, grads, exp_avgs and exp_avg_sqs must have one entry per tensor')
+    _clip_buffer(clip, 'clip', 4)
+    if n == 0:
+        return 0
+    hyper = adamw_hyper(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, step=step)
+    arr, keep = _adamw_array(params, grads, exp_avgs, exp_avg_sqs)
+    if clip.device != keep[0].device:
+        raise RuntimeError('clip must live on the parameters\' device')
+    launches = 0
+    with torch.cuda.device(keep[0].device):
+        lib = _hip.load()
+        stream = _stream(keep[0])
+        for chunk, k in _item_chunks(arr, n):
+            _hip.check(lib.v2w_adamw_multi_clipped(chunk, k, C.byref(hyper), clip.data_ptr(), int(bool(skip_nonfinite)), stream),
+                       'v2w_adamw_multi_clipped')
             launches += 1
     return launches
