@@ -1461,7 +1461,7 @@ def test_conv1d_dgrad_building_block(dev, B, C, L, k, dil):
                                                    (2, 32, 16, 1000, 4, 1, 2), (1, 512, 256, 17, 16, 1, 8),
                                                    # the 8-channel stage of a six-stage (x640) generator: 16-row tiles with the missing rows staged as 0
                                                    (2, 8, 8, 1999, 11, 3, 1), (2, 8, 8, 640, 3, 1, 1), (2, 16, 8, 700, 4, 1, 2),
-                                                   # >= 512 staged items of a one-tile layer: 2 048 slabs, summed in two levels (wgrad_reduce_part_kernel)
+                                                   # >= 512 staged items of a one-tile layer: 2 048 slabs, summed by wgrad_reduce16_kernel (nslab >= 128: 16 slab lanes per block)
                                                    (4, 32, 32, 16384, 3, 1, 1), (3, 16, 16, 22000, 7, 3, 1), (4, 32, 16, 16384, 4, 1, 2)])
 def test_wgrad_matches_autograd(dev, B, cin, cout, L, k, dil, u):
     """dW of the fused [affine] -> lrelu -> Conv1d / ConvTranspose1d against torch autograd in fp64 (weights in [k][C_in][C_out] layout)."""
