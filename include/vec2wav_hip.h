@@ -441,7 +441,9 @@ int v2w_cond_affine_eval(const v2w_cond_eval_args* e, void* stream);
 /* stats: 2C+1 doubles = [sum_c | sumsq_c | count]; count = B*L is written by the kernel so that one
  * all-reduce(sum) of the whole array yields the global sums AND the global element count. */
 int v2w_bn_stats(const float* x, double* stats, double* partial_ws, int B, int C, int L, void* stream);
-/* Fixed-order fp64 reduction of the per-tile partials written by v2w_convt1d_fwd(stats_part) -> stats[2C+1]. */
+/* Fixed-order fp64 reduction of the per-tile partials written by v2w_convt1d_fwd(stats_part) -> stats[2C+1].
+ * part: [ntiles][C][2] floats, each (sum, sumsq) row entry read as one 8-byte pair: `part` must be 8-byte aligned (here and in
+ * v2w_bn_reduce_finalize; every producer's row buffer is). */
 int v2w_bn_reduce_partials(const float* part, int ntiles, int C, double count, double* stats, void* stream);
 int v2w_bn_finalize(const double* stats, const float* gb,
                     float* running_mean, float* running_var, int64_t* num_batches_tracked,
@@ -456,7 +458,8 @@ int v2w_bn_reduce_finalize(const float* part, int ntiles, double count, const fl
 /* Two-level form for layers with thousands of partial rows (ABI v28; the fused stage kernels write one row per 224 positions):
  * v2w_bn_reduce_slices adds slice s of the rows of `part` ([ntiles][C][2] floats) into slices[s][2 C] fp64 ([sum | sumsq], nslices <= 1024
  * blocks reading whole rows), v2w_bn_finalize_slices is v2w_bn_finalize(training = 1) on those slices, added in slice order, with the element
- * count given.  Deterministic; same values as the one-level form up to the order of the fp64 additions. */
+ * count given.  Deterministic; same values as the one-level form up to the order of the fp64 additions.  Both refuse nslices outside
+ * 1 .. 1024 with V2W_E_ARG. */
 int v2w_bn_reduce_slices(const float* part, int ntiles, int C, double* slices, int nslices, void* stream);
 int v2w_bn_finalize_slices(const double* slices, int nslices, double count, const float* gb,
                            float* running_mean, float* running_var, int64_t* num_batches_tracked,
@@ -464,7 +467,7 @@ int v2w_bn_finalize_slices(const double* slices, int nslices, double count, cons
 
 /* ---- K5 (standalone form): out = a[b,c]*x + s[b,c] over (B,C,L).  Only ConditionalBatchNorm1d.forward used on
  * its own (modules.py:20-30) materialises the normalised tensor; Generator.forward folds the affine into its
- * consumers' loads instead. */
+ * consumers' loads instead.  One grid row per (b, c): B * C <= 65 535, V2W_E_SHAPE otherwise. */
 int v2w_affine_apply(const float* x, const float* a, const float* s, float* out, int B, int C, int L, void* stream);
 
 /* ---- backward building blocks (the forward entry points above run dgrad: see v2w_wf_transpose_flip).

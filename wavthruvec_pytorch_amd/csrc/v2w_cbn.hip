@@ -419,6 +419,7 @@ affine_apply_kernel(const float* __restrict__ x, const float* __restrict__ a, co
 
 extern "C" int v2w_affine_apply(const float* x, const float* a, const float* s, float* out, int B, int C, int L, void* stream) {
     if (!x || !a || !s || !out || B <= 0 || C <= 0 || L <= 0) return V2W_E_ARG;
+    if ((long long)B * C > 65535) return V2W_E_SHAPE;   // one grid row per (b, c): gridDim.y ends at 65 535
     int gx = (L + 255) / 256; if (gx > 64) gx = 64;
     V2W_LAUNCH(affine_apply_kernel, dim3(gx, B * C), dim3(256), 0, (hipStream_t)stream, x, a, s, out, L);
     return v2w_launch_status();
@@ -528,7 +529,7 @@ extern "C" int v2w_bn_reduce_slices(const float* part, int ntiles, int C, double
 extern "C" int v2w_bn_finalize_slices(const double* slices, int nslices, double count, const float* gb,
                                       float* running_mean, float* running_var, int64_t* num_batches_tracked,
                                       float* a_out, float* s_out, int B, int C, float momentum, float eps, void* stream) {
-    if (!slices || nslices <= 0 || !(count > 0.0) || !gb || !a_out || !s_out || !running_mean || !running_var || B <= 0 || C <= 0) return V2W_E_ARG;
+    if (!slices || nslices <= 0 || nslices > 1024 || !(count > 0.0) || !gb || !a_out || !s_out || !running_mean || !running_var || B <= 0 || C <= 0) return V2W_E_ARG;
     V2W_LAUNCH(bn_finalize_slices_kernel, dim3((C + 15) / 16), dim3(256), 0, (hipStream_t)stream, slices, nslices, count, gb,
                        running_mean, running_var, num_batches_tracked, a_out, s_out, B, C, momentum, eps);
     return v2w_launch_status();
