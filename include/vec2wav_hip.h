@@ -791,6 +791,74 @@ int v2w_grad_norm_finish(const float* partials, int n_partials, float max_norm, 
 int v2w_scale_multi(const v2w_adamw_item* items, int n, const float* coef, void* stream);
 int v2w_adamw_multi_clipped(const v2w_adamw_item* items, int n, const v2w_adamw_hyper* h, const float* clip, int skip_nonfinite, void* stream);
 
+/* ---- Exponential moving average of the weights (additive in ABI v35; the reference has none - GAN vocoders are evaluated and shipped from
+ * e <- decay e + (1 - decay) p): the average updated by the AdamW step's own kernel, in the pass that already holds p' in registers - read
+ * p, g, m, v, e and write p, m, v, e once, 36 bytes per parameter, one launch per V2W_ADAMW_EMA_MAX_ITEMS tensors - plus the two lines alone
+ * (v2w_ema_multi: parameters stepped by something else, buffers) and an in-place exchange of p and e (v2w_swap_multi: validate or
+ * synthesise from the average without moving a storage pointer).  The descriptors are HOST memory, read before the call returns.
+ * The caller passes ema_omd = 1 - decay, computed in double and rounded ONCE to fp32.
+ *
+ * Arithmetic of the average, after p' of the operation list of v2w_adamw_multi (v2w_ema_multi: with the stored p for p'), every line ONE
+ * correctly rounded fp32 operation:
+ *     de  = p' - e
+ *     e'  = fma(ema_omd, de, e)                   3 roundings on e': ema_omd, de, e'
+ * Against e + (1 - decay)(p' - e) evaluated exactly from the STORED p' and the fp32 ema_omd (whose own rounding is then the caller's, not the
+ * kernel's: 2 of the 3 remain), with u = 2^-24:  |e' - exact| <= 3u (|e| + |p'|)  to first order (|de| <= |p'| + |e|, ema_omd <= 1 and
+ * |e'| <= |e| + |p'|).  ema_omd == 0 leaves every bit of a finite e as it was (fma(0, de, e) = e for a finite de); ema_omd == 1 gives
+ * fma(1, p' - e, e), which is p' to one rounding, not bit for bit.  tests/ema_ref.py restates the lines, the bound and the closed form
+ * e_T = d^T e_0 + (1 - d) sum_t d^(T-1-t) p_t in fp64.
+ *
+ *   v2w_adamw_ema_multi  the AdamW step with the average updated in the same pass.  clip == NULL: the arithmetic of v2w_adamw_multi
+ *       (skip_nonfinite is then not looked at: there is no flag to read); otherwise that of v2w_adamw_multi_clipped, g' = g * clip[1] read
+ *       from DEVICE memory.  The same kernel body as those two, compiled twice more behind a template flag: p', m' and v' are bit for bit
+ *       those of the existing entry points on the same inputs.  Every element of p, m, v and e is written exactly once and nothing else
+ *       is written; no atomics, no scratch, no library state; every value leaves through an ordinary vector store.  With
+ *       skip_nonfinite != 0 and clip[2] == 0 every workgroup returns before its first load: p, m, v AND e keep their bits - a skipped step
+ *       does not move the average either.
+ *   v2w_ema_multi   the two lines alone, p only read: up to V2W_ADAMW_MAX_ITEMS items of v2w_ema_item; every element of e is written once.
+ *   v2w_swap_multi  exchanges the contents of p and e in place: each thread loads both values of its units, then stores both - one launch,
+ *       every element read once and written once, bit for bit.  Its descriptor is v2w_swap_item: the layout of v2w_ema_item with both
+ *       pointers writable (a struct of its own, so that no const is cast away); up to V2W_ADAMW_MAX_ITEMS items.
+ *
+ * The work split is v2w_adamw_multi_plan's: units of four floats, chunk = max(2048, ceil(sum of units / V2W_ADAMW_TARGET_WGS)), starts[],
+ * at least one workgroup per tensor.  An item takes 16-byte accesses only when ALL its pointers share their 16-byte phase - the five of a
+ * v2w_adamw_ema_item, p and e of the other two - and its units are then cut at the 16-byte lines (ceil((numel + s) / 4) units, s = floats
+ * of p past a line); otherwise it takes float-by-float accesses and counts ceil(numel / 4).  v2w_adamw_ema_multi_plan and
+ * v2w_ema_multi_plan (host only; v2w_swap_multi's plan is v2w_ema_multi_plan of the same pointers) read the items like the launch does.
+ *
+ * V2W_ADAMW_EMA_MAX_ITEMS: the table travels by value in the kernel arguments under the library's 3584 bytes: 64 * 48 (items) + 65 * 4
+ * (starts) + 28 (constants) + 4 (ema_omd) + 4 (n) = 3368 bytes; the pair table is 80 * 24 + 81 * 4 + 4 = 2248.
+ *
+ * V2W_E_ARG: every case of v2w_adamw_multi (v2w_adamw_multi_clipped when clip != NULL: clip not 4-byte aligned) with
+ * V2W_ADAMW_EMA_MAX_ITEMS for the item limit; e NULL or not 4-byte aligned; e overlapping p, m or v of its item; ema_omd outside [0, 1] or
+ * NaN.  v2w_ema_multi / v2w_swap_multi: items NULL; n < 1 or n > V2W_ADAMW_MAX_ITEMS; p or e NULL or not 4-byte aligned; numel <= 0; p and e
+ * of one item overlapping; ema_omd outside [0, 1] or NaN.  The plans: the items' cases, and starts NULL.  V2W_E_SHAPE: numel > 2^42. */
+#define V2W_ADAMW_EMA_MAX_ITEMS 64
+typedef struct {
+    float* p;
+    const float* g;
+    float* m;
+    float* v;
+    float* e;
+    int64_t numel;
+} v2w_adamw_ema_item;
+typedef struct {
+    const float* p;
+    float* e;
+    int64_t numel;
+} v2w_ema_item;
+typedef struct {
+    float* p;
+    float* e;
+    int64_t numel;
+} v2w_swap_item;
+int v2w_adamw_ema_multi_plan(const v2w_adamw_ema_item* items, int n, int32_t* starts);
+int v2w_adamw_ema_multi(const v2w_adamw_ema_item* items, int n, const v2w_adamw_hyper* h, const float* clip, int skip_nonfinite, float ema_omd,
+                        void* stream);
+int v2w_ema_multi_plan(const v2w_ema_item* items, int n, int32_t* starts);
+int v2w_ema_multi(const v2w_ema_item* items, int n, float ema_omd, void* stream);
+int v2w_swap_multi(const v2w_swap_item* items, int n, void* stream);
+
 /* ---- Spectral norm of conv weights (additive in ABI v35; legacy torch.nn.utils.spectral_norm as models.py:219-258 applies it to the first
  * DiscriminatorS: one power iteration per training forward, W / sigma): up to V2W_SN_MAX_LAYERS weight matrices per call, the step in 4
  * launches (2 without the iteration), its backward in 2, whatever the number of layers.  Nothing is allocated, no state is kept.

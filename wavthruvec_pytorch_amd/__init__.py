@@ -2,14 +2,15 @@
 
 Public surface = the reference's: `Generator`, `ResBlock1`, `ResBlock2`, `ConditionalBatchNorm1d`,
 `get_padding`, `init_weights`, `hparams`; `AdamW` (optim.py) is torch.optim.AdamW stepping in one launch of the library, with global-norm
-clipping and a non-finite guard that stay on the GPU; `clip_grad_norm_` is the stand-alone clip.  Importing the package does not touch the GPU or load the HIP
+clipping and a non-finite guard that stay on the GPU; `clip_grad_norm_` is the stand-alone clip; `AdamW(ema_decay=)` keeps an
+exponential moving average of the weights in the step's own launch and `ema_state_dict` writes its checkpoint.  Importing the package does not touch the GPU or load the HIP
 library; the first `Generator.forward` does, and raises if the library is missing.
 """
 from .models import Generator, ResBlock1, ResBlock2, LRELU_SLOPE  # noqa: F401
 from .modules import ConditionalBatchNorm1d  # noqa: F401
 from .utils import get_padding, init_weights  # noqa: F401
 from . import hparams  # noqa: F401
-from .optim import AdamW, clip_grad_norm_  # noqa: F401
+from .optim import AdamW, clip_grad_norm_, ema_state_dict  # noqa: F401
 
 __all__ = ['Generator', 'ResBlock1', 'ResBlock2', 'ConditionalBatchNorm1d', 'get_padding', 'init_weights',
-           'hparams', 'LRELU_SLOPE', 'AdamW', 'clip_grad_norm_']
+           'hparams', 'LRELU_SLOPE', 'AdamW', 'clip_grad_norm_', 'ema_state_dict']

@@ -139,6 +139,19 @@ ADAMW_MAX_ITEMS = 80
 ADAMW_TARGET_WGS = 2048
 
 
+class AdamWEmaItem(C.Structure):
+    """include/vec2wav_hip.h `v2w_adamw_ema_item`: a v2w_adamw_item with `e`, the exponential moving average of the parameter."""
+    _fields_ = [('p', _fp), ('g', _fp), ('m', _fp), ('v', _fp), ('e', _fp), ('numel', C.c_int64)]
+
+
+class EmaItem(C.Structure):
+    """include/vec2wav_hip.h `v2w_ema_item` and `v2w_swap_item` (one layout; the latter writes p too): a tensor and its average."""
+    _fields_ = [('p', _fp), ('e', _fp), ('numel', C.c_int64)]
+
+
+ADAMW_EMA_MAX_ITEMS = 64
+
+
 class SnDesc(C.Structure):
     """include/vec2wav_hip.h `v2w_sn_desc`: one spectral-normed conv weight (R = c_out rows of N = c_in * k floats), its u, v and folded output."""
     _fields_ = [('w', _fp), ('u', _fp), ('v', _fp), ('wf', _fp), ('c_out', C.c_int32), ('c_in', C.c_int32), ('k', C.c_int32),
@@ -264,6 +277,12 @@ SIGNATURES = {
     'v2w_grad_norm_finish': (C.c_int, [_fp, C.c_int, C.c_float, _fp, _fp]),
     'v2w_scale_multi': (C.c_int, [C.POINTER(AdamWItem), C.c_int, _fp, _fp]),
     'v2w_adamw_multi_clipped': (C.c_int, [C.POINTER(AdamWItem), C.c_int, C.POINTER(AdamWHyper), _fp, C.c_int, _fp]),
+    # exponential moving average of the weights: host descriptor arrays; clip (or NULL) is DEVICE memory, ema_omd = 1 - decay
+    'v2w_adamw_ema_multi_plan': (C.c_int, [C.POINTER(AdamWEmaItem), C.c_int, C.POINTER(C.c_int32)]),
+    'v2w_adamw_ema_multi': (C.c_int, [C.POINTER(AdamWEmaItem), C.c_int, C.POINTER(AdamWHyper), _fp, C.c_int, C.c_float, _fp]),
+    'v2w_ema_multi_plan': (C.c_int, [C.POINTER(EmaItem), C.c_int, C.POINTER(C.c_int32)]),
+    'v2w_ema_multi': (C.c_int, [C.POINTER(EmaItem), C.c_int, C.c_float, _fp]),
+    'v2w_swap_multi': (C.c_int, [C.POINTER(EmaItem), C.c_int, _fp]),
     # spectral norm: DEVICE descriptors (planned on the host copy), host grids and host pointer arrays, read before the call returns
     'v2w_sn_plan': (C.c_longlong, [C.POINTER(SnDesc), C.c_int, C.POINTER(SnGrids)]),
     'v2w_sn_step': (C.c_int, [_fp, C.c_int, C.c_int, C.POINTER(SnGrids), _fp, _fp, C.c_longlong, _fp]),

@@ -14,6 +14,11 @@
 // plan: grad_sumsq_kernel writes one fp32 sum of squares per workgroup (fixed order, no atomics), grad_norm_finish_kernel adds them in fp64
 // and leaves norm, clip coefficient, finite flag and a running count in four floats of the caller's, grad_scale_kernel is g *= coef[0], and
 // adamw_multi_clipped_kernel is the step's body compiled with g * clip[1] for g - the coefficient never visits the host.
+//
+// The exponential moving average of the weights (include/vec2wav_hip.h, v2w_adamw_ema_multi and its neighbours): the step's body compiled
+// twice more with a fifth tensor e per item - e' = fma(ema_omd, p' - e, e) while p' is in registers, 36 bytes per parameter - on a table of
+// 48-byte items (AdamWEmaArgs, at most V2W_ADAMW_EMA_MAX_ITEMS), and two kernels on a table of {p, e, numel} items (PairArgs): the two lines
+// alone and the exchange of p and e.  find_span and the plan are shared: they are written over the table's type.
 #include "v2w_common.h"
 
 namespace {
@@ -35,12 +40,40 @@ struct AdamWArgs {
 static_assert(sizeof(v2w_adamw_item) == 40 && sizeof(v2w_adamw_hyper) == 32, "include/vec2wav_hip.h states these sizes");
 static_assert(sizeof(AdamWArgs) <= 3584, "kernel arguments travel by value: 4 KB with the hidden ones");
 
+// the step with the average: 48-byte items, the same constants and ema_omd = 1 - decay
+struct AdamWEmaArgs {
+    v2w_adamw_ema_item it[V2W_ADAMW_EMA_MAX_ITEMS];
+    int starts[V2W_ADAMW_EMA_MAX_ITEMS + 1];
+    Coef c;
+    float omd;
+    int n;
+};
+static_assert(sizeof(v2w_adamw_ema_item) == 48 && sizeof(v2w_ema_item) == 24 && sizeof(v2w_swap_item) == 24, "include/vec2wav_hip.h states these sizes");
+static_assert(V2W_ADAMW_EMA_MAX_ITEMS * 48 + (V2W_ADAMW_EMA_MAX_ITEMS + 1) * 4 + sizeof(Coef) + 4 + 4 == sizeof(AdamWEmaArgs), "no padding");
+static_assert(sizeof(AdamWEmaArgs) <= 3584, "kernel arguments travel by value: 4 KB with the hidden ones");
+
+// {p, e, numel} items: Item is v2w_ema_item (p only read) or v2w_swap_item (both written)
+template <class Item>
+struct PairArgs {
+    Item it[V2W_ADAMW_MAX_ITEMS];
+    int starts[V2W_ADAMW_MAX_ITEMS + 1];
+    int n;
+};
+static_assert(sizeof(PairArgs<v2w_ema_item>) <= 3584 && sizeof(PairArgs<v2w_swap_item>) == sizeof(PairArgs<v2w_ema_item>), "by-value table");
+
 __host__ __device__ inline int phase16(const void* p) { return (int)((reinterpret_cast<uintptr_t>(p) >> 2) & 3); }
 __host__ __device__ inline bool same_phase(const v2w_adamw_item& it) {
     const int ph = phase16(it.p);
     return phase16(it.g) == ph && phase16(it.m) == ph && phase16(it.v) == ph;
 }
-__host__ __device__ inline long long item_units(const v2w_adamw_item& it) {
+__host__ __device__ inline bool same_phase(const v2w_adamw_ema_item& it) {
+    const int ph = phase16(it.p);
+    return phase16(it.g) == ph && phase16(it.m) == ph && phase16(it.v) == ph && phase16(it.e) == ph;
+}
+__host__ __device__ inline bool same_phase(const v2w_ema_item& it) { return phase16(it.p) == phase16(it.e); }
+__host__ __device__ inline bool same_phase(const v2w_swap_item& it) { return phase16(it.p) == phase16(it.e); }
+template <class Item>
+__host__ __device__ inline long long item_units(const Item& it) {
     return (it.numel + (same_phase(it) ? phase16(it.p) : 0) + 3) >> 2;
 }
 
@@ -68,13 +101,14 @@ struct Span {
     unsigned cnt;
     bool vec;
 };
-__device__ __forceinline__ Span find_span(const AdamWArgs& A, int wg) {
+template <class Args>
+__device__ __forceinline__ Span find_span(const Args& A, int wg) {
     int lo = 0, hi = A.n;
     while (hi - lo > 1) {                                 // the tensor of this workgroup: starts[lo] <= wg < starts[lo + 1]
         const int mid = (lo + hi) >> 1;
         if (A.starts[mid] <= wg) lo = mid; else hi = mid;
     }
-    const v2w_adamw_item& it = A.it[lo];
+    const auto& it = A.it[lo];
     Span s;
     s.item = lo;
     s.numel = it.numel;
@@ -98,20 +132,24 @@ __device__ __forceinline__ void unit_mask(const Span& s, unsigned t, size_t off,
     if (t >= s.cnt) e0 = e1 = 0;
 }
 
-// CLIP: the step on g * coef (include/vec2wav_hip.h, v2w_adamw_multi_clipped); otherwise coef is not looked at
-template <bool CLIP>
-__device__ __forceinline__ void adamw_body(const AdamWArgs& A, float coef) {
+// CLIP: the step on g * coef (include/vec2wav_hip.h, v2w_adamw_multi_clipped); otherwise coef is not looked at.  EMA: the table is an
+// AdamWEmaArgs and e' = fma(omd, p' - e, e) rides along (v2w_adamw_ema_multi); otherwise neither e nor omd exists
+template <bool CLIP, bool EMA, class Args>
+__device__ __forceinline__ void adamw_body(const Args& A, float coef) {
     const Span s = find_span(A, blockIdx.x);
-    const v2w_adamw_item& it = A.it[s.item];
+    const auto& it = A.it[s.item];
     const bool vec = s.vec;
     float* p = it.p + s.base;
     const float* g = it.g + s.base;
     float* m = it.m + s.base;
     float* v = it.v + s.base;
+    float* e = nullptr;
+    float omd = 0.f;
+    if constexpr (EMA) { e = it.e + s.base; omd = A.omd; }
     const Coef c = A.c;
 
     for (unsigned t0 = threadIdx.x; t0 < s.cnt; t0 += kThreads * kUnroll) {
-        f32x4 xp[kUnroll], xg[kUnroll], xm[kUnroll], xv[kUnroll];
+        f32x4 xp[kUnroll], xg[kUnroll], xm[kUnroll], xv[kUnroll], xe[kUnroll];
         size_t off[kUnroll];
         int e0[kUnroll], e1[kUnroll];
 #pragma unroll
@@ -123,10 +161,11 @@ __device__ __forceinline__ void adamw_body(const AdamWArgs& A, float coef) {
             xg[k] = load_unit(g + off[k], e0[k], e1[k], vec);
             xm[k] = load_unit(m + off[k], e0[k], e1[k], vec);
             xv[k] = load_unit(v + off[k], e0[k], e1[k], vec);
+            if constexpr (EMA) xe[k] = load_unit(e + off[k], e0[k], e1[k], vec);
         }
 #pragma unroll
         for (int k = 0; k < kUnroll; ++k) {
-            f32x4 np, nm, nv;
+            f32x4 np, nm, nv, ne;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {                              // include/vec2wav_hip.h: one fp32 rounding per line
                 const float gj = CLIP ? __fmul_rn(xg[k][j], coef) : xg[k][j];
@@ -139,22 +178,90 @@ __device__ __forceinline__ void adamw_body(const AdamWArgs& A, float coef) {
                 const float den = __fmaf_rn(__fsqrt_rn(nv[j]), c.rbc2, c.eps);
                 const float q = __fdiv_rn(nm[j], den);
                 np[j] = __fmaf_rn(-c.step, q, pd);
+                if constexpr (EMA) {
+                    const float de = __fsub_rn(np[j], xe[k][j]);
+                    ne[j] = __fmaf_rn(omd, de, xe[k][j]);
+                }
             }
             store_unit(p + off[k], np, e0[k], e1[k], vec);
             store_unit(m + off[k], nm, e0[k], e1[k], vec);
             store_unit(v + off[k], nv, e0[k], e1[k], vec);
+            if constexpr (EMA) store_unit(e + off[k], ne, e0[k], e1[k], vec);
         }
     }
 }
 
 __global__ void __launch_bounds__(kThreads)
-adamw_multi_kernel(const AdamWArgs A) { adamw_body<false>(A, 1.f); }
+adamw_multi_kernel(const AdamWArgs A) { adamw_body<false, false>(A, 1.f); }
 
 // clip: the four floats of v2w_grad_norm_finish; a skipped step returns before the first load (the branch is uniform over the launch)
 __global__ void __launch_bounds__(kThreads)
 adamw_multi_clipped_kernel(const AdamWArgs A, const float* __restrict__ clip, int skip_nonfinite) {
     if (skip_nonfinite && clip[2] == 0.f) return;
-    adamw_body<true>(A, clip[1]);
+    adamw_body<true, false>(A, clip[1]);
+}
+
+__global__ void __launch_bounds__(kThreads)
+adamw_ema_multi_kernel(const AdamWEmaArgs A) { adamw_body<false, true>(A, 1.f); }
+
+// a skipped step leaves the average alone too
+__global__ void __launch_bounds__(kThreads)
+adamw_ema_multi_clipped_kernel(const AdamWEmaArgs A, const float* __restrict__ clip, int skip_nonfinite) {
+    if (skip_nonfinite && clip[2] == 0.f) return;
+    adamw_body<true, true>(A, clip[1]);
+}
+
+// e' = fma(omd, p - e, e), every element of e once; p is only read
+__global__ void __launch_bounds__(kThreads)
+ema_multi_kernel(const PairArgs<v2w_ema_item> A, float omd) {
+    const Span s = find_span(A, blockIdx.x);
+    const float* p = A.it[s.item].p + s.base;
+    float* e = A.it[s.item].e + s.base;
+    for (unsigned t0 = threadIdx.x; t0 < s.cnt; t0 += kThreads * kUnroll) {
+        f32x4 xp[kUnroll], xe[kUnroll];
+        size_t off[kUnroll];
+        int e0[kUnroll], e1[kUnroll];
+#pragma unroll
+        for (int k = 0; k < kUnroll; ++k) {
+            const unsigned t = t0 + k * kThreads;
+            off[k] = (size_t)t << 2;
+            unit_mask(s, t, off[k], e0[k], e1[k]);
+            xp[k] = load_unit(p + off[k], e0[k], e1[k], s.vec);
+            xe[k] = load_unit(e + off[k], e0[k], e1[k], s.vec);
+        }
+#pragma unroll
+        for (int k = 0; k < kUnroll; ++k) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) xe[k][j] = __fmaf_rn(omd, __fsub_rn(xp[k][j], xe[k][j]), xe[k][j]);
+            store_unit(e + off[k], xe[k], e0[k], e1[k], s.vec);
+        }
+    }
+}
+
+// p <-> e: a thread loads both values of its units, then stores both; no element belongs to two threads
+__global__ void __launch_bounds__(kThreads)
+swap_multi_kernel(const PairArgs<v2w_swap_item> A) {
+    const Span s = find_span(A, blockIdx.x);
+    float* p = A.it[s.item].p + s.base;
+    float* e = A.it[s.item].e + s.base;
+    for (unsigned t0 = threadIdx.x; t0 < s.cnt; t0 += kThreads * kUnroll) {
+        f32x4 xp[kUnroll], xe[kUnroll];
+        size_t off[kUnroll];
+        int e0[kUnroll], e1[kUnroll];
+#pragma unroll
+        for (int k = 0; k < kUnroll; ++k) {
+            const unsigned t = t0 + k * kThreads;
+            off[k] = (size_t)t << 2;
+            unit_mask(s, t, off[k], e0[k], e1[k]);
+            xp[k] = load_unit(p + off[k], e0[k], e1[k], s.vec);
+            xe[k] = load_unit(e + off[k], e0[k], e1[k], s.vec);
+        }
+#pragma unroll
+        for (int k = 0; k < kUnroll; ++k) {
+            store_unit(p + off[k], xe[k], e0[k], e1[k], s.vec);
+            store_unit(e + off[k], xp[k], e0[k], e1[k], s.vec);
+        }
+    }
 }
 
 // partials[wg] = sum of g^2 over the workgroup's chunk: per thread one fma chain over its units in order, then the fixed block sum.
@@ -252,6 +359,39 @@ int adamw_items(const v2w_adamw_item* items, int n, long long* units) {
     }
     return 0;
 }
+
+// v2w_adamw_ema_item: the checks above, and e against p, m and v
+int adamw_ema_items(const v2w_adamw_ema_item* items, int n, long long* units) {
+    if (!items || n < 1 || n > V2W_ADAMW_EMA_MAX_ITEMS) return V2W_E_ARG;
+    for (int i = 0; i < n; ++i) {
+        const v2w_adamw_ema_item& it = items[i];
+        if (!ptr4(it.p) || !ptr4(it.g) || !ptr4(it.m) || !ptr4(it.v) || !ptr4(it.e) || it.numel <= 0) return V2W_E_ARG;
+        if (it.numel > (kMaxUnits << 2)) return V2W_E_SHAPE;
+        units[i] = item_units(it);
+        if (units[i] > kMaxUnits) return V2W_E_SHAPE;
+        if (overlap(it.p, it.m, it.numel) || overlap(it.p, it.v, it.numel) || overlap(it.m, it.v, it.numel)) return V2W_E_ARG;
+        if (overlap(it.e, it.p, it.numel) || overlap(it.e, it.m, it.numel) || overlap(it.e, it.v, it.numel)) return V2W_E_ARG;
+    }
+    return 0;
+}
+
+// v2w_ema_item / v2w_swap_item
+template <class Item>
+int pair_items(const Item* items, int n, long long* units) {
+    if (!items || n < 1 || n > V2W_ADAMW_MAX_ITEMS) return V2W_E_ARG;
+    for (int i = 0; i < n; ++i) {
+        const Item& it = items[i];
+        if (!ptr4(it.p) || !ptr4(it.e) || it.numel <= 0) return V2W_E_ARG;
+        if (it.numel > (kMaxUnits << 2)) return V2W_E_SHAPE;
+        units[i] = item_units(it);
+        if (units[i] > kMaxUnits) return V2W_E_SHAPE;
+        if (overlap(it.p, it.e, it.numel)) return V2W_E_ARG;
+    }
+    return 0;
+}
+
+// ema_omd = 1 - decay in [0, 1]; a NaN is refused
+inline bool omd_ok(float omd) { return omd >= 0.f && omd <= 1.f; }
 
 // starts[i] = first workgroup of tensor i, starts[n] = workgroups of the launch (returned)
 int adamw_plan(const long long* units, int n, int32_t* starts) {
@@ -373,5 +513,64 @@ extern "C" int v2w_scale_multi(const v2w_adamw_item* items, int n, const float* 
     hipStream_t st = (hipStream_t)stream;
     if (v2w_dry(st)) return 0;
     V2W_LAUNCH(grad_scale_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A, coef);
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_adamw_ema_multi_plan(const v2w_adamw_ema_item* items, int n, int32_t* starts) {
+    if (!starts) return V2W_E_ARG;
+    long long units[V2W_ADAMW_EMA_MAX_ITEMS];
+    if (const int rc = adamw_ema_items(items, n, units)) return rc;
+    return adamw_plan(units, n, starts);
+}
+
+extern "C" int v2w_adamw_ema_multi(const v2w_adamw_ema_item* items, int n, const v2w_adamw_hyper* h, const float* clip, int skip_nonfinite,
+                                   float ema_omd, void* stream) {
+    AdamWEmaArgs A;
+    long long units[V2W_ADAMW_EMA_MAX_ITEMS];
+    if (const int rc = adamw_ema_items(items, n, units)) return rc;
+    if (const int rc = adamw_coef(h, &A.c)) return rc;
+    if (!omd_ok(ema_omd) || (clip && !ptr4(clip))) return V2W_E_ARG;
+    for (int i = 0; i < n; ++i) A.it[i] = items[i];
+    adamw_plan(units, n, A.starts);
+    A.omd = ema_omd;
+    A.n = n;
+    hipStream_t st = (hipStream_t)stream;
+    if (v2w_dry(st)) return 0;
+    if (clip) V2W_LAUNCH(adamw_ema_multi_clipped_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A, clip, skip_nonfinite);
+    else V2W_LAUNCH(adamw_ema_multi_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A);
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_ema_multi_plan(const v2w_ema_item* items, int n, int32_t* starts) {
+    if (!starts) return V2W_E_ARG;
+    long long units[V2W_ADAMW_MAX_ITEMS];
+    if (const int rc = pair_items(items, n, units)) return rc;
+    return adamw_plan(units, n, starts);
+}
+
+extern "C" int v2w_ema_multi(const v2w_ema_item* items, int n, float ema_omd, void* stream) {
+    PairArgs<v2w_ema_item> A;
+    long long units[V2W_ADAMW_MAX_ITEMS];
+    if (const int rc = pair_items(items, n, units)) return rc;
+    if (!omd_ok(ema_omd)) return V2W_E_ARG;
+    for (int i = 0; i < n; ++i) A.it[i] = items[i];
+    adamw_plan(units, n, A.starts);
+    A.n = n;
+    hipStream_t st = (hipStream_t)stream;
+    if (v2w_dry(st)) return 0;
+    V2W_LAUNCH(ema_multi_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A, ema_omd);
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_swap_multi(const v2w_swap_item* items, int n, void* stream) {
+    PairArgs<v2w_swap_item> A;
+    long long units[V2W_ADAMW_MAX_ITEMS];
+    if (const int rc = pair_items(items, n, units)) return rc;
+    for (int i = 0; i < n; ++i) A.it[i] = items[i];
+    adamw_plan(units, n, A.starts);
+    A.n = n;
+    hipStream_t st = (hipStream_t)stream;
+    if (v2w_dry(st)) return 0;
+    V2W_LAUNCH(swap_multi_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A);
     return v2w_launch_status();
 }

@@ -1703,3 +1703,113 @@ def adamw_multi_clipped(params, grads, exp_avgs, exp_avg_sqs, clip, *, skip_nonf
                        'v2w_adamw_multi_clipped')
             launches += 1
     return launches
+
+
+# ---- exponential moving average of the weights (include/vec2wav_hip.h: v2w_adamw_ema_multi, v2w_ema_multi, v2w_swap_multi)
+def ema_omd(ema_decay):
+    """1 - decay for a decay in [0, 1] (ValueError otherwise, NaN included): computed in double here, rounded once to fp32 on the way in."""
+    d = float(ema_decay)
+    if not 0.0 <= d <= 1.0:
+        raise ValueError(f'ema_decay must lie in [0, 1], got {ema_decay}')
+    return 1.0 - d
+
+
+def _chunks_of(arr, n, item, limit):
+    """(pointer to the first descriptor, count) of every run of at most `limit` descriptors of type `item`."""
+    for i0 in range(0, n, limit):
+        yield C.cast(C.byref(arr, i0 * C.sizeof(item)), C.POINTER(item)), min(limit, n - i0)
+
+
+def _pair_array(ps, es, what):
+    """(EmaItem descriptors, the tensors they point into) of two lists of fp32 GPU tensors on one device, entry for entry of one size."""
+    n = len(ps)
+    if n != len(es):
+        raise ValueError(f'{what}: params and emas must have one entry per tensor')
+    if n == 0:
+        raise ValueError(f'{what}: no tensors')
+    dev = ps[0].device
+    arr = (_hip.EmaItem * n)()
+    keep = []
+    for i, (p, e) in enumerate(zip(ps, es)):
+        p, e = p.detach(), e.detach()
+        for t, name in ((p, 'param'), (e, 'ema')):
+            _chk(t, f'{name}[{i}]')
+            if t.device != dev:
+                raise RuntimeError(f'all tensors of one {what} call must live on one device')
+        if e.numel() != p.numel():
+            raise ValueError(f'ema[{i}] has {e.numel()} elements, its parameter {p.numel()}')
+        if p.numel() == 0:
+            raise ValueError(f'param[{i}] is empty')
+        keep += [p, e]
+        arr[i].p, arr[i].e, arr[i].numel = p.data_ptr(), e.data_ptr(), p.numel()
+    return arr, keep
+
+
+def adamw_ema_multi(params, grads, exp_avgs, exp_avg_sqs, emas, clip=None, *, ema_decay, skip_nonfinite=False, lr, betas, eps, weight_decay,
+                    step):
+    """adamw_multi (clip None) or adamw_multi_clipped (`clip`: the four floats of grad_norm_finish on the GPU) with the exponential moving
+    average of every parameter updated in the same pass: emas[i] <- emas[i] + (1 - ema_decay) (params[i]' - emas[i]), in place;
+    params / exp_avgs / exp_avg_sqs get the bits the other two wrappers give.  ceil(n / ADAMW_EMA_MAX_ITEMS) launches; returns their
+    number.  With skip_nonfinite and clip[2] == 0 nothing is written, the averages included."""
+    n = len(params)
+    if not (n == len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(emas)):
+        raise ValueError('params, grads, exp_avgs, exp_avg_sqs and emas must have one entry per tensor')
+    if n == 0:
+        raise ValueError('adamw_ema_multi: no tensors')
+    omd = ema_omd(ema_decay)
+    if clip is not None:
+        _clip_buffer(clip, 'clip', 4)
+    hyper = adamw_hyper(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, step=step)
+    src, keep = _adamw_array(params, grads, exp_avgs, exp_avg_sqs)
+    dev = keep[0].device
+    arr = (_hip.AdamWEmaItem * n)()
+    for i, e in enumerate(emas):
+        e = e.detach()
+        _chk(e, f'ema[{i}]')
+        if e.device != dev:
+            raise RuntimeError('all tensors of one adamw_ema_multi call must live on one device')
+        if e.numel() != src[i].numel:
+            raise ValueError(f'ema[{i}] has {e.numel()} elements, its parameter {src[i].numel}')
+        keep.append(e)
+        d = arr[i]
+        d.p, d.g, d.m, d.v, d.e, d.numel = src[i].p, src[i].g, src[i].m, src[i].v, e.data_ptr(), src[i].numel
+    if clip is not None and clip.device != dev:
+        raise RuntimeError('clip must live on the parameters\' device')
+    launches = 0
+    with torch.cuda.device(dev):
+        lib = _hip.load()
+        stream = _stream(keep[0])
+        for chunk, k in _chunks_of(arr, n, _hip.AdamWEmaItem, _hip.ADAMW_EMA_MAX_ITEMS):
+            _hip.check(lib.v2w_adamw_ema_multi(chunk, k, C.byref(hyper), _hip.ptr(clip), int(bool(skip_nonfinite)), omd, stream),
+                       'v2w_adamw_ema_multi')
+            launches += 1
+    return launches
+
+
+def ema_multi(params, emas, *, ema_decay):
+    """emas[i] <- emas[i] + (1 - ema_decay) (params[i] - emas[i]) in place, params only read: for tensors something else steps, and for
+    buffers.  fp32 contiguous GPU tensors on one device; ceil(n / ADAMW_MAX_ITEMS) launches, returns their number."""
+    omd = ema_omd(ema_decay)
+    arr, keep = _pair_array(params, emas, 'ema_multi')
+    launches = 0
+    with torch.cuda.device(keep[0].device):
+        lib = _hip.load()
+        stream = _stream(keep[0])
+        for chunk, k in _chunks_of(arr, len(params), _hip.EmaItem, _hip.ADAMW_MAX_ITEMS):
+            _hip.check(lib.v2w_ema_multi(chunk, k, omd, stream), 'v2w_ema_multi')
+            launches += 1
+    return launches
+
+
+def swap_multi(params, emas):
+    """Exchanges the contents of params[i] and emas[i] in place, bit for bit; no storage pointer moves.  ceil(n / ADAMW_MAX_ITEMS)
+    launches, returns their number.  The parameters' version counters are NOT bumped: optim.AdamW.swap_ema does."""
+    arr, keep = _pair_array(params, emas, 'swap_multi')
+    launches = 0
+    with torch.cuda.device(keep[0].device):
+        lib = _hip.load()
+        stream = _stream(keep[0])
+        for chunk, k in _chunks_of(arr, len(params), _hip.EmaItem, _hip.ADAMW_MAX_ITEMS):
+            _hip.check(lib.v2w_swap_multi(chunk, k, stream), 'v2w_swap_multi')
+            launches += 1
+    return launches

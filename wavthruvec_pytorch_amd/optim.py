@@ -8,14 +8,20 @@ created at the first step), `state_dict()` / `load_state_dict()`, `param_groups`
 `clip_grad_norm_`: torch.nn.utils.clip_grad_norm_ for fp32 GPU gradients and the 2-norm in one streaming launch per 80 tensors, one
 finishing launch and one scaling launch per 80 tensors (v2w_grad_sumsq_multi / v2w_grad_norm_finish / v2w_scale_multi), without a host
 sync.  `AdamW(max_grad_norm=..., skip_nonfinite=...)` goes one further: the step's kernel reads the clip coefficient from GPU memory, so
-no gradient is rewritten at all."""
+no gradient is rewritten at all.
+
+`AdamW(ema_decay=...)` keeps an exponential moving average of every parameter in `state[p]['ema']`, updated by the step's own kernel
+(v2w_adamw_ema_multi); `swap_ema()` exchanges weights and averages in place for validation or synthesis, `ema_state_dict` writes the
+averaged checkpoint."""
 from __future__ import annotations
+
+import contextlib
 
 import torch
 
 from . import hipops
 
-__all__ = ['AdamW', 'clip_grad_norm_']
+__all__ = ['AdamW', 'clip_grad_norm_', 'ema_state_dict']
 
 _UNSERVED = ('amsgrad', 'maximize', 'capturable', 'differentiable')
 
@@ -36,9 +42,25 @@ class AdamW(torch.optim.AdamW):
     skip_nonfinite without max_grad_norm computes the norm with max_norm = inf (coefficient 1).  Both are attributes of the optimizer,
     not entries of `param_groups`: `state_dict()` is torch's.  With either set, every group must live on ONE GPU (ValueError otherwise).
     Under DistributedDataParallel the gradients are all-reduced before step() runs: every rank computes the same norm, no collective
-    is added."""
+    is added.
+
+    ema_decay (a float in [0, 1), or None): every step also moves an exponential moving average of each parameter it steps,
+    e <- e + (1 - ema_decay) (p' - e), in the same launch (hipops.adamw_ema_multi; with max_grad_norm / skip_nonfinite the clipped form).
+    `state[p]['ema']` is created at the parameter's first step as a clone of p before the update - and likewise when a loaded state has
+    none - and travels in `state_dict()` / `load_state_dict()` like the moments.  A step skipped by skip_nonfinite leaves the averages
+    alone.  There is no warm-up schedule of the decay, and buffers (BatchNorm running statistics, spectral-norm u / v) are not averaged:
+    hipops.ema_multi serves those.  An attribute of the optimizer like max_grad_norm, not an entry of `param_groups`; with None nothing
+    changes and `state_dict()` is torch's.  Every group must live on the GPU (ValueError otherwise).  `ema_parameters()`, `swap_ema()`
+    and `ema_state_dict()` read the averages."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, **kw):
+        ema_decay = kw.pop('ema_decay', None)
+        if ema_decay is not None:
+            ema_decay = float(ema_decay)
+            if not 0.0 <= ema_decay < 1.0:
+                raise ValueError(f'ema_decay must lie in [0, 1), got {ema_decay}')
+        self.ema_decay = ema_decay
+        self._ema_swapped = False
         max_grad_norm = kw.pop('max_grad_norm', None)
         self.skip_nonfinite = bool(kw.pop('skip_nonfinite', False))
         if max_grad_norm is not None:
@@ -116,12 +138,17 @@ class AdamW(torch.optim.AdamW):
                 st['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
             elif not torch.is_tensor(st['step']):   # a state dict written by torch < 1.12 holds a Python int
                 st['step'] = torch.tensor(float(st['step']), dtype=torch.get_default_dtype())
+            if self.ema_decay is not None and 'ema' not in st:      # the first step, or a loaded state without one: start from p
+                st['ema'] = p.detach().clone(memory_format=torch.contiguous_format)
             by_dev.setdefault((p.device, int(st['step'].item()) + 1), []).append((p, g, st))
         for (_dev, t), rows in by_dev.items():      # one call per group (parameters that joined later carry another step count)
             ps = [r[0] for r in rows]
             lists = (ps, [r[1] for r in rows], [r[2]['exp_avg'] for r in rows], [r[2]['exp_avg_sq'] for r in rows])
             hyper = dict(lr=group['lr'], betas=group['betas'], eps=group['eps'], weight_decay=group['weight_decay'], step=t)
-            if clip is None:
+            if self.ema_decay is not None:
+                hipops.adamw_ema_multi(*lists, [r[2]['ema'] for r in rows], clip, ema_decay=self.ema_decay,
+                                       skip_nonfinite=self.skip_nonfinite, **hyper)
+            elif clip is None:
                 hipops.adamw_multi(*lists, **hyper)
             else:
                 hipops.adamw_multi_clipped(*lists, clip, skip_nonfinite=self.skip_nonfinite, **hyper)
@@ -129,8 +156,45 @@ class AdamW(torch.optim.AdamW):
             # the kernel wrote through the raw pointers: the caches of folded / packed weights are keyed on the version counters
             torch.autograd.graph.increment_version(ps)
 
+    def ema_parameters(self):
+        """[(p, e), ...]: every parameter that has state with its average, in the order of the parameter groups."""
+        return [(p, self.state[p]['ema']) for group in self.param_groups for p in group['params']
+                if p in self.state and 'ema' in self.state[p]]
+
+    def _swap(self):
+        by_dev = {}
+        for p, e in self.ema_parameters():
+            by_dev.setdefault(p.device, []).append((p, e))
+        for rows in by_dev.values():
+            ps = [r[0] for r in rows]
+            hipops.swap_multi(ps, [r[1] for r in rows])
+            # as after a step: the caches of folded / packed weights are keyed on the version counters
+            torch.autograd.graph.increment_version(ps)
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """`with opt.swap_ema():` - inside, every parameter that has state holds its average and `state[p]['ema']` holds the weights: one
+        hipops.swap_multi per list on entry and on exit (on exceptions too), the version counters bumped both times so that fold and pack
+        caches refresh.  Storage pointers do not move: recorded launch plans stay valid.  Not re-entrant: nesting it, or step() inside it,
+        raises RuntimeError."""
+        if self.ema_decay is None:
+            raise RuntimeError('wavthruvec_pytorch_amd.optim.AdamW.swap_ema needs ema_decay')
+        if self._ema_swapped:
+            raise RuntimeError('wavthruvec_pytorch_amd.optim.AdamW.swap_ema is not re-entrant')
+        with torch.no_grad():
+            self._swap()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            with torch.no_grad():
+                self._swap()
+            self._ema_swapped = False
+
     @torch.no_grad()
     def step(self, closure=None):
+        if self._ema_swapped:
+            raise RuntimeError('wavthruvec_pytorch_amd.optim.AdamW.step inside swap_ema(): the parameters hold the averages')
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -143,6 +207,8 @@ class AdamW(torch.optim.AdamW):
         if guarded and not all(mine):
             raise ValueError('wavthruvec_pytorch_amd.optim.AdamW: max_grad_norm / skip_nonfinite need every parameter group on the GPU '
                              '(use torch.nn.utils.clip_grad_norm_ for CPU parameters)')
+        if self.ema_decay is not None and not all(mine):
+            raise ValueError('wavthruvec_pytorch_amd.optim.AdamW: ema_decay needs every parameter group on the GPU')
         if not any(mine):
             torch_step(self)
             return loss
@@ -158,6 +224,20 @@ class AdamW(torch.optim.AdamW):
             finally:
                 self.param_groups = groups
         return loss
+
+
+def ema_state_dict(optimizer, module):
+    """`module.state_dict()` with every parameter `optimizer` holds an average of replaced by a clone of that average (shaped like the
+    parameter); buffers and parameters without one are taken as they are (detached clones).  Keys and order are those of
+    `module.state_dict()`: torch.save({'generator': ema_state_dict(opt_g, generator)}, path) is a checkpoint of the averaged weights."""
+    emas = {id(p): e for p, e in optimizer.ema_parameters()}
+    params = dict(module.named_parameters(remove_duplicate=False))
+    out = module.state_dict()
+    for key in out:
+        p = params.get(key)
+        src = emas.get(id(p)) if p is not None else None
+        out[key] = (src.view(p.shape) if src is not None else out[key]).detach().clone()
+    return out
 
 
 def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False):
