@@ -546,7 +546,11 @@ int v2w_mel_finish(const float* spec, const float* basis, float* out, int B, int
  *   v2w_mel_finish_bwd: gout (B, n_mels, F), the forward's spec, basis and basisT (nb, n_mels) -> dspec (B, Cs, FP); the caller
  *                       zero-fills dspec (pad rows and frames >= F are not written).  d log(clamp(x, 1e-5)) = 1/x for x >= 1e-5.
  *   v2w_mel_phases_bwd: dxp (B, hop, FP) -> dy (B, L): every sample sums the padded positions that read it (reflections fold back).
- * Between them the DFT conv's input gradient is v2w_conv1d_fwd with the tap-flipped transposed weights and pad_left = k - 1. */
+ * Between them the DFT conv's input gradient is v2w_conv1d_fwd with the tap-flipped transposed weights and pad_left = k - 1.
+ * V2W_E_ARG: a NULL operand, B <= 0, L <= 1, hop <= 0, pad < 0, pad >= L (the reflection needs more than pad samples), FP <= 0 (phases);
+ * F <= 0, FP < F, nb <= 0, Cs < 2 * nb, n_mels <= 0 (finish).  V2W_E_SHAPE, nothing launched: hop * FP or L + 2 * pad past 2^31 - 1 (the three
+ * phase calls index with int: the largest each takes is 2^31 - 1); nb > 1024 (v2w_mel_finish, _len) or nb + n_mels > 1024 (v2w_mel_finish_bwd):
+ * 64 bytes of LDS per bin, and per mel in the backward, of 64 KiB; n_mels * 16 past 2^31 - 1; F * hop + n_fft past 2^31 - 1 (v2w_mel_finish_len). */
 int v2w_mel_finish_bwd(const float* spec, const float* basis, const float* basisT, const float* gout, float* dspec,
                        int B, int Cs, int FP, int F, int nb, int n_mels, void* stream);
 int v2w_mel_phases_bwd(const float* dxp, float* dy, int B, int L, int hop, int pad, int FP, void* stream);

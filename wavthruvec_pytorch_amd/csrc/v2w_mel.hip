@@ -202,12 +202,19 @@ mel_finish_len_kernel(const float* __restrict__ spec, const float* __restrict__ 
     }
 }
 
+// What the index arithmetic of the phase kernels holds in `int`: hop * FP (the flat index of xp) and L + 2 * pad (the padded length; the
+// reflected indices 2 (L - 1) - s + pad stay below it).  Past 2^31 - 1 the launch would wrap them: V2W_E_SHAPE, nothing is launched.
+inline bool mel_phase_ints_fit(int L, int hop, int pad, int FP) {
+    return (long long)hop * FP <= 0x7fffffffll && (long long)L + 2ll * pad <= 0x7fffffffll;
+}
+
 }  // namespace
 
 // y (B, L) -> xp (B, hop, FP); FP >= F + n_fft/hop - 1 frames columns (F = number of STFT frames), pad = (n_fft - hop)/2.
 extern "C" int v2w_mel_phases(const float* y, float* xp, int B, int L, int hop, int pad, int FP, void* stream) {
     if (!y || !xp || B <= 0 || L <= 1 || hop <= 0 || pad < 0 || pad >= L || FP <= 0) return V2W_E_ARG;
-    int gx = (hop * FP + 255) / 256; if (gx > 1024) gx = 1024;
+    if (!mel_phase_ints_fit(L, hop, pad, FP)) return V2W_E_SHAPE;
+    int gx = (int)(((long long)hop * FP + 255) / 256); if (gx > 1024) gx = 1024;
     V2W_LAUNCH(mel_phase_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, y, xp, L, hop, pad, FP);
     return v2w_launch_status();
 }
@@ -217,7 +224,7 @@ extern "C" int v2w_mel_finish(const float* spec, const float* basis, float* out,
                               void* stream) {
     if (!spec || !basis || !out || B <= 0 || F <= 0 || FP < F || nb <= 0 || Cs < 2 * nb || n_mels <= 0) return V2W_E_ARG;
     const size_t lds = (size_t)nb * V2W_MEL_FT * sizeof(float);
-    if (lds > 64 * 1024) return V2W_E_SHAPE;
+    if (lds > 64 * 1024 || (long long)n_mels * V2W_MEL_FT > 0x7fffffffll) return V2W_E_SHAPE;      // (the kernel's n_mels * 16 is an int)
     V2W_LAUNCH(mel_finish_kernel, dim3((F + V2W_MEL_FT - 1) / V2W_MEL_FT, B), dim3(256), lds, (hipStream_t)stream,
                        spec, basis, out, Cs, FP, F, nb, n_mels);
     return v2w_launch_status();
@@ -227,8 +234,8 @@ extern "C" int v2w_mel_finish(const float* spec, const float* basis, float* out,
 extern "C" int v2w_mel_phases_len(const float* y, float* xp, int B, int L, int hop, int pad, int FP, const int32_t* len, int len_mul,
                                   void* stream) {
     if (!y || !xp || !len || len_mul < 1 || B <= 0 || L <= 1 || hop <= 0 || pad < 0 || pad >= L || FP <= 0 || (2 * pad) % hop) return V2W_E_ARG;
-    if ((long long)hop * FP > 0x7fffffffll) return V2W_E_SHAPE;
-    int gx = (hop * FP + 255) / 256; if (gx > 1024) gx = 1024;
+    if (!mel_phase_ints_fit(L, hop, pad, FP)) return V2W_E_SHAPE;
+    int gx = (int)(((long long)hop * FP + 255) / 256); if (gx > 1024) gx = 1024;
     V2W_LAUNCH(mel_phase_len_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, y, xp, len, len_mul, L, hop, pad, FP);
     return v2w_launch_status();
 }
@@ -238,7 +245,8 @@ extern "C" int v2w_mel_finish_len(const float* spec, const float* basis, float* 
     if (!spec || !basis || !out || B <= 0 || F <= 0 || FP < F || nb <= 0 || Cs < 2 * nb || n_mels <= 0) return V2W_E_ARG;
     if (!len || len_mul < 1 || hop < 1 || n_fft < hop || n_fft % hop || (n_fft - hop) % 2) return V2W_E_ARG;
     const size_t lds = (size_t)nb * V2W_MEL_FT * sizeof(float);
-    if (lds > 64 * 1024) return V2W_E_SHAPE;
+    if (lds > 64 * 1024 || (long long)n_mels * V2W_MEL_FT > 0x7fffffffll) return V2W_E_SHAPE;
+    if ((long long)F * hop + n_fft > 0x7fffffffll) return V2W_E_SHAPE;         // (the kernel's sample count of F frames is an int)
     V2W_LAUNCH(mel_finish_len_kernel, dim3((F + V2W_MEL_FT - 1) / V2W_MEL_FT, B), dim3(256), lds, (hipStream_t)stream,
                        spec, basis, out, len, len_mul, hop, n_fft, Cs, FP, F, nb, n_mels);
     return v2w_launch_status();
@@ -260,7 +268,8 @@ extern "C" int v2w_mel_finish_bwd(const float* spec, const float* basis, const f
 // Backward of v2w_mel_phases: dxp (B, hop, FP) -> dy (B, L); the reflected samples fold back onto their sources.
 extern "C" int v2w_mel_phases_bwd(const float* dxp, float* dy, int B, int L, int hop, int pad, int FP, void* stream) {
     if (!dxp || !dy || B <= 0 || L <= 1 || hop <= 0 || pad < 0 || pad >= L || FP <= 0) return V2W_E_ARG;
-    int gx = (L + 255) / 256; if (gx > 1024) gx = 1024;
+    if (!mel_phase_ints_fit(L, hop, pad, FP)) return V2W_E_SHAPE;
+    int gx = (int)(((long long)L + 255) / 256); if (gx > 1024) gx = 1024;
     V2W_LAUNCH(mel_phase_bwd_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, dxp, dy, L, hop, pad, FP);
     return v2w_launch_status();
 }
