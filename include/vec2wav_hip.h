@@ -571,6 +571,38 @@ int v2w_mel_phases_bwd(const float* dxp, float* dy, int B, int L, int hop, int p
 int v2w_mel_phases_len(const float* y, float* xp, int B, int L, int hop, int pad, int FP, const int32_t* len, int len_mul, void* stream);
 int v2w_mel_finish_len(const float* spec, const float* basis, float* out, int B, int Cs, int FP, int F, int nb, int n_mels,
                        const int32_t* len, int len_mul, int hop, int n_fft, void* stream);
+/* Any frame geometry (additive: the calls above keep their conditions, kernels and bits): 1 <= hop <= n_fft, 1 <= win <= n_fft.  The caller
+ * states every quantity; nothing is derived from another: pad samples of reflection per side (mel_spectrogram: (n_fft - hop) / 2 rounded
+ * down), left = (n_fft - win) / 2 zero weights before the window, k = ceil(win / hop) taps, CP >= hop channels (rounded up to the tile
+ * kernel's channel block), FP >= F + k - 1 columns.  Frame f multiplies the window's support only, ypad[f * hop + left + t] for t < win,
+ * so the DFT conv (v2w_conv1d_fwd, pad_left = 0) has k taps over CP channels and weights [j][p][c] = Wd[c][left + j * hop + p] for
+ * p < hop and j * hop + p < win, else 0.
+ *   v2w_mel_phases_geo:     y (B, L) -> xp (B, CP, FP): xp[b][p][f] = reflect_pad(y, pad)[f * hop + left + p] for p < hop where that index
+ *                           is below L + 2 * pad, else exactly +0.0 (the channels [hop, CP), the columns past the padded signal).
+ *   v2w_mel_phases_geo_len: item b holds Lb = min(len[b] * len_mul, L) samples and F_b = (Lb + 2 * pad - n_fft) / hop + 1 frames if Lb > pad
+ *                           and Lb + 2 * pad >= n_fft, else 0: the bits of the B = 1 v2w_mel_phases_geo call on y[b, :Lb] over that call's
+ *                           roundup4(F_b + k - 1) columns, +0.0 in the columns past them.  No load address is at or past Lb within row b.
+ *   v2w_mel_phases_geo_bwd: dxp (B, CP, FP) -> dy (B, L): the sample's own position s + pad, then its left reflection pad - s
+ *                           (1 <= s <= pad), then its right one 2 (L - 1) - s + pad (L - 1 - pad <= s <= L - 2), added in that order; the
+ *                           padded position i is dxp[b][(i - left) % hop][(i - left) / hop] for 0 <= i - left < hop * FP and 0 elsewhere.
+ *   v2w_mel_finish_geo, _geo_bwd: v2w_mel_finish and v2w_mel_finish_bwd for every nb: where those fit their 16 frames per workgroup into
+ *                           64 KiB of LDS they are called (the same kernel, the same bits); otherwise 8 frames per workgroup (nb = 1025:
+ *                           n_fft 2048), every output the same operations in the same order.
+ *   v2w_mel_finish_geo_len: v2w_mel_finish_len with pad = (n_fft - hop) / 2 rounded down and no condition on n_fft % hop or its parity.
+ * V2W_E_ARG: a NULL operand, B <= 0, L <= 1, hop < 1, n_fft < hop, win < 1, win > n_fft, CP < hop, pad < 0, pad >= L, left < 0,
+ * left + win > n_fft, k < 1, k * hop < win, FP <= 0; len == NULL or len_mul < 1; the finish calls' own.  V2W_E_SHAPE: B > 65535; CP * FP,
+ * hop * FP + left or L + 2 * pad past 2^31 - 1; nb > 2048 (finish, _len) or nb + n_mels > 2048 (backward); F * hop + n_fft past 2^31 - 1 (_len). */
+int v2w_mel_phases_geo(const float* y, float* xp, int B, int L, int n_fft, int win, int hop, int CP, int pad, int left, int k, int FP,
+                       void* stream);
+int v2w_mel_phases_geo_len(const float* y, float* xp, int B, int L, int n_fft, int win, int hop, int CP, int pad, int left, int k, int FP,
+                           const int32_t* len, int len_mul, void* stream);
+int v2w_mel_phases_geo_bwd(const float* dxp, float* dy, int B, int L, int n_fft, int win, int hop, int CP, int pad, int left, int k, int FP,
+                           void* stream);
+int v2w_mel_finish_geo(const float* spec, const float* basis, float* out, int B, int Cs, int FP, int F, int nb, int n_mels, void* stream);
+int v2w_mel_finish_geo_len(const float* spec, const float* basis, float* out, int B, int Cs, int FP, int F, int nb, int n_mels,
+                           const int32_t* len, int len_mul, int hop, int n_fft, void* stream);
+int v2w_mel_finish_geo_bwd(const float* spec, const float* basis, const float* basisT, const float* gout, float* dspec,
+                           int B, int Cs, int FP, int F, int nb, int n_mels, void* stream);
 
 /* ---- MPD / MSD discriminator forwards (models.py:158-275): the memory-bound ends; the convolutions run
  * through v2w_conv1d_fwd (in_ct / out_ct for groups, out_slope for the activated feature maps, dil = period for the (k, 1) Conv2d).
@@ -692,6 +724,10 @@ int v2w_lsgan_multi_bwd(const v2w_lsgan_item* items, int n, const float* gout, c
 int v2w_l1_masked_plan(int C, int F);        /* host only: G > 0, or a V2W_E_* code */
 int v2w_l1_masked(const float* a, const float* b, int B, int C, int F, const int32_t* len, int len_mul, int hop, int n_fft,
                   float* per_item, float* total, void* ws, void* stream);
+/* v2w_l1_masked for any 1 <= hop <= n_fft (additive): the same kernels, launches and bits, pad = (n_fft - hop) / 2 rounded down as
+ * mel_spectrogram pads; no condition on n_fft % hop or on the parity of n_fft - hop. */
+int v2w_l1_masked_geo(const float* a, const float* b, int B, int C, int F, const int32_t* len, int len_mul, int hop, int n_fft,
+                      float* per_item, float* total, void* ws, void* stream);
 
 /* ---- AdamW (additive in ABI v35; torch.optim.AdamW as train.py:96-99 constructs it and train.py:198,215 steps it: decoupled weight
  * decay, no amsgrad, no maximize): the step of up to V2W_ADAMW_MAX_ITEMS parameter tensors in ONE launch that reads p, g, m, v and

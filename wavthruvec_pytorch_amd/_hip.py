@@ -261,6 +261,14 @@ SIGNATURES = {
     'v2w_mel_finish_len': (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     'v2w_l1_masked_plan': (C.c_int, [C.c_int, C.c_int]),
     'v2w_l1_masked': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp]),
+    # the same for any STFT frame geometry (win <= n_fft, 1 <= hop <= n_fft): n_fft, win, hop, CP, pad, left, k, FP are all the caller's
+    'v2w_mel_phases_geo': (C.c_int, [_fp, _fp] + [C.c_int] * 10 + [_fp]),
+    'v2w_mel_phases_geo_len': (C.c_int, [_fp, _fp] + [C.c_int] * 10 + [_fp, C.c_int, _fp]),
+    'v2w_mel_phases_geo_bwd': (C.c_int, [_fp, _fp] + [C.c_int] * 10 + [_fp]),
+    'v2w_mel_finish_geo': (C.c_int, [_fp, _fp, _fp] + [C.c_int] * 6 + [_fp]),
+    'v2w_mel_finish_geo_len': (C.c_int, [_fp, _fp, _fp] + [C.c_int] * 6 + [_fp, C.c_int, C.c_int, C.c_int, _fp]),
+    'v2w_mel_finish_geo_bwd': (C.c_int, [_fp] * 5 + [C.c_int] * 6 + [_fp]),
+    'v2w_l1_masked_geo': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp]),
     # GAN training losses: host descriptor arrays, read before the call returns
     'v2w_l1_multi_plan': (C.c_int, [C.POINTER(L1Pair), C.c_int, C.POINTER(C.c_int32)]),
     'v2w_l1_multi_scratch_bytes': (C.c_longlong, [C.POINTER(L1Pair), C.c_int]),

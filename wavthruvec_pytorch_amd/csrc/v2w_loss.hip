@@ -412,10 +412,11 @@ extern "C" int v2w_l1_masked_plan(int C, int F) {
     return g < 1 ? 1 : (g > kMaskedMaxWgs ? kMaskedMaxWgs : (int)g);
 }
 
-extern "C" int v2w_l1_masked(const float* a, const float* b, int B, int C, int F, const int32_t* len, int len_mul, int hop, int n_fft,
-                             float* per_item, float* total, void* ws, void* stream) {
-    if (!a || !b || !len || !ws || (!per_item && !total) || B <= 0 || len_mul < 1 || hop < 1 || n_fft < hop || n_fft % hop || (n_fft - hop) % 2)
-        return V2W_E_ARG;
+// geo: any 1 <= hop <= n_fft (v2w_l1_masked_geo); the kernels' frame count, pad = (n_fft - hop) / 2 rounded down, is the same
+static int l1_masked(const float* a, const float* b, int B, int C, int F, const int32_t* len, int len_mul, int hop, int n_fft,
+                     float* per_item, float* total, void* ws, void* stream, bool geo) {
+    if (!a || !b || !len || !ws || (!per_item && !total) || B <= 0 || len_mul < 1 || hop < 1 || n_fft < hop) return V2W_E_ARG;
+    if (!geo && (n_fft % hop || (n_fft - hop) % 2)) return V2W_E_ARG;
     if (!ptr4(a) || !ptr4(b) || (reinterpret_cast<uintptr_t>(ws) & 7)) return V2W_E_ARG;
     const int G = v2w_l1_masked_plan(C, F);
     if (G < 0) return G;
@@ -428,6 +429,16 @@ extern "C" int v2w_l1_masked(const float* a, const float* b, int B, int C, int F
         V2W_LAUNCH(l1_masked_kernel<false>, dim3(G, B), dim3(kThreads), 0, st, a, b, len, len_mul, hop, n_fft, C, F, part);
     V2W_LAUNCH(l1_masked_finish_kernel, dim3(1), dim3(kThreads), 0, st, part, len, len_mul, hop, n_fft, B, C, F, G, per_item, total);
     return v2w_launch_status();
+}
+
+extern "C" int v2w_l1_masked(const float* a, const float* b, int B, int C, int F, const int32_t* len, int len_mul, int hop, int n_fft,
+                             float* per_item, float* total, void* ws, void* stream) {
+    return l1_masked(a, b, B, C, F, len, len_mul, hop, n_fft, per_item, total, ws, stream, false);
+}
+
+extern "C" int v2w_l1_masked_geo(const float* a, const float* b, int B, int C, int F, const int32_t* len, int len_mul, int hop, int n_fft,
+                                 float* per_item, float* total, void* ws, void* stream) {
+    return l1_masked(a, b, B, C, F, len, len_mul, hop, n_fft, per_item, total, ws, stream, true);
 }
 
 extern "C" int v2w_lsgan_multi(const v2w_lsgan_item* items, int n, float* term, float* total, void* stream) {

@@ -208,6 +208,169 @@ inline bool mel_phase_ints_fit(int L, int hop, int pad, int FP) {
     return (long long)hop * FP <= 0x7fffffffll && (long long)L + 2ll * pad <= 0x7fffffffll;
 }
 
+// ---- any STFT frame geometry (win <= n_fft, 1 <= hop <= n_fft; include/vec2wav_hip.h, "any frame geometry").  Frame f multiplies the
+// window's support only, ypad[f*hop + left + t] for t < win, so with Xg[b][p][f] = ypad[b][f*hop + left + p] (p < hop) the DFT conv has
+// k = ceil(win / hop) taps over CP >= hop input channels; the channels [hop, CP) are zeros (the tile kernel's channel blocks).  Nothing
+// here is derived from anything else: hop, CP, pad, left, k, n_fft are the caller's (v2w_mel_geo_ok checks them on the host).
+
+// LEN: the reflection about the item's own last sample, 0 from column roundup4(F_b + k - 1) on; every load index s satisfies 0 <= s < Lb
+template <bool LEN>
+__global__ void __launch_bounds__(256)
+mel_phase_geo_kernel(const float* __restrict__ y, float* __restrict__ xp, const int32_t* __restrict__ len, int len_mul,
+                     int L, int hop, int CP, int pad, int left, int k, int n_fft, int FP) {
+    const int b = blockIdx.y;
+    int Lb = L, FPb = FP;
+    if (LEN) {
+        Lb = mel_item_samples(len, b, len_mul, L);
+        const int Fb = mel_item_frames(Lb, hop, pad, n_fft);
+        FPb = Fb > 0 ? (Fb + k - 1 + 3) / 4 * 4 : 0;
+    }
+    const int Lp = Lb + 2 * pad;
+    for (int idx = blockIdx.x * 256 + threadIdx.x; idx < CP * FP; idx += gridDim.x * 256) {
+        const int p = idx / FP, f = idx - p * FP;
+        float v = 0.f;
+        if (p < hop && f < FPb) {
+            const int i = f * hop + left + p;
+            if (i < Lp) {
+                int s = i - pad;
+                s = s < 0 ? -s : (s >= Lb ? 2 * (Lb - 1) - s : s);   // -s <= pad < Lb;  2(Lb-1) - s >= Lb - 1 - pad >= 0
+                v = y[(size_t)b * L + s];
+            }
+        }
+        xp[((size_t)b * CP + p) * FP + f] = v;
+    }
+}
+
+// Backward of mel_phase_geo_kernel<false>: the padded position i is Xg[(i - left) % hop][(i - left) / hop] where 0 <= i - left < hop * FP,
+// and is read by nothing elsewhere.  The sample itself, then the left reflection, then the right one, as mel_phase_bwd_kernel adds them.
+__global__ void __launch_bounds__(256)
+mel_phase_geo_bwd_kernel(const float* __restrict__ dxp, float* __restrict__ dy, int L, int hop, int CP, int pad, int left, int FP) {
+    const int b = blockIdx.y;
+    const float* xb = dxp + (size_t)b * CP * FP;
+    auto at = [&](int i) {
+        const int q = i - left;
+        return (q >= 0 && q / hop < FP) ? xb[(size_t)(q % hop) * FP + q / hop] : 0.f;
+    };
+    for (int s = blockIdx.x * 256 + threadIdx.x; s < L; s += gridDim.x * 256) {
+        float v = at(s + pad);
+        if (s >= 1 && s <= pad) v += at(pad - s);
+        if (s >= L - 1 - pad && s <= L - 2) v += at(2 * (L - 1) - s + pad);
+        dy[(size_t)b * L + s] = v;
+    }
+}
+
+// mel_finish_kernel / mel_finish_len_kernel on 8 frames per workgroup, for the bin counts whose 16-frame block passes 64 KiB of LDS
+// (nb = 1025: n_fft 2048).  Every output is the same chain of operations in the same order: fmaf over the bins c = 0 .. nb - 1.
+#define V2W_MEL_FT8 8
+template <bool LEN>
+__global__ void __launch_bounds__(256)
+mel_finish8_kernel(const float* __restrict__ spec, const float* __restrict__ basis, float* __restrict__ out,
+                   const int32_t* __restrict__ len, int len_mul, int hop, int n_fft, int Cs, int FP, int F, int nb, int n_mels) {
+    extern __shared__ float mag[];                     // [nb][V2W_MEL_FT8]
+    const int b = blockIdx.y, f0 = blockIdx.x * V2W_MEL_FT8;
+    int Fb = F;
+    if (LEN) {
+        const int pad = (n_fft - hop) / 2;
+        const long long n = (long long)len[b] * len_mul;
+        const long long nmax = (long long)F * hop + n_fft;
+        Fb = mel_item_frames((int)(n < 0 ? 0 : (n > nmax ? nmax : n)), hop, pad, n_fft);
+        Fb = Fb < F ? Fb : F;
+        if (f0 >= Fb) {                                // (uniform over the workgroup) zeros, spec unread
+            for (int idx = threadIdx.x; idx < n_mels * V2W_MEL_FT8; idx += 256) {
+                const int m = idx / V2W_MEL_FT8, f = f0 + idx % V2W_MEL_FT8;
+                if (f < F) out[((size_t)b * n_mels + m) * F + f] = 0.f;
+            }
+            return;
+        }
+    }
+    const float* sb = spec + (size_t)b * Cs * FP;
+    for (int idx = threadIdx.x; idx < nb * V2W_MEL_FT8; idx += 256) {
+        const int c = idx / V2W_MEL_FT8, f = f0 + idx % V2W_MEL_FT8;
+        float m = 0.f;
+        if (f < Fb) {
+            const float re = sb[(size_t)c * FP + f], im = sb[(size_t)(nb + c) * FP + f];
+            m = sqrtf(re * re + im * im + 1e-9f);
+        }
+        mag[idx] = m;
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < n_mels * V2W_MEL_FT8; idx += 256) {
+        const int m = idx / V2W_MEL_FT8, ff = idx - m * V2W_MEL_FT8;
+        const int f = f0 + ff;
+        if (f >= F) continue;
+        float v = 0.f;
+        if (f < Fb) {
+            const float* br = basis + (size_t)m * nb;
+            float acc = 0.f;
+            for (int c = 0; c < nb; ++c) acc = fmaf(br[c], mag[c * V2W_MEL_FT8 + ff], acc);
+            v = logf(fmaxf(acc, 1e-5f));
+        }
+        out[((size_t)b * n_mels + m) * F + f] = v;
+    }
+}
+
+// mel_finish_bwd_kernel on 8 frames per workgroup
+__global__ void __launch_bounds__(256)
+mel_finish8_bwd_kernel(const float* __restrict__ spec, const float* __restrict__ basis, const float* __restrict__ basisT,
+                       const float* __restrict__ gout, float* __restrict__ dspec, int Cs, int FP, int F, int nb, int n_mels) {
+    extern __shared__ float mag[];                     // [nb][FT8] then d_acc [n_mels][FT8]
+    float* dacc = mag + (size_t)nb * V2W_MEL_FT8;
+    const int b = blockIdx.y, f0 = blockIdx.x * V2W_MEL_FT8;
+    const float* sb = spec + (size_t)b * Cs * FP;
+    float* db = dspec + (size_t)b * Cs * FP;
+    for (int idx = threadIdx.x; idx < nb * V2W_MEL_FT8; idx += 256) {
+        const int c = idx / V2W_MEL_FT8, f = f0 + idx % V2W_MEL_FT8;
+        float m = 1.f;
+        if (f < F) {
+            const float re = sb[(size_t)c * FP + f], im = sb[(size_t)(nb + c) * FP + f];
+            m = sqrtf(re * re + im * im + 1e-9f);
+        }
+        mag[idx] = m;
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < n_mels * V2W_MEL_FT8; idx += 256) {
+        const int m = idx / V2W_MEL_FT8, ff = idx - m * V2W_MEL_FT8;
+        const int f = f0 + ff;
+        float d = 0.f;
+        if (f < F) {
+            const float* br = basis + (size_t)m * nb;
+            float acc = 0.f;
+            for (int c = 0; c < nb; ++c) acc = fmaf(br[c], mag[c * V2W_MEL_FT8 + ff], acc);
+            if (acc >= 1e-5f) d = gout[((size_t)b * n_mels + m) * F + f] / acc;
+        }
+        dacc[idx] = d;
+    }
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < nb * V2W_MEL_FT8; idx += 256) {
+        const int c = idx / V2W_MEL_FT8, ff = idx - c * V2W_MEL_FT8;
+        const int f = f0 + ff;
+        if (f >= F) continue;
+        const float* bt = basisT + (size_t)c * n_mels;
+        float dm = 0.f;
+        for (int m = 0; m < n_mels; ++m) dm = fmaf(bt[m], dacc[m * V2W_MEL_FT8 + ff], dm);
+        const float s = dm / mag[idx];
+        db[(size_t)c * FP + f] = s * sb[(size_t)c * FP + f];
+        db[(size_t)(nb + c) * FP + f] = s * sb[(size_t)(nb + c) * FP + f];
+    }
+}
+
+// The geometry of the three v2w_mel_phases_geo* calls: 0, V2W_E_ARG or V2W_E_SHAPE (the kernels' int arithmetic: CP * FP, the padded
+// position (FP - 1) * hop + left + hop - 1 and L + 2 * pad)
+inline int mel_geo_ok(int B, int L, int n_fft, int win, int hop, int CP, int pad, int left, int k, int FP) {
+    if (B <= 0 || L <= 1 || hop < 1 || n_fft < hop || win < 1 || win > n_fft || CP < hop || pad < 0 || pad >= L || left < 0 ||
+        left > n_fft - win || k < 1 || (long long)k * hop < win || FP <= 0) return V2W_E_ARG;
+    if (B > 65535) return V2W_E_SHAPE;                        // (grid.y)
+    if ((long long)CP * FP > 0x7fffffffll || (long long)hop * FP + left > 0x7fffffffll || (long long)L + 2ll * pad > 0x7fffffffll)
+        return V2W_E_SHAPE;
+    return 0;
+}
+
+inline int mel_finish_args_ok(const void* spec, const void* basis, const void* out, int B, int Cs, int FP, int F, int nb, int n_mels) {
+    if (!spec || !basis || !out || B <= 0 || F <= 0 || FP < F || nb <= 0 || Cs < 2 * nb || n_mels <= 0) return V2W_E_ARG;
+    if ((long long)n_mels * V2W_MEL_FT > 0x7fffffffll || B > 65535) return V2W_E_SHAPE;
+    return 0;
+}
+
 }  // namespace
 
 // y (B, L) -> xp (B, hop, FP); FP >= F + n_fft/hop - 1 frames columns (F = number of STFT frames), pad = (n_fft - hop)/2.
@@ -271,5 +434,79 @@ extern "C" int v2w_mel_phases_bwd(const float* dxp, float* dy, int B, int L, int
     if (!mel_phase_ints_fit(L, hop, pad, FP)) return V2W_E_SHAPE;
     int gx = (int)(((long long)L + 255) / 256); if (gx > 1024) gx = 1024;
     V2W_LAUNCH(mel_phase_bwd_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, dxp, dy, L, hop, pad, FP);
+    return v2w_launch_status();
+}
+
+// ---- any frame geometry (include/vec2wav_hip.h): y (B, L) -> xp (B, CP, FP), xp[b][p][f] = ypad[b][f*hop + left + p] for p < hop, else 0
+extern "C" int v2w_mel_phases_geo(const float* y, float* xp, int B, int L, int n_fft, int win, int hop, int CP, int pad, int left, int k,
+                                  int FP, void* stream) {
+    if (!y || !xp) return V2W_E_ARG;
+    if (const int rc = mel_geo_ok(B, L, n_fft, win, hop, CP, pad, left, k, FP)) return rc;
+    int gx = (int)(((long long)CP * FP + 255) / 256); if (gx > 1024) gx = 1024;
+    V2W_LAUNCH(mel_phase_geo_kernel<false>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, y, xp, static_cast<const int32_t*>(nullptr), 1,
+                       L, hop, CP, pad, left, k, n_fft, FP);
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_mel_phases_geo_len(const float* y, float* xp, int B, int L, int n_fft, int win, int hop, int CP, int pad, int left, int k,
+                                      int FP, const int32_t* len, int len_mul, void* stream) {
+    if (!y || !xp || !len || len_mul < 1) return V2W_E_ARG;
+    if (const int rc = mel_geo_ok(B, L, n_fft, win, hop, CP, pad, left, k, FP)) return rc;
+    int gx = (int)(((long long)CP * FP + 255) / 256); if (gx > 1024) gx = 1024;
+    V2W_LAUNCH(mel_phase_geo_kernel<true>, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, y, xp, len, len_mul,
+                       L, hop, CP, pad, left, k, n_fft, FP);
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_mel_phases_geo_bwd(const float* dxp, float* dy, int B, int L, int n_fft, int win, int hop, int CP, int pad, int left, int k,
+                                      int FP, void* stream) {
+    if (!dxp || !dy) return V2W_E_ARG;
+    if (const int rc = mel_geo_ok(B, L, n_fft, win, hop, CP, pad, left, k, FP)) return rc;
+    int gx = (int)(((long long)L + 255) / 256); if (gx > 1024) gx = 1024;
+    V2W_LAUNCH(mel_phase_geo_bwd_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)stream, dxp, dy, L, hop, CP, pad, left, FP);
+    return v2w_launch_status();
+}
+
+// v2w_mel_finish for any nb whose 8-frame block fits 64 KiB of LDS: the 16-frame kernel (and its bits) wherever v2w_mel_finish takes it
+extern "C" int v2w_mel_finish_geo(const float* spec, const float* basis, float* out, int B, int Cs, int FP, int F, int nb, int n_mels,
+                                  void* stream) {
+    if (const int rc = mel_finish_args_ok(spec, basis, out, B, Cs, FP, F, nb, n_mels)) return rc;
+    if ((size_t)nb * V2W_MEL_FT * sizeof(float) <= 64 * 1024) return v2w_mel_finish(spec, basis, out, B, Cs, FP, F, nb, n_mels, stream);
+    const size_t lds = (size_t)nb * V2W_MEL_FT8 * sizeof(float);
+    if (lds > 64 * 1024) return V2W_E_SHAPE;
+    V2W_LAUNCH(mel_finish8_kernel<false>, dim3((F + V2W_MEL_FT8 - 1) / V2W_MEL_FT8, B), dim3(256), lds, (hipStream_t)stream,
+                       spec, basis, out, static_cast<const int32_t*>(nullptr), 1, 1, 1, Cs, FP, F, nb, n_mels);
+    return v2w_launch_status();
+}
+
+// v2w_mel_finish_len without its conditions on n_fft / hop: pad = (n_fft - hop) / 2 rounded down, as mel_spectrogram pads
+extern "C" int v2w_mel_finish_geo_len(const float* spec, const float* basis, float* out, int B, int Cs, int FP, int F, int nb, int n_mels,
+                                      const int32_t* len, int len_mul, int hop, int n_fft, void* stream) {
+    if (const int rc = mel_finish_args_ok(spec, basis, out, B, Cs, FP, F, nb, n_mels)) return rc;
+    if (!len || len_mul < 1 || hop < 1 || n_fft < hop) return V2W_E_ARG;
+    if ((long long)F * hop + n_fft > 0x7fffffffll) return V2W_E_SHAPE;         // (the kernel's sample count of F frames is an int)
+    size_t lds = (size_t)nb * V2W_MEL_FT * sizeof(float);
+    if (lds <= 64 * 1024) {
+        V2W_LAUNCH(mel_finish_len_kernel, dim3((F + V2W_MEL_FT - 1) / V2W_MEL_FT, B), dim3(256), lds, (hipStream_t)stream,
+                           spec, basis, out, len, len_mul, hop, n_fft, Cs, FP, F, nb, n_mels);
+        return v2w_launch_status();
+    }
+    lds = (size_t)nb * V2W_MEL_FT8 * sizeof(float);
+    if (lds > 64 * 1024) return V2W_E_SHAPE;
+    V2W_LAUNCH(mel_finish8_kernel<true>, dim3((F + V2W_MEL_FT8 - 1) / V2W_MEL_FT8, B), dim3(256), lds, (hipStream_t)stream,
+                       spec, basis, out, len, len_mul, hop, n_fft, Cs, FP, F, nb, n_mels);
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_mel_finish_geo_bwd(const float* spec, const float* basis, const float* basisT, const float* gout, float* dspec,
+                                      int B, int Cs, int FP, int F, int nb, int n_mels, void* stream) {
+    if (!basisT || !gout) return V2W_E_ARG;
+    if (const int rc = mel_finish_args_ok(spec, basis, dspec, B, Cs, FP, F, nb, n_mels)) return rc;
+    if ((size_t)(nb + n_mels) * V2W_MEL_FT * sizeof(float) <= 64 * 1024)
+        return v2w_mel_finish_bwd(spec, basis, basisT, gout, dspec, B, Cs, FP, F, nb, n_mels, stream);
+    const size_t lds = (size_t)(nb + n_mels) * V2W_MEL_FT8 * sizeof(float);
+    if (lds > 64 * 1024) return V2W_E_SHAPE;
+    V2W_LAUNCH(mel_finish8_bwd_kernel, dim3((F + V2W_MEL_FT8 - 1) / V2W_MEL_FT8, B), dim3(256), lds, (hipStream_t)stream,
+                       spec, basis, basisT, gout, dspec, Cs, FP, F, nb, n_mels);
     return v2w_launch_status();
 }

@@ -7,7 +7,10 @@ back-propagates through it, train.py:204).
 
 The STFT runs as ONE fused Conv1d on the f32 MFMA tile kernel: the reflect-padded signal is de-interleaved by hop phase
 (`v2w_mel_phases`), the windowed DFT rows are the conv weights (hop input channels x n_fft/hop taps), and `v2w_mel_finish`
-does magnitude -> filterbank -> log.  Batches of unequal lengths (the reference's validation loop, batched: validate.py) take the per-item
+does magnitude -> filterbank -> log.  That is the reference geometry 1024 / 256 / 1024 and its like (win_size == n_fft, n_fft % hop_size == 0,
+hop_size % 32 == 0).  Every other geometry with 1 <= hop_size <= n_fft, 1 <= win_size <= n_fft <= 2048 takes the `v2w_mel_*_geo` siblings of
+the two ends (`stft_geometry`): the conv then contracts over the window's support only - ceil(win_size / hop_size) taps over hop_size channels
+rounded up to 32, the first of them `left = (n_fft - win_size) // 2` samples into the frame.  Batches of unequal lengths (the reference's validation loop, batched: validate.py) take the per-item
 form of the two ends (`lengths=`) and the masked L1 `mel_l1`.  Constants (DFT rows, hann window, Slaney mel filterbank = librosa.filters.mel of the
 reference's librosa, restated because librosa is not a dependency here) are built once per configuration with numpy in fp64.
 """
@@ -52,25 +55,59 @@ def mel_filterbank(sr, n_fft, n_mels, fmin=0.0, fmax=None):
     return w.astype(np.float32)
 
 
+MAX_N_FFT = 2048        # nb = 1025 bins: what the finish kernels' 8-frame block holds in 64 KiB of LDS next to 80 mels
+CHANNEL_BLOCK = 32      # the DFT conv's input channels: C_in % 32 == 0 is what the f32 tile kernel's wide configurations take (v2w_layer_cfg)
+
+
+def stft_geometry(n_fft, hop_size, win_size):
+    """The frame geometry of `mel_spectrogram` (host only, no GPU): the reference's arithmetic (dataset.py:66-70) for any 1 <= hop_size <= n_fft,
+    1 <= win_size <= n_fft <= 2048, a ValueError that names the condition otherwise.
+      pad   samples of reflection per side, int((n_fft - hop_size) / 2): rounded down when the difference is odd
+      left  zero weights before the window inside a frame, (n_fft - win_size) // 2 (torch.stft centres a short window)
+      k     taps of the DFT conv: frame f multiplies ypad[f * hop + left + t] for t < win_size only, so k = ceil(win_size / hop_size)
+      cp    its input channels: hop_size rounded up to CHANNEL_BLOCK; the channels [hop_size, cp) are zeros on both operands
+      nb    bins, n_fft // 2 + 1;  cs: the 2 nb DFT rows rounded up to the conv tile's row block (64)
+      old   win_size == n_fft, n_fft % hop_size == 0, hop_size % 32 == 0: the geometries the first entry points serve (and keep serving)"""
+    n_fft, hop, win = int(n_fft), int(hop_size), int(win_size)
+    if not 1 <= n_fft <= MAX_N_FFT:
+        raise ValueError(f'mel_spectrogram (HIP): needs 1 <= n_fft <= {MAX_N_FFT}, got n_fft = {n_fft}')
+    if not 1 <= hop <= n_fft:
+        raise ValueError(f'mel_spectrogram (HIP): needs 1 <= hop_size <= n_fft, got hop_size = {hop}, n_fft = {n_fft}')
+    if not 1 <= win <= n_fft:
+        raise ValueError(f'mel_spectrogram (HIP): needs 1 <= win_size <= n_fft, got win_size = {win}, n_fft = {n_fft}')
+    nb = n_fft // 2 + 1
+    return dict(n_fft=n_fft, hop=hop, win=win, pad=int((n_fft - hop) / 2), left=(n_fft - win) // 2, k=-(-win // hop),
+                cp=-(-hop // CHANNEL_BLOCK) * CHANNEL_BLOCK, nb=nb, cs=(2 * nb + 63) // 64 * 64,
+                old=win == n_fft and n_fft % hop == 0 and hop % 32 == 0)
+
+
+def dft_conv_weights(n_fft, hop_size, win_size):
+    """-> (geometry, w): the windowed DFT rows as the DFT conv's weights, numpy fp64 (host only).  w[j][p][c] = Wd[c][left + j * hop + p] for
+    p < hop and j * hop + p < win_size, else 0; rows c < nb are cos(2 pi c n / n_fft) * hann(n - left), rows nb <= c < 2 nb the -sin ones,
+    the rest (up to cs) zeros.  With xg[p][f] = ypad[f * hop + left + p]:  S[c][f] = sum_{j < k} sum_{p < hop} w[j][p][c] * xg[p][f + j]."""
+    g = stft_geometry(n_fft, hop_size, win_size)
+    n_fft, hop, win, nb, k, cs = g['n_fft'], g['hop'], g['win'], g['nb'], g['k'], g['cs']
+    t = np.arange(k * hop, dtype=np.float64)                    # offset into the window's support (the last tap may run past it)
+    hann = np.where(t < win, 0.5 - 0.5 * np.cos(2.0 * np.pi * t / win), 0.0)           # torch.hann_window(win_size): periodic
+    if win == 1:
+        hann[0] = 1.0                                           # (torch.hann_window(1) is [1.])
+    ang = 2.0 * np.pi * np.outer(np.arange(nb, dtype=np.float64), t + g['left']) / n_fft
+    wd = np.zeros((cs, k * hop), dtype=np.float64)
+    wd[:nb] = np.cos(ang) * hann
+    wd[nb:2 * nb] = -np.sin(ang) * hann
+    w = np.zeros((k, g['cp'], cs), dtype=np.float64)
+    w[:, :hop, :] = wd.reshape(cs, k, hop).transpose(1, 2, 0)   # [tap j][channel p][row c] = Wd[c][j*hop + p]
+    return g, w
+
+
 def _constants(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, device):
     key = (n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, str(device))
     c = _CONSTS.get(key)
     if c is None:
-        if n_fft % hop_size or hop_size % 32 or win_size != n_fft:
-            raise NotImplementedError('mel_spectrogram (HIP): needs win_size == n_fft, n_fft % hop_size == 0 and hop_size % 32 == 0 '
-                                      '(the reference configuration: 1024 / 256 / 1024)')
-        nb, k = n_fft // 2 + 1, n_fft // hop_size
-        cs = (2 * nb + 63) // 64 * 64                           # DFT rows padded to the conv tile's row block
-        t = np.arange(n_fft, dtype=np.float64)
-        win = 0.5 - 0.5 * np.cos(2.0 * np.pi * t / win_size)    # torch.hann_window(win_size): periodic
-        ang = 2.0 * np.pi * np.outer(np.arange(nb, dtype=np.float64), t) / n_fft
-        wd = np.zeros((cs, n_fft), dtype=np.float64)
-        wd[:nb] = np.cos(ang) * win
-        wd[nb:2 * nb] = -np.sin(ang) * win
-        # conv weights [tap j][channel p][row c] = Wd[c][j*hop + p]
-        wf = torch.from_numpy(np.ascontiguousarray(wd.reshape(cs, k, hop_size).transpose(1, 2, 0)).astype(np.float32)).to(device)
-        c = dict(nb=nb, k=k, cs=cs, wf=wf, wp=hipops.pack_mfma(wf),
-                 basis=torch.from_numpy(mel_filterbank(sampling_rate, n_fft, num_mels, fmin, fmax)).to(device))
+        g, w = dft_conv_weights(n_fft, hop_size, win_size)
+        wf = torch.from_numpy(np.ascontiguousarray(w).astype(np.float32)).to(device)
+        c = dict(g, wf=wf, wp=hipops.pack_mfma(wf),
+                 basis=torch.from_numpy(mel_filterbank(sampling_rate, g['n_fft'], num_mels, fmin, fmax)).to(device))
         _CONSTS[key] = c
     return c
 
@@ -119,34 +156,71 @@ def _lengths_buffer(src, device):
     return buf
 
 
+def _geo_args(c, B, L, FP):
+    """The leading integers of the three v2w_mel_phases_geo* calls."""
+    return B, L, c['n_fft'], c['win'], c['hop'], c['cp'], c['pad'], c['left'], c['k'], FP
+
+
 def _forward(y, cfg, lens=None, len_mul=1):
     """-> (out, spec, geometry): the three launches of the forward; `spec` is what the backward needs.  lens (B int32 on the device): the
-    per-item form of the two ends (forward only); the DFT conv between them runs on the whole padded batch either way."""
+    per-item form of the two ends (forward only); the DFT conv between them runs on the whole padded batch either way.  A geometry the first
+    entry points serve (stft_geometry: `old`) keeps them, and with them its bits; the others take the v2w_mel_*_geo calls."""
     n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax = cfg
     B, L = y.shape
     c = _constants(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, y.device)
-    pad = int((n_fft - hop_size) / 2)
+    pad, hop = c['pad'], c['hop']
     if pad >= L:
         raise RuntimeError('mel_spectrogram: reflect padding needs more than (n_fft - hop)/2 samples')
-    F = (L + 2 * pad - n_fft) // hop_size + 1
+    if L + 2 * pad < c['n_fft']:
+        raise RuntimeError('mel_spectrogram: the padded signal is shorter than one frame of n_fft samples')
+    F = (L + 2 * pad - c['n_fft']) // hop + 1
     FP = (F + c['k'] - 1 + 3) // 4 * 4
     lib, st = _hip.load(), torch.cuda.current_stream(y.device).cuda_stream
-    xp = torch.empty((B, hop_size, FP), device=y.device)
-    if lens is None:
-        _hip.check(lib.v2w_mel_phases(y.data_ptr(), xp.data_ptr(), B, L, hop_size, pad, FP, st), 'v2w_mel_phases')
+    xp = torch.empty((B, c['cp'], FP), device=y.device)
+    if c['old']:
+        if lens is None:
+            _hip.check(lib.v2w_mel_phases(y.data_ptr(), xp.data_ptr(), B, L, hop, pad, FP, st), 'v2w_mel_phases')
+        else:
+            _hip.check(lib.v2w_mel_phases_len(y.data_ptr(), xp.data_ptr(), B, L, hop, pad, FP, lens.data_ptr(), len_mul, st),
+                       'v2w_mel_phases_len')
+    elif lens is None:
+        _hip.check(lib.v2w_mel_phases_geo(y.data_ptr(), xp.data_ptr(), *_geo_args(c, B, L, FP), st), 'v2w_mel_phases_geo')
     else:
-        _hip.check(lib.v2w_mel_phases_len(y.data_ptr(), xp.data_ptr(), B, L, hop_size, pad, FP, lens.data_ptr(), len_mul, st),
-                   'v2w_mel_phases_len')
+        _hip.check(lib.v2w_mel_phases_geo_len(y.data_ptr(), xp.data_ptr(), *_geo_args(c, B, L, FP), lens.data_ptr(), len_mul, st),
+                   'v2w_mel_phases_geo_len')
     spec = torch.empty((B, c['cs'], FP), device=y.device)
     hipops.conv1d(xp, c['wf'], None, spec, k=c['k'], dil=1, slope=1.0, pad_left=0, wp=c['wp'])
     out = torch.empty((B, num_mels, F), device=y.device)
+    old = c['old'] and c['nb'] * 64 <= 65536                  # (16 frames x 4 bytes per bin of the first kernels' LDS block)
+    fin = (spec.data_ptr(), c['basis'].data_ptr(), out.data_ptr(), B, c['cs'], FP, F, c['nb'], num_mels)
     if lens is None:
-        _hip.check(lib.v2w_mel_finish(spec.data_ptr(), c['basis'].data_ptr(), out.data_ptr(), B, c['cs'], FP, F, c['nb'], num_mels, st),
-                   'v2w_mel_finish')
+        name = 'v2w_mel_finish' if old else 'v2w_mel_finish_geo'
+        _hip.check(getattr(lib, name)(*fin, st), name)
     else:
-        _hip.check(lib.v2w_mel_finish_len(spec.data_ptr(), c['basis'].data_ptr(), out.data_ptr(), B, c['cs'], FP, F, c['nb'], num_mels,
-                                          lens.data_ptr(), len_mul, hop_size, n_fft, st), 'v2w_mel_finish_len')
+        name = 'v2w_mel_finish_len' if old else 'v2w_mel_finish_geo_len'
+        _hip.check(getattr(lib, name)(*fin, lens.data_ptr(), len_mul, hop, c['n_fft'], st), name)
     return out, spec, (B, L, pad, F, FP)
+
+
+BWD_ROWS = 128         # DFT rows per launch of the input-gradient conv at the geometries the `_geo` calls serve (see _dft_conv_bwd)
+
+
+def _dft_conv_bwd(c, dspec, dxp):
+    """dspec (B, cs, FP) -> dxp (B, cp, FP): the DFT conv's input gradient.  One launch at the geometries the first entry points serve (their
+    bits).  Elsewhere the cs rows go BWD_ROWS at a time, each launch adding its sum to dxp (`accumulate`): a dot product of k * cs fp32
+    terms added in one chain drifts by about sqrt(k * cs / 2) roundings (51 at 1024 / 120 / 600, 72 at n_fft 2048), which put d y at 7.7 and
+    4.8 times the float32 gap of torch.stft's FFT there; chains of k * BWD_ROWS terms joined by cs / BWD_ROWS additions bring it to 2.4 and
+    1.6 (64 rows per launch measure the same, 256 rows 3.3 and 1.8: DESIGN.md 3d''')."""
+    k, cs = c['k'], c['cs']
+    if c['old'] or cs <= BWD_ROWS:
+        hipops.conv1d(dspec, c['wT'], None, dxp, k=k, dil=1, slope=1.0, pad_left=k - 1, wp=c['wTp'])
+        return
+    if 'wT_rows' not in c:
+        parts = [c['wT'][:, r:r + BWD_ROWS, :].contiguous() for r in range(0, cs, BWD_ROWS)]
+        c['wT_rows'] = [(w, hipops.pack_mfma(w)) for w in parts]
+    for i, (w, wp) in enumerate(c['wT_rows']):
+        r = i * BWD_ROWS
+        hipops.conv1d(dspec[:, r:r + BWD_ROWS], w, None, dxp, k=k, dil=1, slope=1.0, pad_left=k - 1, wp=wp, in_ct=cs, accumulate=i > 0)
 
 
 def _backward(g, spec, geom, cfg):
@@ -157,19 +231,23 @@ def _backward(g, spec, geom, cfg):
     dev = spec.device
     c = _constants(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, dev)
     if 'wT' not in c:
-        # wT[j'][row c][phase p] = Wd[c][(k-1-j')*hop + p]
+        # wT[j'][row c][phase p] = Wd[c][left + (k-1-j')*hop + p]
         c['wT'] = c['wf'].flip(0).transpose(1, 2).contiguous()
         c['wTp'] = hipops.pack_mfma(c['wT'])
         c['basisT'] = c['basis'].t().contiguous()
     lib, st = _hip.load(), torch.cuda.current_stream(dev).cuda_stream
     g = g.contiguous().float()
     dspec = torch.zeros_like(spec)
-    _hip.check(lib.v2w_mel_finish_bwd(spec.data_ptr(), c['basis'].data_ptr(), c['basisT'].data_ptr(), g.data_ptr(), dspec.data_ptr(),
-                                      B, c['cs'], FP, F, c['nb'], num_mels, st), 'v2w_mel_finish_bwd')
-    dxp = torch.empty((B, hop_size, FP), device=dev)
-    hipops.conv1d(dspec, c['wT'], None, dxp, k=c['k'], dil=1, slope=1.0, pad_left=c['k'] - 1, wp=c['wTp'])
+    name = 'v2w_mel_finish_bwd' if c['old'] and (c['nb'] + num_mels) * 64 <= 65536 else 'v2w_mel_finish_geo_bwd'
+    _hip.check(getattr(lib, name)(spec.data_ptr(), c['basis'].data_ptr(), c['basisT'].data_ptr(), g.data_ptr(), dspec.data_ptr(),
+                                  B, c['cs'], FP, F, c['nb'], num_mels, st), name)
+    dxp = torch.empty((B, c['cp'], FP), device=dev)
+    _dft_conv_bwd(c, dspec, dxp)
     dy = torch.empty((B, L), device=dev)
-    _hip.check(lib.v2w_mel_phases_bwd(dxp.data_ptr(), dy.data_ptr(), B, L, hop_size, pad, FP, st), 'v2w_mel_phases_bwd')
+    if c['old']:
+        _hip.check(lib.v2w_mel_phases_bwd(dxp.data_ptr(), dy.data_ptr(), B, L, c['hop'], pad, FP, st), 'v2w_mel_phases_bwd')
+    else:
+        _hip.check(lib.v2w_mel_phases_geo_bwd(dxp.data_ptr(), dy.data_ptr(), *_geo_args(c, B, L, FP), st), 'v2w_mel_phases_geo_bwd')
     return dy
 
 
@@ -193,12 +271,18 @@ def mel_spectrogram(y, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin,
     """y (B, L) float32 on the GPU -> (B, num_mels, frames) float32; differentiable with respect to y (the training loss
     F.l1_loss(y_mel, mel_spectrogram(y_g_hat.squeeze(1), ...)), train.py:172-174,204).
 
+    Any frame geometry with 1 <= hop_size <= n_fft and 1 <= win_size <= n_fft <= 2048 (a ValueError names the condition otherwise), with the
+    reference's arithmetic: reflect padding of int((n_fft - hop_size) / 2) samples per side, a periodic hann window of win_size samples
+    centred in the frame, (L + 2 pad - n_fft) // hop_size + 1 frames.  center=True is not implemented.  A hop_size far below 32 pays for 32
+    channels per tap.
+
     lengths (optional, no-grad only; B integers, a list or a tensor on any device) and len_mul: item b holds min(lengths[b] * len_mul, L)
     samples - a batch of generated utterances of unequal length as Generator.forward(lengths=...) returns it, len_mul = prod(upsample_rates).
     out[b, :, :F_b] is then what y[b:b+1, :n_b] alone gives (F_b = mel_frames(n_b, n_fft, hop_size)), out[b, :, F_b:] is exactly 0 - the zero
     padding of a padded target mel (dataset.py:194-218) - and y[b, n_b:] has no effect, whatever it holds."""
     if center:
         raise NotImplementedError('mel_spectrogram (HIP): center=False only (the reference never passes True)')
+    stft_geometry(n_fft, hop_size, win_size)               # ValueError outside 1 <= hop_size, win_size <= n_fft <= 2048
     src = None
     if lengths is not None:
         if y.dim() != 2:
@@ -224,11 +308,15 @@ def mel_l1(a, b, lengths, len_mul=1, *, n_fft, hop_size):
     F_i = min(mel_frames(lengths[i] * len_mul, n_fft, hop_size), F) frames.  -> (total, per_item): per_item[i] = mean |a - b| over item i's
     num_mels x F_i elements (F.l1_loss of the trimmed pair; 0 for F_i = 0), total = the mean over every valid element of the batch.
     Deterministic (fixed-order fp64 sums, no atomics); an item's value does not depend on the other items."""
+    n_fft, hop_size = int(n_fft), int(hop_size)
+    if not 1 <= hop_size <= n_fft:
+        raise ValueError(f'mel_l1: needs 1 <= hop_size <= n_fft, got hop_size = {hop_size}, n_fft = {n_fft}')
     if not (a.is_cuda and b.is_cuda):
         raise RuntimeError('mel_l1 runs on the MI355X HIP path only (no CPU fallback)')
     if a.dim() != 3 or a.shape != b.shape or a.device != b.device:
         raise ValueError('mel_l1: a and b must be (B, num_mels, F) tensors of one shape on one device')
     B, Cm, F = a.shape
+    old = n_fft % hop_size == 0 and (n_fft - hop_size) % 2 == 0           # what v2w_l1_masked takes; the same kernels either way
     len_mul = int(len_mul)
     src = check_lengths(lengths, B, None, len_mul)          # (frame counts past F are clamped to F)
     with torch.no_grad():
@@ -241,6 +329,7 @@ def mel_l1(a, b, lengths, len_mul=1, *, n_fft, hop_size):
         ws = torch.empty((B * G,), dtype=torch.float64, device=a.device)
         per_item = torch.empty((B,), device=a.device)
         total = torch.empty((1,), device=a.device)
-        _hip.check(lib.v2w_l1_masked(a.data_ptr(), b.data_ptr(), B, Cm, F, lens.data_ptr(), len_mul, hop_size, n_fft,
-                                     per_item.data_ptr(), total.data_ptr(), ws.data_ptr(), st), 'v2w_l1_masked')
+        name = 'v2w_l1_masked' if old else 'v2w_l1_masked_geo'
+        _hip.check(getattr(lib, name)(a.data_ptr(), b.data_ptr(), B, Cm, F, lens.data_ptr(), len_mul, hop_size, n_fft,
+                                      per_item.data_ptr(), total.data_ptr(), ws.data_ptr(), st), name)
     return total[0], per_item
