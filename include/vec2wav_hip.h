@@ -192,9 +192,12 @@ int v2w_conv1d_fwd_multi(const v2w_conv1d_args* a, int n, void* stream);
 
 /* ---- split-f16 weights (V2W_ALGO_SPLIT).  wf [k][C_in][C_out] (folded fp32) -> wps: k*C_in*C_out*4 + 2048 bytes (the tail is padding) holding, per 32-row
  * block, chunk of 32 input channels and tap, the (hi, lo) half-precision MFMA A fragments of scale*w in consumption order;
- * scale = the power of two that puts max|w| of the layer into [8192, 16384) (both halves stay in the normal f16 range).
+ * scale = the power of two that puts max|w| of the layer into [8192, 16384).  The halves do NOT all stay in the normal f16 range: a scaled
+ * weight below about 2^-3 - a weight some 2^-16 of the layer's maximum or less - has an f16 SUBNORMAL lo half, which carries an absolute error
+ * of 2^-25 / scale (<= 2^-38 max|w|) instead of the relative 2^-22.
  * sc: 4 floats of device memory: [0] = 1/scale (the `winv` of v2w_conv1d_args), [1] = scale, [2] = scratch.
- * Activations are split on the fly by the conv kernel and must satisfy |x| <= 65504 (they are clamped there). */
+ * Activations are split on the fly by the conv kernel and must satisfy |x| <= 65504 (they are clamped there); they are not scaled: below
+ * |x| of about 2^-3 their lo half is subnormal as well (absolute error 2^-25 per operand instead of 2^-22 |x|). */
 int v2w_split_supported(int c_in, int c_out, int u);   /* 1 when V2W_ALGO_SPLIT serves this layer shape */
 int v2w_split_packable(int c_in, int c_out);           /* 1 when v2w_pack_split / _bf16 / _batch accept the shape (C_in % 16; C_out % 32, or C_out == 16 zero-padded to 32 rows) */
 int v2w_pack_split(const float* wf, void* wps, float* sc, int k, int c_in, int c_out, void* stream);

@@ -29,11 +29,19 @@ TANH_C: the device tanhf's own error in units of 2^-24, doubled and rounded up. 
 test_stage_kernels_gpu.py::test_device_tanhf_error (a tail record whose pre-activation is an exact fp32 number, 114 688 arguments over
 [-9, 9], against fp64 tanh of the same argument): 1.253 * 2^-24 (at a = 0.66635), hence TANH_C = 3.
 
+  split-f16 form    (csrc/v2w_stage_split.hip, `split=True`) every product is the sum of three f16 x f16 products: n counts three accumulations
+                    per product, and each phase adds the per-product terms of tests/split_ref.py on its own operand and weights,
+                    3 * 2^-22 * (sum of |a w|) + 2^-25 * W1 + 2^-38 * wmax * A1.  The residuals x and t1_j exist only as the (hi, lo) halves of
+                    their ACTIVATED values; v = unlrelu(hi + lo) is granted 2^-22 |v| (`rebuilt`) and one fp32 division by the slope on the
+                    negative side, counted in n.  (Where lo is an f16 subnormal, |a| below about 2^-3, hi + lo is in principle only within
+                    2^-25 of a; that floor is NOT granted here, and the records hold without it.)
+
 With lengths, x and every t1_j are zero at and past min(L, len[b] * len_mul); entries there are unspecified (NaN in value and bound), except
 the tail's, which are exactly 0 (bound 0)."""
 import torch
 import torch.nn.functional as F
 
+from tests import split_ref
 from tests.disc_ref import U, f64
 from tests.tile_ref import _s, lrelu, mask_factor, taps_sum, unspecified_past
 from tests.wino_ref import CLASSES, segments
@@ -114,20 +122,38 @@ def spread(E, wf, dil, wino=False):
     return taps_sum(E, f64(wf).abs(), dil, dil * (wf.shape[0] - 1) // 2)[0]
 
 
-def two_convs(x, br, n1, n2, slope, ends=None, wino=False, res_mode=0):
+def split_terms(act, S, wf, dil):
+    """The per-product terms of the split-f16 form on one conv phase (tests/split_ref.py): S is the phase's sum of |a w|."""
+    h = dil * (wf.shape[0] - 1) // 2
+    W1 = taps_sum(torch.ones_like(act), f64(wf).abs(), dil, h)[0]
+    A1 = taps_sum(act.abs(), torch.ones_like(f64(wf)), dil, h)[0]
+    return split_ref.REL * S + split_ref.A_FLOOR * W1 + split_ref.W_FLOOR * f64(wf).abs().max() * A1
+
+
+def rebuilt(v):
+    """What a residual rebuilt from the halves of its activated value may differ from v by (see the module docstring)."""
+    return 2.0 ** -22 * v.abs()
+
+
+def two_convs(x, br, n1, n2, slope, ends=None, wino=False, res_mode=0, split=False):
     """One branch on x (B, C, L), br = dict(w1, b1, w2, b2, d1, d2) with the weights [k][C][C]:
     res_mode 0: t1 = x + conv1(lrelu(x)) + b1, r = t1 + conv2(lrelu(t1)) + b2;  res_mode 1: t1 = conv1(lrelu(x)) + b1, r = x + conv2(lrelu(t1)) + b2.
-    -> (r, E(r), t1, E1)."""
-    c1, S1 = phase(lrelu(x, slope), br['w1'], br['d1'], wino)
+    split: the split-f16 form (res_mode 0, no Winograd).  -> (r, E(r), t1, E1)."""
+    assert not split or (res_mode == 0 and not wino)
+    a1 = lrelu(x, slope)
+    c1, S1 = phase(a1, br['w1'], br['d1'], wino)
+    X1 = split_terms(a1, S1, br['w1'], br['d1']) + rebuilt(x) if split else 0.0
     t1, S1 = c1 + _bias(br['b1']), S1 + (0.0 if br['b1'] is None else _bias(br['b1']).abs())
     if res_mode == 0:
         t1, S1 = t1 + x, S1 + x.abs()
-    t1, E1 = _zero_past(t1, ends), _zero_past(n1 * U * S1, ends)
-    c2, S2 = phase(lrelu(t1, slope), br['w2'], br['d2'], wino)
+    t1, E1 = _zero_past(t1, ends), _zero_past(n1 * U * S1 + X1, ends)
+    a2 = lrelu(t1, slope)
+    c2, S2 = phase(a2, br['w2'], br['d2'], wino)
+    X2 = split_terms(a2, S2, br['w2'], br['d2']) + rebuilt(t1) if split else 0.0
     res = t1 if res_mode == 0 else x
     r = res + c2 + _bias(br['b2'])
     S2 = res.abs() + S2 + (0.0 if br['b2'] is None else _bias(br['b2']).abs())
-    Er = (E1 if res_mode == 0 else 0.0) + spread(E1, br['w2'], br['d2'], wino) + n2 * U * S2
+    Er = (E1 if res_mode == 0 else 0.0) + spread(E1, br['w2'], br['d2'], wino) + n2 * U * S2 + X2
     return r, Er, t1, E1
 
 
@@ -138,13 +164,13 @@ def _divide(v, E, out_div):
     return v, E
 
 
-def section(x_in, branches, n1, n2, *, slope, in_a=None, in_s=None, out_div=0.0, ends=None, wino=False):
+def section(x_in, branches, n1, n2, *, slope, in_a=None, in_s=None, out_div=0.0, ends=None, wino=False, split=False):
     """v2w_resblock2_stage_fwd / _wino_fwd / _small_fwd (and their _len forms): out = ((r_0 + r_1) + ...) / out_div.  n1 / n2: the chain
     lengths of every branch's two phases.  -> (value, bound), NaN at and past an item's end."""
     x = affine(x_in, in_a, in_s, ends)
     tot = E = R = None
     for j, br in enumerate(branches):
-        r, Er, _, _ = two_convs(x, br, n1[j], n2[j], slope, ends, wino)
+        r, Er, _, _ = two_convs(x, br, n1[j], n2[j], slope, ends, wino, split=split)
         tot, E, R = (r, Er, r.abs()) if tot is None else (tot + r, E + Er, R + r.abs())
     E = E + (len(branches) - 1) * U * R
     tot, E = _divide(tot, E, out_div)

@@ -3,7 +3,8 @@
 //   out[b,co,l] = bias[co] + sum_{ci,t} W[t][ci][co] * act(in[b,ci,l + (t-(k-1)/2)*dil])      (models.py:37-44, 65-70, 123)
 //
 // Every fp32 operand is split into two halves-precision parts  x = x_hi + x_lo  (x_hi = rne_f16(x), x_lo = rne_f16(x - x_hi);
-// weights are first scaled by a per-layer power of two so that both parts sit in the normal f16 range) and the product is
+// weights are first scaled by a per-layer power of two so that the largest lands in [8192, 16384); a lo part below 2^-14 - a weight more
+// than about 2^-16 under the layer's maximum (scaled: below about 2^-3), an activation below about 2^-3 - is an f16 subnormal with an absolute error of 2^-25) and the product is
 // accumulated in fp32 as  x_hi*w_hi + x_hi*w_lo + x_lo*w_hi  - three v_mfma_f32_32x32x16_f16.  x_hi*w_hi is exact in fp32
 // (11 x 11 bits), the dropped x_lo*w_lo term is <= 2^-22 |x w|: the result carries ~22 bits per product against fp32's 24,
 // i.e. it differs from the exact-fp32 kernel by about as much as two fp32 summation orders differ from each other
