@@ -19,6 +19,9 @@
 // [unit][term], 1 KiB per fragment, a 4-deep ring in registers as in conv_tile_kernel.
 // Tile: 64 output channels x 64 pairs (MI = 1), 4 accumulator sets = 64 registers per lane; launch bound three waves per SIMD (measured
 // at B = 32 x T = 256: two waves per SIMD with the register-prefetched staging ran 10-20 % slower, MI = 2 at one wave slower still: 9.95 against 8.97 ms per forward).
+// Tail tile: d ceil(L / 2d) pairs seldom fill the last tile of a row (dil 3, L = 1280: 642 pairs, the 11th tile holds 2, one live).  A column-wave with no
+// output position below the end runs no segment and no epilogue, and the partial tail tiles of a problem are its last workgroups
+// (wino_tile_order): stage 0's k = 11 launch 448 -> 430 us, stage 1's 464 -> 447 us.
 // Epilogue: the output transform in registers, then bias [+ res_a*res + res_s] [+ add0 (+ add1) | + out] [/ out_div] per element
 // in conv_tile_kernel's order; second outputs of a pair at or past L are not stored.  Fixed summation order, no atomics.
 #include "v2w_tile.h"
@@ -32,6 +35,19 @@ typedef TileGeom<32, WCK> WG;           // the LDS signal tile of conv_tile_kern
 constexpr int WGPC = 4;                 // A fragments (units of 4 k-steps) per chunk and term
 constexpr int WHMAX = 32;               // staging slots cover 2 NTP + 2 WHMAX rows
 __host__ __device__ inline int wino_tpos(int P, int d) { const int q = P / d; return 2 * d * q + (P - q * d); }
+__host__ __device__ inline int wino_npairs(int L, int d) { return d * ((L + 2 * d - 1) / (2 * d)); }   // output pairs of a row of L positions
+
+// Position tile `v` of a problem in launch order -> batch item b and tile tl of the item (v2w_tile.h places v on a workgroup).  Item-major
+// (v = b * ntl + tl) unless the item's last tile is partial (tail_last: npairs % NTP != 0): that tile's dead column-waves do no matrix work,
+// so the B tail tiles take the highest v - no full workgroup then queues behind a cheap one at the end of the problem.
+__host__ __device__ inline void wino_tile_order(int v, int B, int ntl, bool tail_last, int& b, int& tl) {
+    b = v / ntl; tl = v - b * ntl;
+    if (tail_last) {
+        const int nf = ntl - 1, nfull = B * nf;
+        if (v >= nfull) { b = v - nfull; tl = nf; }
+        else { b = v / nf; tl = v - b * nf; }
+    }
+}
 
 // LEN: per-item valid lengths, as in conv_tile_body (v2w_conv_mfma.hip): inputs at and past Lb = min(L, len[b] * len_mul) select 0, a tile
 // whose first output position lies there returns at once; its own kernel name (conv_wino_len_kernel).
@@ -52,12 +68,13 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
     const int mtiles = p.Cout / MT;
     const int id = blockIdx.x - m.start[pq];
     const TileId ti = tile_coords(mtiles, id);
-    const int mt = ti.mt, tile = ti.tile;
-    if (tile >= p.ntiles) return;
-    const int b = tile / p.ntl;
-    const int P0 = (tile % p.ntl) * NTP;     // first output pair of the tile
-    const int m0 = mt * MT;
+    const int mt = ti.mt;
+    if (ti.tile >= p.ntiles) return;
     const int d = p.dil;
+    int b, tl;
+    wino_tile_order(ti.tile, p.B, p.ntl, wino_npairs(p.L, d) % NTP != 0, b, tl);
+    const int P0 = tl * NTP;                 // first output pair of the tile
+    const int m0 = mt * MT;
     int Lb = p.L;                            // end of this item's sequence (LEN; else the tensor's)
     if constexpr (LEN) {
         const int lv = p.len[b] * p.len_mul;
@@ -72,6 +89,9 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
     const int hk = lane >> 5;
     const int wm0 = (wave / WN) * (32 * MI);
     const int wn0 = (wave % WN) * 32;
+    // a column-wave whose first (smallest) output position lies at or past the end stores nothing: it stages and keeps every barrier, but
+    // runs no segment (no A-fragment load, no MFMA) and no epilogue - the tail tile of a row whose pairs do not fill it, a LEN item's last tile
+    const bool live = wino_tpos(P0 + wn0, d) < Lb;
     const int L = p.L, K = p.K;
     const float slope = p.slope;
     const int nch = p.Cin / WCK;
@@ -243,11 +263,13 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
         const float* Xs = smem + (ch & 1) * bufsz;
         float* Xn = smem + ((ch + 1) & 1) * bufsz;
         const bool more = ch + 1 < nch;
-        const float* xt = Xs + lbase;
-        int s = 0;
-        for (; s + 3 <= K; s += 3) segment(S3{}, xt + s * dstep, dstep);
-        if (K - s == 2) segment(S2{}, xt + s * dstep, dstep);
-        else if (K - s == 1) segment(S1{}, xt + s * dstep, dstep);
+        if (live) {
+            const float* xt = Xs + lbase;
+            int s = 0;
+            for (; s + 3 <= K; s += 3) segment(S3{}, xt + s * dstep, dstep);
+            if (K - s == 2) segment(S2{}, xt + s * dstep, dstep);
+            else if (K - s == 1) segment(S1{}, xt + s * dstep, dstep);
+        }
         if (more) {
             if constexpr (VEC) { prefetch((ch + 1) * WCK); commit((ch + 1) * WCK, Xn); }
             else stage_scalar((ch + 1) * WCK, Xn);
@@ -255,6 +277,7 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
         }
     }
 
+    if (!live) return;
     // ---- epilogue: output transform, then + bias [+ residual] [+ addends | + out] [/ out_div], conv_tile_kernel's order
     float* const outp = p.out;
     const float dinv = p.out_div != 0.f ? 1.f / p.out_div : 1.f;
@@ -309,8 +332,7 @@ int launch_wino(const TileArgs* ps, int nprob, hipStream_t stream) {
         TileArgs p = ps[i];
         if (p.Cout % MT != 0) return V2W_E_SHAPE;
         const int d = p.dil;
-        const int npairs = d * ((p.L + 2 * d - 1) / (2 * d));
-        p.ntl = (npairs + NTP - 1) / NTP;
+        p.ntl = (wino_npairs(p.L, d) + NTP - 1) / NTP;
         p.ntiles = p.B * p.ntl;
         int rows = 0;                       // LDS rows the widest tile reads: x_K of the last pair's second output
         for (int tl = 0; tl < p.ntl; ++tl) {
@@ -385,8 +407,7 @@ int v2w_conv1d_wino(const v2w_conv1d_args* a, int n, hipStream_t stream, const i
         p.hl = p.hr = q->dil * (q->k - 1) / 2;
         p.slope = q->slope; p.accumulate = q->accumulate; p.out_div = q->out_div;
         ps[i] = p;
-        const int npairs = q->dil * ((q->L + 2 * q->dil - 1) / (2 * q->dil));
-        wgs += (long)q->B * ((npairs + 63) / 64) * (q->C_out / MT);
+        wgs += (long)q->B * ((wino_npairs(q->L, q->dil) + 63) / 64) * (q->C_out / MT);
     }
     if (wgs <= 128) return V2W_E_SHAPE;     // (the f32 MFMA path splits such launches over C_in: inference at B = 1)
     // (MI = 2, a 128 x 64-pair tile with 128 accumulators per lane, spills at two waves per SIMD and ran slower at one)
