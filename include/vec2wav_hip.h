@@ -533,6 +533,16 @@ int v2w_conv_post_tanh(const float* in, const float* wf, const float* bias, floa
  * _WINO (no direct-kernel fallback), mask_src / rowsum_part / out_slope / channel slices / in_stride > 1, stats_part, the input-gradient form. */
 int v2w_conv1d_fwd_len(const v2w_conv1d_args* a, int n, const int32_t* len, int len_mul, void* stream);   /* n <= 4 problems as _fwd_multi */
 int v2w_convt1d_fwd_len(const v2w_convt1d_args* a, const int32_t* len, int len_mul, void* stream);
+/* The second convs of a ResBlock2 stage's branches as ONE Winograd launch on one accumulator (additive in ABI v35; fp32; the f32 counterpart
+ * of v2w_branch_convs_bf16_fwd mode 1).  a[0 .. n), n <= 3, are the SOURCES: of each, `in` (B, C, L), `wp` (its v2w_pack_wino / fold `wpw`
+ * stream), `bias`, `k`, `dil`, `slope`; C_in == C_out, and B, C, L, dil and slope are shared.  `out` and `out_div` are a[0]'s.  Every source's
+ * input is also its residual:
+ *     out = ((y + ((b_0 + b_1) + b_2)) + ((in_0 + in_1) + in_2)) / out_div,   y = sum_j conv_j(lrelu(in_j)) from the shared accumulators
+ * (the division as in v2w_conv1d_fwd; a different rounding order from three convs that add r_0, r_1, r_2).  res / add0 / add1 / accumulate
+ * must be unset (V2W_E_ARG).  len == NULL: full lengths; else as v2w_conv1d_fwd_len.  V2W_E_SHAPE (nothing launched): an input affine
+ * (in_a), dilations that differ, an even k, C % 64 != 0, and whatever V2W_ALGO_WINO declines but a small launch - the caller then issues
+ * the convs one by one. */
+int v2w_conv1d_wino_sum_fwd(const v2w_conv1d_args* a, int n, const int32_t* len, int len_mul, void* stream);
 int v2w_resblock2_stage_fwd_len(const v2w_stage_args* a, const int32_t* len, int len_mul, void* stream);
 int v2w_conv_post_tanh_len(const float* in, const float* wf, const float* bias, float* out,
                            int B, int C_in, int L, int k, float slope, const int32_t* len, int len_mul, void* stream);

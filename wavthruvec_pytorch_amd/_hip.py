@@ -254,6 +254,7 @@ SIGNATURES = {
     # batches of unequal lengths (per-item valid lengths: a device int32 array and len_mul; the argument structs are unchanged)
     'v2w_conv1d_fwd_len': (C.c_int, [C.POINTER(Conv1dArgs), C.c_int, _fp, C.c_int, _fp]),
     'v2w_convt1d_fwd_len': (C.c_int, [C.POINTER(ConvT1dArgs), _fp, C.c_int, _fp]),
+    'v2w_conv1d_wino_sum_fwd': (C.c_int, [C.POINTER(Conv1dArgs), C.c_int, _fp, C.c_int, _fp]),
     'v2w_resblock2_stage_fwd_len': (C.c_int, [C.POINTER(StageArgs), _fp, C.c_int, _fp]),
     'v2w_conv_post_tanh_len': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, C.c_int, _fp]),
     # mel_spectrogram and the mel L1 of a batch of unequal lengths (forward only)

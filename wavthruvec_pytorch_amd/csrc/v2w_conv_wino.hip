@@ -24,6 +24,9 @@
 // (wino_tile_order): stage 0's k = 11 launch 448 -> 430 us, stage 1's 464 -> 447 us.
 // Epilogue: the output transform in registers, then bias [+ res_a*res + res_s] [+ add0 (+ add1) | + out] [/ out_div] per element
 // in conv_tile_kernel's order; second outputs of a pair at or past L are not stored.  Fixed summation order, no atomics.
+// Summed form (conv_wino_sum_kernel, v2w_conv1d_wino_sum_fwd): up to three convs of one dilation - the second convs of a stage's branches - on
+// the same accumulators, one output transform, then t = y + ((b0 + b1) + b2); t += (in_0[go] + in_1[go]) + in_2[go]; t = t / out_div (the
+// division above): NOT the rounding order of three launches that add r0, r1, r2 (B = 32 x T = 256: max |dy| = 3.7e-7 at max |y| = 0.40).
 #include "v2w_tile.h"
 #include "v2w_internal.h"
 #include "v2w_wino.h"
@@ -49,10 +52,26 @@ __host__ __device__ inline void wino_tile_order(int v, int B, int ntl, bool tail
     }
 }
 
+// The summed form (v2w_conv1d_wino_sum_fwd): up to WSRC convs of one dilation whose results add - the second convs of a ResBlock2 stage's
+// branches.  The output transform is linear, so every source's terms add into the same four accumulator classes: one workgroup walks the
+// sources one after another (own input, weight stream, K, halo), pays prologue, output transform and epilogue once and writes only the sum.
+// `p` holds what the sources share (and source 0); the input of each source is also its residual.
+constexpr int WSRC = 3;
+struct WinoSumArgs {
+    TileArgs p;
+    const float* in[WSRC]; const float* wp[WSRC]; const float* bias[WSRC];
+    int K[WSRC], hl[WSRC];
+    int nsrc;
+};
+__device__ __forceinline__ const TileArgs& wino_problem(const MultiArgs& m, int pq) { return m.p[pq]; }
+__device__ __forceinline__ const TileArgs& wino_problem(const WinoSumArgs& a, int) { return a.p; }
+
 // LEN: per-item valid lengths, as in conv_tile_body (v2w_conv_mfma.hip): inputs at and past Lb = min(L, len[b] * len_mul) select 0, a tile
 // whose first output position lies there returns at once; its own kernel name (conv_wino_len_kernel).
-template <int MI, int WN, int NPF, bool VEC, bool LEN>
-__device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
+// ARGS = WinoSumArgs: the summed form (one problem per launch); MultiArgs: one conv per problem.
+template <int MI, int WN, int NPF, bool VEC, bool LEN, class ARGS>
+__device__ __forceinline__ void conv_wino_body(const ARGS& m) {
+    constexpr bool SUM = std::is_same<ARGS, WinoSumArgs>::value;
     typedef Frag<32> F;
     typedef F::acc_t acc_t;
     constexpr int WM = 2;
@@ -63,10 +82,10 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
-    const int pq = tile_problem(m);
-    const TileArgs& p = m.p[pq];
+    int pq = 0, id = blockIdx.x;
+    if constexpr (!SUM) { pq = tile_problem(m); id = blockIdx.x - m.start[pq]; }
+    const TileArgs& p = wino_problem(m, pq);
     const int mtiles = p.Cout / MT;
-    const int id = blockIdx.x - m.start[pq];
     const TileId ti = tile_coords(mtiles, id);
     const int mt = ti.mt;
     if (ti.tile >= p.ntiles) return;
@@ -92,10 +111,12 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
     // a column-wave whose first (smallest) output position lies at or past the end stores nothing: it stages and keeps every barrier, but
     // runs no segment (no A-fragment load, no MFMA) and no epilogue - the tail tile of a row whose pairs do not fill it, a LEN item's last tile
     const bool live = wino_tpos(P0 + wn0, d) < Lb;
-    const int L = p.L, K = p.K;
+    const int L = p.L;
+    int K = p.K, hl = p.hl;                  // (SUM: of the source whose chunks are being multiplied)
+    const float* sin = p.in;                 // the tensor the staging reads, pos0 the position of its LDS row 0 (floor to a float4) -
+    int pos0 = (wino_tpos(P0, d) - hl) & ~3; // SUM: already the NEXT source's while the last chunk of a source is multiplied
     const float slope = p.slope;
     const int nch = p.Cin / WCK;
-    const int pos0 = (wino_tpos(P0, d) - p.hl) & ~3;     // position of LDS row 0 (floor to a float4)
     const int bufsz = p.xrows * WG::RS;
     float* const etab = smem + p.atab_off;   // bias, res_a, res_s [MT] each
     float* const atab = etab + 3 * MT;       // folded CondBN affine of this batch item: a[Cin] then s[Cin]
@@ -129,15 +150,15 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
         in_seq = in_img && pos >= 0 && pos < L;
     };
     auto prefetch = [&](int ci0) {
-        const float* src = p.in + (size_t)(b * p.CinT + ci0) * L + pos0;
+        const float* xsrc = sin + (size_t)(b * p.CinT + ci0) * L + pos0;
 #pragma unroll
         for (int s = 0; s < NPF; ++s) {
             int c0, row; bool in_img, in_seq;
             item(s, c0, row, in_img, in_seq);
             pf[s][0] = zero4; pf[s][1] = zero4;
             if (in_seq) {
-                pf[s][0] = *reinterpret_cast<const f32x4*>(src + (size_t)c0 * L + row);
-                pf[s][1] = *reinterpret_cast<const f32x4*>(src + (size_t)(c0 + 2) * L + row);
+                pf[s][0] = *reinterpret_cast<const f32x4*>(xsrc + (size_t)c0 * L + row);
+                pf[s][1] = *reinterpret_cast<const f32x4*>(xsrc + (size_t)(c0 + 2) * L + row);
             }
         }
     };
@@ -148,7 +169,7 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
             item(s, c0, row, in_img, in_seq);
             if (!in_img) continue;
             float a0 = 1.f, s0 = 0.f, a1 = 1.f, s1 = 0.f;
-            if (p.in_a) {
+            if (!SUM && p.in_a) {
                 a0 = atab[ci0 + c0]; s0 = atab[p.Cin + ci0 + c0];
                 a1 = atab[ci0 + c0 + 2]; s1 = atab[p.Cin + ci0 + c0 + 2];
             }
@@ -166,21 +187,21 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
     auto stage_scalar = [&](int ci0, float* Xs) {   // any L / alignment: dword loads straight into LDS
         for (int c = wave; c < WCK; c += WM * WN) {
             const int ch = b * p.CinT + ci0 + c;
-            const float* src = p.in + (size_t)ch * L;
-            const float av = p.in_a ? p.in_a[ch] : 1.f;
-            const float sv = p.in_s ? p.in_s[ch] : 0.f;
+            const float* xsrc = sin + (size_t)ch * L;
+            const float av = !SUM && p.in_a ? p.in_a[ch] : 1.f;
+            const float sv = !SUM && p.in_s ? p.in_s[ch] : 0.f;
             float* dst = Xs + WG::slot(c);
             for (int j = lane; j < p.xrows; j += 64) {
                 const int l = pos0 + j;
                 float v = 0.f;
-                if (l >= 0 && l < Lb) v = v2w_lrelu(fmaf(av, src[l], sv), slope);
+                if (l >= 0 && l < Lb) v = v2w_lrelu(fmaf(av, xsrc[l], sv), slope);
                 dst[j * WG::RS] = v;
             }
         }
     };
 
     // ---- weight ring: fragments in consumption order, "next" is always +1 KiB per row block
-    const int nfrag = nch * wino_terms(K) * WGPC;
+    int nfrag = nch * wino_terms(K) * WGPC;
     const f32x4* ap[MI];
 #pragma unroll
     for (int i = 0; i < MI; ++i)
@@ -233,12 +254,20 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
     };
 
     // ---- prologue: epilogue constants, affine table, chunk 0, first fragments
+    int nsrc = 1;
+    if constexpr (SUM) nsrc = m.nsrc;
     for (int c = tid; c < MT; c += NTHREADS) {
+        if constexpr (SUM) {                 // (b0 + b1) + b2
+            float bv = m.bias[0] ? m.bias[0][m0 + c] : 0.f;
+            for (int j = 1; j < nsrc; ++j) bv += m.bias[j] ? m.bias[j][m0 + c] : 0.f;
+            etab[c] = bv;
+            continue;
+        }
         etab[c] = p.bias ? p.bias[m0 + c] : 0.f;
         etab[MT + c] = p.res_a ? p.res_a[b * p.Cout + m0 + c] : 1.f;
         etab[2 * MT + c] = p.res_a ? p.res_s[b * p.Cout + m0 + c] : 0.f;
     }
-    if (p.in_a) {
+    if (!SUM && p.in_a) {
         for (int c = tid; c < p.Cin; c += NTHREADS) {
             atab[c] = p.in_a[b * p.Cin + c];
             atab[p.Cin + c] = p.in_s[b * p.Cin + c];
@@ -254,26 +283,47 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
 
     const int P = P0 + wn0 + lr;                   // this lane's output pair
     const int t0 = wino_tpos(P, d);                // ... and its first output position
-    const int lbase = (t0 - p.hl - pos0) * WG::RS + 4 * hk;   // x of tap 0 for output t0, unit 0
+    int lbase = (t0 - hl - pos0) * WG::RS + 4 * hk;           // x of tap 0 for output t0, unit 0
     const int dstep = d * WG::RS;
     typedef std::integral_constant<int, 3> S3;
     typedef std::integral_constant<int, 2> S2;
     typedef std::integral_constant<int, 1> S1;
-    for (int ch = 0; ch < nch; ++ch) {
-        const float* Xs = smem + (ch & 1) * bufsz;
-        float* Xn = smem + ((ch + 1) & 1) * bufsz;
-        const bool more = ch + 1 < nch;
-        if (live) {
-            const float* xt = Xs + lbase;
-            int s = 0;
-            for (; s + 3 <= K; s += 3) segment(S3{}, xt + s * dstep, dstep);
-            if (K - s == 2) segment(S2{}, xt + s * dstep, dstep);
-            else if (K - s == 1) segment(S1{}, xt + s * dstep, dstep);
-        }
-        if (more) {
-            if constexpr (VEC) { prefetch((ch + 1) * WCK); commit((ch + 1) * WCK, Xn); }
-            else stage_scalar((ch + 1) * WCK, Xn);
-            __syncthreads();
+    // SUM: the sources one after another on the same accumulators; the double buffer runs on across a source boundary (the last chunk of a
+    // source stages chunk 0 of the next: one prologue staging per workgroup), the fragment pointer and the weight ring restart there.
+    for (int js = 0, cc = 0; js < nsrc; ++js) {
+        for (int ch = 0; ch < nch; ++ch, ++cc) {
+            const int par = SUM ? cc : ch;
+            const float* Xs = smem + (par & 1) * bufsz;
+            float* Xn = smem + ((par + 1) & 1) * bufsz;
+            bool more = ch + 1 < nch;
+            int cn = (ch + 1) * WCK;
+            if (live) {
+                const float* xt = Xs + lbase;
+                int s = 0;
+                for (; s + 3 <= K; s += 3) segment(S3{}, xt + s * dstep, dstep);
+                if (K - s == 2) segment(S2{}, xt + s * dstep, dstep);
+                else if (K - s == 1) segment(S1{}, xt + s * dstep, dstep);
+            }
+            if constexpr (SUM) {
+                if (!more && js + 1 < nsrc) {
+                    more = true; cn = 0;
+                    K = m.K[js + 1]; hl = m.hl[js + 1]; sin = m.in[js + 1];
+                    pos0 = (wino_tpos(P0, d) - hl) & ~3;
+                    lbase = (t0 - hl - pos0) * WG::RS + 4 * hk;
+                    nfrag = nch * wino_terms(K) * WGPC;
+#pragma unroll
+                    for (int i = 0; i < MI; ++i)
+                        ap[i] = reinterpret_cast<const f32x4*>(m.wp[js + 1]) + ((size_t)((m0 + wm0) / 32 + i) * nfrag) * 64;
+                    fidx = 0;
+#pragma unroll
+                    for (int g = 0; g + 1 < RING; ++g) load_next(ar[g]);
+                }
+            }
+            if (more) {
+                if constexpr (VEC) { prefetch(cn); commit(cn, Xn); }
+                else stage_scalar(cn, Xn);
+                __syncthreads();
+            }
         }
     }
 
@@ -296,6 +346,14 @@ __device__ __forceinline__ void conv_wino_body(const MultiArgs& m) {
                 if (pos >= L) continue;
                 const size_t go = rowoff + pos;
                 float t = y[h] + bias;
+                if constexpr (SUM) {         // the sources' own inputs are their residuals: (t1_0 + t1_1) + t1_2
+                    float r = m.in[0][go];
+                    for (int j = 1; j < nsrc; ++j) r += m.in[j][go];
+                    t += r;
+                    if (p.out_div != 0.f) t = v2w_div_by(t, p.out_div, dinv);
+                    outp[go] = t;
+                    continue;
+                }
                 if (p.res) t += fmaf(ra, p.res[go], rs);
                 if (p.add1) t += p.add0[go] + p.add1[go];      // (add0 + add1) + value: the reference's `xs += ...` order
                 else if (p.accumulate) t += outp[go];
@@ -317,6 +375,18 @@ template <int MI, int WN, int NPF, bool VEC>
 __global__ void __launch_bounds__(128 * WN, 3)
 conv_wino_len_kernel(const MultiArgs m) {
     conv_wino_body<MI, WN, NPF, VEC, true>(m);
+}
+
+template <int MI, int WN, int NPF, bool VEC>
+__global__ void __launch_bounds__(128 * WN, 3)
+conv_wino_sum_kernel(const WinoSumArgs a) {
+    conv_wino_body<MI, WN, NPF, VEC, false>(a);
+}
+
+template <int MI, int WN, int NPF, bool VEC>
+__global__ void __launch_bounds__(128 * WN, 3)
+conv_wino_sum_len_kernel(const WinoSumArgs a) {
+    conv_wino_body<MI, WN, NPF, VEC, true>(a);
 }
 
 template <int MI, int WN>
@@ -357,6 +427,43 @@ int launch_wino(const TileArgs* ps, int nprob, hipStream_t stream) {
     auto kern = lens ? (vec ? conv_wino_len_kernel<MI, WN, NPF, true> : conv_wino_len_kernel<MI, WN, NPF, false>)
                     : (vec ? conv_wino_kernel<MI, WN, NPF, true> : conv_wino_kernel<MI, WN, NPF, false>);
     return v2w_launch_lds(kern, dim3(grid), dim3(NTHREADS), lds, stream, m);
+}
+
+// The summed form: ps[0 .. nsrc) are the sources (shared B, C, L, dil, slope, out, out_div, len); one problem, one grid.
+template <int MI, int WN>
+int launch_wino_sum(const TileArgs* ps, int nsrc, hipStream_t stream) {
+    constexpr int MT = 64 * MI, NTP = 32 * WN, NTHREADS = 128 * WN;
+    constexpr int NPF = ((WCK / 2) * (((2 * NTP + 2 * WHMAX) / 4 + 7) / 8 * 8) + NTHREADS - 1) / NTHREADS;
+    WinoSumArgs a{};
+    TileArgs p = ps[0];
+    if (p.Cout % MT != 0) return V2W_E_SHAPE;
+    const int d = p.dil;
+    p.ntl = (wino_npairs(p.L, d) + NTP - 1) / NTP;
+    p.ntiles = p.B * p.ntl;
+    int rows = 0;                           // LDS rows the widest tile of the widest source reads
+    bool vec = p.L % 4 == 0;
+    for (int j = 0; j < nsrc; ++j) {
+        for (int tl = 0; tl < p.ntl; ++tl) {
+            const int P0 = tl * NTP;
+            const int pos0 = (wino_tpos(P0, d) - ps[j].hl) & ~3;
+            const int r = wino_tpos(P0 + NTP - 1, d) + d + ps[j].hr - pos0 + 1;
+            if (r > rows) rows = r;
+        }
+        vec = vec && v2w_al16(ps[j].in);
+        a.in[j] = ps[j].in; a.wp[j] = ps[j].wp; a.bias[j] = ps[j].bias; a.K[j] = ps[j].K; a.hl[j] = ps[j].hl;
+    }
+    a.nsrc = nsrc;
+    p.xrows = (rows + 3) & ~3;
+    if (p.xrows > 2 * NTP + 2 * WHMAX) return V2W_E_SHAPE;
+    p.vec4 = vec;
+    const int nbuf = nsrc * (p.Cin / WCK) > 1 ? 2 : 1;
+    p.atab_off = nbuf * p.xrows * WG::RS;
+    const size_t lds = ((size_t)p.atab_off + 3 * MT) * sizeof(float);
+    a.p = p;
+    const int grid = tile_blocks(p.ntiles, p.Cout / MT);
+    auto kern = p.len ? (vec ? conv_wino_sum_len_kernel<MI, WN, NPF, true> : conv_wino_sum_len_kernel<MI, WN, NPF, false>)
+                      : (vec ? conv_wino_sum_kernel<MI, WN, NPF, true> : conv_wino_sum_kernel<MI, WN, NPF, false>);
+    return v2w_launch_lds(kern, dim3(grid), dim3(NTHREADS), lds, stream, a);
 }
 
 // wpw float index o = (((mb * nch + ch) * nfr + fi) * 64 + lane) * 4 + j, nfr = wino_terms(k) * 4, fragment fi = (segment, unit gg, term)
@@ -412,6 +519,31 @@ int v2w_conv1d_wino(const v2w_conv1d_args* a, int n, hipStream_t stream, const i
     if (wgs <= 128) return V2W_E_SHAPE;     // (the f32 MFMA path splits such launches over C_in: inference at B = 1)
     // (MI = 2, a 128 x 64-pair tile with 128 accumulators per lane, spills at two waves per SIMD and ran slower at one)
     return launch_wino<1, 2>(ps, n, stream);
+}
+
+// The summed form (include/vec2wav_hip.h): out = (sum_j in_j + sum_j conv_j(lrelu(in_j)) + sum_j bias_j) [/ out_div] in one launch.
+// Serves what v2w_conv1d_wino serves, of any size, with C_in == C_out, one dilation and no input affine; V2W_E_SHAPE otherwise.
+extern "C" int v2w_conv1d_wino_sum_fwd(const v2w_conv1d_args* a, int n, const int32_t* len, int len_mul, void* stream) {
+    if (!a || n < 1 || n > WSRC || (len && len_mul < 1)) return V2W_E_ARG;
+    TileArgs ps[WSRC];
+    for (int i = 0; i < n; ++i) {
+        const v2w_conv1d_args* q = a + i;
+        if (!q->in || !q->wp || !a->out) return V2W_E_ARG;
+        if (q->B <= 0 || q->C_in <= 0 || q->L <= 0 || q->k <= 0 || q->dil <= 0) return V2W_E_ARG;
+        if (q->res || q->res_a || q->add0 || q->add1 || q->accumulate || (q->in_a == nullptr) != (q->in_s == nullptr)) return V2W_E_ARG;
+        if (q->B != a->B || q->C_in != a->C_in || q->C_out != a->C_in || q->L != a->L || q->dil != a->dil || q->slope != a->slope) return V2W_E_SHAPE;
+        if (q->in_a) return V2W_E_SHAPE;        // (the second convs read lrelu(t1_j); one conv with an input affine: V2W_ALGO_WINO)
+        if (q->C_in % 64 != 0 || wino_terms(q->k) == 0 || q->pad_left >= 0) return V2W_E_SHAPE;
+        if (q->in_stride > 1 || q->mask_src || q->rowsum_part || q->out_slope != 0.f || q->in_ct > 0 || q->out_ct > 0) return V2W_E_SHAPE;
+        TileArgs p{};
+        p.len = len; p.len_mul = len_mul;
+        p.in = q->in; p.wp = q->wp; p.bias = q->bias; p.out = a->out;
+        p.B = q->B; p.Cin = p.Cout = p.CinT = p.CoutT = q->C_in; p.L = q->L; p.K = q->k; p.dil = q->dil;
+        p.hl = p.hr = q->dil * (q->k - 1) / 2;
+        p.slope = q->slope; p.out_div = a->out_div;
+        ps[i] = p;
+    }
+    return launch_wino_sum<1, 2>(ps, n, (hipStream_t)stream);
 }
 
 extern "C" int v2w_wino_terms(int k) { return wino_terms(k); }

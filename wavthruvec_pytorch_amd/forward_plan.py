@@ -69,6 +69,16 @@ def stage_wino_selected(wino_stage, precision, algo, C, blocks) -> bool:
     return bool(wino_stage) and precision == 'f32' and algo != hipops.ALGO_DIRECT and C == 32 and list(blocks) == STAGE_WINO_BLOCKS
 
 
+def wino_sum_selected(wino_sum, precision, algo, C, blocks) -> bool:
+    """Do the second convs of a wide ResBlock2 stage run as ONE Winograd launch on one accumulator (hipops.conv1d_wino_sum)?  Exact fp32 on
+    the MFMA path, C in `wino_sum` (Generator.wino_sum: the stages that form was measured faster on), 2 or 3 branches of odd k >= 3 and one
+    dilation.  `blocks`: (kernel size, second dilation) per branch.  Read by the planner (rb2_layers; the plain forward only) and by the
+    fold (Generator._wino_sum_layers: which layers get a Winograd stream)."""
+    blocks = list(blocks)
+    return (C in tuple(wino_sum or ()) and precision == 'f32' and algo != hipops.ALGO_DIRECT and C % 64 == 0 and 2 <= len(blocks) <= 3
+            and all(k >= 3 and k % 2 == 1 and d == blocks[0][1] for k, d in blocks))
+
+
 def _branches(rbs, names, wps):
     return [dict(wps1=wps[nm + '.convs.0'], b1=rb.convs[0].bias.detach(), wps2=wps[nm + '.convs.1'], b2=rb.convs[1].bias.detach(),
                  k=rb.kernel_size, dil1=rb.convs[0].dilation, dil2=rb.convs[1].dilation) for nm, rb in zip(names, rbs)]
@@ -563,8 +573,23 @@ class ForwardPlanner:
         self.launch('0', {j: (j, (self.xr, self.wf[names[j] + '.convs.0'], rbs[j].convs[0].bias.detach(), self.t1s[j],
                                   dict(k=rbs[j].kernel_size, dil=rbs[j].convs[0].dilation, slope=LRELU_SLOPE, in_affine=self.aff, res=self.xr,
                                        res_affine=self.aff, **self.ck(names[j] + '.convs.0')))) for j in range(self.nk)})
-        self.launch_conv2('1', self.conv2_problems())
+        if not self.conv2_sum():
+            self.launch_conv2('1', self.conv2_problems())
         return True
+
+    def conv2_sum(self):
+        """The second convs of all branches as one Winograd launch on one accumulator (o_j never written); False: not selected or declined."""
+        g, rbs, names = self.g, self.rbs, self.names
+        if self.save is not None or self.st or not wino_sum_selected(g.wino_sum, g.precision, self.algo, self.C,
+                                                                     [(rb.kernel_size, rb.convs[1].dilation) for rb in rbs]):
+            return False
+        wpw = {**g._fold_key.get('wpw_sum', {}), **g._fold_key.get('wpw', {})}
+        if not all(f'{nm}.convs.1' in wpw for nm in names):
+            return False
+        lk = self.lkw(self.lmul * g.ups[self.stage_i].stride)
+        return self.timed('bconv1:' + '+'.join(f'{nm}.1' for nm in names), hipops.conv1d_wino_sum,
+                          [(t1, wpw[f'{nm}.convs.1'], rb.convs[1].bias.detach(), rb.kernel_size) for t1, nm, rb in zip(self.t1s, names, rbs)],
+                          self.xs, dil=rbs[0].convs[1].dilation, slope=LRELU_SLOPE, out_div=float(self.nk), **lk)
 
     # ---------------------------------------------------------------------------------------------------------------------------
     def residual1(self, i):

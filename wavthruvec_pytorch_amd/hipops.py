@@ -328,6 +328,23 @@ def conv1d_wino_multi(problems, splitk_ws=None):
     conv1d_multi([(x, wf, bias, out, {q: v for q, v in kw.items() if q != 'wpw'}) for x, wf, bias, out, kw in problems], splitk_ws=splitk_ws)
 
 
+def conv1d_wino_sum(sources, out, *, dil, slope, out_div=0.0, in_affine=None, lengths=None, len_mul=1):
+    """The summed form of the Winograd F(2,3) kernel (v2w_conv1d_wino_sum_fwd): `sources` = up to three (x_j, wpw_j, bias_j, k_j) of one
+    dilation - the second convs of a ResBlock2 stage's branches - in ONE launch on one accumulator:
+    out = (sum_j x_j + sum_j conv_j(lrelu(x_j)) + sum_j bias_j) [/ out_div].  Returns False (nothing launched) when the library declines
+    the shape (V2W_E_SHAPE); the caller then issues the convs one by one."""
+    n = len(sources)
+    arr = (_hip.Conv1dArgs * max(n, 1))()
+    for a, (x, wpw, bias, k) in zip(arr, sources):
+        _conv1d_args(a, x, None, bias, out, k=k, dil=dil, slope=slope, out_div=out_div, algo=ALGO_WINO, wp=wpw, in_affine=in_affine)
+    lp = _len_ptr(lengths, len_mul) if lengths is not None else None
+    rc = _hip.load().v2w_conv1d_wino_sum_fwd(arr, n, lp, int(len_mul), _stream(out))
+    if rc == -2:
+        return False
+    _hip.check(rc, 'v2w_conv1d_wino_sum_fwd')
+    return True
+
+
 def convt1d(x, wf, bias, out, *, k, u, slope=1.0, algo=ALGO_AUTO, wp=None, stats_part=None, splitk_ws=None, lengths=None, len_mul=1):
     """Fused leaky_relu -> ConvTranspose1d(k, stride u, padding (k-u)//2) -> +bias.  lengths / len_mul: per-item valid lengths at the INPUT
     rate (see _len_ptr; v2w_convt1d_fwd_len); outputs past lengths[b] * len_mul * u are unspecified."""

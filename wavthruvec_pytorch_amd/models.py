@@ -226,6 +226,8 @@ class Generator(nn.Module):
         self.wino_stage = True                # precision 'f32': the fused 32-channel stage kernel in its Winograd F(2,3) form (standard block set; forward_plan.stage_wino_selected)
                                               # (hipops.ALGO_WINO: 4 / 10 / 15 instead of 6 / 14 / 22 products per output pair for k = 3 / 7 / 11),
                                               # weights transformed by the batched fold; a launch the kernel declines runs on the direct-form tile
+        self.wino_sum = (64,)                 # precision 'f32', plain forward: channel counts of the wide ResBlock2 stages whose second convs run as ONE Winograd launch on one
+                                              # accumulator (hipops.conv1d_wino_sum; forward_plan.wino_sum_selected): r0 / r1 never written, one epilogue.  () = off
         self.merge_waits = True               # bf16 storage: one wait per side stream and call, earlier steps of the stream count as met (forward_plan.need)
         self.cond_stream = None               # bf16 storage, train mode: the conditioning chain on a second side stream, beside the weight folds instead of between them.  None: where it pays - while conv_pre + ups.0 are shorter than the one side stream's chain + folds (measured, tools/exp/cond_stream_sweep.py: -26 / -12 us at B x T = 4 096 / 8 192 frames, +8 at 2 048, +13 .. +28 from 12 288 up); True / False: always / never
         self.fuse_post = True                 # leaky_relu -> conv_post -> tanh inside the kernel of the last (C = 16) stage (bf16 storage, and - round 5 - the fp32 stage kernel): the stage's
@@ -410,7 +412,8 @@ class Generator(nn.Module):
             vers.append(tuple((p.data_ptr(), p._version) for p in ps))
         wino = self.wino and self.precision == 'f32' and self.algo != hipops.ALGO_DIRECT
         stage_names = self._wino_stage_layers()
-        state = (tuple(vers), self.algo, str(device), need_wf, bf16_only, wino, bool(stage_names))
+        sum_names = self._wino_sum_layers()
+        state = (tuple(vers), self.algo, str(device), need_wf, bf16_only, wino, bool(stage_names), tuple(sorted(sum_names)))
         force = (self.training and self.always_refold) or need_wf
         if not force and self._fold_key.get('state') == state:
             return self._fold_key['wf'], self._fold_key['wp']
@@ -418,6 +421,7 @@ class Generator(nn.Module):
         wpd = {}        # need_wf: fragment streams of the input-gradient convs of the C -> C residual convs (backward.py), from the same pass
         wpw = {}        # wino: the Winograd F(2,3) streams of the layers that kernel serves (forward_plan.ck), from the same pass
         wpw_stage = {}  # wino_stage: the same streams for the six layers of the 32-channel stage (the fused stage kernel's Winograd form)
+        wpw_sum = {}    # wino_sum: the same streams for second convs the summed launch serves but `wino` leaves on the direct form (64 channels, dilation 3)
         for name, m in layers:
             if bf16_only and name != 'conv_post':      # bf16 activation storage: every other layer runs on its bf16 fragments (_split_weights):
                 wf[name], wp[name] = None, None        # no fp32 fold / fragment stream is read, none is built
@@ -435,6 +439,8 @@ class Generator(nn.Module):
                 wpwb = wpw[name] = self._wbuf('wpw.' + name, (hipops.wino_terms(m.kernel_size) * m.in_channels * m.out_channels,), device=device)
             if mfma_ok and name in stage_names:
                 wpwb = wpw_stage[name] = self._wbuf('wpw.' + name, (hipops.wino_terms(m.kernel_size) * m.in_channels * m.out_channels,), device=device)
+            if mfma_ok and wpwb is None and name in sum_names:
+                wpwb = wpw_sum[name] = self._wbuf('wpw.' + name, (hipops.wino_terms(m.kernel_size) * m.in_channels * m.out_channels,), device=device)
             if mfma_ok and need_wf:     # a forward that will be back-propagated: dgrad / wgrad also read the plain layout - written by the
                 # same batched fold (was: three launches per layer, ~100 host-bound launches and 1.6 ms in front of every training forward)
                 n_el = m.kernel_size * m.in_channels * m.out_channels
@@ -464,7 +470,7 @@ class Generator(nn.Module):
                 plan.key = key
                 self._fold_key['plan'] = plan
             plan.run()
-        self._fold_key.update(state=state, wf=wf, wp=wp, wpd=wpd, wpw=wpw, wpw_stage=wpw_stage, vers=tuple(vers), gen=self._fold_key.get('gen', 0) + 1)
+        self._fold_key.update(state=state, wf=wf, wp=wp, wpd=wpd, wpw=wpw, wpw_stage=wpw_stage, wpw_sum=wpw_sum, vers=tuple(vers), gen=self._fold_key.get('gen', 0) + 1)
         return wf, wp
 
     def _wino_stage_layers(self):
@@ -478,6 +484,18 @@ class Generator(nn.Module):
                     self.wino_stage, self.precision, self.algo, up.out_channels,
                     [(rb.kernel_size, rb.convs[0].dilation, rb.convs[1].dilation) for rb in rbs]):
                 names.update(f'resblocks.{i * nk + j}.convs.{c}' for j in range(nk) for c in (0, 1))
+        return names
+
+    def _wino_sum_layers(self):
+        """Names of the second convs (`convs.1`) of the stages whose branch sum runs as one Winograd launch (forward_plan.wino_sum_selected):
+        the fold gives each a Winograd stream, also where `wino` leaves the layer on the direct form."""
+        from .forward_plan import wino_sum_selected
+        names, nk = set(), self.num_kernels
+        for i, up in enumerate(self.ups):
+            rbs = [self.resblocks[i * nk + j] for j in range(nk)]
+            if all(isinstance(rb, ResBlock2) for rb in rbs) and wino_sum_selected(
+                    self.wino_sum, self.precision, self.algo, up.out_channels, [(rb.kernel_size, rb.convs[1].dilation) for rb in rbs]):
+                names.update(f'resblocks.{i * nk + j}.convs.1' for j in range(nk))
         return names
 
     def _split_weights(self, device, all_ups=False, ups_stream=None, mark=None, between=None):
@@ -690,7 +708,7 @@ class Generator(nn.Module):
         ptrs = tuple(p.data_ptr() for p in self.parameters()) + tuple(b.data_ptr() for b in self.buffers())
         return (tuple(x.shape), str(x.device), torch.cuda.current_stream(x.device).cuda_stream, self.training, self.precision, self.algo, self.bf16_storage, tuple(self.fuse_stage), tuple(self.fuse_pairs),
                 self.fuse_wide, self.fuse_wide_stage, self.fuse_up, self.fuse_post, self.fuse_bn_finalize, self.cond_stream, self.merge_waits, self.split_min_channels,
-                self.always_refold, self.wino, self.wino_stage, ptrs)
+                self.always_refold, self.wino, self.wino_stage, tuple(self.wino_sum), ptrs)
 
     def _forward_hip(self, x, spk, nz, save, lens=None):
         """One forward through the C ABI.  `save` (a dict) asks for the back-propagatable form (forward_plan.py).  A no-grad forward is PLANNED
