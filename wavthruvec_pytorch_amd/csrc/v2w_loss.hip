@@ -3,20 +3,17 @@
 // their backwards in one launch each.  The maps are read where the discriminators left them: `rows` rows of `valid` floats `pitch`
 // floats apart ([valid, pitch) is never read), so the [:, :, :U] views of the pitched feature-map buffers need no copy.
 //
-// Work split (host, v2w_l1_multi_plan): a pair is cut into UNITS of four floats - per row ceil(valid / 4) of them, the last one of a
-// row partial; a pair whose two sides are dense is one row of rows * valid floats whose units are cut at the 16-byte boundaries of
-// `a`.  Workgroups are dealt in proportion to the units (the element counts of one call span four orders of magnitude), at least one
-// per pair, about V2W_L1_TARGET_WGS in all: starts[i] is the first workgroup of pair i.  The plan depends on the descriptors only (not
-// on the device), every workgroup writes ONE fp64 partial and the finishing launch adds them in index order: the same call gives the
-// same bits.
-#include "v2w_common.h"
+// The multi-tensor L1 launches are built from v2w_multi.h: its units of four floats, its plan (about V2W_L1_TARGET_WGS workgroups, at least
+// one per pair), its search for a workgroup's pair and its unit access.  Their own here is the row arithmetic: a pair has per row
+// ceil(valid / 4) units, the last one of a row partial; a pair whose two sides are dense is one row of rows * valid floats whose units are
+// cut at the 16-byte boundaries of `a`.  The plan depends on the descriptors only (not on the device), every workgroup writes ONE fp64
+// partial and the finishing launch adds them in index order: the same call gives the same bits.
+// The masked L1, the LSGAN kernels and both finishing kernels do not share that skeleton: of v2w_multi.h they use the constants only.
+#include "v2w_multi.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kUnroll = 4;                       // units in flight per thread: 2 x 4 x 16 B of loads before the first use
-constexpr long long kMinChunk = kThreads * 8;    // units: no workgroup for less than 64 KB of reads unless the pair is smaller
-constexpr long long kMaxUnits = 1ll << 40;
 
 struct L1Item {
     const float* a; const float* b; float* da; float* db;
@@ -42,25 +39,6 @@ struct LsArgs {
     const float* gout; const float* gterm;
 };
 
-__device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// elements [e0, e1) of the four floats at p (the others read as 0 and are never touched); one 16-byte load when all four are wanted
-// and p allows it
-__device__ __forceinline__ f32x4 load_unit(const float* p, int e0, int e1) {
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (e0 == 0 && e1 == 4 && aligned16(p)) return *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (j >= e0 && j < e1) v[j] = p[j];
-    return v;
-}
-__device__ __forceinline__ void store_unit(float* p, f32x4 v, int e0, int e1) {
-    if (e0 == 0 && e1 == 4 && aligned16(p)) { *reinterpret_cast<f32x4*>(p) = v; return; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (j >= e0 && j < e1) p[j] = v[j];
-}
-
 // BWD = false: part[workgroup] = sum |a - b| over the workgroup's units (fp64).
 // BWD = true:  da = sgn(a - b) * (scale * gout / numel), db = -da, dense (rows x len); sgn = (a > b) - (a < b).
 template <bool BWD>
@@ -68,25 +46,18 @@ __global__ void __launch_bounds__(kThreads)
 l1_multi_kernel(const L1Args A, double* __restrict__ part) {
     __shared__ double red[16];
     const int wg = blockIdx.x;
-    int lo = 0, hi = A.n;
-    while (hi - lo > 1) {                                 // the pair of this workgroup: starts[lo] <= wg < starts[lo + 1]
-        const int mid = (lo + hi) >> 1;
-        if (A.starts[mid] <= wg) lo = mid; else hi = mid;
-    }
+    const int lo = find_item(A.starts, A.n, wg);
     const L1Item& it = A.it[lo];
     const float* a = it.a;
     const float* b = it.b;
     const long long len = it.len();
     const bool flat = it.flat();
     const int rows = it.rows();
-    const int shift = flat ? (int)((reinterpret_cast<uintptr_t>(a) >> 2) & 3) : 0;      // units of a flat pair start at a's 16-byte lines
-    const long long upr = (len + shift + 3) >> 2;                                       // units per row
-    const long long units = upr * rows;
-    const int nwg = A.starts[lo + 1] - A.starts[lo];
-    const long long chunk = (units + nwg - 1) / nwg;
-    const long long u0 = (long long)(wg - A.starts[lo]) * chunk;
-    const long long u1 = u0 + chunk < units ? u0 + chunk : units;
-    const unsigned cnt = u1 > u0 ? (unsigned)(u1 - u0) : 0u;
+    const int shift = flat ? phase16(a) : 0;              // units of a flat pair start at a's 16-byte lines
+    const long long upr = (len + shift + 3) >> 2;         // units per row
+    long long u0;
+    unsigned cnt;
+    chunk_of(A.starts, lo, wg, upr * rows, u0, cnt);
     const long long r0 = flat ? 0 : u0 / upr;
     const long long q0 = u0 - r0 * upr;
     const unsigned upr32 = flat ? 1u : (unsigned)upr, q032 = flat ? 0u : (unsigned)q0;
@@ -128,8 +99,8 @@ l1_multi_kernel(const L1Args A, double* __restrict__ part) {
             e0[k] = p < 0 ? (int)-p : 0;
             e1[k] = len - p < 4 ? (int)(len - p) : 4;
             if (t >= cnt) e0[k] = e1[k] = 0;
-            va[k] = load_unit(a + oa, e0[k], e1[k]);
-            vb[k] = load_unit(b + ob, e0[k], e1[k]);
+            va[k] = load_unit(a + oa, e0[k], e1[k], aligned16(a + oa));
+            vb[k] = load_unit(b + ob, e0[k], e1[k], aligned16(b + ob));
         }
 #pragma unroll
         for (int k = 0; k < kUnroll; ++k) {
@@ -143,8 +114,8 @@ l1_multi_kernel(const L1Args A, double* __restrict__ part) {
                     d[j] = va[k][j] > vb[k][j] ? coef : (va[k][j] < vb[k][j] ? -coef : 0.f);
                     nd[j] = -d[j];
                 }
-                if (da) store_unit(da + oo[k], d, e0[k], e1[k]);
-                if (db) store_unit(db + oo[k], nd, e0[k], e1[k]);
+                if (da) store_unit(da + oo[k], d, e0[k], e1[k], aligned16(da + oo[k]));
+                if (db) store_unit(db + oo[k], nd, e0[k], e1[k], aligned16(db + oo[k]));
             }
         }
     }
@@ -293,26 +264,23 @@ l1_masked_finish_kernel(const double* __restrict__ part, const int32_t* __restri
     if (threadIdx.x == 0 && total) total[0] = cnt > 0.0 ? (float)(tot / cnt) : 0.f;
 }
 
-inline bool ptr16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool ptr4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
 // checks every descriptor, normalises it into the kernel's form and counts its units (four floats; see the head of this file)
 int l1_items(const v2w_l1_pair* pairs, int n, L1Item* items, long long* units) {
     if (!pairs || n < 1 || n > V2W_LOSS_MAX_ITEMS) return V2W_E_ARG;
     for (int i = 0; i < n; ++i) {
         const v2w_l1_pair& p = pairs[i];
-        if (!p.a || !p.b || !ptr4(p.a) || !ptr4(p.b) || p.rows <= 0 || p.valid <= 0 || p.pitch_a < 0 || p.pitch_b < 0) return V2W_E_ARG;
+        if (!ptr4(p.a) || !ptr4(p.b) || p.rows <= 0 || p.valid <= 0 || p.pitch_a < 0 || p.pitch_b < 0) return V2W_E_ARG;
         const int pa = p.pitch_a ? p.pitch_a : p.valid, pb = p.pitch_b ? p.pitch_b : p.valid;
         if (pa < p.valid || pb < p.valid) return V2W_E_ARG;
-        if (pa != p.valid && ((pa & 3) || !ptr16(p.a))) return V2W_E_ARG;       // pitched rows begin on 16-byte lines
-        if (pb != p.valid && ((pb & 3) || !ptr16(p.b))) return V2W_E_ARG;
+        if (pa != p.valid && ((pa & 3) || !aligned16(p.a))) return V2W_E_ARG;       // pitched rows begin on 16-byte lines
+        if (pb != p.valid && ((pb & 3) || !aligned16(p.b))) return V2W_E_ARG;
         if ((p.da && !ptr4(p.da)) || (p.db && !ptr4(p.db))) return V2W_E_ARG;
         L1Item& it = items[i];
         it.a = p.a; it.b = p.b; it.da = p.da; it.db = p.db;
         if (p.rows == 1 || (pa == p.valid && pb == p.valid)) {
             it.shape = (long long)p.rows * p.valid; it.pa = it.pb = 0;
-            const int shift = (int)((reinterpret_cast<uintptr_t>(p.a) >> 2) & 3);
-            units[i] = (it.shape + shift + 3) >> 2;
+            units[i] = (it.shape + phase16(p.a) + 3) >> 2;
         } else {
             if (p.rows > 0x7fffffffll) return V2W_E_SHAPE;
             it.shape = (p.rows << 32) | p.valid; it.pa = pa; it.pb = pb;
@@ -323,26 +291,10 @@ int l1_items(const v2w_l1_pair* pairs, int n, L1Item* items, long long* units) {
     return 0;
 }
 
-// starts[i] = first workgroup of pair i, starts[n] = workgroups of the launch (returned)
-int l1_plan(const long long* units, int n, int32_t* starts) {
-    long long total = 0;
-    for (int i = 0; i < n; ++i) total += units[i];
-    long long chunk = (total + V2W_L1_TARGET_WGS - 1) / V2W_L1_TARGET_WGS;
-    if (chunk < kMinChunk) chunk = kMinChunk;
-    int w = 0;
-    for (int i = 0; i < n; ++i) {
-        starts[i] = w;
-        const long long k = (units[i] + chunk - 1) / chunk;
-        w += k < 1 ? 1 : (int)k;
-    }
-    starts[n] = w;
-    return w;
-}
-
 int l1_args(const v2w_l1_pair* pairs, int n, float scale, const float* gout, L1Args* A) {
     long long units[V2W_LOSS_MAX_ITEMS];
     if (const int rc = l1_items(pairs, n, A->it, units)) return rc;
-    l1_plan(units, n, A->starts);
+    deal_workgroups(units, n, V2W_L1_TARGET_WGS, A->starts);
     A->n = n; A->scale = scale; A->gout = gout;
     return 0;
 }
@@ -352,7 +304,7 @@ int ls_args(const v2w_lsgan_item* items, int n, bool bwd, LsArgs* A, unsigned* m
     *maxnumel = 0;
     for (int i = 0; i < n; ++i) {
         const v2w_lsgan_item& p = items[i];
-        if (!p.s || !ptr4(p.s) || p.rows <= 0 || p.valid <= 0 || p.pitch < 0 || (p.pitch && p.pitch < p.valid)) return V2W_E_ARG;
+        if (!ptr4(p.s) || p.rows <= 0 || p.valid <= 0 || p.pitch < 0 || (p.pitch && p.pitch < p.valid)) return V2W_E_ARG;
         if (p.target != 0.f && p.target != 1.f) return V2W_E_ARG;
         if (bwd && p.ds && !ptr4(p.ds)) return V2W_E_ARG;
         const long long numel = (long long)p.rows * p.valid;
@@ -373,7 +325,7 @@ extern "C" int v2w_l1_multi_plan(const v2w_l1_pair* pairs, int n, int32_t* start
     L1Item items[V2W_LOSS_MAX_ITEMS];
     long long units[V2W_LOSS_MAX_ITEMS];
     if (const int rc = l1_items(pairs, n, items, units)) return rc;
-    return l1_plan(units, n, starts);
+    return deal_workgroups(units, n, V2W_L1_TARGET_WGS, starts);
 }
 
 extern "C" long long v2w_l1_multi_scratch_bytes(const v2w_l1_pair* pairs, int n) {
@@ -423,7 +375,7 @@ static int l1_masked(const float* a, const float* b, int B, int C, int F, const 
     if (B > 65535) return V2W_E_SHAPE;                        // (grid.y)
     hipStream_t st = (hipStream_t)stream;
     double* part = static_cast<double*>(ws);
-    if (F % 4 == 0 && ptr16(a) && ptr16(b))
+    if (F % 4 == 0 && aligned16(a) && aligned16(b))
         V2W_LAUNCH(l1_masked_kernel<true>, dim3(G, B), dim3(kThreads), 0, st, a, b, len, len_mul, hop, n_fft, C, F, part);
     else
         V2W_LAUNCH(l1_masked_kernel<false>, dim3(G, B), dim3(kThreads), 0, st, a, b, len, len_mul, hop, n_fft, C, F, part);

@@ -1,32 +1,22 @@
 // AdamW (torch.optim.AdamW as the reference calls it, train.py:96-99,198,215: decoupled weight decay, no amsgrad, no maximize): the step of
-// up to V2W_ADAMW_MAX_ITEMS parameter tensors in ONE streaming launch.  One pass reads p, g, m, v and writes p, m, v (28 bytes per
-// parameter); the arithmetic, its order and its fp32 roundings are stated in include/vec2wav_hip.h.
-//
-// Work split (host, v2w_adamw_multi_plan; the shape of v2w_l1_multi_plan): a tensor is cut into UNITS of four floats.  When the four
-// pointers of an item share their 16-byte phase (s floats past a 16-byte line) the units are cut at the 16-byte lines - the first and the
-// last one partial - and every whole unit is one 16-byte load / store per lane and tensor; otherwise the units start at element 0 and the
-// item takes float-by-float accesses, chosen by a branch that is uniform over the workgroup.  Workgroups are dealt in proportion to the
-// units (the parameter sizes of one call span six orders of magnitude), at least one per tensor, about V2W_ADAMW_TARGET_WGS in all:
-// starts[i] is the first workgroup of tensor i, found from blockIdx.x by a search every lane makes alike.  The plan depends on the
-// descriptors only.  Every element of p, m and v is written exactly once, nothing else is written; no atomics, no LDS, no scratch.
-//
-// Global-norm clipping and the non-finite guard (include/vec2wav_hip.h, v2w_grad_sumsq_multi and its neighbours) ride on the same table and
-// plan: grad_sumsq_kernel writes one fp32 sum of squares per workgroup (fixed order, no atomics), grad_norm_finish_kernel adds them in fp64
-// and leaves norm, clip coefficient, finite flag and a running count in four floats of the caller's, grad_scale_kernel is g *= coef[0], and
-// adamw_multi_clipped_kernel is the step's body compiled with g * clip[1] for g - the coefficient never visits the host.
-//
-// The exponential moving average of the weights (include/vec2wav_hip.h, v2w_adamw_ema_multi and its neighbours): the step's body compiled
-// twice more with a fifth tensor e per item - e' = fma(ema_omd, p' - e, e) while p' is in registers, 36 bytes per parameter - on a table of
-// 48-byte items (AdamWEmaArgs, at most V2W_ADAMW_EMA_MAX_ITEMS), and two kernels on a table of {p, e, numel} items (PairArgs): the two lines
-// alone and the exchange of p and e.  find_span and the plan are shared: they are written over the table's type.
-#include "v2w_common.h"
+// up to V2W_ADAMW_MAX_ITEMS parameter tensors in ONE streaming launch, and the launches that ride on the same mechanism.  The arithmetic,
+// its order and its fp32 roundings are stated in include/vec2wav_hip.h; the units of four floats, the plan, the search for a workgroup's
+// tensor and its Span are in v2w_multi.h.  What this file adds to them:
+//   - ItemPtrs of its item types: which pointers an item has and which must not overlap;
+//   - the kernels: the step (adamw_body: p, g, m, v [, e], 28 or 36 bytes per parameter; compiled with and without the clip coefficient
+//     and the average), the average alone, the exchange of p and e, the sum of squares of g (one fp32 partial per workgroup, fixed
+//     order), g *= coef.  Each writes out the same loop - the masks and all loads of kUnroll units, then the arithmetic and the stores -
+//     ON PURPOSE: behind one loop template taking the arithmetic as a functor the compiler laid the masked paths out of line, and the
+//     step measured 2 % slower on the generator's list (same bits); the small kernels follow the step.  Every element of a written
+//     tensor is written exactly once, nothing else is written; no atomics, no scratch;
+//   - check_items and fill_table, the host side of every entry point: check, extras, fill, dry-run return, V2W_LAUNCH, status.
+// Global-norm clipping never visits the host: grad_norm_finish_kernel adds the partials in fp64 and leaves norm, clip coefficient, finite
+// flag and a running count in four floats of the caller's, which the clipped step reads.
+#include "v2w_multi.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kUnroll = 2;                       // units in flight per thread: 2 x 4 tensors x 16 B of loads before the first use
-constexpr long long kMinChunk = kThreads * 8;    // units: no workgroup for less than 4 x 32 KB of reads unless the tensor is smaller
-constexpr long long kMaxUnits = 1ll << 40;
 
 // the launch's constants, each derived from the v2w_adamw_hyper in double and rounded ONCE to fp32 (host)
 struct Coef { float decay, omb1, beta2, omb2, rbc2, eps, step; };
@@ -52,85 +42,40 @@ static_assert(sizeof(v2w_adamw_ema_item) == 48 && sizeof(v2w_ema_item) == 24 && 
 static_assert(V2W_ADAMW_EMA_MAX_ITEMS * 48 + (V2W_ADAMW_EMA_MAX_ITEMS + 1) * 4 + sizeof(Coef) + 4 + 4 == sizeof(AdamWEmaArgs), "no padding");
 static_assert(sizeof(AdamWEmaArgs) <= 3584, "kernel arguments travel by value: 4 KB with the hidden ones");
 
-// {p, e, numel} items: Item is v2w_ema_item (p only read) or v2w_swap_item (both written)
+// the launches that touch g only read g and numel of the caller's v2w_adamw_item: one pointer, so every span takes the 16-byte path
+struct GradItem {
+    float* g;
+    long long numel;
+    GradItem() = default;
+    GradItem(const v2w_adamw_item& it) : g(const_cast<float*>(it.g)), numel(it.numel) {}
+};
+
+// a table without constants: Item is v2w_ema_item (p only read), v2w_swap_item (both written) or GradItem
 template <class Item>
-struct PairArgs {
+struct ItemArgs {
     Item it[V2W_ADAMW_MAX_ITEMS];
     int starts[V2W_ADAMW_MAX_ITEMS + 1];
     int n;
 };
-static_assert(sizeof(PairArgs<v2w_ema_item>) <= 3584 && sizeof(PairArgs<v2w_swap_item>) == sizeof(PairArgs<v2w_ema_item>), "by-value table");
+static_assert(sizeof(ItemArgs<v2w_ema_item>) <= 3584 && sizeof(ItemArgs<v2w_swap_item>) == sizeof(ItemArgs<v2w_ema_item>), "by-value table");
 
-__host__ __device__ inline int phase16(const void* p) { return (int)((reinterpret_cast<uintptr_t>(p) >> 2) & 3); }
-__host__ __device__ inline bool same_phase(const v2w_adamw_item& it) {
-    const int ph = phase16(it.p);
-    return phase16(it.g) == ph && phase16(it.m) == ph && phase16(it.v) == ph;
-}
-__host__ __device__ inline bool same_phase(const v2w_adamw_ema_item& it) {
-    const int ph = phase16(it.p);
-    return phase16(it.g) == ph && phase16(it.m) == ph && phase16(it.v) == ph && phase16(it.e) == ph;
-}
-__host__ __device__ inline bool same_phase(const v2w_ema_item& it) { return phase16(it.p) == phase16(it.e); }
-__host__ __device__ inline bool same_phase(const v2w_swap_item& it) { return phase16(it.p) == phase16(it.e); }
-template <class Item>
-__host__ __device__ inline long long item_units(const Item& it) {
-    return (it.numel + (same_phase(it) ? phase16(it.p) : 0) + 3) >> 2;
-}
-
-// elements [e0, e1) of the four floats at q (the others read as 0 and are never touched); one 16-byte access when all four are wanted
-// and the item's pointers allow it (`vec`: q is then on a 16-byte line)
-__device__ __forceinline__ f32x4 load_unit(const float* q, int e0, int e1, bool vec) {
-    f32x4 x = {0.f, 0.f, 0.f, 0.f};
-    if (vec && e0 == 0 && e1 == 4) return *reinterpret_cast<const f32x4*>(q);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (j >= e0 && j < e1) x[j] = q[j];
-    return x;
-}
-__device__ __forceinline__ void store_unit(float* q, f32x4 x, int e0, int e1, bool vec) {
-    if (vec && e0 == 0 && e1 == 4) { *reinterpret_cast<f32x4*>(q) = x; return; }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (j >= e0 && j < e1) q[j] = x[j];
-}
-
-// the chunk of workgroup wg: its tensor, and units [u0, u0 + cnt) of it
-struct Span {
-    int item;
-    long long numel, base;      // base: element index of the first float of unit u0 (negative inside a partial first unit)
-    unsigned cnt;
-    bool vec;
+template <int N_, int W_, int MAX_>
+struct PtrList { static constexpr int N = N_, W = W_, MAX = MAX_; };
+template <> struct ItemPtrs<v2w_adamw_item> : PtrList<4, 3, V2W_ADAMW_MAX_ITEMS> {
+    __host__ __device__ static void get(const v2w_adamw_item& it, const void** q) { q[0] = it.p; q[1] = it.m; q[2] = it.v; q[3] = it.g; }
 };
-template <class Args>
-__device__ __forceinline__ Span find_span(const Args& A, int wg) {
-    int lo = 0, hi = A.n;
-    while (hi - lo > 1) {                                 // the tensor of this workgroup: starts[lo] <= wg < starts[lo + 1]
-        const int mid = (lo + hi) >> 1;
-        if (A.starts[mid] <= wg) lo = mid; else hi = mid;
-    }
-    const auto& it = A.it[lo];
-    Span s;
-    s.item = lo;
-    s.numel = it.numel;
-    s.vec = same_phase(it);
-    const int shift = s.vec ? phase16(it.p) : 0;
-    const long long units = (s.numel + shift + 3) >> 2;
-    const int nwg = A.starts[lo + 1] - A.starts[lo];
-    const long long chunk = (units + nwg - 1) / nwg;
-    const long long u0 = (long long)(wg - A.starts[lo]) * chunk;
-    const long long u1 = u0 + chunk < units ? u0 + chunk : units;
-    s.cnt = u1 > u0 ? (unsigned)(u1 - u0) : 0u;
-    // unit u holds elements [4u - shift, 4u - shift + 4) of the tensor; the floats before element 0 and past numel are masked
-    s.base = (u0 << 2) - shift;
-    return s;
-}
-// the floats [e0, e1) of unit t of the span that belong to the tensor (none for t >= cnt)
-__device__ __forceinline__ void unit_mask(const Span& s, unsigned t, size_t off, int& e0, int& e1) {
-    const long long pos = s.base + (long long)off;                    // element index of the unit's first float
-    e0 = pos < 0 ? (int)-pos : 0;
-    e1 = s.numel - pos < 4 ? (int)(s.numel - pos) : 4;
-    if (t >= s.cnt) e0 = e1 = 0;
-}
+template <> struct ItemPtrs<v2w_adamw_ema_item> : PtrList<5, 4, V2W_ADAMW_EMA_MAX_ITEMS> {
+    __host__ __device__ static void get(const v2w_adamw_ema_item& it, const void** q) { q[0] = it.p; q[1] = it.m; q[2] = it.v; q[3] = it.e; q[4] = it.g; }
+};
+template <> struct ItemPtrs<v2w_ema_item> : PtrList<2, 2, V2W_ADAMW_MAX_ITEMS> {      // (p is only read, and still kept off e)
+    __host__ __device__ static void get(const v2w_ema_item& it, const void** q) { q[0] = it.p; q[1] = it.e; }
+};
+template <> struct ItemPtrs<v2w_swap_item> : PtrList<2, 2, V2W_ADAMW_MAX_ITEMS> {
+    __host__ __device__ static void get(const v2w_swap_item& it, const void** q) { q[0] = it.p; q[1] = it.e; }
+};
+template <> struct ItemPtrs<GradItem> : PtrList<1, 0, V2W_ADAMW_MAX_ITEMS> {
+    __host__ __device__ static void get(const GradItem& it, const void** q) { q[0] = it.g; }
+};
 
 // CLIP: the step on g * coef (include/vec2wav_hip.h, v2w_adamw_multi_clipped); otherwise coef is not looked at.  EMA: the table is an
 // AdamWEmaArgs and e' = fma(omd, p' - e, e) rides along (v2w_adamw_ema_multi); otherwise neither e nor omd exists
@@ -213,7 +158,7 @@ adamw_ema_multi_clipped_kernel(const AdamWEmaArgs A, const float* __restrict__ c
 
 // e' = fma(omd, p - e, e), every element of e once; p is only read
 __global__ void __launch_bounds__(kThreads)
-ema_multi_kernel(const PairArgs<v2w_ema_item> A, float omd) {
+ema_multi_kernel(const ItemArgs<v2w_ema_item> A, float omd) {
     const Span s = find_span(A, blockIdx.x);
     const float* p = A.it[s.item].p + s.base;
     float* e = A.it[s.item].e + s.base;
@@ -240,7 +185,7 @@ ema_multi_kernel(const PairArgs<v2w_ema_item> A, float omd) {
 
 // p <-> e: a thread loads both values of its units, then stores both; no element belongs to two threads
 __global__ void __launch_bounds__(kThreads)
-swap_multi_kernel(const PairArgs<v2w_swap_item> A) {
+swap_multi_kernel(const ItemArgs<v2w_swap_item> A) {
     const Span s = find_span(A, blockIdx.x);
     float* p = A.it[s.item].p + s.base;
     float* e = A.it[s.item].e + s.base;
@@ -264,10 +209,9 @@ swap_multi_kernel(const PairArgs<v2w_swap_item> A) {
     }
 }
 
-// partials[wg] = sum of g^2 over the workgroup's chunk: per thread one fma chain over its units in order, then the fixed block sum.
-// The items arrive with p = m = v = g: every span takes the 16-byte path.
+// partials[wg] = sum of g^2 over the workgroup's chunk: per thread one fma chain over its units in order, then the fixed block sum
 __global__ void __launch_bounds__(kThreads)
-grad_sumsq_kernel(const AdamWArgs A, float* __restrict__ partials) {
+grad_sumsq_kernel(const ItemArgs<GradItem> A, float* __restrict__ partials) {
     __shared__ float red[16];
     const Span s = find_span(A, blockIdx.x);
     const float* g = A.it[s.item].g + s.base;
@@ -293,9 +237,9 @@ grad_sumsq_kernel(const AdamWArgs A, float* __restrict__ partials) {
 
 // g *= coef[0], every element once
 __global__ void __launch_bounds__(kThreads)
-grad_scale_kernel(const AdamWArgs A, const float* __restrict__ coef) {
+grad_scale_kernel(const ItemArgs<GradItem> A, const float* __restrict__ coef) {
     const Span s = find_span(A, blockIdx.x);
-    float* g = const_cast<float*>(A.it[s.item].g) + s.base;
+    float* g = A.it[s.item].g + s.base;
     const float c = coef[0];
     for (unsigned t0 = threadIdx.x; t0 < s.cnt; t0 += kThreads * kUnroll) {
         f32x4 x[kUnroll];
@@ -340,74 +284,44 @@ grad_norm_finish_kernel(const float* __restrict__ partials, int n, float max_nor
     }
 }
 
-inline bool ptr4(const void* p) { return p && (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 inline bool overlap(const void* a, const void* b, long long numel) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b), bytes = (uintptr_t)numel * 4;
     return x < y ? y - x < bytes : x - y < bytes;
 }
 
-// checks every descriptor and counts its units (four floats; see the head of this file)
-int adamw_items(const v2w_adamw_item* items, int n, long long* units) {
-    if (!items || n < 1 || n > V2W_ADAMW_MAX_ITEMS) return V2W_E_ARG;
+// checks every descriptor - read as the table's Item - and counts its units: all pointers of ItemPtrs<Item> 4-byte aligned and not NULL,
+// the written ones apart from one another
+template <class Item, class Src>
+int check_items(const Src* items, int n, long long* units) {
+    typedef ItemPtrs<Item> P;
+    if (!items || n < 1 || n > P::MAX) return V2W_E_ARG;
     for (int i = 0; i < n; ++i) {
-        const v2w_adamw_item& it = items[i];
-        if (!ptr4(it.p) || !ptr4(it.g) || !ptr4(it.m) || !ptr4(it.v) || it.numel <= 0) return V2W_E_ARG;
+        const Item it(items[i]);
+        const void* q[P::N];
+        P::get(it, q);
+        bool ok = it.numel > 0;
+        for (int k = 0; k < P::N; ++k) ok = ok && ptr4(q[k]);
+        if (!ok) return V2W_E_ARG;
         if (it.numel > (kMaxUnits << 2)) return V2W_E_SHAPE;
         units[i] = item_units(it);
         if (units[i] > kMaxUnits) return V2W_E_SHAPE;
-        if (overlap(it.p, it.m, it.numel) || overlap(it.p, it.v, it.numel) || overlap(it.m, it.v, it.numel)) return V2W_E_ARG;
+        for (int k = 1; k < P::W; ++k)
+            for (int l = 0; l < k; ++l)
+                if (overlap(q[k], q[l], it.numel)) return V2W_E_ARG;
     }
     return 0;
 }
 
-// v2w_adamw_ema_item: the checks above, and e against p, m and v
-int adamw_ema_items(const v2w_adamw_ema_item* items, int n, long long* units) {
-    if (!items || n < 1 || n > V2W_ADAMW_EMA_MAX_ITEMS) return V2W_E_ARG;
-    for (int i = 0; i < n; ++i) {
-        const v2w_adamw_ema_item& it = items[i];
-        if (!ptr4(it.p) || !ptr4(it.g) || !ptr4(it.m) || !ptr4(it.v) || !ptr4(it.e) || it.numel <= 0) return V2W_E_ARG;
-        if (it.numel > (kMaxUnits << 2)) return V2W_E_SHAPE;
-        units[i] = item_units(it);
-        if (units[i] > kMaxUnits) return V2W_E_SHAPE;
-        if (overlap(it.p, it.m, it.numel) || overlap(it.p, it.v, it.numel) || overlap(it.m, it.v, it.numel)) return V2W_E_ARG;
-        if (overlap(it.e, it.p, it.numel) || overlap(it.e, it.m, it.numel) || overlap(it.e, it.v, it.numel)) return V2W_E_ARG;
-    }
-    return 0;
-}
-
-// v2w_ema_item / v2w_swap_item
-template <class Item>
-int pair_items(const Item* items, int n, long long* units) {
-    if (!items || n < 1 || n > V2W_ADAMW_MAX_ITEMS) return V2W_E_ARG;
-    for (int i = 0; i < n; ++i) {
-        const Item& it = items[i];
-        if (!ptr4(it.p) || !ptr4(it.e) || it.numel <= 0) return V2W_E_ARG;
-        if (it.numel > (kMaxUnits << 2)) return V2W_E_SHAPE;
-        units[i] = item_units(it);
-        if (units[i] > kMaxUnits) return V2W_E_SHAPE;
-        if (overlap(it.p, it.e, it.numel)) return V2W_E_ARG;
-    }
-    return 0;
+// it[], starts[] and n of a by-value table from checked items; returns the workgroups of the launch
+template <class Args, class Src>
+int fill_table(Args& A, const Src* items, int n, const long long* units) {
+    for (int i = 0; i < n; ++i) A.it[i] = items[i];
+    A.n = n;
+    return deal_workgroups(units, n, V2W_ADAMW_TARGET_WGS, A.starts);
 }
 
 // ema_omd = 1 - decay in [0, 1]; a NaN is refused
 inline bool omd_ok(float omd) { return omd >= 0.f && omd <= 1.f; }
-
-// starts[i] = first workgroup of tensor i, starts[n] = workgroups of the launch (returned)
-int adamw_plan(const long long* units, int n, int32_t* starts) {
-    long long total = 0;
-    for (int i = 0; i < n; ++i) total += units[i];
-    long long chunk = (total + V2W_ADAMW_TARGET_WGS - 1) / V2W_ADAMW_TARGET_WGS;
-    if (chunk < kMinChunk) chunk = kMinChunk;
-    int w = 0;
-    for (int i = 0; i < n; ++i) {
-        starts[i] = w;
-        const long long k = (units[i] + chunk - 1) / chunk;
-        w += k < 1 ? 1 : (int)k;
-    }
-    starts[n] = w;
-    return w;
-}
 
 // the comparisons are written so that a NaN is refused
 int adamw_coef(const v2w_adamw_hyper* h, Coef* c) {
@@ -424,45 +338,30 @@ int adamw_coef(const v2w_adamw_hyper* h, Coef* c) {
     return 0;
 }
 
-// the table of the launches that touch g only: every item with p = m = v = g (the plan then counts g's own phase and every span takes
-// 16-byte accesses); only g and numel of the caller's items are looked at
-int grad_args(const v2w_adamw_item* items, int n, AdamWArgs* A) {
-    if (!items || n < 1 || n > V2W_ADAMW_MAX_ITEMS) return V2W_E_ARG;
-    long long units[V2W_ADAMW_MAX_ITEMS];
-    for (int i = 0; i < n; ++i) {
-        if (!ptr4(items[i].g) || items[i].numel <= 0) return V2W_E_ARG;
-        if (items[i].numel > (kMaxUnits << 2)) return V2W_E_SHAPE;
-        float* g = const_cast<float*>(items[i].g);
-        A->it[i] = v2w_adamw_item{g, g, g, g, items[i].numel};
-        units[i] = item_units(A->it[i]);
-        if (units[i] > kMaxUnits) return V2W_E_SHAPE;
-    }
-    adamw_plan(units, n, A->starts);
-    A->c = Coef{};
-    A->n = n;
-    return 0;
+// the host-only plan queries: the items' checks, then the deal
+template <class Item>
+int plan_of(const Item* items, int n, int32_t* starts) {
+    if (!starts) return V2W_E_ARG;
+    long long units[ItemPtrs<Item>::MAX];
+    if (const int rc = check_items<Item>(items, n, units)) return rc;
+    return deal_workgroups(units, n, V2W_ADAMW_TARGET_WGS, starts);
 }
 
 }  // namespace
 
-extern "C" int v2w_adamw_multi_plan(const v2w_adamw_item* items, int n, int32_t* starts) {
-    if (!starts) return V2W_E_ARG;
-    long long units[V2W_ADAMW_MAX_ITEMS];
-    if (const int rc = adamw_items(items, n, units)) return rc;
-    return adamw_plan(units, n, starts);
-}
+extern "C" int v2w_adamw_multi_plan(const v2w_adamw_item* items, int n, int32_t* starts) { return plan_of(items, n, starts); }
+extern "C" int v2w_adamw_ema_multi_plan(const v2w_adamw_ema_item* items, int n, int32_t* starts) { return plan_of(items, n, starts); }
+extern "C" int v2w_ema_multi_plan(const v2w_ema_item* items, int n, int32_t* starts) { return plan_of(items, n, starts); }
 
 extern "C" int v2w_adamw_multi(const v2w_adamw_item* items, int n, const v2w_adamw_hyper* h, void* stream) {
     AdamWArgs A;
     long long units[V2W_ADAMW_MAX_ITEMS];
-    if (const int rc = adamw_items(items, n, units)) return rc;
+    if (const int rc = check_items<v2w_adamw_item>(items, n, units)) return rc;
     if (const int rc = adamw_coef(h, &A.c)) return rc;
-    for (int i = 0; i < n; ++i) A.it[i] = items[i];
-    adamw_plan(units, n, A.starts);
-    A.n = n;
+    const int wgs = fill_table(A, items, n, units);
     hipStream_t st = (hipStream_t)stream;
     if (v2w_dry(st)) return 0;
-    V2W_LAUNCH(adamw_multi_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A);
+    V2W_LAUNCH(adamw_multi_kernel, dim3(wgs), dim3(kThreads), 0, st, A);
     return v2w_launch_status();
 }
 
@@ -470,31 +369,32 @@ extern "C" int v2w_adamw_multi_clipped(const v2w_adamw_item* items, int n, const
                                        void* stream) {
     AdamWArgs A;
     long long units[V2W_ADAMW_MAX_ITEMS];
-    if (const int rc = adamw_items(items, n, units)) return rc;
+    if (const int rc = check_items<v2w_adamw_item>(items, n, units)) return rc;
     if (const int rc = adamw_coef(h, &A.c)) return rc;
     if (!ptr4(clip)) return V2W_E_ARG;
-    for (int i = 0; i < n; ++i) A.it[i] = items[i];
-    adamw_plan(units, n, A.starts);
-    A.n = n;
+    const int wgs = fill_table(A, items, n, units);
     hipStream_t st = (hipStream_t)stream;
     if (v2w_dry(st)) return 0;
-    V2W_LAUNCH(adamw_multi_clipped_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A, clip, skip_nonfinite);
+    V2W_LAUNCH(adamw_multi_clipped_kernel, dim3(wgs), dim3(kThreads), 0, st, A, clip, skip_nonfinite);
     return v2w_launch_status();
 }
 
 extern "C" int v2w_grad_sumsq_partials(const v2w_adamw_item* items, int n) {
-    AdamWArgs A;
-    if (const int rc = grad_args(items, n, &A)) return rc;
-    return A.starts[n];
+    ItemArgs<GradItem> A;
+    long long units[V2W_ADAMW_MAX_ITEMS];
+    if (const int rc = check_items<GradItem>(items, n, units)) return rc;
+    return fill_table(A, items, n, units);
 }
 
 extern "C" int v2w_grad_sumsq_multi(const v2w_adamw_item* items, int n, float* partials, void* stream) {
-    AdamWArgs A;
-    if (const int rc = grad_args(items, n, &A)) return rc;
+    ItemArgs<GradItem> A;
+    long long units[V2W_ADAMW_MAX_ITEMS];
+    if (const int rc = check_items<GradItem>(items, n, units)) return rc;
     if (!ptr4(partials)) return V2W_E_ARG;
+    const int wgs = fill_table(A, items, n, units);
     hipStream_t st = (hipStream_t)stream;
     if (v2w_dry(st)) return 0;
-    V2W_LAUNCH(grad_sumsq_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A, partials);
+    V2W_LAUNCH(grad_sumsq_kernel, dim3(wgs), dim3(kThreads), 0, st, A, partials);
     return v2w_launch_status();
 }
 
@@ -507,70 +407,52 @@ extern "C" int v2w_grad_norm_finish(const float* partials, int n_partials, float
 }
 
 extern "C" int v2w_scale_multi(const v2w_adamw_item* items, int n, const float* coef, void* stream) {
-    AdamWArgs A;
-    if (const int rc = grad_args(items, n, &A)) return rc;
+    ItemArgs<GradItem> A;
+    long long units[V2W_ADAMW_MAX_ITEMS];
+    if (const int rc = check_items<GradItem>(items, n, units)) return rc;
     if (!ptr4(coef)) return V2W_E_ARG;
+    const int wgs = fill_table(A, items, n, units);
     hipStream_t st = (hipStream_t)stream;
     if (v2w_dry(st)) return 0;
-    V2W_LAUNCH(grad_scale_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A, coef);
+    V2W_LAUNCH(grad_scale_kernel, dim3(wgs), dim3(kThreads), 0, st, A, coef);
     return v2w_launch_status();
-}
-
-extern "C" int v2w_adamw_ema_multi_plan(const v2w_adamw_ema_item* items, int n, int32_t* starts) {
-    if (!starts) return V2W_E_ARG;
-    long long units[V2W_ADAMW_EMA_MAX_ITEMS];
-    if (const int rc = adamw_ema_items(items, n, units)) return rc;
-    return adamw_plan(units, n, starts);
 }
 
 extern "C" int v2w_adamw_ema_multi(const v2w_adamw_ema_item* items, int n, const v2w_adamw_hyper* h, const float* clip, int skip_nonfinite,
                                    float ema_omd, void* stream) {
     AdamWEmaArgs A;
     long long units[V2W_ADAMW_EMA_MAX_ITEMS];
-    if (const int rc = adamw_ema_items(items, n, units)) return rc;
+    if (const int rc = check_items<v2w_adamw_ema_item>(items, n, units)) return rc;
     if (const int rc = adamw_coef(h, &A.c)) return rc;
     if (!omd_ok(ema_omd) || (clip && !ptr4(clip))) return V2W_E_ARG;
-    for (int i = 0; i < n; ++i) A.it[i] = items[i];
-    adamw_plan(units, n, A.starts);
+    const int wgs = fill_table(A, items, n, units);
     A.omd = ema_omd;
-    A.n = n;
     hipStream_t st = (hipStream_t)stream;
     if (v2w_dry(st)) return 0;
-    if (clip) V2W_LAUNCH(adamw_ema_multi_clipped_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A, clip, skip_nonfinite);
-    else V2W_LAUNCH(adamw_ema_multi_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A);
+    if (clip) V2W_LAUNCH(adamw_ema_multi_clipped_kernel, dim3(wgs), dim3(kThreads), 0, st, A, clip, skip_nonfinite);
+    else V2W_LAUNCH(adamw_ema_multi_kernel, dim3(wgs), dim3(kThreads), 0, st, A);
     return v2w_launch_status();
 }
 
-extern "C" int v2w_ema_multi_plan(const v2w_ema_item* items, int n, int32_t* starts) {
-    if (!starts) return V2W_E_ARG;
-    long long units[V2W_ADAMW_MAX_ITEMS];
-    if (const int rc = pair_items(items, n, units)) return rc;
-    return adamw_plan(units, n, starts);
-}
-
 extern "C" int v2w_ema_multi(const v2w_ema_item* items, int n, float ema_omd, void* stream) {
-    PairArgs<v2w_ema_item> A;
+    ItemArgs<v2w_ema_item> A;
     long long units[V2W_ADAMW_MAX_ITEMS];
-    if (const int rc = pair_items(items, n, units)) return rc;
+    if (const int rc = check_items<v2w_ema_item>(items, n, units)) return rc;
     if (!omd_ok(ema_omd)) return V2W_E_ARG;
-    for (int i = 0; i < n; ++i) A.it[i] = items[i];
-    adamw_plan(units, n, A.starts);
-    A.n = n;
+    const int wgs = fill_table(A, items, n, units);
     hipStream_t st = (hipStream_t)stream;
     if (v2w_dry(st)) return 0;
-    V2W_LAUNCH(ema_multi_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A, ema_omd);
+    V2W_LAUNCH(ema_multi_kernel, dim3(wgs), dim3(kThreads), 0, st, A, ema_omd);
     return v2w_launch_status();
 }
 
 extern "C" int v2w_swap_multi(const v2w_swap_item* items, int n, void* stream) {
-    PairArgs<v2w_swap_item> A;
+    ItemArgs<v2w_swap_item> A;
     long long units[V2W_ADAMW_MAX_ITEMS];
-    if (const int rc = pair_items(items, n, units)) return rc;
-    for (int i = 0; i < n; ++i) A.it[i] = items[i];
-    adamw_plan(units, n, A.starts);
-    A.n = n;
+    if (const int rc = check_items<v2w_swap_item>(items, n, units)) return rc;
+    const int wgs = fill_table(A, items, n, units);
     hipStream_t st = (hipStream_t)stream;
     if (v2w_dry(st)) return 0;
-    V2W_LAUNCH(swap_multi_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A);
+    V2W_LAUNCH(swap_multi_kernel, dim3(wgs), dim3(kThreads), 0, st, A);
     return v2w_launch_status();
 }

@@ -1410,13 +1410,18 @@ def _l1_pair_array(pairs):
     return arr, keep
 
 
+def _multi_plan(entry, arr, n):
+    """(starts, workgroups) of the host-only plan query `entry` for n descriptors."""
+    starts = (C.c_int32 * (n + 1))()
+    nwg = getattr(_hip.load(), entry)(arr, n, starts)
+    if nwg <= 0:
+        _hip.check(nwg or -1, entry)
+    return list(starts), nwg
+
+
 def l1_plan(arr, n):
     """(starts, workgroups) of v2w_l1_multi_plan for n descriptors."""
-    starts = (C.c_int32 * (n + 1))()
-    nwg = _hip.load().v2w_l1_multi_plan(arr, n, starts)
-    if nwg <= 0:
-        _hip.check(nwg or -1, 'v2w_l1_multi_plan')
-    return list(starts), nwg
+    return _multi_plan('v2w_l1_multi_plan', arr, n)
 
 
 def l1_mean_multi(pairs, scale=1.0):
@@ -1519,14 +1524,10 @@ def lsgan_multi_bwd(scores, targets, gout=None, gterms=None, need=None):
     return ds
 
 
-# ---- AdamW (include/vec2wav_hip.h: v2w_adamw_multi)
+# ---- multi-tensor launches over flat tensors (csrc/v2w_multi.h): AdamW, the global-norm clip, the average of the weights
 def adamw_plan(arr, n):
     """(starts, workgroups) of v2w_adamw_multi_plan for n descriptors."""
-    starts = (C.c_int32 * (n + 1))()
-    nwg = _hip.load().v2w_adamw_multi_plan(arr, n, starts)
-    if nwg <= 0:
-        _hip.check(nwg or -1, 'v2w_adamw_multi_plan')
-    return list(starts), nwg
+    return _multi_plan('v2w_adamw_multi_plan', arr, n)
 
 
 def adamw_hyper(*, lr, betas, eps, weight_decay, step):
@@ -1538,36 +1539,86 @@ def adamw_hyper(*, lr, betas, eps, weight_decay, step):
     return _hip.AdamWHyper(float(lr), b1, b2, float(eps), float(weight_decay), 1.0 - b1 ** step, (1.0 - b2 ** step) ** 0.5, 0)
 
 
-def _adamw_array(params, grads, exp_avgs, exp_avg_sqs):
-    """(descriptors, the tensors they point into) of one AdamW call; fp32 GPU tensors on one device, a non-contiguous gradient is copied."""
-    n = len(params)
-    if not (n == len(grads) == len(exp_avgs) == len(exp_avg_sqs)):
-        raise ValueError('params, grads, exp_avgs and exp_avg_sqs must have one entry per tensor')
-    dev = params[0].device
-    arr = (_hip.AdamWItem * n)()
+_FIELD = {'param': 'p', 'grad': 'g', 'exp_avg': 'm', 'exp_avg_sq': 'v', 'ema': 'e'}
+
+
+def _flat_items(item, what, lists, copied=None, in_place=()):
+    """(descriptors of ctypes type `item`, the tensors they point into) of `lists` = {name: tensors}, entry for entry one tensor of each
+    name: fp32 contiguous GPU tensors on one device, of the numel (> 0) of the first list's.  A non-contiguous tensor of the list `copied`
+    is copied for reading, unless that list is also among the ones written `in_place`: then it is refused."""
+    names = list(lists)
+    dev = lists[names[0]][0].device
+    items = list(zip(*lists.values()))
+    arr = (item * max(len(items), 1))()
     keep = []
-    for i, (p, g, m, v) in enumerate(zip(params, grads, exp_avgs, exp_avg_sqs)):
-        p, g, m, v = p.detach(), g.detach(), m.detach(), v.detach()
-        if g.is_cuda and g.dtype == torch.float32 and not g.is_contiguous():
-            g = g.contiguous()
-        for t, name in ((p, 'param'), (g, 'grad'), (m, 'exp_avg'), (v, 'exp_avg_sq')):
+    for i, (d, ts) in enumerate(zip(arr, items)):
+        numel = ts[0].numel()
+        for name, t in zip(names, ts):
+            t = t.detach()
+            if name == copied and t.is_cuda and t.dtype == torch.float32 and not t.is_contiguous():
+                if name in in_place:
+                    raise ValueError(f'{name}[{i}] is not contiguous: it cannot be scaled in place')
+                t = t.contiguous()
             _chk(t, f'{name}[{i}]')
             if t.device != dev:
-                raise RuntimeError('all tensors of one adamw_multi call must live on one device')
-            if t.numel() != p.numel():
-                raise ValueError(f'{name}[{i}] has {t.numel()} elements, its parameter {p.numel()}')
-        if p.numel() == 0:
-            raise ValueError(f'param[{i}] is empty')
-        keep += [p, g, m, v]
-        d = arr[i]
-        d.p, d.g, d.m, d.v, d.numel = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+                raise RuntimeError(f'all tensors of one {what} call must live on one device')
+            if t.numel() != numel:
+                raise ValueError(f'{name}[{i}] has {t.numel()} elements, its parameter {numel}')
+            keep.append(t)
+            setattr(d, _FIELD[name], t.data_ptr())
+        if numel == 0:
+            raise ValueError(f'{names[0]}[{i}] is empty')
+        d.numel = numel
     return arr, keep
 
 
-def _item_chunks(arr, n):
-    """(pointer to the first descriptor, count) of every run of at most ADAMW_MAX_ITEMS descriptors."""
-    for i0 in range(0, n, _hip.ADAMW_MAX_ITEMS):
-        yield C.cast(C.byref(arr, i0 * C.sizeof(_hip.AdamWItem)), C.POINTER(_hip.AdamWItem)), min(_hip.ADAMW_MAX_ITEMS, n - i0)
+def _chunks_of(arr, n, item, limit):
+    """(pointer to the first descriptor, count) of every run of at most `limit` descriptors of type `item`."""
+    for i0 in range(0, n, limit):
+        yield C.cast(C.byref(arr, i0 * C.sizeof(item)), C.POINTER(item)), min(limit, n - i0)
+
+
+def _launch_chunks(entry, arr, n, item, limit, on, extra=()):
+    """lib.`entry`(descriptors, count, *extra, stream) for every run of at most `limit` of the n descriptors, on the device and the current
+    stream of the tensor `on`; `extra`: the arguments in between, or a function (descriptors, count) -> them.  Returns the launches."""
+    launches = 0
+    with torch.cuda.device(on.device):
+        fn = getattr(_hip.load(), entry)
+        stream = _stream(on)
+        for chunk, k in _chunks_of(arr, n, item, limit):
+            _hip.check(fn(chunk, k, *(extra(chunk, k) if callable(extra) else extra), stream), entry)
+            launches += 1
+    return launches
+
+
+def _adamw_step(entry, params, grads, exp_avgs, exp_avg_sqs, emas=None, clip=None, *, ema_decay=None, skip_nonfinite=False, **hyper):
+    """The three steps' common course; `entry`: v2w_adamw_multi, v2w_adamw_multi_clipped (clip required) or v2w_adamw_ema_multi (emas
+    required, clip optional, an empty list refused)."""
+    lists = {'param': params, 'grad': grads, 'exp_avg': exp_avgs, 'exp_avg_sq': exp_avg_sqs}
+    if emas is not None:
+        lists['ema'] = emas
+    n = len(params)
+    if any(len(ts) != n for ts in lists.values()):
+        plural = [name + 's' for name in lists]
+        raise ValueError(f'{", ".join(plural[:-1])} and {plural[-1]} must have one entry per tensor')
+    if emas is not None and n == 0:
+        raise ValueError('adamw_ema_multi: no tensors')
+    omd = None if emas is None else ema_omd(ema_decay)
+    if clip is not None or entry == 'v2w_adamw_multi_clipped':
+        _clip_buffer(clip, 'clip', 4)
+    if n == 0:
+        return 0
+    hyper = adamw_hyper(**hyper)
+    item, limit = (_hip.AdamWItem, _hip.ADAMW_MAX_ITEMS) if emas is None else (_hip.AdamWEmaItem, _hip.ADAMW_EMA_MAX_ITEMS)
+    arr, keep = _flat_items(item, entry[4:], lists, copied='grad')
+    if clip is not None and clip.device != keep[0].device:
+        raise RuntimeError('clip must live on the parameters\' device')
+    extra = (C.byref(hyper),)
+    if emas is not None:
+        extra += (_hip.ptr(clip), int(bool(skip_nonfinite)), omd)
+    elif clip is not None:
+        extra += (clip.data_ptr(), int(bool(skip_nonfinite)))
+    return _launch_chunks(entry, arr, n, item, limit, keep[0], extra)
 
 
 def adamw_multi(params, grads, exp_avgs, exp_avg_sqs, *, lr, betas, eps, weight_decay, step):
@@ -1575,21 +1626,8 @@ def adamw_multi(params, grads, exp_avgs, exp_avg_sqs, *, lr, betas, eps, weight_
     ceil(n / ADAMW_MAX_ITEMS) launches on the current stream.  `step` is the number of THIS step (1 for the first).  fp32 GPU tensors on
     one device; params and moments must be contiguous (they are written in place), a non-contiguous gradient is copied.  Returns the
     number of launches.  The parameters' version counters are NOT bumped (the kernels write through raw pointers): optim.AdamW does."""
-    n = len(params)
-    if not (n == len(grads) == len(exp_avgs) == len(exp_avg_sqs)):
-        raise ValueError('params, grads, exp_avgs and exp_avg_sqs must have one entry per tensor')
-    if n == 0:
-        return 0
-    hyper = adamw_hyper(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, step=step)
-    arr, keep = _adamw_array(params, grads, exp_avgs, exp_avg_sqs)
-    launches = 0
-    with torch.cuda.device(keep[0].device):
-        lib = _hip.load()
-        stream = _stream(keep[0])
-        for chunk, k in _item_chunks(arr, n):
-            _hip.check(lib.v2w_adamw_multi(chunk, k, C.byref(hyper), stream), 'v2w_adamw_multi')
-            launches += 1
-    return launches
+    return _adamw_step('v2w_adamw_multi', params, grads, exp_avgs, exp_avg_sqs,
+                       lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, step=step)
 
 
 # ---- global-norm clipping and the non-finite guard (include/vec2wav_hip.h: v2w_grad_sumsq_multi and its neighbours)
@@ -1600,31 +1638,15 @@ def _clip_buffer(t, name, floats):
 
 
 def _grad_array(grads, in_place=False):
-    """(descriptors with g and numel set, the tensors they point into); fp32 GPU tensors on one device.  A non-contiguous gradient is
-    copied for reading; one that is to be written in place is refused."""
-    n = len(grads)
-    arr = (_hip.AdamWItem * max(n, 1))()
-    keep = []
-    for i, g in enumerate(grads):
-        g = g.detach()
-        if g.is_cuda and g.dtype == torch.float32 and not g.is_contiguous():
-            if in_place:
-                raise ValueError(f'grad[{i}] is not contiguous: it cannot be scaled in place')
-            g = g.contiguous()
-        _chk(g, f'grad[{i}]')
-        if g.device != grads[0].device:
-            raise RuntimeError('all gradients of one call must live on one device')
-        if g.numel() == 0:
-            raise ValueError(f'grad[{i}] is empty')
-        keep.append(g)
-        arr[i].g, arr[i].numel = g.data_ptr(), g.numel()
-    return arr, keep
+    """(descriptors with g and numel set, the tensors they point into).  A non-contiguous gradient is copied for reading; one that is to be
+    written in place is refused."""
+    return _flat_items(_hip.AdamWItem, 'gradient', {'grad': grads}, copied='grad', in_place=('grad',) if in_place else ())
 
 
 def _sumsq_partials(arr, n):
     lib = _hip.load()
     total = 0
-    for chunk, k in _item_chunks(arr, n):
+    for chunk, k in _chunks_of(arr, n, _hip.AdamWItem, _hip.ADAMW_MAX_ITEMS):
         w = lib.v2w_grad_sumsq_partials(chunk, k)
         if w <= 0:
             _hip.check(w or -1, 'v2w_grad_sumsq_partials')
@@ -1649,19 +1671,19 @@ def grad_sumsq_multi(grads, partials=None):
         raise ValueError('no gradients')
     arr, keep = _grad_array(grads)
     dev = keep[0].device
-    with torch.cuda.device(dev):
-        lib = _hip.load()
-        count = _sumsq_partials(arr, n)
-        if partials is None:
-            partials = torch.empty((count,), device=dev, dtype=torch.float32)
-        _clip_buffer(partials, 'partials', count)
-        if partials.device != dev:
-            raise RuntimeError('partials must live on the gradients\' device')
-        stream = _stream(keep[0])
-        at = 0
-        for chunk, k in _item_chunks(arr, n):
-            _hip.check(lib.v2w_grad_sumsq_multi(chunk, k, partials.data_ptr() + 4 * at, stream), 'v2w_grad_sumsq_multi')
-            at += lib.v2w_grad_sumsq_partials(chunk, k)
+    count = _sumsq_partials(arr, n)
+    if partials is None:
+        partials = torch.empty((count,), device=dev, dtype=torch.float32)
+    _clip_buffer(partials, 'partials', count)
+    if partials.device != dev:
+        raise RuntimeError('partials must live on the gradients\' device')
+    at = [0]
+
+    def its_range(chunk, k):                              # every launch writes behind the one before
+        first = partials.data_ptr() + 4 * at[0]
+        at[0] += _hip.load().v2w_grad_sumsq_partials(chunk, k)
+        return (first,)
+    _launch_chunks('v2w_grad_sumsq_multi', arr, n, _hip.AdamWItem, _hip.ADAMW_MAX_ITEMS, keep[0], its_range)
     return partials, count
 
 
@@ -1688,38 +1710,14 @@ def scale_multi(grads, coef):
         return 0
     arr, keep = _grad_array(grads, in_place=True)
     _clip_buffer(coef, 'coef', 1)
-    launches = 0
-    with torch.cuda.device(keep[0].device):
-        lib = _hip.load()
-        stream = _stream(keep[0])
-        for chunk, k in _item_chunks(arr, n):
-            _hip.check(lib.v2w_scale_multi(chunk, k, coef.data_ptr(), stream), 'v2w_scale_multi')
-            launches += 1
-    return launches
+    return _launch_chunks('v2w_scale_multi', arr, n, _hip.AdamWItem, _hip.ADAMW_MAX_ITEMS, keep[0], (coef.data_ptr(),))
 
 
 def adamw_multi_clipped(params, grads, exp_avgs, exp_avg_sqs, clip, *, skip_nonfinite=False, lr, betas, eps, weight_decay, step):
     """adamw_multi on g * clip[1], `clip` the four floats of grad_norm_finish on the GPU, read by the kernel: the gradients are not
     written, the host reads nothing.  With skip_nonfinite and clip[2] == 0 (a non-finite norm) the launches write nothing."""
-    n = len(params)
-    if not (n == len(grads) == len(exp_avgs) == len(exp_avg_sqs)):
-        raise ValueError('params, grads, exp_avgs and exp_avg_sqs must have one entry per tensor')
-    _clip_buffer(clip, 'clip', 4)
-    if n == 0:
-        return 0
-    hyper = adamw_hyper(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, step=step)
-    arr, keep = _adamw_array(params, grads, exp_avgs, exp_avg_sqs)
-    if clip.device != keep[0].device:
-        raise RuntimeError('clip must live on the parameters\' device')
-    launches = 0
-    with torch.cuda.device(keep[0].device):
-        lib = _hip.load()
-        stream = _stream(keep[0])
-        for chunk, k in _item_chunks(arr, n):
-            _hip.check(lib.v2w_adamw_multi_clipped(chunk, k, C.byref(hyper), clip.data_ptr(), int(bool(skip_nonfinite)), stream),
-                       'v2w_adamw_multi_clipped')
-            launches += 1
-    return launches
+    return _adamw_step('v2w_adamw_multi_clipped', params, grads, exp_avgs, exp_avg_sqs, None, clip, skip_nonfinite=skip_nonfinite,
+                       lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, step=step)
 
 
 # ---- exponential moving average of the weights (include/vec2wav_hip.h: v2w_adamw_ema_multi, v2w_ema_multi, v2w_swap_multi)
@@ -1731,35 +1729,13 @@ def ema_omd(ema_decay):
     return 1.0 - d
 
 
-def _chunks_of(arr, n, item, limit):
-    """(pointer to the first descriptor, count) of every run of at most `limit` descriptors of type `item`."""
-    for i0 in range(0, n, limit):
-        yield C.cast(C.byref(arr, i0 * C.sizeof(item)), C.POINTER(item)), min(limit, n - i0)
-
-
 def _pair_array(ps, es, what):
     """(EmaItem descriptors, the tensors they point into) of two lists of fp32 GPU tensors on one device, entry for entry of one size."""
-    n = len(ps)
-    if n != len(es):
+    if len(ps) != len(es):
         raise ValueError(f'{what}: params and emas must have one entry per tensor')
-    if n == 0:
+    if len(ps) == 0:
         raise ValueError(f'{what}: no tensors')
-    dev = ps[0].device
-    arr = (_hip.EmaItem * n)()
-    keep = []
-    for i, (p, e) in enumerate(zip(ps, es)):
-        p, e = p.detach(), e.detach()
-        for t, name in ((p, 'param'), (e, 'ema')):
-            _chk(t, f'{name}[{i}]')
-            if t.device != dev:
-                raise RuntimeError(f'all tensors of one {what} call must live on one device')
-        if e.numel() != p.numel():
-            raise ValueError(f'ema[{i}] has {e.numel()} elements, its parameter {p.numel()}')
-        if p.numel() == 0:
-            raise ValueError(f'param[{i}] is empty')
-        keep += [p, e]
-        arr[i].p, arr[i].e, arr[i].numel = p.data_ptr(), e.data_ptr(), p.numel()
-    return arr, keep
+    return _flat_items(_hip.EmaItem, what, {'param': ps, 'ema': es})
 
 
 def adamw_ema_multi(params, grads, exp_avgs, exp_avg_sqs, emas, clip=None, *, ema_decay, skip_nonfinite=False, lr, betas, eps, weight_decay,
@@ -1768,39 +1744,8 @@ def adamw_ema_multi(params, grads, exp_avgs, exp_avg_sqs, emas, clip=None, *, em
     average of every parameter updated in the same pass: emas[i] <- emas[i] + (1 - ema_decay) (params[i]' - emas[i]), in place;
     params / exp_avgs / exp_avg_sqs get the bits the other two wrappers give.  ceil(n / ADAMW_EMA_MAX_ITEMS) launches; returns their
     number.  With skip_nonfinite and clip[2] == 0 nothing is written, the averages included."""
-    n = len(params)
-    if not (n == len(grads) == len(exp_avgs) == len(exp_avg_sqs) == len(emas)):
-        raise ValueError('params, grads, exp_avgs, exp_avg_sqs and emas must have one entry per tensor')
-    if n == 0:
-        raise ValueError('adamw_ema_multi: no tensors')
-    omd = ema_omd(ema_decay)
-    if clip is not None:
-        _clip_buffer(clip, 'clip', 4)
-    hyper = adamw_hyper(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, step=step)
-    src, keep = _adamw_array(params, grads, exp_avgs, exp_avg_sqs)
-    dev = keep[0].device
-    arr = (_hip.AdamWEmaItem * n)()
-    for i, e in enumerate(emas):
-        e = e.detach()
-        _chk(e, f'ema[{i}]')
-        if e.device != dev:
-            raise RuntimeError('all tensors of one adamw_ema_multi call must live on one device')
-        if e.numel() != src[i].numel:
-            raise ValueError(f'ema[{i}] has {e.numel()} elements, its parameter {src[i].numel}')
-        keep.append(e)
-        d = arr[i]
-        d.p, d.g, d.m, d.v, d.e, d.numel = src[i].p, src[i].g, src[i].m, src[i].v, e.data_ptr(), src[i].numel
-    if clip is not None and clip.device != dev:
-        raise RuntimeError('clip must live on the parameters\' device')
-    launches = 0
-    with torch.cuda.device(dev):
-        lib = _hip.load()
-        stream = _stream(keep[0])
-        for chunk, k in _chunks_of(arr, n, _hip.AdamWEmaItem, _hip.ADAMW_EMA_MAX_ITEMS):
-            _hip.check(lib.v2w_adamw_ema_multi(chunk, k, C.byref(hyper), _hip.ptr(clip), int(bool(skip_nonfinite)), omd, stream),
-                       'v2w_adamw_ema_multi')
-            launches += 1
-    return launches
+    return _adamw_step('v2w_adamw_ema_multi', params, grads, exp_avgs, exp_avg_sqs, emas, clip, ema_decay=ema_decay,
+                       skip_nonfinite=skip_nonfinite, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, step=step)
 
 
 def ema_multi(params, emas, *, ema_decay):
@@ -1808,25 +1753,11 @@ def ema_multi(params, emas, *, ema_decay):
     buffers.  fp32 contiguous GPU tensors on one device; ceil(n / ADAMW_MAX_ITEMS) launches, returns their number."""
     omd = ema_omd(ema_decay)
     arr, keep = _pair_array(params, emas, 'ema_multi')
-    launches = 0
-    with torch.cuda.device(keep[0].device):
-        lib = _hip.load()
-        stream = _stream(keep[0])
-        for chunk, k in _chunks_of(arr, len(params), _hip.EmaItem, _hip.ADAMW_MAX_ITEMS):
-            _hip.check(lib.v2w_ema_multi(chunk, k, omd, stream), 'v2w_ema_multi')
-            launches += 1
-    return launches
+    return _launch_chunks('v2w_ema_multi', arr, len(params), _hip.EmaItem, _hip.ADAMW_MAX_ITEMS, keep[0], (omd,))
 
 
 def swap_multi(params, emas):
     """Exchanges the contents of params[i] and emas[i] in place, bit for bit; no storage pointer moves.  ceil(n / ADAMW_MAX_ITEMS)
     launches, returns their number.  The parameters' version counters are NOT bumped: optim.AdamW.swap_ema does."""
     arr, keep = _pair_array(params, emas, 'swap_multi')
-    launches = 0
-    with torch.cuda.device(keep[0].device):
-        lib = _hip.load()
-        stream = _stream(keep[0])
-        for chunk, k in _chunks_of(arr, len(params), _hip.EmaItem, _hip.ADAMW_MAX_ITEMS):
-            _hip.check(lib.v2w_swap_multi(chunk, k, stream), 'v2w_swap_multi')
-            launches += 1
-    return launches
+    return _launch_chunks('v2w_swap_multi', arr, len(params), _hip.EmaItem, _hip.ADAMW_MAX_ITEMS, keep[0])
