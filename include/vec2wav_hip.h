@@ -543,6 +543,12 @@ int v2w_convt1d_fwd_len(const v2w_convt1d_args* a, const int32_t* len, int len_m
  * (in_a), dilations that differ, an even k, C % 64 != 0, and whatever V2W_ALGO_WINO declines but a small launch - the caller then issues
  * the convs one by one. */
 int v2w_conv1d_wino_sum_fwd(const v2w_conv1d_args* a, int n, const int32_t* len, int len_mul, void* stream);
+/* The same with the order given in which a workgroup walks the sources: `order` (host memory) is a permutation of 0 .. n - 1 (V2W_E_ARG
+ * otherwise), NULL leaves the choice to the library (v2w_conv1d_wino_sum_fwd).  The order changes only the order in which the sources'
+ * products are accumulated; bias and residual sums keep the association above, by source index.  v2w_wino_sum_order: the library's
+ * choice for sources of kernel sizes k[0 .. n), n <= 3 (host only, launches nothing).  New symbols over unchanged structs. */
+int v2w_conv1d_wino_sum_fwd_order(const v2w_conv1d_args* a, int n, const int32_t* len, int len_mul, const int32_t* order, void* stream);
+int v2w_wino_sum_order(const int32_t* k, int n, int32_t* order);
 int v2w_resblock2_stage_fwd_len(const v2w_stage_args* a, const int32_t* len, int len_mul, void* stream);
 int v2w_conv_post_tanh_len(const float* in, const float* wf, const float* bias, float* out,
                            int B, int C_in, int L, int k, float slope, const int32_t* len, int len_mul, void* stream);

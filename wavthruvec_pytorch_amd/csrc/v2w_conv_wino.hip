@@ -27,6 +27,10 @@
 // Summed form (conv_wino_sum_kernel, v2w_conv1d_wino_sum_fwd): up to three convs of one dilation - the second convs of a stage's branches - on
 // the same accumulators, one output transform, then t = y + ((b0 + b1) + b2); t += (in_0[go] + in_1[go]) + in_2[go]; t = t / out_div (the
 // division above): NOT the rounding order of three launches that add r0, r1, r2 (B = 32 x T = 256: max |dy| = 3.7e-7 at max |y| = 0.40).
+// Its epilogue loads the residuals of four rows (24 loads with three sources, the count a compile-time constant then) before the rows'
+// output transform and stores - they were three dependent loads per stored element behind the last MFMA: the summed launches of stages
+// 0 / 1 / 2 805 -> 789, 760 -> 740, 807 -> 767 us.  The sources are walked in branch order (wino_sum_order; any other order can be asked
+// for, v2w_conv1d_wino_sum_fwd_order - none measured faster); bias and residual sums are by branch index whatever the walk.
 #include "v2w_tile.h"
 #include "v2w_internal.h"
 #include "v2w_wino.h"
@@ -55,12 +59,16 @@ __host__ __device__ inline void wino_tile_order(int v, int B, int ntl, bool tail
 // The summed form (v2w_conv1d_wino_sum_fwd): up to WSRC convs of one dilation whose results add - the second convs of a ResBlock2 stage's
 // branches.  The output transform is linear, so every source's terms add into the same four accumulator classes: one workgroup walks the
 // sources one after another (own input, weight stream, K, halo), pays prologue, output transform and epilogue once and writes only the sum.
-// `p` holds what the sources share (and source 0); the input of each source is also its residual.
+// `p` holds what the sources share (and the first source walked); the input of each source is also its residual.
+// in / wp / K / hl are in WALK order (launch_wino_sum picks it: it fixes which source's chunk 0 is staged under which source's last chunk and
+// which source runs last, next to the epilogue); res / bias are in BRANCH order, so that the bias and residual sums keep their association
+// (b0 + b1) + b2 and (t1_0 + t1_1) + t1_2 whatever the walk - only the accumulation order of the products follows it.
 constexpr int WSRC = 3;
 struct WinoSumArgs {
     TileArgs p;
-    const float* in[WSRC]; const float* wp[WSRC]; const float* bias[WSRC];
+    const float* in[WSRC]; const float* wp[WSRC];
     int K[WSRC], hl[WSRC];
+    const float* res[WSRC]; const float* bias[WSRC];
     int nsrc;
 };
 __device__ __forceinline__ const TileArgs& wino_problem(const MultiArgs& m, int pq) { return m.p[pq]; }
@@ -331,6 +339,59 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
     // ---- epilogue: output transform, then + bias [+ residual] [+ addends | + out] [/ out_div], conv_tile_kernel's order
     float* const outp = p.out;
     const float dinv = p.out_div != 0.f ? 1.f / p.out_div : 1.f;
+    if constexpr (SUM) {
+        // The sources' own inputs are their residuals: t = (y + bias) + ((t1_0 + t1_1) + t1_2).  The residual loads of EB rows (2 EB NS
+        // of them) are issued before the rows' output transform and stores, so that they fly together: one by one behind each store
+        // (the output may alias an input for all the compiler knows) they were 3 dependent round trips per stored element after the last MFMA.
+        // NS: the number of sources at compile time (3: a ResBlock2 stage), 0: m.nsrc at run time.
+        auto epilogue = [&](auto ns_c) {
+            constexpr int NS = decltype(ns_c)::value;
+            constexpr int NR = NS ? NS : WSRC;
+            constexpr int EB = 4;
+            const int ns = NS ? NS : nsrc;
+#pragma unroll
+            for (int e0 = 0; e0 < 16; e0 += EB) {
+                float rv[EB][2][NR];
+#pragma unroll
+                for (int q = 0; q < EB; ++q) {
+                    const size_t rowoff = ((size_t)b * p.CoutT + m0 + wm0 + F::row(e0 + q, hk)) * L;
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const int pos = t0 + h * d;
+#pragma unroll
+                        for (int j = 0; j < NR; ++j) rv[q][h][j] = (pos < L && j < ns) ? m.res[j][rowoff + pos] : 0.f;
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < EB; ++q) {
+                    const int e = e0 + q, col = wm0 + F::row(e, hk);
+                    const float M0 = acc[0][0][e], M1 = acc[1][0][e], M2 = acc[2][0][e], M3 = acc[3][0][e];
+                    const float y[2] = {(M0 + M1) + M2, (M1 - M2) - M3};
+                    const size_t rowoff = ((size_t)b * p.CoutT + m0 + col) * L;
+                    const float bias = etab[col];
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const int pos = t0 + h * d;
+                        if (pos >= L) continue;
+                        float t = y[h] + bias;
+                        float r = rv[q][h][0];
+                        if (NS == 3) r = (r + rv[q][h][1]) + rv[q][h][2];
+                        else {
+#pragma unroll
+                            for (int j = 1; j < NR; ++j) if (j < ns) r += rv[q][h][j];
+                        }
+                        t += r;
+                        if (p.out_div != 0.f) t = v2w_div_by(t, p.out_div, dinv);
+                        outp[rowoff + pos] = t;
+                    }
+                }
+            }
+        };
+        static_assert(!SUM || MI == 1, "the summed form's epilogue is written for MI = 1");
+        if (nsrc == 3) epilogue(std::integral_constant<int, 3>{});
+        else epilogue(std::integral_constant<int, 0>{});
+        return;
+    }
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
 #pragma unroll
@@ -346,14 +407,6 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
                 if (pos >= L) continue;
                 const size_t go = rowoff + pos;
                 float t = y[h] + bias;
-                if constexpr (SUM) {         // the sources' own inputs are their residuals: (t1_0 + t1_1) + t1_2
-                    float r = m.in[0][go];
-                    for (int j = 1; j < nsrc; ++j) r += m.in[j][go];
-                    t += r;
-                    if (p.out_div != 0.f) t = v2w_div_by(t, p.out_div, dinv);
-                    outp[go] = t;
-                    continue;
-                }
                 if (p.res) t += fmaf(ra, p.res[go], rs);
                 if (p.add1) t += p.add0[go] + p.add1[go];      // (add0 + add1) + value: the reference's `xs += ...` order
                 else if (p.accumulate) t += outp[go];
@@ -430,12 +483,33 @@ int launch_wino(const TileArgs* ps, int nprob, hipStream_t stream) {
 }
 
 // The summed form: ps[0 .. nsrc) are the sources (shared B, C, L, dil, slope, out, out_div, len); one problem, one grid.
+// The order in which a workgroup of the summed form walks its sources (branch indices; Ks: their kernel sizes).  Branch order: on MI355X
+// k = 3 last, longest first and the other four orders of k = (3, 7, 11) all ran within the launches' own spread of it at C = 256 / 128 / 64
+// (profiles/r14_cfg2_wino_sum_walk_orders.txt), and this one keeps the 64-channel stage's accumulation order.
+inline void wino_sum_order(const int* Ks, int nsrc, int* walk) {
+    (void)Ks;
+    for (int j = 0; j < nsrc; ++j) walk[j] = j;
+}
+
+// `order`: the walk order, a permutation of 0 .. nsrc - 1 (null: wino_sum_order's).
 template <int MI, int WN>
-int launch_wino_sum(const TileArgs* ps, int nsrc, hipStream_t stream) {
+int launch_wino_sum(const TileArgs* ps, int nsrc, const int32_t* order, hipStream_t stream) {
     constexpr int MT = 64 * MI, NTP = 32 * WN, NTHREADS = 128 * WN;
     constexpr int NPF = ((WCK / 2) * (((2 * NTP + 2 * WHMAX) / 4 + 7) / 8 * 8) + NTHREADS - 1) / NTHREADS;
     WinoSumArgs a{};
-    TileArgs p = ps[0];
+    int walk[WSRC];
+    int Ks[WSRC];
+    for (int j = 0; j < nsrc; ++j) Ks[j] = ps[j].K;
+    wino_sum_order(Ks, nsrc, walk);
+    if (order) {
+        unsigned seen = 0;
+        for (int j = 0; j < nsrc; ++j) {
+            if (order[j] < 0 || order[j] >= nsrc || (seen >> order[j] & 1u)) return V2W_E_ARG;
+            seen |= 1u << order[j];
+            walk[j] = order[j];
+        }
+    }
+    TileArgs p = ps[walk[0]];
     if (p.Cout % MT != 0) return V2W_E_SHAPE;
     const int d = p.dil;
     p.ntl = (wino_npairs(p.L, d) + NTP - 1) / NTP;
@@ -450,7 +524,9 @@ int launch_wino_sum(const TileArgs* ps, int nsrc, hipStream_t stream) {
             if (r > rows) rows = r;
         }
         vec = vec && v2w_al16(ps[j].in);
-        a.in[j] = ps[j].in; a.wp[j] = ps[j].wp; a.bias[j] = ps[j].bias; a.K[j] = ps[j].K; a.hl[j] = ps[j].hl;
+        const TileArgs& w = ps[walk[j]];
+        a.in[j] = w.in; a.wp[j] = w.wp; a.K[j] = w.K; a.hl[j] = w.hl;
+        a.res[j] = ps[j].in; a.bias[j] = ps[j].bias;
     }
     a.nsrc = nsrc;
     p.xrows = (rows + 3) & ~3;
@@ -524,6 +600,12 @@ int v2w_conv1d_wino(const v2w_conv1d_args* a, int n, hipStream_t stream, const i
 // The summed form (include/vec2wav_hip.h): out = (sum_j in_j + sum_j conv_j(lrelu(in_j)) + sum_j bias_j) [/ out_div] in one launch.
 // Serves what v2w_conv1d_wino serves, of any size, with C_in == C_out, one dilation and no input affine; V2W_E_SHAPE otherwise.
 extern "C" int v2w_conv1d_wino_sum_fwd(const v2w_conv1d_args* a, int n, const int32_t* len, int len_mul, void* stream) {
+    return v2w_conv1d_wino_sum_fwd_order(a, n, len, len_mul, nullptr, stream);
+}
+
+// ... with the walk order given: `order` (host memory) is a permutation of 0 .. n - 1, null leaves the choice to the library.  The order
+// changes only the order in which the sources' products are accumulated, never the bias or the residual sum.
+extern "C" int v2w_conv1d_wino_sum_fwd_order(const v2w_conv1d_args* a, int n, const int32_t* len, int len_mul, const int32_t* order, void* stream) {
     if (!a || n < 1 || n > WSRC || (len && len_mul < 1)) return V2W_E_ARG;
     TileArgs ps[WSRC];
     for (int i = 0; i < n; ++i) {
@@ -543,7 +625,16 @@ extern "C" int v2w_conv1d_wino_sum_fwd(const v2w_conv1d_args* a, int n, const in
         p.slope = q->slope; p.out_div = a->out_div;
         ps[i] = p;
     }
-    return launch_wino_sum<1, 2>(ps, n, (hipStream_t)stream);
+    return launch_wino_sum<1, 2>(ps, n, order, (hipStream_t)stream);
+}
+
+extern "C" int v2w_wino_sum_order(const int32_t* k, int n, int32_t* order) {
+    if (!k || !order || n < 1 || n > WSRC) return V2W_E_ARG;
+    int Ks[WSRC], walk[WSRC];
+    for (int j = 0; j < n; ++j) Ks[j] = k[j];
+    wino_sum_order(Ks, n, walk);
+    for (int j = 0; j < n; ++j) order[j] = walk[j];
+    return 0;
 }
 
 extern "C" int v2w_wino_terms(int k) { return wino_terms(k); }

@@ -580,7 +580,9 @@ class ForwardPlanner:
     def conv2_sum(self):
         """The second convs of all branches as one Winograd launch on one accumulator (o_j never written); False: not selected or declined."""
         g, rbs, names = self.g, self.rbs, self.names
-        if self.save is not None or self.st or not wino_sum_selected(g.wino_sum, g.precision, self.algo, self.C,
+        # (wino_sum: stages the fold gives streams of their own; wino_sum_wide: stages that reuse the streams `wino` folds - none without it)
+        listed = tuple(g.wino_sum or ()) + tuple(g.wino_sum_wide or ())
+        if self.save is not None or self.st or not wino_sum_selected(listed, g.precision, self.algo, self.C,
                                                                      [(rb.kernel_size, rb.convs[1].dilation) for rb in rbs]):
             return False
         wpw = {**g._fold_key.get('wpw_sum', {}), **g._fold_key.get('wpw', {})}

@@ -328,21 +328,33 @@ def conv1d_wino_multi(problems, splitk_ws=None):
     conv1d_multi([(x, wf, bias, out, {q: v for q, v in kw.items() if q != 'wpw'}) for x, wf, bias, out, kw in problems], splitk_ws=splitk_ws)
 
 
-def conv1d_wino_sum(sources, out, *, dil, slope, out_div=0.0, in_affine=None, lengths=None, len_mul=1):
+def conv1d_wino_sum(sources, out, *, dil, slope, out_div=0.0, in_affine=None, lengths=None, len_mul=1, order=None):
     """The summed form of the Winograd F(2,3) kernel (v2w_conv1d_wino_sum_fwd): `sources` = up to three (x_j, wpw_j, bias_j, k_j) of one
     dilation - the second convs of a ResBlock2 stage's branches - in ONE launch on one accumulator:
     out = (sum_j x_j + sum_j conv_j(lrelu(x_j)) + sum_j bias_j) [/ out_div].  Returns False (nothing launched) when the library declines
-    the shape (V2W_E_SHAPE); the caller then issues the convs one by one."""
+    the shape (V2W_E_SHAPE); the caller then issues the convs one by one.  `order`: the order in which a workgroup walks the sources (a
+    permutation of range(len(sources)); v2w_conv1d_wino_sum_fwd_order) - None: the library's choice (wino_sum_order)."""
     n = len(sources)
     arr = (_hip.Conv1dArgs * max(n, 1))()
     for a, (x, wpw, bias, k) in zip(arr, sources):
         _conv1d_args(a, x, None, bias, out, k=k, dil=dil, slope=slope, out_div=out_div, algo=ALGO_WINO, wp=wpw, in_affine=in_affine)
     lp = _len_ptr(lengths, len_mul) if lengths is not None else None
-    rc = _hip.load().v2w_conv1d_wino_sum_fwd(arr, n, lp, int(len_mul), _stream(out))
+    if order is None:
+        rc = _hip.load().v2w_conv1d_wino_sum_fwd(arr, n, lp, int(len_mul), _stream(out))
+    else:
+        rc = _hip.load().v2w_conv1d_wino_sum_fwd_order(arr, n, lp, int(len_mul), (C.c_int32 * max(n, 1))(*order), _stream(out))
     if rc == -2:
         return False
     _hip.check(rc, 'v2w_conv1d_wino_sum_fwd')
     return True
+
+
+def wino_sum_order(ks):
+    """The order in which the summed launch walks sources of kernel sizes `ks` when none is given (v2w_wino_sum_order; host only)."""
+    n = len(ks)
+    out = (C.c_int32 * n)()
+    _hip.check(_hip.load().v2w_wino_sum_order((C.c_int32 * n)(*ks), n, out), 'v2w_wino_sum_order')
+    return tuple(out)
 
 
 def convt1d(x, wf, bias, out, *, k, u, slope=1.0, algo=ALGO_AUTO, wp=None, stats_part=None, splitk_ws=None, lengths=None, len_mul=1):
