@@ -549,6 +549,15 @@ int v2w_conv1d_wino_sum_fwd(const v2w_conv1d_args* a, int n, const int32_t* len,
  * choice for sources of kernel sizes k[0 .. n), n <= 3 (host only, launches nothing).  New symbols over unchanged structs. */
 int v2w_conv1d_wino_sum_fwd_order(const v2w_conv1d_args* a, int n, const int32_t* len, int len_mul, const int32_t* order, void* stream);
 int v2w_wino_sum_order(const int32_t* k, int n, int32_t* order);
+/* The FIRST convs of a ResBlock2 stage's branches as ONE Winograd launch that stages their common input once per tile (additive in ABI v35;
+ * fp32).  a[0 .. n), n <= 3, are convs over the same input: they share `in`, `in_a` / `in_s`, `res`, `res_a` / `res_s`, B, C_in, C_out, L,
+ * `dil` and `slope` (V2W_E_ARG otherwise, and for two problems with one `out`); each has its own `wp` (v2w_pack_wino / fold `wpw` stream),
+ * `bias`, `k` and `out`:
+ *     out_j = conv_j(lrelu(in_a * in + in_s)) + bias_j [+ (res_a * res + res_s)]
+ * with the operations of the V2W_ALGO_WINO launch of a[j] alone, in its order: the same bits.  V2W_E_SHAPE (nothing launched; the caller
+ * issues v2w_conv1d_fwd_multi): C_in > 64 (the kernel's two chunk buffers must hold the whole input window), add0 / add1 / accumulate /
+ * out_div set, and whatever V2W_ALGO_WINO declines but a small launch.  No per-item lengths.  A new symbol over unchanged structs. */
+int v2w_conv1d_wino_fan_fwd(const v2w_conv1d_args* a, int n, void* stream);
 int v2w_resblock2_stage_fwd_len(const v2w_stage_args* a, const int32_t* len, int len_mul, void* stream);
 int v2w_conv_post_tanh_len(const float* in, const float* wf, const float* bias, float* out,
                            int B, int C_in, int L, int k, float slope, const int32_t* len, int len_mul, void* stream);

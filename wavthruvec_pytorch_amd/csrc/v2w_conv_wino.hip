@@ -31,6 +31,10 @@
 // output transform and stores - they were three dependent loads per stored element behind the last MFMA: the summed launches of stages
 // 0 / 1 / 2 805 -> 789, 760 -> 740, 807 -> 767 us.  The sources are walked in branch order (wino_sum_order; any other order can be asked
 // for, v2w_conv1d_wino_sum_fwd_order - none measured faster); bias and residual sums are by branch index whatever the walk.
+// Fan-out form (conv_wino_fan_kernel, v2w_conv1d_wino_fan_fwd): up to three convs of one dilation over ONE input of at most 64 channels - the
+// first convs of the 64-channel stage's branches - in one workgroup per tile: tables and the activated window staged once (the two chunk
+// buffers hold its whole K extent), then branch after branch accumulate, transform, store to out_j, zero.  Each conv keeps the one-conv
+// kernel's operations and their order, so its bits.  B = 32 x L = 20 480, k = (3, 7, 11): 893 us in 15 360 workgroups -> 750 us in 5 120.
 #include "v2w_tile.h"
 #include "v2w_internal.h"
 #include "v2w_wino.h"
@@ -71,15 +75,31 @@ struct WinoSumArgs {
     const float* res[WSRC]; const float* bias[WSRC];
     int nsrc;
 };
+// The fan-out form (v2w_conv1d_wino_fan_fwd): up to WSRC convs of one dilation over ONE input - the first convs of a ResBlock2 stage's
+// branches - each with its own weight stream, bias and output.  At C_in <= 64 the kernel's two chunk buffers hold the whole K extent of the
+// activated signal, so one workgroup stages it once (with the widest branch's halo: the LDS rows and pos0 serve every branch) and walks the
+// branches one after another: accumulate, output transform, epilogue, store to out_j, zero the accumulators, next weight stream.  Every
+// branch runs the one-conv kernel's operations in its order (same staged values, fragment order, epilogue expression): the same bits.
+// `p` holds what the branches share (input, affines, residual, sizes; hl / hr: the widest branch's halo).
+struct WinoFanArgs {
+    TileArgs p;
+    const float* wp[WSRC]; const float* bias[WSRC]; float* out[WSRC];
+    int K[WSRC], hl[WSRC];
+    int nsrc;
+};
 __device__ __forceinline__ const TileArgs& wino_problem(const MultiArgs& m, int pq) { return m.p[pq]; }
 __device__ __forceinline__ const TileArgs& wino_problem(const WinoSumArgs& a, int) { return a.p; }
+__device__ __forceinline__ const TileArgs& wino_problem(const WinoFanArgs& a, int) { return a.p; }
 
 // LEN: per-item valid lengths, as in conv_tile_body (v2w_conv_mfma.hip): inputs at and past Lb = min(L, len[b] * len_mul) select 0, a tile
 // whose first output position lies there returns at once; its own kernel name (conv_wino_len_kernel).
-// ARGS = WinoSumArgs: the summed form (one problem per launch); MultiArgs: one conv per problem.
+// ARGS = WinoSumArgs: the summed form (one problem per launch); WinoFanArgs: the fan-out form (one problem per launch, C_in <= 64, no LEN);
+// MultiArgs: one conv per problem.
 template <int MI, int WN, int NPF, bool VEC, bool LEN, class ARGS>
 __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
     constexpr bool SUM = std::is_same<ARGS, WinoSumArgs>::value;
+    constexpr bool FAN = std::is_same<ARGS, WinoFanArgs>::value;
+    static_assert(!FAN || (MI == 1 && !LEN), "the fan-out form is written for MI = 1 without per-item lengths");
     typedef Frag<32> F;
     typedef F::acc_t acc_t;
     constexpr int WM = 2;
@@ -91,7 +111,7 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     int pq = 0, id = blockIdx.x;
-    if constexpr (!SUM) { pq = tile_problem(m); id = blockIdx.x - m.start[pq]; }
+    if constexpr (!SUM && !FAN) { pq = tile_problem(m); id = blockIdx.x - m.start[pq]; }
     const TileArgs& p = wino_problem(m, pq);
     const int mtiles = p.Cout / MT;
     const TileId ti = tile_coords(mtiles, id);
@@ -123,11 +143,12 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
     int K = p.K, hl = p.hl;                  // (SUM: of the source whose chunks are being multiplied)
     const float* sin = p.in;                 // the tensor the staging reads, pos0 the position of its LDS row 0 (floor to a float4) -
     int pos0 = (wino_tpos(P0, d) - hl) & ~3; // SUM: already the NEXT source's while the last chunk of a source is multiplied
+    if constexpr (FAN) { K = m.K[0]; hl = m.hl[0]; }          // (p.hl: the widest branch's - pos0 and the LDS rows serve every branch)
     const float slope = p.slope;
     const int nch = p.Cin / WCK;
     const int bufsz = p.xrows * WG::RS;
-    float* const etab = smem + p.atab_off;   // bias, res_a, res_s [MT] each
-    float* const atab = etab + 3 * MT;       // folded CondBN affine of this batch item: a[Cin] then s[Cin]
+    float* const etab = smem + p.atab_off;   // bias, res_a, res_s [MT] each (FAN: bias [WSRC][MT], then res_a, res_s)
+    float* const atab = etab + (FAN ? WSRC + 2 : 3) * MT;     // folded CondBN affine of this batch item: a[Cin] then s[Cin]
 
     acc_t acc[4][MI];
 #pragma unroll
@@ -263,8 +284,14 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
 
     // ---- prologue: epilogue constants, affine table, chunk 0, first fragments
     int nsrc = 1;
-    if constexpr (SUM) nsrc = m.nsrc;
+    if constexpr (SUM || FAN) nsrc = m.nsrc;
     for (int c = tid; c < MT; c += NTHREADS) {
+        if constexpr (FAN) {
+            for (int j = 0; j < nsrc; ++j) etab[j * MT + c] = m.bias[j] ? m.bias[j][m0 + c] : 0.f;
+            etab[WSRC * MT + c] = p.res_a ? p.res_a[b * p.Cout + m0 + c] : 1.f;
+            etab[(WSRC + 1) * MT + c] = p.res_a ? p.res_s[b * p.Cout + m0 + c] : 0.f;
+            continue;
+        }
         if constexpr (SUM) {                 // (b0 + b1) + b2
             float bv = m.bias[0] ? m.bias[0][m0 + c] : 0.f;
             for (int j = 1; j < nsrc; ++j) bv += m.bias[j] ? m.bias[j][m0 + c] : 0.f;
@@ -296,6 +323,51 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
     typedef std::integral_constant<int, 3> S3;
     typedef std::integral_constant<int, 2> S2;
     typedef std::integral_constant<int, 1> S1;
+    // FAN: one branch's output transform and epilogue, t = y + bias_j [+ fmaf(res_a, res[go], res_s)] as the one-conv epilogue below computes
+    // it; the residual loads of EB rows are issued before the rows' output transform and stores (as in the summed epilogue), and are
+    // reloaded per branch - kept across the branches they would cost 32 registers next to the 64 accumulators.
+    auto fan_epilogue = [&](int j) {
+        if constexpr (FAN) {
+            float* const outp = m.out[j];
+            const float* const res = p.res;
+            const float* const bt = etab + j * MT;
+            constexpr int EB = 4;
+            // (the addresses are the same for every branch: behind this opaque copy they are computed per branch, in the epilogue -
+            // hoisted in front of the branch loop the 32 row addresses lived in scratch)
+            int lq = tid;
+            asm volatile("" : "+v"(lq));
+            const int tq = wino_tpos(P0 + wn0 + (lq & 31), d), hq = (lq & 63) >> 5;      // t0 and hk again, from the thread index
+#pragma unroll
+            for (int e0 = 0; e0 < 16; e0 += EB) {
+                float rv[EB][2];
+#pragma unroll
+                for (int q = 0; q < EB; ++q) {
+                    const size_t rowoff = ((size_t)b * p.CoutT + m0 + wm0 + F::row(e0 + q, hq)) * L;
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const int pos = tq + h * d;
+                        rv[q][h] = (res && pos < L) ? res[rowoff + pos] : 0.f;
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < EB; ++q) {
+                    const int e = e0 + q, col = wm0 + F::row(e, hq);
+                    const float M0 = acc[0][0][e], M1 = acc[1][0][e], M2 = acc[2][0][e], M3 = acc[3][0][e];
+                    const float y[2] = {(M0 + M1) + M2, (M1 - M2) - M3};
+                    const size_t rowoff = ((size_t)b * p.CoutT + m0 + col) * L;
+                    const float bias = bt[col], ra = etab[WSRC * MT + col], rs = etab[(WSRC + 1) * MT + col];
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const int pos = tq + h * d;
+                        if (pos >= L) continue;
+                        float t = y[h] + bias;
+                        if (res) t += fmaf(ra, rv[q][h], rs);
+                        outp[rowoff + pos] = t;
+                    }
+                }
+            }
+        }
+    };
     // SUM: the sources one after another on the same accumulators; the double buffer runs on across a source boundary (the last chunk of a
     // source stages chunk 0 of the next: one prologue staging per workgroup), the fragment pointer and the weight ring restart there.
     for (int js = 0, cc = 0; js < nsrc; ++js) {
@@ -304,6 +376,7 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
             const float* Xs = smem + (par & 1) * bufsz;
             float* Xn = smem + ((par + 1) & 1) * bufsz;
             bool more = ch + 1 < nch;
+            if constexpr (FAN) more = more && js == 0;     // branch 0 stages chunk 1 into the other buffer; the later branches find both there
             int cn = (ch + 1) * WCK;
             if (live) {
                 const float* xt = Xs + lbase;
@@ -333,7 +406,33 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
                 __syncthreads();
             }
         }
+        if constexpr (FAN) {
+            // branch boundary (no barrier from here on: neither buffer is overwritten, the tables are constant): the next branch's stream,
+            // K, fragment count and base row, the ring restarted - its first fragments fly under this branch's epilogue - then the
+            // accumulators start from zero.  pos0 and sin stay.
+            if (!live) return;
+            if (js + 1 < nsrc) {
+                K = m.K[js + 1];
+                lbase += (hl - m.hl[js + 1]) * WG::RS;        // = (t0 - hl_j - pos0) * RS + 4 hk of the next branch
+                hl = m.hl[js + 1];
+                nfrag = nch * wino_terms(K) * WGPC;
+#pragma unroll
+                for (int i = 0; i < MI; ++i)
+                    ap[i] = reinterpret_cast<const f32x4*>(m.wp[js + 1]) + ((size_t)((m0 + wm0) / 32 + i) * nfrag) * 64;
+                fidx = 0;
+#pragma unroll
+                for (int g = 0; g + 1 < RING; ++g) load_next(ar[g]);
+            }
+            fan_epilogue(js);
+#pragma unroll
+            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                for (int i = 0; i < MI; ++i)
+#pragma unroll
+                    for (int e = 0; e < 16; ++e) acc[c][i][e] = 0.f;
+        }
     }
+    if constexpr (FAN) return;
 
     if (!live) return;
     // ---- epilogue: output transform, then + bias [+ residual] [+ addends | + out] [/ out_div], conv_tile_kernel's order
@@ -442,6 +541,12 @@ conv_wino_sum_len_kernel(const WinoSumArgs a) {
     conv_wino_body<MI, WN, NPF, VEC, true>(a);
 }
 
+template <int MI, int WN, int NPF, bool VEC>
+__global__ void __launch_bounds__(128 * WN, 3)
+conv_wino_fan_kernel(const WinoFanArgs a) {
+    conv_wino_body<MI, WN, NPF, VEC, false>(a);
+}
+
 template <int MI, int WN>
 int launch_wino(const TileArgs* ps, int nprob, hipStream_t stream) {
     constexpr int MT = 64 * MI, NTP = 32 * WN, NTHREADS = 128 * WN;
@@ -542,6 +647,45 @@ int launch_wino_sum(const TileArgs* ps, int nsrc, const int32_t* order, hipStrea
     return v2w_launch_lds(kern, dim3(grid), dim3(NTHREADS), lds, stream, a);
 }
 
+// The fan-out form: ps[0 .. nsrc) are the branches (shared in, in_a / in_s, res, res_a / res_s, B, C, L, dil, slope); one problem, one grid
+// of one workgroup per tile.  C_in of at most two chunks: the double buffer then holds the whole activated window (V2W_E_SHAPE otherwise).
+template <int MI, int WN>
+int launch_wino_fan(const TileArgs* ps, int nsrc, hipStream_t stream) {
+    constexpr int MT = 64 * MI, NTP = 32 * WN, NTHREADS = 128 * WN;
+    constexpr int NPF = ((WCK / 2) * (((2 * NTP + 2 * WHMAX) / 4 + 7) / 8 * 8) + NTHREADS - 1) / NTHREADS;
+    WinoFanArgs a{};
+    TileArgs p = ps[0];
+    const int nch = p.Cin / WCK;
+    if (p.Cout % MT != 0 || nch > 2) return V2W_E_SHAPE;
+    int hmax = 0;
+    for (int j = 0; j < nsrc; ++j) {
+        a.wp[j] = ps[j].wp; a.bias[j] = ps[j].bias; a.out[j] = ps[j].out; a.K[j] = ps[j].K; a.hl[j] = ps[j].hl;
+        if (ps[j].hl > hmax) hmax = ps[j].hl;
+    }
+    a.nsrc = nsrc;
+    p.hl = p.hr = hmax;
+    const int d = p.dil;
+    p.ntl = (wino_npairs(p.L, d) + NTP - 1) / NTP;
+    p.ntiles = p.B * p.ntl;
+    int rows = 0;                           // LDS rows the widest tile of the widest branch reads
+    for (int tl = 0; tl < p.ntl; ++tl) {
+        const int P0 = tl * NTP;
+        const int pos0 = (wino_tpos(P0, d) - hmax) & ~3;
+        const int r = wino_tpos(P0 + NTP - 1, d) + d + hmax - pos0 + 1;
+        if (r > rows) rows = r;
+    }
+    p.xrows = (rows + 3) & ~3;
+    if (p.xrows > 2 * NTP + 2 * WHMAX) return V2W_E_SHAPE;
+    const bool vec = (p.L % 4 == 0) && v2w_al16(p.in);
+    p.vec4 = vec;
+    p.atab_off = nch * p.xrows * WG::RS;
+    const size_t lds = ((size_t)p.atab_off + (WSRC + 2) * MT + (p.in_a ? 2 * p.Cin : 0)) * sizeof(float);
+    a.p = p;
+    const int grid = tile_blocks(p.ntiles, p.Cout / MT);
+    auto kern = vec ? conv_wino_fan_kernel<MI, WN, NPF, true> : conv_wino_fan_kernel<MI, WN, NPF, false>;
+    return v2w_launch_lds(kern, dim3(grid), dim3(NTHREADS), lds, stream, a);
+}
+
 // wpw float index o = (((mb * nch + ch) * nfr + fi) * 64 + lane) * 4 + j, nfr = wino_terms(k) * 4, fragment fi = (segment, unit gg, term)
 // (wino_frag) holds the term's transformed weight at channel ch*32 + gg*8 + 2j + lane/32, output channel mb*32 + lane%32.
 __global__ void __launch_bounds__(256)
@@ -626,6 +770,37 @@ extern "C" int v2w_conv1d_wino_sum_fwd_order(const v2w_conv1d_args* a, int n, co
         ps[i] = p;
     }
     return launch_wino_sum<1, 2>(ps, n, order, (hipStream_t)stream);
+}
+
+// The fan-out form (include/vec2wav_hip.h): out_j = conv_j(lrelu(in_a * in + in_s)) + bias_j [+ res_a * res + res_s], j < n, in one launch
+// that stages the input once per tile.  Every out_j holds the bits of the V2W_ALGO_WINO launch of a[j] alone.
+extern "C" int v2w_conv1d_wino_fan_fwd(const v2w_conv1d_args* a, int n, void* stream) {
+    if (!a || n < 1 || n > WSRC) return V2W_E_ARG;
+    TileArgs ps[WSRC];
+    for (int i = 0; i < n; ++i) {
+        const v2w_conv1d_args* q = a + i;
+        if (!q->in || !q->wp || !q->out) return V2W_E_ARG;
+        if (q->B <= 0 || q->C_in <= 0 || q->C_out <= 0 || q->L <= 0 || q->k <= 0 || q->dil <= 0) return V2W_E_ARG;
+        if ((q->in_a == nullptr) != (q->in_s == nullptr) || (q->res_a == nullptr) != (q->res_s == nullptr)) return V2W_E_ARG;
+        if (q->in != a->in || q->in_a != a->in_a || q->in_s != a->in_s || q->res != a->res || q->res_a != a->res_a || q->res_s != a->res_s)
+            return V2W_E_ARG;
+        if (q->B != a->B || q->C_in != a->C_in || q->C_out != a->C_out || q->L != a->L || q->dil != a->dil || q->slope != a->slope) return V2W_E_ARG;
+        for (int j = 0; j < i; ++j)
+            if (a[j].out == q->out) return V2W_E_ARG;
+        if (q->C_in % WCK != 0 || q->C_in < 64 || q->C_out % 64 != 0 || wino_terms(q->k) == 0 || q->pad_left >= 0) return V2W_E_SHAPE;
+        if (q->in_stride > 1 || q->mask_src || q->rowsum_part || (q->out_slope != 0.f && q->out_slope != 1.f)) return V2W_E_SHAPE;
+        if (q->in_ct > 0 || q->out_ct > 0) return V2W_E_SHAPE;
+        if (q->add0 || q->add1 || q->accumulate || q->out_div != 0.f) return V2W_E_SHAPE;     // (the first convs have none of these)
+        TileArgs p{};
+        p.in = q->in; p.in_a = q->in_a; p.in_s = q->in_s; p.wp = q->wp; p.bias = q->bias;
+        p.res = q->res; p.res_a = q->res_a; p.res_s = q->res_s; p.out = q->out;
+        p.B = q->B; p.Cin = q->C_in; p.Cout = q->C_out; p.L = q->L; p.K = q->k; p.dil = q->dil;
+        p.CinT = q->C_in; p.CoutT = q->C_out;
+        p.hl = p.hr = q->dil * (q->k - 1) / 2;
+        p.slope = q->slope;
+        ps[i] = p;
+    }
+    return launch_wino_fan<1, 2>(ps, n, (hipStream_t)stream);
 }
 
 extern "C" int v2w_wino_sum_order(const int32_t* k, int n, int32_t* order) {

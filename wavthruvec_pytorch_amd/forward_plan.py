@@ -79,6 +79,17 @@ def wino_sum_selected(wino_sum, precision, algo, C, blocks) -> bool:
             and all(k >= 3 and k % 2 == 1 and d == blocks[0][1] for k, d in blocks))
 
 
+def wino_fan_selected(wino_fan, precision, algo, C, blocks, *, save=False, lengths=False, streams=True) -> bool:
+    """Do the FIRST convs of a ResBlock2 stage run as ONE Winograd launch that stages their common input once (hipops.conv1d_wino_fan)?
+    Exact fp32 on the MFMA path, C in `wino_fan` (Generator.wino_fan), 1 to 3 branches of odd k >= 3 and one dilation, the plain forward
+    only (`save`: the forward is back-propagated), no per-item `lengths`, and `streams`: every branch's `convs.0` has the Winograd stream
+    `Generator.wino` folds.  `blocks`: (kernel size, first dilation) per branch.  Read by the planner (rb2_layers); the fold is asked for
+    nothing.  The same bits either way: each conv runs the one-conv kernel's operations in its order."""
+    blocks = list(blocks)
+    return (C in tuple(wino_fan or ()) and precision == 'f32' and algo != hipops.ALGO_DIRECT and not save and not lengths and bool(streams)
+            and 1 <= len(blocks) <= 3 and all(k >= 3 and k % 2 == 1 and d == blocks[0][1] for k, d in blocks))
+
+
 def _branches(rbs, names, wps):
     return [dict(wps1=wps[nm + '.convs.0'], b1=rb.convs[0].bias.detach(), wps2=wps[nm + '.convs.1'], b2=rb.convs[1].bias.detach(),
                  k=rb.kernel_size, dil1=rb.convs[0].dilation, dil2=rb.convs[1].dilation) for nm, rb in zip(names, rbs)]
@@ -570,12 +581,27 @@ class ForwardPlanner:
     def rb2_layers(self, i):
         """Layer by layer: conv1 of the three branches in ONE launch, conv2 of branches 0 .. nk - 2 in one, the last branch's conv2 adds them."""
         rbs, names = self.rbs, self.names
-        self.launch('0', {j: (j, (self.xr, self.wf[names[j] + '.convs.0'], rbs[j].convs[0].bias.detach(), self.t1s[j],
-                                  dict(k=rbs[j].kernel_size, dil=rbs[j].convs[0].dilation, slope=LRELU_SLOPE, in_affine=self.aff, res=self.xr,
-                                       res_affine=self.aff, **self.ck(names[j] + '.convs.0')))) for j in range(self.nk)})
+        if not self.conv1_fan():
+            self.launch('0', {j: (j, (self.xr, self.wf[names[j] + '.convs.0'], rbs[j].convs[0].bias.detach(), self.t1s[j],
+                                      dict(k=rbs[j].kernel_size, dil=rbs[j].convs[0].dilation, slope=LRELU_SLOPE, in_affine=self.aff, res=self.xr,
+                                           res_affine=self.aff, **self.ck(names[j] + '.convs.0')))) for j in range(self.nk)})
         if not self.conv2_sum():
             self.launch_conv2('1', self.conv2_problems())
         return True
+
+    def conv1_fan(self):
+        """The first convs of all branches as one Winograd launch that stages x once per tile (each t1_j the bits of its own launch); False:
+        not selected or declined - rb2_layers then issues the multi-problem launch."""
+        g, rbs, names = self.g, self.rbs, self.names
+        wpw = g._fold_key.get('wpw', {})
+        if self.st or not wino_fan_selected(g.wino_fan, g.precision, self.algo, self.C, [(rb.kernel_size, rb.convs[0].dilation) for rb in rbs],
+                                            save=self.save is not None, lengths=self.lens is not None,
+                                            streams=all(f'{nm}.convs.0' in wpw for nm in names)):
+            return False
+        return self.timed('bconv0:' + '+'.join(f'{nm}.0' for nm in names), hipops.conv1d_wino_fan, self.xr,
+                          [(wpw[f'{nm}.convs.0'], rb.convs[0].bias.detach(), t1, rb.kernel_size) for t1, nm, rb in zip(self.t1s, names, rbs)],
+                          dil=rbs[0].convs[0].dilation, slope=LRELU_SLOPE, in_affine=self.aff, res=self.xr, res_affine=self.aff,
+                          only_if_multi_wino=True)
 
     def conv2_sum(self):
         """The second convs of all branches as one Winograd launch on one accumulator (o_j never written); False: not selected or declined."""

@@ -349,6 +349,35 @@ def conv1d_wino_sum(sources, out, *, dil, slope, out_div=0.0, in_affine=None, le
     return True
 
 
+def wino_multi_taken(n, B, c_out, L, dil):
+    """Does a V2W_ALGO_WINO launch of n problems of these sizes pass the library's size rule (v2w_conv1d_wino: more than 128 workgroups of
+    64 channels x 64 output pairs; below that the caller's f32 MFMA stream runs, split over C_in)?  Host arithmetic, the library's."""
+    npairs = dil * ((L + 2 * dil - 1) // (2 * dil))
+    return n * B * ((npairs + 63) // 64) * (c_out // 64) > 128
+
+
+def conv1d_wino_fan(x, branches, *, dil, slope, in_affine=None, res=None, res_affine=None, lengths=None, len_mul=1, only_if_multi_wino=False):
+    """The fan-out form of the Winograd F(2,3) kernel (v2w_conv1d_wino_fan_fwd): `branches` = up to three (wpw_j, bias_j, out_j, k_j) of one
+    dilation over the SAME input `x` - the first convs of a ResBlock2 stage's branches - in ONE launch that stages x once per tile:
+    out_j = conv_j(lrelu(in_affine(x))) + bias_j [+ res_affine(res)], the bits of each conv's own ALGO_WINO launch.  Returns False (nothing
+    launched) when the library declines the shape (V2W_E_SHAPE: more than 64 input channels, ...) and for a call with per-item lengths, which
+    this form does not serve; the caller then issues conv1d_multi.  `only_if_multi_wino`: also decline a launch that conv1d_wino_multi would
+    not run on the Winograd kernel (too few workgroups: its f32 MFMA fallback rounds otherwise) - the planner's "the same bits either way"."""
+    if lengths is not None:
+        return False
+    n = len(branches)
+    if only_if_multi_wino and not wino_multi_taken(n, x.shape[0], branches[0][2].shape[1], x.shape[2], dil):
+        return False
+    arr = (_hip.Conv1dArgs * max(n, 1))()
+    for a, (wpw, bias, out, k) in zip(arr, branches):
+        _conv1d_args(a, x, None, bias, out, k=k, dil=dil, slope=slope, algo=ALGO_WINO, wp=wpw, in_affine=in_affine, res=res, res_affine=res_affine)
+    rc = _hip.load().v2w_conv1d_wino_fan_fwd(arr, n, _stream(x))
+    if rc == -2:
+        return False
+    _hip.check(rc, 'v2w_conv1d_wino_fan_fwd')
+    return True
+
+
 def wino_sum_order(ks):
     """The order in which the summed launch walks sources of kernel sizes `ks` when none is given (v2w_wino_sum_order; host only)."""
     n = len(ks)

@@ -231,6 +231,10 @@ class Generator(nn.Module):
         self.wino_sum_wide = (256, 128)       # the same form for stages whose second convs `wino` already runs on the Winograd kernel: the summed launch reads the `wpw` streams they
                                               # have, the fold is asked for nothing (_wino_sum_layers names only `wino_sum`'s stages; without `wino` these stages keep their two launches).
                                               # Every stage listed in either was measured faster that way (profiles/r14_cfg2_wino_sum_wide_per_layer.txt).  () = off
+        self.wino_fan = (64,)                 # precision 'f32', plain forward without lengths: channel counts of the ResBlock2 stages whose FIRST convs run as ONE Winograd launch
+                                              # that stages their common input once per tile (hipops.conv1d_wino_fan; forward_plan.wino_fan_selected): the `wpw` streams `wino` folds,
+                                              # the bits of the separate launches.  The kernel serves C <= 64 (its two chunk buffers hold the whole window).  Measured faster at
+                                              # C = 64 (893 -> 750 us per forward; profiles/r15_cfg2_wino_fan_per_layer.txt).  () = off
         self.merge_waits = True               # bf16 storage: one wait per side stream and call, earlier steps of the stream count as met (forward_plan.need)
         self.cond_stream = None               # bf16 storage, train mode: the conditioning chain on a second side stream, beside the weight folds instead of between them.  None: where it pays - while conv_pre + ups.0 are shorter than the one side stream's chain + folds (measured, tools/exp/cond_stream_sweep.py: -26 / -12 us at B x T = 4 096 / 8 192 frames, +8 at 2 048, +13 .. +28 from 12 288 up); True / False: always / never
         self.fuse_post = True                 # leaky_relu -> conv_post -> tanh inside the kernel of the last (C = 16) stage (bf16 storage, and - round 5 - the fp32 stage kernel): the stage's
@@ -711,7 +715,7 @@ class Generator(nn.Module):
         ptrs = tuple(p.data_ptr() for p in self.parameters()) + tuple(b.data_ptr() for b in self.buffers())
         return (tuple(x.shape), str(x.device), torch.cuda.current_stream(x.device).cuda_stream, self.training, self.precision, self.algo, self.bf16_storage, tuple(self.fuse_stage), tuple(self.fuse_pairs),
                 self.fuse_wide, self.fuse_wide_stage, self.fuse_up, self.fuse_post, self.fuse_bn_finalize, self.cond_stream, self.merge_waits, self.split_min_channels,
-                self.always_refold, self.wino, self.wino_stage, tuple(self.wino_sum), tuple(self.wino_sum_wide), ptrs)
+                self.always_refold, self.wino, self.wino_stage, tuple(self.wino_sum), tuple(self.wino_sum_wide), tuple(self.wino_fan), ptrs)
 
     def _forward_hip(self, x, spk, nz, save, lens=None):
         """One forward through the C ABI.  `save` (a dict) asks for the back-propagatable form (forward_plan.py).  A no-grad forward is PLANNED
