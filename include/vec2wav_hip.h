@@ -757,6 +757,69 @@ int v2w_l1_masked(const float* a, const float* b, int B, int C, int F, const int
 int v2w_l1_masked_geo(const float* a, const float* b, int B, int C, int F, const int32_t* len, int len_mul, int hop, int n_fft,
                       float* per_item, float* total, void* ws, void* stream);
 
+/* ---- Multi-resolution STFT loss (additive in ABI v35; Yamamoto et al., Parallel WaveGAN: spectral convergence + log-magnitude L1 over
+ * several STFT resolutions), forward and backward, on the DFT conv's output as the mel_spectrogram pipeline leaves it - the project's own
+ * framing (v2w_mel_phases[_geo]: reflect padding of (n_fft - hop) / 2 per side, no centring), not torch.stft(center=True).  Up to
+ * V2W_STFT_LOSS_MAX_ITEMS resolutions per call, every one of them in the same launches; the descriptors are a HOST array, read before the
+ * call returns.
+ *
+ * Operands of one resolution: spec_x (generated) and spec_y (target), each (B, Cs, FP) fp32 with rows [0, nb) = Re and rows [nb, 2 nb) = Im
+ * over the frames [0, F).  The rows [2 nb, Cs) and the columns [F, FP) are not part of the spectrum: the rows are never read, the columns
+ * may be loaded but are selected away (never multiplied by a mask), so Inf or NaN made from whatever they hold reaches nothing.  FP % 4 == 0
+ * and 16-byte aligned bases (every row starts on a 16-byte line); F % 4 is arbitrary.  With N = B * nb * F and per entry
+ *     X = sqrt(Re_x^2 + Im_x^2 + 1e-9f),  Y = sqrt(Re_y^2 + Im_y^2 + 1e-9f)        (v2w_mel_finish's magnitude: X, Y >= 3.1e-5)
+ *   forward   Sd = sum (Y - X)^2,  Sy = sum Y^2,  Sl = sum |log Y - log X|  over the N entries;
+ *             sc[r] = sqrt(Sd) / sqrt(Sy) = ||Y - X||_F / ||Y||_F,  mag[r] = Sl / N,  total[0] = (sum_r sc_r) / n,  total[1] = (sum_r mag_r) / n
+ *             in list order; sums[3 r + {0, 1, 2}] = (Sd, Sy, Sl) of resolution r, DEVICE fp64, what the backward reads.  sc, mag (n floats),
+ *             total (2 floats) and sums (3 n doubles, 8-byte aligned) may each be NULL, not all four.
+ *   backward  g_sc_r = g_sc[0] / n + gterm_sc[r],  g_mag_r = g_mag[0] / n + gterm_mag[r]: DEVICE pointers read by the kernel (no host sync), each
+ *             may be NULL (= 0), not all four; gterm_*: n floats, the gradients that arrived on the single terms.  With those,
+ *                 dX = g_sc_r (X - Y) / (sqrt(Sd) sqrt(Sy)) + g_mag_r sgn(X - Y) / (N X),   dRe = dX Re_x / X,   dIm = dX Im_x / X
+ *             into dspec_x (B, Cs, FP).  The first term is exactly 0 when Sd == 0 (torch's subgradient of a norm at 0); sgn(0) = 0; the sign
+ *             is that of the fp32 difference X - Y of the fp32 magnitudes.  Magnitudes are recomputed from the specs, not stored.
+ *             The KERNEL writes every float of dspec_x exactly once: the rows [2 nb, Cs) and the columns [F, FP) are +0.0 on return
+ *             (the input-gradient conv reads them), so the caller need not zero-fill the buffer.  spec_y gets no gradient.
+ * Work split.  A unit is four consecutive frames of one (item, bin): four 16-byte loads.  The forward counts B * nb * ceil(F / 4) units per
+ * resolution, the backward B * (nb + ceil((Cs - 2 nb) / 2)) * (FP / 4) (the pad rows two at a time).  Resolution r gets
+ * ceil(units_r / chunk_r) workgroups of 256 threads, chunk_r = max(2048, ceil(units_r / V2W_STFT_LOSS_TARGET_WGS)): at least one, at most
+ * V2W_STFT_LOSS_TARGET_WGS, from its own descriptor only.
+ *   v2w_stft_loss_plan (host only): the forward's split: starts[i] = first workgroup of resolution i, starts[n] = workgroups of the streaming
+ *             launch, also the return value (> 0).
+ *   v2w_stft_loss_scratch_bytes (host only): bytes of caller-owned `scratch` (8-byte aligned) the forward needs: 24 per workgroup.
+ * Deterministic: each workgroup of the streaming launch writes ONE fp64 triple to scratch; the finishing launch (one workgroup) adds a
+ * resolution's triples - thread t the triples t, t + 256, ... in index order, the 256 sums through the fixed-order block reduction - no
+ * atomics, the same call gives the same bits, and a resolution's values (given the same g_sc_r and g_mag_r, its gradient too) are the bits of the call that holds it alone.
+ * Roundings on the way to one value (u = 2^-24).  X = sqrt(fma(Im, Im, Re * Re) + 1e-9f), each operation ONE fp32 rounding and the same
+ * three for both signals (equal spectra give X == Y bit for bit, hence sc == 0, mag == 0 and dspec_x == 0): [3] on a sum of positive terms
+ * under the root and [1] the root (correctly rounded), at most 2.5 u relative.  Y - X and log Y - log X: [1] fp32 each on the fp32 magnitudes and their logf (logf: a few u relative to
+ * |log|, measured in tests/mel_ref.py); the squares, every sum, both roots, the quotients and the means over r are fp64 - per thread at most
+ * 4 * ceil(chunk / 256) additions in a chain, [6 + 4] in the workgroup's reduction, [ceil(workgroups / 256) + 6 + 4] over the triples - then
+ * [1] fp32 for each stored value.  Backward, per entry, every line ONE correctly rounded fp32 operation on the fp32 X, Y:
+ *     c_sc = g_sc_r / (sqrt(Sd) sqrt(Sy)), c_mag = g_mag_r / N      each computed in fp64 and rounded once to fp32 (c_sc = 0 for Sd == 0);
+ *                                                                   g_*_r itself: [1] the division by n, [1] the addition
+ *     d  = X - Y
+ *     r  = 1 / X
+ *     m  = c_mag * r,  signed by d (0 for d == 0)
+ *     dX = fma(c_sc, d, m)
+ *     w  = dX * r
+ *     dRe = w * Re_x,  dIm = w * Im_x
+ * V2W_E_ARG: a NULL items / spec_x / spec_y (backward: dspec_x, sums) or scratch, every output NULL (backward: every gradient NULL), n < 1
+ * or n > V2W_STFT_LOSS_MAX_ITEMS, B / F / nb <= 0, FP < F, Cs < 2 nb, FP % 4 != 0, a spec not 16-byte, a double not 8-byte or a float not
+ * 4-byte aligned.  V2W_E_SHAPE: Cs * FP or B * Cs * FP past 2^31 - 1. */
+#define V2W_STFT_LOSS_MAX_ITEMS  8
+#define V2W_STFT_LOSS_TARGET_WGS 1024
+typedef struct {
+    const float* spec_x; const float* spec_y;
+    float* dspec_x;                        /* backward only */
+    int32_t B, Cs, FP, F, nb, _pad;
+} v2w_stft_loss_item;
+int       v2w_stft_loss_plan(const v2w_stft_loss_item* items, int n, int32_t* starts);
+long long v2w_stft_loss_scratch_bytes(const v2w_stft_loss_item* items, int n);
+int v2w_stft_loss_multi(const v2w_stft_loss_item* items, int n, float* sc, float* mag, float* total, double* sums, void* scratch,
+                        void* stream);
+int v2w_stft_loss_multi_bwd(const v2w_stft_loss_item* items, int n, const double* sums, const float* g_sc, const float* g_mag,
+                            const float* gterm_sc, const float* gterm_mag, void* stream);
+
 /* ---- AdamW (additive in ABI v35; torch.optim.AdamW as train.py:96-99 constructs it and train.py:198,215 steps it: decoupled weight
  * decay, no amsgrad, no maximize): the step of up to V2W_ADAMW_MAX_ITEMS parameter tensors in ONE launch that reads p, g, m, v and
  * writes p, m, v once (28 bytes per parameter).  The descriptors and the hyperparameters are HOST memory, read before the call returns.

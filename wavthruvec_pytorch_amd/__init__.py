@@ -11,6 +11,8 @@ from .modules import ConditionalBatchNorm1d  # noqa: F401
 from .utils import get_padding, init_weights  # noqa: F401
 from . import hparams  # noqa: F401
 from .optim import AdamW, clip_grad_norm_, ema_state_dict  # noqa: F401
+from . import stft_loss  # noqa: F401  (the module: stft_loss.stft_loss is the one-resolution function)
+from .stft_loss import MultiResolutionSTFTLoss  # noqa: F401
 
 __all__ = ['Generator', 'ResBlock1', 'ResBlock2', 'ConditionalBatchNorm1d', 'get_padding', 'init_weights',
-           'hparams', 'LRELU_SLOPE', 'AdamW', 'clip_grad_norm_', 'ema_state_dict']
+           'hparams', 'LRELU_SLOPE', 'AdamW', 'clip_grad_norm_', 'ema_state_dict', 'MultiResolutionSTFTLoss', 'stft_loss']

@@ -124,6 +124,16 @@ LOSS_MAX_ITEMS = 64
 L1_TARGET_WGS = 2048
 
 
+class StftLossItem(C.Structure):
+    """include/vec2wav_hip.h `v2w_stft_loss_item`: one resolution of the multi-resolution STFT loss, the DFT conv's output for both signals."""
+    _fields_ = [('spec_x', _fp), ('spec_y', _fp), ('dspec_x', _fp), ('B', C.c_int32), ('Cs', C.c_int32), ('FP', C.c_int32),
+                ('F', C.c_int32), ('nb', C.c_int32), ('_pad', C.c_int32)]
+
+
+STFT_LOSS_MAX_ITEMS = 8
+STFT_LOSS_TARGET_WGS = 1024
+
+
 class AdamWItem(C.Structure):
     """include/vec2wav_hip.h `v2w_adamw_item`: one parameter tensor of the multi-tensor AdamW step, its gradient and its two moments."""
     _fields_ = [('p', _fp), ('g', _fp), ('m', _fp), ('v', _fp), ('numel', C.c_int64)]
@@ -280,6 +290,11 @@ SIGNATURES = {
     'v2w_l1_mean_multi_bwd': (C.c_int, [C.POINTER(L1Pair), C.c_int, C.c_float, _fp, _fp]),
     'v2w_lsgan_multi': (C.c_int, [C.POINTER(LsganItem), C.c_int, _fp, _fp, _fp]),
     'v2w_lsgan_multi_bwd': (C.c_int, [C.POINTER(LsganItem), C.c_int, _fp, _fp, _fp]),
+    # multi-resolution STFT loss: host descriptor array; sc / mag / total / sums / scratch and the gradients are DEVICE memory
+    'v2w_stft_loss_plan': (C.c_int, [C.POINTER(StftLossItem), C.c_int, C.POINTER(C.c_int32)]),
+    'v2w_stft_loss_scratch_bytes': (C.c_longlong, [C.POINTER(StftLossItem), C.c_int]),
+    'v2w_stft_loss_multi': (C.c_int, [C.POINTER(StftLossItem), C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),
+    'v2w_stft_loss_multi_bwd': (C.c_int, [C.POINTER(StftLossItem), C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),
     # AdamW: host descriptor array and hyperparameters, read before the call returns
     'v2w_adamw_multi_plan': (C.c_int, [C.POINTER(AdamWItem), C.c_int, C.POINTER(C.c_int32)]),
     'v2w_adamw_multi': (C.c_int, [C.POINTER(AdamWItem), C.c_int, C.POINTER(AdamWHyper), _fp]),

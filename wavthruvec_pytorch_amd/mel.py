@@ -223,18 +223,23 @@ def _dft_conv_bwd(c, dspec, dxp):
         hipops.conv1d(dspec[:, r:r + BWD_ROWS], w, None, dxp, k=k, dil=1, slope=1.0, pad_left=k - 1, wp=wp, in_ct=cs, accumulate=i > 0)
 
 
+def _bwd_constants(c):
+    """The constants of a configuration with what its backward adds to them (built at the first backward)."""
+    if 'wT' not in c:
+        # wT[j'][row c][phase p] = Wd[c][left + (k-1-j')*hop + p]
+        c['wT'] = c['wf'].flip(0).transpose(1, 2).contiguous()
+        c['wTp'] = hipops.pack_mfma(c['wT'])
+        c['basisT'] = c['basis'].t().contiguous()
+    return c
+
+
 def _backward(g, spec, geom, cfg):
     """d out (B, num_mels, F) -> d y (B, L): finish^T -> the DFT conv's input gradient (the same MFMA conv kernel with the
     tap-flipped transposed rows, pad_left = k-1) -> phase re-interleave with the reflections folded back."""
     n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax = cfg
     B, L, pad, F, FP = geom
     dev = spec.device
-    c = _constants(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, dev)
-    if 'wT' not in c:
-        # wT[j'][row c][phase p] = Wd[c][left + (k-1-j')*hop + p]
-        c['wT'] = c['wf'].flip(0).transpose(1, 2).contiguous()
-        c['wTp'] = hipops.pack_mfma(c['wT'])
-        c['basisT'] = c['basis'].t().contiguous()
+    c = _bwd_constants(_constants(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, dev))
     lib, st = _hip.load(), torch.cuda.current_stream(dev).cuda_stream
     g = g.contiguous().float()
     dspec = torch.zeros_like(spec)
