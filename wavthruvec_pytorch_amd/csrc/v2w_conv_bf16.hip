@@ -569,7 +569,13 @@ conv_bf16_kernel(const MultiArgs m) {
             const int i = ps / (NI / 2), jh = (ps % (NI / 2)) * 2;
             const int cbase = wm0 + i * 32;
             const int qb = n0 + wn0 + jh * 32;
-            if (!pass_live(ps)) continue;
+            if (!pass_live(ps)) {       // a pass past L still hands its slot on: the next row block's first pass may be inside L again
+                if (ps + NB < NPASS) {
+#pragma unroll
+                    for (int g = 0; g < NIT; ++g) request(rr[ps % NB], ps + NB, g);
+                }
+                continue;
+            }
 #pragma unroll
             for (int jj = 0; jj < 2; ++jj)
 #pragma unroll
