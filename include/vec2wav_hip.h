@@ -120,7 +120,11 @@ typedef struct {
                          * the fragment stream of the layer's INPUT-GRADIENT conv (tap-reversed transpose, what v2w_pack_mfma_dgrad builds
                          * from wf) in the same pass */
     float* wpw;         /* optional (ABI v35; Conv1d layers whose tile configuration is MF == CK == 32 with an odd k >= 3, else must be NULL):
-                         * the V2W_ALGO_WINO stream of the layer (what v2w_pack_wino builds from wf) in the same pass */
+                         * the V2W_ALGO_WINO stream of the layer (what v2w_pack_wino builds from wf) in the same pass.
+                         * A transposed layer with k == 2 u, u in {2, 4}, C_in % 32 == 0 and >= 64, u * C_out % 64 == 0: the stream of
+                         * v2w_convt1d_wino_fwd, 3 * u * C_out * C_in floats - the weight as a two-tap Conv1d over u * C_out rows (row =
+                         * co * u + phase, taps (w[phase + u], w[phase]) on (x[t - 1], x[t])), per row the terms g0, g0 + g1, g1 of the two-tap
+                         * segment, in MFMA A-fragment order [32-row block][32-channel chunk][4-k-step unit][term] */
 } v2w_fold_desc;
 int v2w_fold_plan(v2w_fold_desc* descs, int n, int32_t* starts);
 int v2w_fold_pack_batch(const v2w_fold_desc* descs_dev, const int32_t* starts_dev, int n,
@@ -558,6 +562,15 @@ int v2w_wino_sum_order(const int32_t* k, int n, int32_t* order);
  * issues v2w_conv1d_fwd_multi): C_in > 64 (the kernel's two chunk buffers must hold the whole input window), add0 / add1 / accumulate /
  * out_div set, and whatever V2W_ALGO_WINO declines but a small launch.  No per-item lengths.  A new symbol over unchanged structs. */
 int v2w_conv1d_wino_fan_fwd(const v2w_conv1d_args* a, int n, void* stream);
+/* The upsampler form of the Winograd kernel: out = ConvTranspose1d(lrelu(in_a * in + in_s)) + bias for k == 2 u run as ONE two-tap Conv1d
+ * over u * C_out rows and a pixel shuffle, 3 products per output pair and row where v2w_convt1d_fwd issues 4.  a->wp = the layer's fold
+ * `wpw` stream (v2w_fold_desc); in_a / in_s (B, C_in): optional per-(item, channel) affine in front of the leaky_relu (both or neither);
+ * a->stats_part (optional): [v2w_convt1d_wino_tiles(a)][C_out][2] per-tile (sum, sumsq) of the stored values for v2w_bn_reduce_partials.
+ * a->wf, algo, splitk_ws are not read.  Served: u in {2, 4}, C_in % 32 == 0 and >= 64, u * C_out % 64 == 0, any B and L; V2W_E_SHAPE
+ * otherwise (nothing launched).  The values differ from v2w_convt1d_fwd's in the last bits (other products, other rounding order).
+ * v2w_convt1d_wino_tiles (host-only; only the sizes of `a` are read): the launch's position tiles, and in *wgs (optional) its workgroups. */
+int v2w_convt1d_wino_fwd(const v2w_convt1d_args* a, const float* in_a, const float* in_s, void* stream);
+int v2w_convt1d_wino_tiles(const v2w_convt1d_args* a, int32_t* wgs);
 int v2w_resblock2_stage_fwd_len(const v2w_stage_args* a, const int32_t* len, int len_mul, void* stream);
 int v2w_conv_post_tanh_len(const float* in, const float* wf, const float* bias, float* out,
                            int B, int C_in, int L, int k, float slope, const int32_t* len, int len_mul, void* stream);

@@ -268,6 +268,8 @@ SIGNATURES = {
     'v2w_conv1d_wino_sum_fwd_order': (C.c_int, [C.POINTER(Conv1dArgs), C.c_int, _fp, C.c_int, C.POINTER(C.c_int32), _fp]),
     'v2w_wino_sum_order': (C.c_int, [C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_int32)]),
     'v2w_conv1d_wino_fan_fwd': (C.c_int, [C.POINTER(Conv1dArgs), C.c_int, _fp]),
+    'v2w_convt1d_wino_fwd': (C.c_int, [C.POINTER(ConvT1dArgs), _fp, _fp, _fp]),
+    'v2w_convt1d_wino_tiles': (C.c_int, [C.POINTER(ConvT1dArgs), C.POINTER(C.c_int32)]),
     'v2w_resblock2_stage_fwd_len': (C.c_int, [C.POINTER(StageArgs), _fp, C.c_int, _fp]),
     'v2w_conv_post_tanh_len': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _fp, C.c_int, _fp]),
     # mel_spectrogram and the mel L1 of a batch of unequal lengths (forward only)

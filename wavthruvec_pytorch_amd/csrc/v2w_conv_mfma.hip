@@ -869,7 +869,25 @@ fold_pack_batch_kernel(const v2w_fold_desc* __restrict__ descs, const int32_t* _
         dst[o] = d.transposed ? tile[c * rstride + co * K + t] : tile[co * rstride + c * K + t];
     }
     // ---- ... and as block (mb, ch) of the Winograd F(2,3) stream (v2w_pack_wino's layout; MF == CK == 32 Conv1d layers only)
-    if (d.wpw) {
+    // transposed, k == 2 u: the stream of the upsampler form (v2w_convt1d_wino_fwd) - the weight viewed as a two-tap Conv1d over u * C_out rows,
+    // row = co * u + phase, taps (w[phase + u], w[phase]) on (x[t - 1], x[t]).  This block's 32 output channels are u row blocks of 32, its 16
+    // input channels units 2 (ch & 1), + 1 of the 32-channel chunk ch / 2; per (row block, chunk) the fragments are [unit][term] (wino_frag of
+    // one two-tap segment), so the block writes fragments 6 (ch & 1) .. + 5 of each of its u row blocks.
+    if (d.wpw && d.transposed) {
+        constexpr int NT = wino_seg_terms(2), WGPC = 4;
+        const int nchw = nch / 2;
+        for (int o = threadIdx.x; o < U * GPC * NT * 256; o += 256) {
+            const int j = o & 3, lane = (o >> 2) & 63;
+            int rest = o >> 8;
+            const int term = rest % NT; rest /= NT;
+            const int g2 = rest % GPC, r = rest / GPC;
+            const int row = r * 32 + lane % 32, co = row / U, ph = row - co * U;
+            const int c = g2 * CKG + j * KSTEP + lane / MF;
+            const float* w = tile + c * rstride + co * K;
+            const int fi = ((ch & 1) * GPC + g2) * NT + term;
+            d.wpw[((((size_t)(mb * U + r) * nchw + ch / 2) * (NT * WGPC) + fi) * 64 + lane) * 4 + j] = wino_weight(2, term, w[ph + U], w[ph], 0.f);
+        }
+    } else if (d.wpw) {
         const int nfr = wino_terms(K) * GPC;
         float* dw = d.wpw + (size_t)(mb * nch + ch) * nfr * 256;
         for (int o = threadIdx.x; o < nfr * 256; o += 256) {
@@ -1052,7 +1070,10 @@ extern "C" int v2w_fold_plan(v2w_fold_desc* descs, int n, int32_t* starts) {
         if (!cfg.mf) return V2W_E_SHAPE;
         d.mf = cfg.mf; d.ck = cfg.ck;
         if (d.wpd && (d.transposed || d.c_in != d.c_out || cfg.mf != cfg.ck)) return V2W_E_ARG;
-        if (d.wpw && (d.transposed || cfg.mf != 32 || cfg.ck != 32 || wino_terms(d.k) == 0)) return V2W_E_ARG;   // the Winograd stream: v2w_pack_wino's shapes   // the gradient stream comes from the same LDS block only then
+        if (d.wpw && !d.transposed && (cfg.mf != 32 || cfg.ck != 32 || wino_terms(d.k) == 0)) return V2W_E_ARG;   // the Winograd stream: v2w_pack_wino's shapes   // the gradient stream comes from the same LDS block only then
+        // ... of a transposed layer: the upsampler form's (v2w_convt1d_wino_fwd: k == 2 u, u in {2, 4}, 32-channel chunks, 64-row tiles)
+        if (d.wpw && d.transposed && (cfg.mf != 32 || cfg.ck != 16 || (d.u != 2 && d.u != 4) || d.k != 2 * d.u || d.c_in % 32 != 0 || d.c_in < 64
+                                      || (d.u * d.c_out) % 64 != 0)) return V2W_E_ARG;
         starts[i] = bs; starts[n + 1 + i] = bp;
         bs += d.transposed ? d.c_in : d.c_out;
         bp += (d.c_out / cfg.mf) * (d.c_in / cfg.ck);

@@ -35,6 +35,10 @@
 // first convs of the 64-channel stage's branches - in one workgroup per tile: tables and the activated window staged once (the two chunk
 // buffers hold its whole K extent), then branch after branch accumulate, transform, store to out_j, zero.  Each conv keeps the one-conv
 // kernel's operations and their order, so its bits.  B = 32 x L = 20 480, k = (3, 7, 11): 893 us in 15 360 workgroups -> 750 us in 5 120.
+// Upsampler form (conv_wino_up_kernel, v2w_convt1d_wino_fwd): ConvTranspose1d(k = 2 u, stride u) as one two-tap conv over u * C_out rows (row =
+// channel * u + phase) on the two-tap segment - 3 products per output pair where the direct tile issues 4 - with a pixel-shuffle store straight
+// from the accumulators (a lane's four consecutive rows are the u phases of 4 / u channels: 2 u contiguous output floats per channel) and
+// conv_tile_kernel's per-tile BatchNorm sums.  B = 32 x T = 256: ups.1 / ups.2 / ups.3 219 / 225 / 158 -> 181 / 190 / 128 us.
 #include "v2w_tile.h"
 #include "v2w_internal.h"
 #include "v2w_wino.h"
@@ -87,19 +91,30 @@ struct WinoFanArgs {
     int K[WSRC], hl[WSRC];
     int nsrc;
 };
+// The upsampler form (v2w_convt1d_wino_fwd): ConvTranspose1d(k = 2 U, stride U, padding U / 2) as ONE two-tap Conv1d over U * C_out rows
+// (row = channel * U + phase; taps (w[phase + U], w[phase]) on (x[t - 1], x[t]), t = 0 .. L) followed by a pixel shuffle: the two-tap
+// segment's 3 products per output pair (v2w_wino.h) where the direct tile issues 4.  `p` is the conv's problem: Cout = U * C_out ROWS, CoutT =
+// C_out channels of `out` (B, C_out, U L), K = 2, dil = 1, hl = 1, hr = 0, L = the INPUT length (the conv has L + 1 output positions), `bias`
+// per channel, `evec` = out is 8-byte aligned, `stats_part` as in conv_tile_kernel's transposed form.
+template <int U> struct WinoUpArgs { TileArgs p; };
+template <class A> struct wino_up_of { static constexpr int value = 0; };
+template <int U> struct wino_up_of<WinoUpArgs<U>> { static constexpr int value = U; };
 __device__ __forceinline__ const TileArgs& wino_problem(const MultiArgs& m, int pq) { return m.p[pq]; }
+template <int U> __device__ __forceinline__ const TileArgs& wino_problem(const WinoUpArgs<U>& a, int) { return a.p; }
 __device__ __forceinline__ const TileArgs& wino_problem(const WinoSumArgs& a, int) { return a.p; }
 __device__ __forceinline__ const TileArgs& wino_problem(const WinoFanArgs& a, int) { return a.p; }
 
 // LEN: per-item valid lengths, as in conv_tile_body (v2w_conv_mfma.hip): inputs at and past Lb = min(L, len[b] * len_mul) select 0, a tile
 // whose first output position lies there returns at once; its own kernel name (conv_wino_len_kernel).
 // ARGS = WinoSumArgs: the summed form (one problem per launch); WinoFanArgs: the fan-out form (one problem per launch, C_in <= 64, no LEN);
-// MultiArgs: one conv per problem.
+// MultiArgs: one conv per problem; WinoUpArgs<U>: the upsampler form (one problem per launch, no LEN).
 template <int MI, int WN, int NPF, bool VEC, bool LEN, class ARGS>
 __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
     constexpr bool SUM = std::is_same<ARGS, WinoSumArgs>::value;
     constexpr bool FAN = std::is_same<ARGS, WinoFanArgs>::value;
+    constexpr int UP = wino_up_of<ARGS>::value;              // the upsampler form's stride (0: a Conv1d)
     static_assert(!FAN || (MI == 1 && !LEN), "the fan-out form is written for MI = 1 without per-item lengths");
+    static_assert(!UP || (MI == 1 && !LEN && (UP == 2 || UP == 4)), "the upsampler form is written for MI = 1, stride 2 / 4, without per-item lengths");
     typedef Frag<32> F;
     typedef F::acc_t acc_t;
     constexpr int WM = 2;
@@ -111,7 +126,7 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     int pq = 0, id = blockIdx.x;
-    if constexpr (!SUM && !FAN) { pq = tile_problem(m); id = blockIdx.x - m.start[pq]; }
+    if constexpr (!SUM && !FAN && !UP) { pq = tile_problem(m); id = blockIdx.x - m.start[pq]; }
     const TileArgs& p = wino_problem(m, pq);
     const int mtiles = p.Cout / MT;
     const TileId ti = tile_coords(mtiles, id);
@@ -119,7 +134,7 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
     if (ti.tile >= p.ntiles) return;
     const int d = p.dil;
     int b, tl;
-    wino_tile_order(ti.tile, p.B, p.ntl, wino_npairs(p.L, d) % NTP != 0, b, tl);
+    wino_tile_order(ti.tile, p.B, p.ntl, wino_npairs(UP ? p.L + 1 : p.L, d) % NTP != 0, b, tl);      // (UP: output positions t = 0 .. L)
     const int P0 = tl * NTP;                 // first output pair of the tile
     const int m0 = mt * MT;
     int Lb = p.L;                            // end of this item's sequence (LEN; else the tensor's)
@@ -138,7 +153,7 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
     const int wn0 = (wave % WN) * 32;
     // a column-wave whose first (smallest) output position lies at or past the end stores nothing: it stages and keeps every barrier, but
     // runs no segment (no A-fragment load, no MFMA) and no epilogue - the tail tile of a row whose pairs do not fill it, a LEN item's last tile
-    const bool live = wino_tpos(P0 + wn0, d) < Lb;
+    const bool live = wino_tpos(P0 + wn0, d) < (UP ? Lb + 1 : Lb);
     const int L = p.L;
     int K = p.K, hl = p.hl;                  // (SUM: of the source whose chunks are being multiplied)
     const float* sin = p.in;                 // the tensor the staging reads, pos0 the position of its LDS row 0 (floor to a float4) -
@@ -230,7 +245,7 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
     };
 
     // ---- weight ring: fragments in consumption order, "next" is always +1 KiB per row block
-    int nfrag = nch * wino_terms(K) * WGPC;
+    int nfrag = nch * (UP ? wino_seg_terms(2) : wino_terms(K)) * WGPC;
     const f32x4* ap[MI];
 #pragma unroll
     for (int i = 0; i < MI; ++i)
@@ -290,6 +305,10 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
             for (int j = 0; j < nsrc; ++j) etab[j * MT + c] = m.bias[j] ? m.bias[j][m0 + c] : 0.f;
             etab[WSRC * MT + c] = p.res_a ? p.res_a[b * p.Cout + m0 + c] : 1.f;
             etab[(WSRC + 1) * MT + c] = p.res_a ? p.res_s[b * p.Cout + m0 + c] : 0.f;
+            continue;
+        }
+        if constexpr (UP) {                  // row c of the tile is channel (m0 + c) / UP
+            etab[c] = p.bias ? p.bias[(m0 + c) / UP] : 0.f;
             continue;
         }
         if constexpr (SUM) {                 // (b0 + b1) + b2
@@ -380,10 +399,13 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
             int cn = (ch + 1) * WCK;
             if (live) {
                 const float* xt = Xs + lbase;
-                int s = 0;
-                for (; s + 3 <= K; s += 3) segment(S3{}, xt + s * dstep, dstep);
-                if (K - s == 2) segment(S2{}, xt + s * dstep, dstep);
-                else if (K - s == 1) segment(S1{}, xt + s * dstep, dstep);
+                if constexpr (UP) segment(S2{}, xt, dstep);
+                else {
+                    int s = 0;
+                    for (; s + 3 <= K; s += 3) segment(S3{}, xt + s * dstep, dstep);
+                    if (K - s == 2) segment(S2{}, xt + s * dstep, dstep);
+                    else if (K - s == 1) segment(S1{}, xt + s * dstep, dstep);
+                }
             }
             if constexpr (SUM) {
                 if (!more && js + 1 < nsrc) {
@@ -433,6 +455,64 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
         }
     }
     if constexpr (FAN) return;
+
+    if constexpr (UP) {
+        // ---- upsampler epilogue: output transform (the two-tap segment feeds M0, M1, M3: y(t) = M0 + M1, y(t + 1) = M1 - M3), + bias[channel],
+        // pixel-shuffle store out[b][c][UP t + phase - PAD].  A lane's four consecutive rows are 4 / UP channels x UP phases, so with its pair
+        // (t0, t0 + 1) it owns 2 UP contiguous output floats per channel from o0 = UP t0 - PAD on; t0 is even, so o0 has PAD's parity and the
+        // run goes out as 8-byte stores (UP = 4: four; UP = 2: a float, a pair, a float).  Outputs outside [0, UP L) are not stored.
+        // stats_part: per (tile, channel) (sum, sumsq) of the stored values - lanes, then the 32 lanes of a row through shuffles, then the WN
+        // column-waves through LDS in wave order, one slot per (tile, channel); no atomics.  A dead column-wave contributes zeros.
+        constexpr int PAD = UP / 2, NV = 2 * UP, CT = MT / UP;
+        float* const stats = p.stats_part;
+        if (!live && !stats) return;
+        float* const outp = p.out;
+        const int Lo = UP * L, o0 = UP * t0 - PAD;
+        const bool evec = p.evec != 0;
+        float* const red = etab + MT;         // [WN][CT][2] (the residual-affine slots of the table: this form has no residual)
+#pragma unroll
+        for (int r0 = 0; r0 < 16; r0 += UP) {
+            const int row = wm0 + F::row(r0, hk);             // first row of the channel inside the tile (a multiple of UP)
+            const float bias = etab[row];
+            float v[NV];
+#pragma unroll
+            for (int ph = 0; ph < UP; ++ph) {
+                const float M0 = acc[0][0][r0 + ph], M1 = acc[1][0][r0 + ph], M3 = acc[3][0][r0 + ph];
+                v[ph] = (M0 + M1) + bias; v[UP + ph] = (M1 - M3) + bias;
+            }
+            float* const orow = outp + ((size_t)b * p.CoutT + (m0 + row) / UP) * Lo;
+            float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const int o = o0 + i;
+                const bool ok = live && o >= 0 && o < Lo;
+                if (ok) { s1 += v[i]; s2 = fmaf(v[i], v[i], s2); }
+                if (!ok) continue;
+                // (element i opens an aligned pair when o is even, i.e. i has PAD's parity: Lo is even, so its partner is inside too)
+                if (((i ^ PAD) & 1) == 0 && i + 1 < NV && evec) { f32x2 w = {v[i], v[i + 1]}; *reinterpret_cast<f32x2*>(orow + o) = w; }
+                else if (((i ^ PAD) & 1) == 0 || i == 0 || !evec) orow[o] = v[i];
+            }
+            if (stats) {
+#pragma unroll
+                for (int off = 16; off > 0; off >>= 1) { s1 += __shfl_xor(s1, off, 64); s2 += __shfl_xor(s2, off, 64); }
+                if (lr == 0) {
+                    red[((wave % WN) * CT + row / UP) * 2 + 0] = s1;
+                    red[((wave % WN) * CT + row / UP) * 2 + 1] = s2;
+                }
+            }
+        }
+        if (stats) {
+            __syncthreads();
+            for (int c = tid; c < CT; c += NTHREADS) {
+                float t1 = 0.f, t2 = 0.f;
+#pragma unroll
+                for (int w = 0; w < WN; ++w) { t1 += red[(w * CT + c) * 2]; t2 += red[(w * CT + c) * 2 + 1]; }
+                stats[((size_t)ti.tile * p.CoutT + m0 / UP + c) * 2 + 0] = t1;
+                stats[((size_t)ti.tile * p.CoutT + m0 / UP + c) * 2 + 1] = t2;
+            }
+        }
+        return;
+    }
 
     if (!live) return;
     // ---- epilogue: output transform, then + bias [+ residual] [+ addends | + out] [/ out_div], conv_tile_kernel's order
@@ -544,6 +624,12 @@ conv_wino_sum_len_kernel(const WinoSumArgs a) {
 template <int MI, int WN, int NPF, bool VEC>
 __global__ void __launch_bounds__(128 * WN, 3)
 conv_wino_fan_kernel(const WinoFanArgs a) {
+    conv_wino_body<MI, WN, NPF, VEC, false>(a);
+}
+
+template <int U, int MI, int WN, int NPF, bool VEC>
+__global__ void __launch_bounds__(128 * WN, 3)
+conv_wino_up_kernel(const WinoUpArgs<U> a) {
     conv_wino_body<MI, WN, NPF, VEC, false>(a);
 }
 
@@ -686,6 +772,47 @@ int launch_wino_fan(const TileArgs* ps, int nsrc, hipStream_t stream) {
     return v2w_launch_lds(kern, dim3(grid), dim3(NTHREADS), lds, stream, a);
 }
 
+// The upsampler form: `p` as WinoUpArgs describes it but for the launch geometry, filled here.
+constexpr int WUP_NTP = 64, WUP_MT = 64;
+template <int U>
+int launch_wino_up(TileArgs p, hipStream_t stream) {
+    constexpr int MI = 1, WN = 2, MT = WUP_MT, NTP = WUP_NTP, NTHREADS = 128 * WN;
+    constexpr int NPF = ((WCK / 2) * (((2 * NTP + 2 * WHMAX) / 4 + 7) / 8 * 8) + NTHREADS - 1) / NTHREADS;
+    static_assert(MT == 64 * MI && NTP == 32 * WN, "tile of the one-conv kernel");
+    p.ntl = (wino_npairs(p.L + 1, 1) + NTP - 1) / NTP;
+    p.ntiles = p.B * p.ntl;
+    int rows = 0;                           // LDS rows the widest tile reads: x[t - 1] of its first pair .. x[t + 1] of its last
+    for (int tl = 0; tl < p.ntl; ++tl) {
+        const int P0 = tl * NTP;
+        const int pos0 = (wino_tpos(P0, 1) - p.hl) & ~3;
+        const int r = wino_tpos(P0 + NTP - 1, 1) + 1 + p.hr - pos0 + 1;
+        if (r > rows) rows = r;
+    }
+    p.xrows = (rows + 3) & ~3;
+    if (p.xrows > 2 * NTP + 2 * WHMAX) return V2W_E_SHAPE;
+    const bool vec = (p.L % 4 == 0) && v2w_al16(p.in);
+    p.vec4 = vec;
+    p.evec = (reinterpret_cast<uintptr_t>(p.out) & 7) == 0;
+    const int nbuf = p.Cin / WCK > 1 ? 2 : 1;
+    p.atab_off = nbuf * p.xrows * WG::RS;
+    const size_t lds = ((size_t)p.atab_off + 3 * MT + (p.in_a ? 2 * p.Cin : 0)) * sizeof(float);
+    WinoUpArgs<U> a{};
+    a.p = p;
+    const int grid = tile_blocks(p.ntiles, p.Cout / MT);
+    auto kern = vec ? conv_wino_up_kernel<U, MI, WN, NPF, true> : conv_wino_up_kernel<U, MI, WN, NPF, false>;
+    return v2w_launch_lds(kern, dim3(grid), dim3(NTHREADS), lds, stream, a);
+}
+
+// Which transposed convs the upsampler form serves: k == 2 u, u in {2, 4}, C_in % 32 == 0 and >= 64, u * C_out % 64 == 0, fp32 tensors.
+int wino_up_shape(const v2w_convt1d_args* a) {
+    if (!a) return V2W_E_ARG;
+    if (a->B <= 0 || a->C_in <= 0 || a->C_out <= 0 || a->L <= 0 || a->k <= 0 || a->u <= 0 || a->io_bf16 != 0) return V2W_E_ARG;
+    if ((a->u != 2 && a->u != 4) || a->k != 2 * a->u) return V2W_E_SHAPE;
+    if (a->C_in % WCK != 0 || a->C_in < 64 || (a->u * a->C_out) % WUP_MT != 0) return V2W_E_SHAPE;
+    if ((long long)a->u * a->L >= (1ll << 31) - 4 * WUP_NTP * a->u) return V2W_E_SHAPE;      // (output positions are ints)
+    return 0;
+}
+
 // wpw float index o = (((mb * nch + ch) * nfr + fi) * 64 + lane) * 4 + j, nfr = wino_terms(k) * 4, fragment fi = (segment, unit gg, term)
 // (wino_frag) holds the term's transformed weight at channel ch*32 + gg*8 + 2j + lane/32, output channel mb*32 + lane%32.
 __global__ void __launch_bounds__(256)
@@ -801,6 +928,30 @@ extern "C" int v2w_conv1d_wino_fan_fwd(const v2w_conv1d_args* a, int n, void* st
         ps[i] = p;
     }
     return launch_wino_fan<1, 2>(ps, n, (hipStream_t)stream);
+}
+
+// The upsampler form (include/vec2wav_hip.h): out = ConvTranspose1d(lrelu(in_a * in + in_s); k = 2 u, stride u, padding u / 2) + bias on the
+// two-tap Winograd segment, a->wp = the layer's fold `wpw` stream; any launch size.  V2W_E_SHAPE: not served, nothing launched.
+extern "C" int v2w_convt1d_wino_fwd(const v2w_convt1d_args* a, const float* in_a, const float* in_s, void* stream) {
+    if (const int rc = wino_up_shape(a)) return rc;
+    if (!a->in || !a->wp || !a->out || (in_a == nullptr) != (in_s == nullptr)) return V2W_E_ARG;
+    TileArgs p{};
+    p.in = a->in; p.in_a = in_a; p.in_s = in_s; p.wp = a->wp; p.bias = a->bias; p.out = a->out; p.stats_part = a->stats_part;
+    p.B = a->B; p.Cin = p.CinT = a->C_in; p.Cout = a->u * a->C_out; p.CoutT = a->C_out; p.L = a->L; p.K = 2; p.dil = 1;
+    p.hl = 1; p.hr = 0; p.pad = a->u / 2; p.up_u = a->u;
+    p.slope = a->slope;
+    return a->u == 4 ? launch_wino_up<4>(p, (hipStream_t)stream) : launch_wino_up<2>(p, (hipStream_t)stream);
+}
+
+// Host-only shape query of the upsampler form: the number of position tiles (= rows of stats_part) of the launch v2w_convt1d_wino_fwd
+// would make, and in *wgs (optional) its live workgroups - the planner's size rule reads them; V2W_E_SHAPE when the form does not serve it.
+extern "C" int v2w_convt1d_wino_tiles(const v2w_convt1d_args* a, int32_t* wgs) {
+    if (const int rc = wino_up_shape(a)) return rc;
+    const long long ntl = (wino_npairs(a->L + 1, 1) + WUP_NTP - 1) / WUP_NTP;
+    const long long tiles = (long long)a->B * ntl, w = tiles * (a->u * a->C_out / WUP_MT);
+    if (w >= (1ll << 31)) return V2W_E_SHAPE;
+    if (wgs) *wgs = (int32_t)w;
+    return (int)tiles;
 }
 
 extern "C" int v2w_wino_sum_order(const int32_t* k, int n, int32_t* order) {

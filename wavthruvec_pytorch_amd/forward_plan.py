@@ -90,6 +90,22 @@ def wino_fan_selected(wino_fan, precision, algo, C, blocks, *, save=False, lengt
             and 1 <= len(blocks) <= 3 and all(k >= 3 and k % 2 == 1 and d == blocks[0][1] for k, d in blocks))
 
 
+def wino_up_shape(c_in, c_out, k, u) -> bool:
+    """The transposed convs the upsampler form of the Winograd kernel serves (v2w_convt1d_wino_fwd): k == 2 u, so every output phase is a
+    two-tap conv, u in (2, 4), 32-channel chunks, 64-row tiles of the u * C_out virtual rows."""
+    return u in (2, 4) and k == 2 * u and c_in % 32 == 0 and c_in >= 64 and (u * c_out) % 64 == 0
+
+
+def wino_up_selected(wino_up, i, precision, algo, c_in, c_out, k, u, *, save=False, lengths=False, stream=True) -> bool:
+    """Does upsampler `i` run as ONE two-tap Winograd conv over u * C_out rows with a pixel-shuffle store (hipops.convt1d_wino: 3 products
+    per output pair where the direct tile issues 4)?  Exact fp32 on the MFMA path, i in `wino_up` (Generator.wino_up: the upsamplers that
+    form was measured faster on), a shape the kernel serves, the plain forward only (`save`: the forward is back-propagated), no per-item
+    `lengths`, and `stream`: the fold has built the layer's Winograd stream.  Read by the planner (upsample) and, without the last three, by
+    the fold (Generator._wino_up_layers).  The values differ from the direct tile's in the last bits."""
+    return (i in tuple(wino_up or ()) and precision == 'f32' and algo != hipops.ALGO_DIRECT and wino_up_shape(c_in, c_out, k, u)
+            and not save and not lengths and bool(stream))
+
+
 def _branches(rbs, names, wps):
     return [dict(wps1=wps[nm + '.convs.0'], b1=rb.convs[0].bias.detach(), wps2=wps[nm + '.convs.1'], b2=rb.convs[1].bias.detach(),
                  k=rb.kernel_size, dil1=rb.convs[0].dilation, dil2=rb.convs[1].dilation) for nm, rb in zip(names, rbs)]
@@ -326,10 +342,13 @@ class ForwardPlanner:
         elif f'ups.{i}' in self.wps:                        # the side stream holds this upsampler's packed weights (bf16 / f16x3 modes)
             self.join_side()
         part, nt_stats = None, 0
+        wpw, nt_wino = self.wino_up(i)
         if self.training:
             # fused statistics: the MFMA transposed conv emits per-tile (sum, sumsq) from its accumulators
             if self.up_done is not None:
                 nt_stats = self.up_done
+            elif nt_wino:
+                nt_stats = nt_wino
             elif f'ups.{i}' in self.wps:
                 nt_stats = hipops.convt_bf16_stats_tiles(self.cur, self.xr, up.kernel_size, up.stride, io_bf16=3 if st else 0)
             elif self.algo != hipops.ALGO_DIRECT and self.wp[f'ups.{i}'] is not None:
@@ -338,6 +357,15 @@ class ForwardPlanner:
                 part = self.buf(f'bn.part{i}', (nt_stats * C * 2,))
         if self.up_done is not None:
             pass        # the previous stage's kernel has written xr (and the partial sums): models.py:128-129 ran fused behind it
+        elif nt_wino and self.timed(f'ups.{i}', hipops.convt1d_wino, self.cur, wpw, up.bias.detach(), self.xr, k=up.kernel_size, u=up.stride,
+                                    slope=LRELU_SLOPE, stats_part=part):
+            pass        # the upsampler form of the Winograd kernel took it
+        elif nt_wino:   # ... declined it after all: today's launch, with its own partial rows
+            if self.training:
+                nt_stats = hipops.convt_stats_tiles(B, up.in_channels, C, L, up.kernel_size, up.stride)
+                part = self.buf(f'bn.part{i}', (nt_stats * C * 2,)) if nt_stats else None
+            self.timed(f'ups.{i}', hipops.convt1d, self.cur, self.wf[f'ups.{i}'], up.bias.detach(), self.xr, k=up.kernel_size,
+                       u=up.stride, slope=LRELU_SLOPE, algo=self.algo, wp=self.wp[f'ups.{i}'], stats_part=part, splitk_ws=self.slab)
         elif f'ups.{i}' in self.wps and (nt_stats or not self.training):
             self.timed(f'ups.{i}', hipops.convt1d_bf16, self.cur, self.wps[f'ups.{i}'], up.bias.detach(), self.xr, k=up.kernel_size,
                        u=up.stride, slope=LRELU_SLOPE, stats_part=part, io_bf16=3 if st else 0)
@@ -348,6 +376,18 @@ class ForwardPlanner:
                        u=up.stride, slope=LRELU_SLOPE, algo=self.algo, wp=self.wp[f'ups.{i}'], stats_part=part, splitk_ws=self.slab, **self.lkw())
         self.up_done = None
         return nt_stats, part
+
+    def wino_up(self, i):
+        """(Winograd stream, position tiles) when upsampler i runs in the upsampler form of the Winograd kernel (wino_up_selected, the library
+        takes the shape, and - the one-conv kernel's rule - the launch has more than 128 workgroups), else (None, 0): today's launch."""
+        g, up = self.g, self.g.ups[i]
+        wpw = g._fold_key.get('wpw_up', {}).get(f'ups.{i}')
+        if (self.st or self.up_done is not None or f'ups.{i}' in self.wps
+                or not wino_up_selected(g.wino_up, i, g.precision, self.algo, up.in_channels, up.out_channels, up.kernel_size, up.stride,
+                                        save=self.save is not None, lengths=self.lens is not None, stream=wpw is not None)):
+            return None, 0
+        tiles, wgs = hipops.convt_wino_tiles(self.B, up.in_channels, up.out_channels, self.L, up.kernel_size, up.stride)
+        return (wpw, tiles) if tiles and wgs > 128 else (None, 0)
 
     def statistics(self, i, nt_stats, part):
         """K4: batch statistics (train) -> [all-reduce] -> folded per-sample affine a, s (modules.py:20-30)."""

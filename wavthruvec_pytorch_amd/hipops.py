@@ -404,6 +404,34 @@ def convt1d(x, wf, bias, out, *, k, u, slope=1.0, algo=ALGO_AUTO, wp=None, stats
     return out
 
 
+def convt_wino_tiles(B, c_in, c_out, L, k, u):
+    """(position tiles = rows of `stats_part`, workgroups) of the launch convt1d_wino would make for this problem, (0, 0) when the
+    upsampler form of the Winograd kernel does not serve the shape (v2w_convt1d_wino_tiles; host only)."""
+    a = _hip.ConvT1dArgs(); a.B, a.C_in, a.C_out, a.L, a.k, a.u = B, c_in, c_out, L, k, u
+    wgs = C.c_int32(0)
+    tiles = _hip.load().v2w_convt1d_wino_tiles(C.byref(a), C.byref(wgs))
+    return (int(tiles), int(wgs.value)) if tiles > 0 else (0, 0)
+
+
+def convt1d_wino(x, wpw, bias, out, *, k, u, slope=1.0, in_affine=None, stats_part=None):
+    """The upsampler form of the Winograd F(2,3) kernel (v2w_convt1d_wino_fwd): leaky_relu -> ConvTranspose1d(k = 2 u, stride u, padding
+    u // 2) -> + bias as ONE two-tap conv over u * C_out rows with a pixel-shuffle store; `wpw` = the layer's Winograd stream (the batched
+    fold's), `stats_part`: [convt_wino_tiles(...)[0]][C_out][2] per-tile (sum, sumsq).  Returns False (nothing launched) when the library
+    declines the shape (V2W_E_SHAPE); the caller then runs convt1d."""
+    B, ci, L = x.shape
+    a = _hip.ConvT1dArgs()
+    a.in_ = x.data_ptr(); a.wp = _hip.ptr(wpw); a.bias = _hip.ptr(bias); a.out = out.data_ptr()
+    a.stats_part = _hip.ptr(stats_part)
+    a.B, a.C_in, a.C_out, a.L, a.k, a.u = B, ci, out.shape[1], L, k, u
+    a.slope = slope
+    ia, is_ = (None, None) if in_affine is None else in_affine
+    rc = _hip.load().v2w_convt1d_wino_fwd(C.byref(a), _hip.ptr(ia), _hip.ptr(is_), _stream(x))
+    if rc == -2:
+        return False
+    _hip.check(rc, 'v2w_convt1d_wino_fwd')
+    return True
+
+
 def pack_bf16_convt(wf, u, out=None):
     """ConvTranspose1d weights wf [k][C_in][C_out] -> bf16 fragments of the virtual 3-tap conv v2w_convt1d_bf16_fwd runs, or None when
     the shape is not served."""

@@ -235,6 +235,11 @@ class Generator(nn.Module):
                                               # that stages their common input once per tile (hipops.conv1d_wino_fan; forward_plan.wino_fan_selected): the `wpw` streams `wino` folds,
                                               # the bits of the separate launches.  The kernel serves C <= 64 (its two chunk buffers hold the whole window).  Measured faster at
                                               # C = 64 (893 -> 750 us per forward; profiles/r15_cfg2_wino_fan_per_layer.txt).  () = off
+        self.wino_up = (1, 2, 3)              # precision 'f32', plain forward without lengths: indices of the upsamplers with k == 2 u that run as ONE two-tap Winograd conv over
+                                              # u * C_out rows with a pixel-shuffle store (hipops.convt1d_wino; forward_plan.wino_up_selected): 3 products per output pair where the
+                                              # direct tile issues 4, the stream built by the batched fold.  Last bits differ from the direct tile's.  Only upsamplers measured
+                                              # faster that way are listed: ups.1 / ups.2 / ups.3 219 / 225 / 158 -> 181 / 190 / 128 us at B = 32 x T = 256 (DESIGN.md 3a;
+                                              # profiles/r16_cfg2_wino_up_per_layer.txt); ups.0 (k 11, u 5) and ups.4 (C_in 32) are not served.  () = off
         self.merge_waits = True               # bf16 storage: one wait per side stream and call, earlier steps of the stream count as met (forward_plan.need)
         self.cond_stream = None               # bf16 storage, train mode: the conditioning chain on a second side stream, beside the weight folds instead of between them.  None: where it pays - while conv_pre + ups.0 are shorter than the one side stream's chain + folds (measured, tools/exp/cond_stream_sweep.py: -26 / -12 us at B x T = 4 096 / 8 192 frames, +8 at 2 048, +13 .. +28 from 12 288 up); True / False: always / never
         self.fuse_post = True                 # leaky_relu -> conv_post -> tanh inside the kernel of the last (C = 16) stage (bf16 storage, and - round 5 - the fp32 stage kernel): the stage's
@@ -420,7 +425,8 @@ class Generator(nn.Module):
         wino = self.wino and self.precision == 'f32' and self.algo != hipops.ALGO_DIRECT
         stage_names = self._wino_stage_layers()
         sum_names = self._wino_sum_layers()
-        state = (tuple(vers), self.algo, str(device), need_wf, bf16_only, wino, bool(stage_names), tuple(sorted(sum_names)))
+        up_names = set() if need_wf else self._wino_up_layers()      # (a forward that is back-propagated keeps the direct tile)
+        state = (tuple(vers), self.algo, str(device), need_wf, bf16_only, wino, bool(stage_names), tuple(sorted(sum_names)), tuple(sorted(up_names)))
         force = (self.training and self.always_refold) or need_wf
         if not force and self._fold_key.get('state') == state:
             return self._fold_key['wf'], self._fold_key['wp']
@@ -429,6 +435,7 @@ class Generator(nn.Module):
         wpw = {}        # wino: the Winograd F(2,3) streams of the layers that kernel serves (forward_plan.ck), from the same pass
         wpw_stage = {}  # wino_stage: the same streams for the six layers of the 32-channel stage (the fused stage kernel's Winograd form)
         wpw_sum = {}    # wino_sum: the same streams for second convs the summed launch serves but `wino` leaves on the direct form (64 channels, dilation 3)
+        wpw_up = {}     # wino_up: the two-tap streams of the upsamplers that run in the upsampler form of the Winograd kernel (u * C_out rows, 3 terms)
         for name, m in layers:
             if bf16_only and name != 'conv_post':      # bf16 activation storage: every other layer runs on its bf16 fragments (_split_weights):
                 wf[name], wp[name] = None, None        # no fp32 fold / fragment stream is read, none is built
@@ -448,6 +455,8 @@ class Generator(nn.Module):
                 wpwb = wpw_stage[name] = self._wbuf('wpw.' + name, (hipops.wino_terms(m.kernel_size) * m.in_channels * m.out_channels,), device=device)
             if mfma_ok and wpwb is None and name in sum_names:
                 wpwb = wpw_sum[name] = self._wbuf('wpw.' + name, (hipops.wino_terms(m.kernel_size) * m.in_channels * m.out_channels,), device=device)
+            if mfma_ok and name in up_names:
+                wpwb = wpw_up[name] = self._wbuf('wpw.' + name, (3 * m.stride * m.out_channels * m.in_channels,), device=device)
             if mfma_ok and need_wf:     # a forward that will be back-propagated: dgrad / wgrad also read the plain layout - written by the
                 # same batched fold (was: three launches per layer, ~100 host-bound launches and 1.6 ms in front of every training forward)
                 n_el = m.kernel_size * m.in_channels * m.out_channels
@@ -477,7 +486,7 @@ class Generator(nn.Module):
                 plan.key = key
                 self._fold_key['plan'] = plan
             plan.run()
-        self._fold_key.update(state=state, wf=wf, wp=wp, wpd=wpd, wpw=wpw, wpw_stage=wpw_stage, wpw_sum=wpw_sum, vers=tuple(vers), gen=self._fold_key.get('gen', 0) + 1)
+        self._fold_key.update(state=state, wf=wf, wp=wp, wpd=wpd, wpw=wpw, wpw_stage=wpw_stage, wpw_sum=wpw_sum, wpw_up=wpw_up, vers=tuple(vers), gen=self._fold_key.get('gen', 0) + 1)
         return wf, wp
 
     def _wino_stage_layers(self):
@@ -492,6 +501,13 @@ class Generator(nn.Module):
                     [(rb.kernel_size, rb.convs[0].dilation, rb.convs[1].dilation) for rb in rbs]):
                 names.update(f'resblocks.{i * nk + j}.convs.{c}' for j in range(nk) for c in (0, 1))
         return names
+
+    def _wino_up_layers(self):
+        """Names of the upsamplers that get the two-tap Winograd stream of the upsampler form (forward_plan.wino_up_selected) - none with
+        `wino_up` empty."""
+        from .forward_plan import wino_up_selected
+        return {f'ups.{i}' for i, up in enumerate(self.ups)
+                if wino_up_selected(self.wino_up, i, self.precision, self.algo, up.in_channels, up.out_channels, up.kernel_size, up.stride)}
 
     def _wino_sum_layers(self):
         """Names of the second convs (`convs.1`) of the stages whose branch sum runs as one Winograd launch (forward_plan.wino_sum_selected):
@@ -715,7 +731,7 @@ class Generator(nn.Module):
         ptrs = tuple(p.data_ptr() for p in self.parameters()) + tuple(b.data_ptr() for b in self.buffers())
         return (tuple(x.shape), str(x.device), torch.cuda.current_stream(x.device).cuda_stream, self.training, self.precision, self.algo, self.bf16_storage, tuple(self.fuse_stage), tuple(self.fuse_pairs),
                 self.fuse_wide, self.fuse_wide_stage, self.fuse_up, self.fuse_post, self.fuse_bn_finalize, self.cond_stream, self.merge_waits, self.split_min_channels,
-                self.always_refold, self.wino, self.wino_stage, tuple(self.wino_sum), tuple(self.wino_sum_wide), tuple(self.wino_fan), ptrs)
+                self.always_refold, self.wino, self.wino_stage, tuple(self.wino_sum), tuple(self.wino_sum_wide), tuple(self.wino_fan), tuple(self.wino_up), ptrs)
 
     def _forward_hip(self, x, spk, nz, save, lens=None):
         """One forward through the C ABI.  `save` (a dict) asks for the back-propagatable form (forward_plan.py).  A no-grad forward is PLANNED
