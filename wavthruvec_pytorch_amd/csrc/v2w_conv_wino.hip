@@ -39,6 +39,10 @@
 // channel * u + phase) on the two-tap segment - 3 products per output pair where the direct tile issues 4 - with a pixel-shuffle store straight
 // from the accumulators (a lane's four consecutive rows are the u phases of 4 / u channels: 2 u contiguous output floats per channel) and
 // conv_tile_kernel's per-tile BatchNorm sums.  B = 32 x T = 256: ups.1 / ups.2 / ups.3 219 / 225 / 158 -> 181 / 190 / 128 us.
+// Host side: the forms share the tile constants (WinoTile), the launch geometry (wino_geometry: tiles, LDS rows and their bound, table offset,
+// LDS bytes - a launcher passes only its form's halo, resident chunks, table rows and affine), the served-conv test (wino_served) and the
+// TileArgs builder (wino_tile_args).  In the body the output transform is one lambda; the zeroing of the accumulators and the restarts of
+// a weight stream stay written out at each site: as lambdas they changed hipcc's register assignment.
 #include "v2w_tile.h"
 #include "v2w_internal.h"
 #include "v2w_wino.h"
@@ -49,6 +53,16 @@ constexpr int WCK = 32;                 // channels per chunk
 typedef TileGeom<32, WCK> WG;           // the LDS signal tile of conv_tile_kernel's 32-channel chunks (v2w_tile.h)
 constexpr int WGPC = 4;                 // A fragments (units of 4 k-steps) per chunk and term
 constexpr int WHMAX = 32;               // staging slots cover 2 NTP + 2 WHMAX rows
+// The tile of <MI, WN>: the one set of constants the device body, the kernels' launchers and the host queries derive theirs from.
+template <int MI, int WN> struct WinoTile {
+    static constexpr int WM = 2, NTHREADS = 64 * WM * WN;
+    static constexpr int MT = 32 * MI * WM, NTP = 32 * WN;             // output channels x output pairs of a workgroup
+    static constexpr int XMAX = 2 * NTP + 2 * WHMAX;                   // the most LDS rows a tile may read (wino_geometry checks it)
+    static constexpr int NPF = ((WCK / 2) * ((XMAX / 4 + 7) / 8 * 8) + NTHREADS - 1) / NTHREADS;      // staging items per thread
+    static_assert(NTHREADS * NPF < 8 * 8192, "item index range of the magic division");
+};
+// (MI = 2, a 128 x 64-pair tile with 128 accumulators per lane, spills at two waves per SIMD and ran slower at one)
+typedef WinoTile<1, 2> WT;              // the tile every entry point launches
 __host__ __device__ inline int wino_tpos(int P, int d) { const int q = P / d; return 2 * d * q + (P - q * d); }
 __host__ __device__ inline int wino_npairs(int L, int d) { return d * ((L + 2 * d - 1) / (2 * d)); }   // output pairs of a row of L positions
 
@@ -117,10 +131,9 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
     static_assert(!UP || (MI == 1 && !LEN && (UP == 2 || UP == 4)), "the upsampler form is written for MI = 1, stride 2 / 4, without per-item lengths");
     typedef Frag<32> F;
     typedef F::acc_t acc_t;
-    constexpr int WM = 2;
-    constexpr int NTHREADS = 64 * WM * WN;
-    constexpr int MT = 32 * MI * WM;
-    constexpr int NTP = 32 * WN;
+    typedef WinoTile<MI, WN> T;
+    constexpr int WM = T::WM, NTHREADS = T::NTHREADS, MT = T::MT, NTP = T::NTP;
+    static_assert(NPF == T::NPF, "the launchers instantiate the kernels with the tile's own NPF");
     constexpr int RING = 4;
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -172,6 +185,12 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
         for (int i = 0; i < MI; ++i)
 #pragma unroll
             for (int e = 0; e < 16; ++e) acc[c][i][e] = 0.f;
+
+    // the output transform of accumulator element e of row block i: the pair's two outputs
+    auto out_transform = [&](int e, int i, float (&y)[2]) {
+        const float M0 = acc[0][i][e], M1 = acc[1][i][e], M2 = acc[2][i][e], M3 = acc[3][i][e];
+        y[0] = (M0 + M1) + M2; y[1] = (M1 - M2) - M3;
+    };
 
     // ---- signal staging: conv_tile_kernel's (an item = one slot-adjacent channel pair x 4 positions)
     const int nq = p.xrows >> 2;
@@ -371,8 +390,8 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
 #pragma unroll
                 for (int q = 0; q < EB; ++q) {
                     const int e = e0 + q, col = wm0 + F::row(e, hq);
-                    const float M0 = acc[0][0][e], M1 = acc[1][0][e], M2 = acc[2][0][e], M3 = acc[3][0][e];
-                    const float y[2] = {(M0 + M1) + M2, (M1 - M2) - M3};
+                    float y[2];
+                    out_transform(e, 0, y);
                     const size_t rowoff = ((size_t)b * p.CoutT + m0 + col) * L;
                     const float bias = bt[col], ra = etab[WSRC * MT + col], rs = etab[(WSRC + 1) * MT + col];
 #pragma unroll
@@ -544,8 +563,8 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
 #pragma unroll
                 for (int q = 0; q < EB; ++q) {
                     const int e = e0 + q, col = wm0 + F::row(e, hk);
-                    const float M0 = acc[0][0][e], M1 = acc[1][0][e], M2 = acc[2][0][e], M3 = acc[3][0][e];
-                    const float y[2] = {(M0 + M1) + M2, (M1 - M2) - M3};
+                    float y[2];
+                    out_transform(e, 0, y);
                     const size_t rowoff = ((size_t)b * p.CoutT + m0 + col) * L;
                     const float bias = etab[col];
 #pragma unroll
@@ -576,8 +595,8 @@ __device__ __forceinline__ void conv_wino_body(const ARGS& m) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int col = wm0 + i * 32 + F::row(e, hk);
-            const float M0 = acc[0][i][e], M1 = acc[1][i][e], M2 = acc[2][i][e], M3 = acc[3][i][e];
-            const float y[2] = {(M0 + M1) + M2, (M1 - M2) - M3};
+            float y[2];
+            out_transform(e, i, y);
             const size_t rowoff = ((size_t)b * p.CoutT + m0 + col) * L;
             const float bias = etab[col], ra = etab[MT + col], rs = etab[2 * MT + col];
 #pragma unroll
@@ -633,44 +652,66 @@ conv_wino_up_kernel(const WinoUpArgs<U> a) {
     conv_wino_body<MI, WN, NPF, VEC, false>(a);
 }
 
+// The launch geometry of a problem, the one place that computes it (the four launchers and v2w_convt1d_wino_tiles call it): position tiles
+// (ntl per item, ntiles) of `npos` output positions, the LDS rows of the widest tile for the halo hl / hr (xrows), the offset of the
+// prologue tables behind `resident_chunks` chunk buffers (atab_off) and in *lds the dynamic LDS bytes with `etab_rows` epilogue rows of MT
+// floats [+ the affine table].  p.xrows only grows (a fresh problem holds 0): the summed form calls this once per source and so sizes the
+// launch for the widest.  V2W_E_SHAPE: more rows than the staging slots cover, or more tiles than an int holds.
+template <class T>
+int wino_geometry(TileArgs& p, int npos, int hl, int hr, int resident_chunks, int etab_rows, bool affine, size_t* lds) {
+    const int d = p.dil;
+    p.ntl = (wino_npairs(npos, d) + T::NTP - 1) / T::NTP;
+    const long long ntiles = (long long)p.B * p.ntl;
+    if (ntiles >= (1ll << 31)) return V2W_E_SHAPE;
+    p.ntiles = (int)ntiles;
+    int rows = p.xrows;                     // LDS rows the widest tile reads: x_K of the last pair's second output
+    for (int tl = 0; tl < p.ntl; ++tl) {
+        const int P0 = tl * T::NTP;
+        const int pos0 = (wino_tpos(P0, d) - hl) & ~3;
+        const int r = wino_tpos(P0 + T::NTP - 1, d) + d + hr - pos0 + 1;
+        if (r > rows) rows = r;
+    }
+    p.xrows = (rows + 3) & ~3;
+    if (p.xrows > T::XMAX) return V2W_E_SHAPE;
+    p.atab_off = resident_chunks * p.xrows * WG::RS;
+    *lds = ((size_t)p.atab_off + etab_rows * T::MT + (affine ? 2 * p.Cin : 0)) * sizeof(float);
+    return 0;
+}
+// ... with the inputs of the forms that run one conv per problem (one-conv, upsampler): own halo, two chunk buffers when there is a second
+// chunk, bias / res_a / res_s rows, the affine table when the problem has one
+template <class T>
+int wino_geometry_conv(TileArgs& p, int npos, size_t* lds) {
+    return wino_geometry<T>(p, npos, p.hl, p.hr, p.Cin / WCK > 1 ? 2 : 1, 3, p.in_a != nullptr, lds);
+}
+inline bool wino_vec4(const TileArgs& p) { return p.L % 4 == 0 && v2w_al16(p.in); }      // float4 staging: rows of whole, aligned quads
+
+// One conv per problem.  V2W_E_SHAPE also for a launch of at most `min_wgs` live workgroups (the caller's size rule).
 template <int MI, int WN>
-int launch_wino(const TileArgs* ps, int nprob, hipStream_t stream) {
-    constexpr int MT = 64 * MI, NTP = 32 * WN, NTHREADS = 128 * WN;
-    constexpr int NPF = ((WCK / 2) * (((2 * NTP + 2 * WHMAX) / 4 + 7) / 8 * 8) + NTHREADS - 1) / NTHREADS;
-    static_assert(NTHREADS * NPF < 8 * 8192, "item index range of the magic division");
+int launch_wino(const TileArgs* ps, int nprob, long min_wgs, hipStream_t stream) {
+    typedef WinoTile<MI, WN> T;
+    constexpr int NPF = T::NPF;
     MultiArgs m{};
     size_t lds = 0;
     int blocks[V2W_MAX_MULTI];
     bool vec = true;
+    long wgs = 0;
     for (int i = 0; i < nprob; ++i) {
-        TileArgs p = ps[i];
-        if (p.Cout % MT != 0) return V2W_E_SHAPE;
-        const int d = p.dil;
-        p.ntl = (wino_npairs(p.L, d) + NTP - 1) / NTP;
-        p.ntiles = p.B * p.ntl;
-        int rows = 0;                       // LDS rows the widest tile reads: x_K of the last pair's second output
-        for (int tl = 0; tl < p.ntl; ++tl) {
-            const int P0 = tl * NTP;
-            const int pos0 = (wino_tpos(P0, d) - p.hl) & ~3;
-            const int r = wino_tpos(P0 + NTP - 1, d) + d + p.hr - pos0 + 1;
-            if (r > rows) rows = r;
-        }
-        p.xrows = (rows + 3) & ~3;
-        if (p.xrows > 2 * NTP + 2 * WHMAX) return V2W_E_SHAPE;
-        p.vec4 = (p.L % 4 == 0) && v2w_al16(p.in);
-        vec = vec && p.vec4;
-        const int nbuf = p.Cin / WCK > 1 ? 2 : 1;
-        p.atab_off = nbuf * p.xrows * WG::RS;
-        const size_t l = ((size_t)p.atab_off + 3 * MT + (p.in_a ? 2 * p.Cin : 0)) * sizeof(float);
+        TileArgs& p = m.p[i] = ps[i];
+        if (p.Cout % T::MT != 0) return V2W_E_SHAPE;
+        size_t l;
+        if (const int rc = wino_geometry_conv<T>(p, p.L, &l)) return rc;
         if (l > lds) lds = l;
-        m.p[i] = p;
-        blocks[i] = tile_blocks(p.ntiles, p.Cout / MT);
+        p.vec4 = wino_vec4(p);
+        vec = vec && p.vec4;
+        blocks[i] = tile_blocks(p.ntiles, p.Cout / T::MT);
+        wgs += (long)p.ntiles * (p.Cout / T::MT);
     }
+    if (wgs <= min_wgs) return V2W_E_SHAPE;
     const int grid = v2w_fill_starts(m.start, V2W_MAX_MULTI, blocks, nprob);
     const bool lens = m.p[0].len != nullptr;      // (all problems of the launch or none: v2w_conv1d_wino)
     auto kern = lens ? (vec ? conv_wino_len_kernel<MI, WN, NPF, true> : conv_wino_len_kernel<MI, WN, NPF, false>)
                     : (vec ? conv_wino_kernel<MI, WN, NPF, true> : conv_wino_kernel<MI, WN, NPF, false>);
-    return v2w_launch_lds(kern, dim3(grid), dim3(NTHREADS), lds, stream, m);
+    return v2w_launch_lds(kern, dim3(grid), dim3(T::NTHREADS), lds, stream, m);
 }
 
 // The summed form: ps[0 .. nsrc) are the sources (shared B, C, L, dil, slope, out, out_div, len); one problem, one grid.
@@ -685,8 +726,8 @@ inline void wino_sum_order(const int* Ks, int nsrc, int* walk) {
 // `order`: the walk order, a permutation of 0 .. nsrc - 1 (null: wino_sum_order's).
 template <int MI, int WN>
 int launch_wino_sum(const TileArgs* ps, int nsrc, const int32_t* order, hipStream_t stream) {
-    constexpr int MT = 64 * MI, NTP = 32 * WN, NTHREADS = 128 * WN;
-    constexpr int NPF = ((WCK / 2) * (((2 * NTP + 2 * WHMAX) / 4 + 7) / 8 * 8) + NTHREADS - 1) / NTHREADS;
+    typedef WinoTile<MI, WN> T;
+    constexpr int NPF = T::NPF;
     WinoSumArgs a{};
     int walk[WSRC];
     int Ks[WSRC];
@@ -701,106 +742,50 @@ int launch_wino_sum(const TileArgs* ps, int nsrc, const int32_t* order, hipStrea
         }
     }
     TileArgs p = ps[walk[0]];
-    if (p.Cout % MT != 0) return V2W_E_SHAPE;
-    const int d = p.dil;
-    p.ntl = (wino_npairs(p.L, d) + NTP - 1) / NTP;
-    p.ntiles = p.B * p.ntl;
-    int rows = 0;                           // LDS rows the widest tile of the widest source reads
-    bool vec = p.L % 4 == 0;
-    for (int j = 0; j < nsrc; ++j) {
-        for (int tl = 0; tl < p.ntl; ++tl) {
-            const int P0 = tl * NTP;
-            const int pos0 = (wino_tpos(P0, d) - ps[j].hl) & ~3;
-            const int r = wino_tpos(P0 + NTP - 1, d) + d + ps[j].hr - pos0 + 1;
-            if (r > rows) rows = r;
-        }
-        vec = vec && v2w_al16(ps[j].in);
+    if (p.Cout % T::MT != 0) return V2W_E_SHAPE;
+    const int nbuf = nsrc * (p.Cin / WCK) > 1 ? 2 : 1;
+    size_t lds = 0;
+    bool vec = true;
+    for (int j = 0; j < nsrc; ++j) {        // (the rows of the widest source: wino_geometry keeps the maximum)
+        if (const int rc = wino_geometry<T>(p, p.L, ps[j].hl, ps[j].hr, nbuf, 3, false, &lds)) return rc;
+        vec = vec && wino_vec4(ps[j]);
         const TileArgs& w = ps[walk[j]];
         a.in[j] = w.in; a.wp[j] = w.wp; a.K[j] = w.K; a.hl[j] = w.hl;
         a.res[j] = ps[j].in; a.bias[j] = ps[j].bias;
     }
     a.nsrc = nsrc;
-    p.xrows = (rows + 3) & ~3;
-    if (p.xrows > 2 * NTP + 2 * WHMAX) return V2W_E_SHAPE;
     p.vec4 = vec;
-    const int nbuf = nsrc * (p.Cin / WCK) > 1 ? 2 : 1;
-    p.atab_off = nbuf * p.xrows * WG::RS;
-    const size_t lds = ((size_t)p.atab_off + 3 * MT) * sizeof(float);
     a.p = p;
-    const int grid = tile_blocks(p.ntiles, p.Cout / MT);
+    const int grid = tile_blocks(p.ntiles, p.Cout / T::MT);
     auto kern = p.len ? (vec ? conv_wino_sum_len_kernel<MI, WN, NPF, true> : conv_wino_sum_len_kernel<MI, WN, NPF, false>)
                       : (vec ? conv_wino_sum_kernel<MI, WN, NPF, true> : conv_wino_sum_kernel<MI, WN, NPF, false>);
-    return v2w_launch_lds(kern, dim3(grid), dim3(NTHREADS), lds, stream, a);
+    return v2w_launch_lds(kern, dim3(grid), dim3(T::NTHREADS), lds, stream, a);
 }
 
 // The fan-out form: ps[0 .. nsrc) are the branches (shared in, in_a / in_s, res, res_a / res_s, B, C, L, dil, slope); one problem, one grid
 // of one workgroup per tile.  C_in of at most two chunks: the double buffer then holds the whole activated window (V2W_E_SHAPE otherwise).
 template <int MI, int WN>
 int launch_wino_fan(const TileArgs* ps, int nsrc, hipStream_t stream) {
-    constexpr int MT = 64 * MI, NTP = 32 * WN, NTHREADS = 128 * WN;
-    constexpr int NPF = ((WCK / 2) * (((2 * NTP + 2 * WHMAX) / 4 + 7) / 8 * 8) + NTHREADS - 1) / NTHREADS;
+    typedef WinoTile<MI, WN> T;
+    constexpr int NPF = T::NPF;
     WinoFanArgs a{};
     TileArgs p = ps[0];
     const int nch = p.Cin / WCK;
-    if (p.Cout % MT != 0 || nch > 2) return V2W_E_SHAPE;
+    if (p.Cout % T::MT != 0 || nch > 2) return V2W_E_SHAPE;
     int hmax = 0;
     for (int j = 0; j < nsrc; ++j) {
         a.wp[j] = ps[j].wp; a.bias[j] = ps[j].bias; a.out[j] = ps[j].out; a.K[j] = ps[j].K; a.hl[j] = ps[j].hl;
         if (ps[j].hl > hmax) hmax = ps[j].hl;
     }
     a.nsrc = nsrc;
-    p.hl = p.hr = hmax;
-    const int d = p.dil;
-    p.ntl = (wino_npairs(p.L, d) + NTP - 1) / NTP;
-    p.ntiles = p.B * p.ntl;
-    int rows = 0;                           // LDS rows the widest tile of the widest branch reads
-    for (int tl = 0; tl < p.ntl; ++tl) {
-        const int P0 = tl * NTP;
-        const int pos0 = (wino_tpos(P0, d) - hmax) & ~3;
-        const int r = wino_tpos(P0 + NTP - 1, d) + d + hmax - pos0 + 1;
-        if (r > rows) rows = r;
-    }
-    p.xrows = (rows + 3) & ~3;
-    if (p.xrows > 2 * NTP + 2 * WHMAX) return V2W_E_SHAPE;
-    const bool vec = (p.L % 4 == 0) && v2w_al16(p.in);
-    p.vec4 = vec;
-    p.atab_off = nch * p.xrows * WG::RS;
-    const size_t lds = ((size_t)p.atab_off + (WSRC + 2) * MT + (p.in_a ? 2 * p.Cin : 0)) * sizeof(float);
+    p.hl = p.hr = hmax;                     // (the widest branch's rows serve every branch; all nch chunks stay resident)
+    size_t lds;
+    if (const int rc = wino_geometry<T>(p, p.L, hmax, hmax, nch, WSRC + 2, p.in_a != nullptr, &lds)) return rc;
+    const bool vec = p.vec4 = wino_vec4(p);
     a.p = p;
-    const int grid = tile_blocks(p.ntiles, p.Cout / MT);
+    const int grid = tile_blocks(p.ntiles, p.Cout / T::MT);
     auto kern = vec ? conv_wino_fan_kernel<MI, WN, NPF, true> : conv_wino_fan_kernel<MI, WN, NPF, false>;
-    return v2w_launch_lds(kern, dim3(grid), dim3(NTHREADS), lds, stream, a);
-}
-
-// The upsampler form: `p` as WinoUpArgs describes it but for the launch geometry, filled here.
-constexpr int WUP_NTP = 64, WUP_MT = 64;
-template <int U>
-int launch_wino_up(TileArgs p, hipStream_t stream) {
-    constexpr int MI = 1, WN = 2, MT = WUP_MT, NTP = WUP_NTP, NTHREADS = 128 * WN;
-    constexpr int NPF = ((WCK / 2) * (((2 * NTP + 2 * WHMAX) / 4 + 7) / 8 * 8) + NTHREADS - 1) / NTHREADS;
-    static_assert(MT == 64 * MI && NTP == 32 * WN, "tile of the one-conv kernel");
-    p.ntl = (wino_npairs(p.L + 1, 1) + NTP - 1) / NTP;
-    p.ntiles = p.B * p.ntl;
-    int rows = 0;                           // LDS rows the widest tile reads: x[t - 1] of its first pair .. x[t + 1] of its last
-    for (int tl = 0; tl < p.ntl; ++tl) {
-        const int P0 = tl * NTP;
-        const int pos0 = (wino_tpos(P0, 1) - p.hl) & ~3;
-        const int r = wino_tpos(P0 + NTP - 1, 1) + 1 + p.hr - pos0 + 1;
-        if (r > rows) rows = r;
-    }
-    p.xrows = (rows + 3) & ~3;
-    if (p.xrows > 2 * NTP + 2 * WHMAX) return V2W_E_SHAPE;
-    const bool vec = (p.L % 4 == 0) && v2w_al16(p.in);
-    p.vec4 = vec;
-    p.evec = (reinterpret_cast<uintptr_t>(p.out) & 7) == 0;
-    const int nbuf = p.Cin / WCK > 1 ? 2 : 1;
-    p.atab_off = nbuf * p.xrows * WG::RS;
-    const size_t lds = ((size_t)p.atab_off + 3 * MT + (p.in_a ? 2 * p.Cin : 0)) * sizeof(float);
-    WinoUpArgs<U> a{};
-    a.p = p;
-    const int grid = tile_blocks(p.ntiles, p.Cout / MT);
-    auto kern = vec ? conv_wino_up_kernel<U, MI, WN, NPF, true> : conv_wino_up_kernel<U, MI, WN, NPF, false>;
-    return v2w_launch_lds(kern, dim3(grid), dim3(NTHREADS), lds, stream, a);
+    return v2w_launch_lds(kern, dim3(grid), dim3(T::NTHREADS), lds, stream, a);
 }
 
 // Which transposed convs the upsampler form serves: k == 2 u, u in {2, 4}, C_in % 32 == 0 and >= 64, u * C_out % 64 == 0, fp32 tensors.
@@ -808,9 +793,33 @@ int wino_up_shape(const v2w_convt1d_args* a) {
     if (!a) return V2W_E_ARG;
     if (a->B <= 0 || a->C_in <= 0 || a->C_out <= 0 || a->L <= 0 || a->k <= 0 || a->u <= 0 || a->io_bf16 != 0) return V2W_E_ARG;
     if ((a->u != 2 && a->u != 4) || a->k != 2 * a->u) return V2W_E_SHAPE;
-    if (a->C_in % WCK != 0 || a->C_in < 64 || (a->u * a->C_out) % WUP_MT != 0) return V2W_E_SHAPE;
-    if ((long long)a->u * a->L >= (1ll << 31) - 4 * WUP_NTP * a->u) return V2W_E_SHAPE;      // (output positions are ints)
+    if (a->C_in % WCK != 0 || a->C_in < 64 || (a->u * a->C_out) % WT::MT != 0) return V2W_E_SHAPE;
+    if ((long long)a->u * a->L >= (1ll << 31) - 4 * WT::NTP * a->u) return V2W_E_SHAPE;      // (output positions are ints)
     return 0;
+}
+// The upsampler form's problem (as WinoUpArgs describes it) and its launch geometry: the launcher and the tile query share both, so the
+// planner's bn.part{i} rows are the launch's tiles.  The conv has L + 1 output positions.
+TileArgs wino_up_problem(const v2w_convt1d_args* a, const float* in_a, const float* in_s) {
+    TileArgs p{};
+    p.in = a->in; p.in_a = in_a; p.in_s = in_s; p.wp = a->wp; p.bias = a->bias; p.out = a->out; p.stats_part = a->stats_part;
+    p.B = a->B; p.Cin = p.CinT = a->C_in; p.Cout = a->u * a->C_out; p.CoutT = a->C_out; p.L = a->L; p.K = 2; p.dil = 1;
+    p.hl = 1; p.hr = 0; p.pad = a->u / 2; p.up_u = a->u;
+    p.slope = a->slope;
+    return p;
+}
+inline int wino_up_geometry(TileArgs& p, size_t* lds) { return wino_geometry_conv<WT>(p, p.L + 1, lds); }
+
+template <int U>
+int launch_wino_up(TileArgs p, hipStream_t stream) {
+    size_t lds;
+    if (const int rc = wino_up_geometry(p, &lds)) return rc;
+    const bool vec = p.vec4 = wino_vec4(p);
+    p.evec = (reinterpret_cast<uintptr_t>(p.out) & 7) == 0;
+    WinoUpArgs<U> a{};
+    a.p = p;
+    const int grid = tile_blocks(p.ntiles, p.Cout / WT::MT);
+    auto kern = vec ? conv_wino_up_kernel<U, 1, 2, WT::NPF, true> : conv_wino_up_kernel<U, 1, 2, WT::NPF, false>;
+    return v2w_launch_lds(kern, dim3(grid), dim3(WT::NTHREADS), lds, stream, a);
 }
 
 // wpw float index o = (((mb * nch + ch) * nfr + fi) * 64 + lane) * 4 + j, nfr = wino_terms(k) * 4, fragment fi = (segment, unit gg, term)
@@ -833,39 +842,42 @@ pack_wino_kernel(const float* __restrict__ wf, float* __restrict__ wp, int K, in
     }
 }
 
+// Which Conv1d problems the kernel serves, whatever the form: C_in % 32 == 0 and >= 64, C_out % 64 == 0, odd k >= 3 with symmetric padding,
+// plain unit-stride input, no channel slices, none of the backward / discriminator epilogues.
+bool wino_served(const v2w_conv1d_args* q) {
+    return q->C_in % WCK == 0 && q->C_in >= 64 && q->C_out % WT::MT == 0 && wino_terms(q->k) != 0 && q->pad_left < 0
+        && q->in_stride <= 1 && !q->mask_src && !q->rowsum_part && (q->out_slope == 0.f || q->out_slope == 1.f)
+        && (q->in_ct <= 0 || q->in_ct == q->C_in) && (q->out_ct <= 0 || q->out_ct == q->C_out);
+}
+// ... and the problem of a served conv
+TileArgs wino_tile_args(const v2w_conv1d_args* q, const int32_t* len, int len_mul) {
+    TileArgs p{};
+    p.len = len; p.len_mul = len_mul;
+    p.in = q->in; p.in_a = q->in_a; p.in_s = q->in_s; p.wp = q->wp; p.bias = q->bias;
+    p.res = q->res; p.res_a = q->res_a; p.res_s = q->res_s; p.out = q->out;
+    p.add0 = q->add0; p.add1 = q->add1;
+    p.B = q->B; p.Cin = q->C_in; p.Cout = q->C_out; p.L = q->L; p.K = q->k; p.dil = q->dil;
+    p.CinT = q->C_in; p.CoutT = q->C_out;
+    p.hl = p.hr = q->dil * (q->k - 1) / 2;
+    p.slope = q->slope; p.accumulate = q->accumulate; p.out_div = q->out_div;
+    return p;
+}
+
 }  // namespace
 
-// Which shapes the Winograd kernel serves (V2W_E_SHAPE otherwise; the caller then uses the direct-form f32 MFMA kernel):
-// C_in % 32 == 0 and >= 64, C_out % 64 == 0, odd k >= 3 with symmetric padding, plain unit-stride input, no channel slices, none of
-// the backward / discriminator epilogues, and launches of more than 128 workgroups of 64 channels x 64 pairs.
+// V2W_ALGO_WINO (V2W_E_SHAPE: not served; the caller then uses the direct-form f32 MFMA kernel): what wino_served serves, in launches of
+// more than 128 workgroups of 64 channels x 64 pairs.
 int v2w_conv1d_wino(const v2w_conv1d_args* a, int n, hipStream_t stream, const int32_t* len, int len_mul) {
     if (n < 1 || n > V2W_MAX_MULTI) return V2W_E_ARG;
     TileArgs ps[V2W_MAX_MULTI];
-    long wgs = 0;
-    const int MT = 64;
     for (int i = 0; i < n; ++i) {
         const v2w_conv1d_args* q = a + i;
-        if (q->B != a->B || q->C_in != a->C_in || q->C_out != a->C_out || q->L != a->L) return V2W_E_SHAPE;
-        if (q->C_in % WCK != 0 || q->C_in < 64 || q->C_out % 64 != 0 || wino_terms(q->k) == 0 || q->pad_left >= 0) return V2W_E_SHAPE;
-        if (q->in_stride > 1 || q->mask_src || q->rowsum_part || (q->out_slope != 0.f && q->out_slope != 1.f)) return V2W_E_SHAPE;
-        if ((q->in_ct > 0 && q->in_ct != q->C_in) || (q->out_ct > 0 && q->out_ct != q->C_out)) return V2W_E_SHAPE;
+        if (q->B != a->B || q->C_in != a->C_in || q->C_out != a->C_out || q->L != a->L || !wino_served(q)) return V2W_E_SHAPE;
         if (!q->wp) return V2W_E_ARG;
         if (len && len_mul < 1) return V2W_E_ARG;
-        TileArgs p{};
-        p.len = len; p.len_mul = len_mul;
-        p.in = q->in; p.in_a = q->in_a; p.in_s = q->in_s; p.wp = q->wp; p.bias = q->bias;
-        p.res = q->res; p.res_a = q->res_a; p.res_s = q->res_s; p.out = q->out;
-        p.add0 = q->add0; p.add1 = q->add1;
-        p.B = q->B; p.Cin = q->C_in; p.Cout = q->C_out; p.L = q->L; p.K = q->k; p.dil = q->dil;
-        p.CinT = q->C_in; p.CoutT = q->C_out;
-        p.hl = p.hr = q->dil * (q->k - 1) / 2;
-        p.slope = q->slope; p.accumulate = q->accumulate; p.out_div = q->out_div;
-        ps[i] = p;
-        wgs += (long)q->B * ((wino_npairs(q->L, q->dil) + 63) / 64) * (q->C_out / MT);
+        ps[i] = wino_tile_args(q, len, len_mul);
     }
-    if (wgs <= 128) return V2W_E_SHAPE;     // (the f32 MFMA path splits such launches over C_in: inference at B = 1)
-    // (MI = 2, a 128 x 64-pair tile with 128 accumulators per lane, spills at two waves per SIMD and ran slower at one)
-    return launch_wino<1, 2>(ps, n, stream);
+    return launch_wino<1, 2>(ps, n, 128, stream);     // (the f32 MFMA path splits launches of <= 128 workgroups over C_in: inference at B = 1)
 }
 
 // The summed form (include/vec2wav_hip.h): out = (sum_j in_j + sum_j conv_j(lrelu(in_j)) + sum_j bias_j) [/ out_div] in one launch.
@@ -886,15 +898,9 @@ extern "C" int v2w_conv1d_wino_sum_fwd_order(const v2w_conv1d_args* a, int n, co
         if (q->res || q->res_a || q->add0 || q->add1 || q->accumulate || (q->in_a == nullptr) != (q->in_s == nullptr)) return V2W_E_ARG;
         if (q->B != a->B || q->C_in != a->C_in || q->C_out != a->C_in || q->L != a->L || q->dil != a->dil || q->slope != a->slope) return V2W_E_SHAPE;
         if (q->in_a) return V2W_E_SHAPE;        // (the second convs read lrelu(t1_j); one conv with an input affine: V2W_ALGO_WINO)
-        if (q->C_in % 64 != 0 || wino_terms(q->k) == 0 || q->pad_left >= 0) return V2W_E_SHAPE;
-        if (q->in_stride > 1 || q->mask_src || q->rowsum_part || q->out_slope != 0.f || q->in_ct > 0 || q->out_ct > 0) return V2W_E_SHAPE;
-        TileArgs p{};
-        p.len = len; p.len_mul = len_mul;
-        p.in = q->in; p.wp = q->wp; p.bias = q->bias; p.out = a->out;
-        p.B = q->B; p.Cin = p.Cout = p.CinT = p.CoutT = q->C_in; p.L = q->L; p.K = q->k; p.dil = q->dil;
-        p.hl = p.hr = q->dil * (q->k - 1) / 2;
-        p.slope = q->slope; p.out_div = a->out_div;
-        ps[i] = p;
+        if (!wino_served(q)) return V2W_E_SHAPE;
+        ps[i] = wino_tile_args(q, len, len_mul);
+        ps[i].out = a->out; ps[i].out_div = a->out_div;
     }
     return launch_wino_sum<1, 2>(ps, n, order, (hipStream_t)stream);
 }
@@ -914,18 +920,9 @@ extern "C" int v2w_conv1d_wino_fan_fwd(const v2w_conv1d_args* a, int n, void* st
         if (q->B != a->B || q->C_in != a->C_in || q->C_out != a->C_out || q->L != a->L || q->dil != a->dil || q->slope != a->slope) return V2W_E_ARG;
         for (int j = 0; j < i; ++j)
             if (a[j].out == q->out) return V2W_E_ARG;
-        if (q->C_in % WCK != 0 || q->C_in < 64 || q->C_out % 64 != 0 || wino_terms(q->k) == 0 || q->pad_left >= 0) return V2W_E_SHAPE;
-        if (q->in_stride > 1 || q->mask_src || q->rowsum_part || (q->out_slope != 0.f && q->out_slope != 1.f)) return V2W_E_SHAPE;
-        if (q->in_ct > 0 || q->out_ct > 0) return V2W_E_SHAPE;
+        if (!wino_served(q)) return V2W_E_SHAPE;
         if (q->add0 || q->add1 || q->accumulate || q->out_div != 0.f) return V2W_E_SHAPE;     // (the first convs have none of these)
-        TileArgs p{};
-        p.in = q->in; p.in_a = q->in_a; p.in_s = q->in_s; p.wp = q->wp; p.bias = q->bias;
-        p.res = q->res; p.res_a = q->res_a; p.res_s = q->res_s; p.out = q->out;
-        p.B = q->B; p.Cin = q->C_in; p.Cout = q->C_out; p.L = q->L; p.K = q->k; p.dil = q->dil;
-        p.CinT = q->C_in; p.CoutT = q->C_out;
-        p.hl = p.hr = q->dil * (q->k - 1) / 2;
-        p.slope = q->slope;
-        ps[i] = p;
+        ps[i] = wino_tile_args(q, nullptr, 0);
     }
     return launch_wino_fan<1, 2>(ps, n, (hipStream_t)stream);
 }
@@ -935,11 +932,7 @@ extern "C" int v2w_conv1d_wino_fan_fwd(const v2w_conv1d_args* a, int n, void* st
 extern "C" int v2w_convt1d_wino_fwd(const v2w_convt1d_args* a, const float* in_a, const float* in_s, void* stream) {
     if (const int rc = wino_up_shape(a)) return rc;
     if (!a->in || !a->wp || !a->out || (in_a == nullptr) != (in_s == nullptr)) return V2W_E_ARG;
-    TileArgs p{};
-    p.in = a->in; p.in_a = in_a; p.in_s = in_s; p.wp = a->wp; p.bias = a->bias; p.out = a->out; p.stats_part = a->stats_part;
-    p.B = a->B; p.Cin = p.CinT = a->C_in; p.Cout = a->u * a->C_out; p.CoutT = a->C_out; p.L = a->L; p.K = 2; p.dil = 1;
-    p.hl = 1; p.hr = 0; p.pad = a->u / 2; p.up_u = a->u;
-    p.slope = a->slope;
+    const TileArgs p = wino_up_problem(a, in_a, in_s);
     return a->u == 4 ? launch_wino_up<4>(p, (hipStream_t)stream) : launch_wino_up<2>(p, (hipStream_t)stream);
 }
 
@@ -947,11 +940,13 @@ extern "C" int v2w_convt1d_wino_fwd(const v2w_convt1d_args* a, const float* in_a
 // would make, and in *wgs (optional) its live workgroups - the planner's size rule reads them; V2W_E_SHAPE when the form does not serve it.
 extern "C" int v2w_convt1d_wino_tiles(const v2w_convt1d_args* a, int32_t* wgs) {
     if (const int rc = wino_up_shape(a)) return rc;
-    const long long ntl = (wino_npairs(a->L + 1, 1) + WUP_NTP - 1) / WUP_NTP;
-    const long long tiles = (long long)a->B * ntl, w = tiles * (a->u * a->C_out / WUP_MT);
+    TileArgs p = wino_up_problem(a, nullptr, nullptr);
+    size_t lds;
+    if (const int rc = wino_up_geometry(p, &lds)) return rc;
+    const long long w = (long long)p.ntiles * (p.Cout / WT::MT);
     if (w >= (1ll << 31)) return V2W_E_SHAPE;
     if (wgs) *wgs = (int32_t)w;
-    return (int)tiles;
+    return p.ntiles;
 }
 
 extern "C" int v2w_wino_sum_order(const int32_t* k, int n, int32_t* order) {

@@ -32,6 +32,14 @@ def _stream(t: torch.Tensor) -> int:
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
+def _declined(rc: int, name: str) -> bool:
+    """True when the library declined the shape (V2W_E_SHAPE: nothing was launched, the caller falls through); raises on any other error."""
+    if rc == _hip.E_SHAPE:
+        return True
+    _hip.check(rc, name)
+    return False
+
+
 def fold_conv_weight(v, g, out=None, scratch=None):
     """weight_v (C_out,C_in,k), weight_g (C_out,1,1)|None -> wf [k][C_in][C_out]."""
     _chk(v, 'v'); _chk(g, 'g')
@@ -84,10 +92,7 @@ def pack_mfma(wf, out=None, u=1):
     if out is None:
         out = torch.empty((k * ci * co,), device=wf.device, dtype=torch.float32)
     rc = _hip.load().v2w_pack_mfma(wf.data_ptr(), out.data_ptr(), k, ci, co, u, _stream(wf))
-    if rc == -2:
-        return None
-    _hip.check(rc, 'v2w_pack_mfma')
-    return out
+    return None if _declined(rc, 'v2w_pack_mfma') else out
 
 
 def pack_mfma_dgrad(wf):
@@ -96,10 +101,7 @@ def pack_mfma_dgrad(wf):
     k, ci, co = wf.shape
     out = torch.empty((k * ci * co,), device=wf.device, dtype=torch.float32)
     rc = _hip.load().v2w_pack_mfma_dgrad(wf.data_ptr(), out.data_ptr(), k, co, ci, _stream(wf))
-    if rc == -2:
-        return None
-    _hip.check(rc, 'v2w_pack_mfma_dgrad')
-    return out
+    return None if _declined(rc, 'v2w_pack_mfma_dgrad') else out
 
 
 def pack_mfma_batch(w4):
@@ -147,10 +149,7 @@ def pack_wino(wf, out=None):
     if out is None:
         out = torch.empty((n,), device=wf.device, dtype=torch.float32)
     rc = _hip.load().v2w_pack_wino(wf.data_ptr(), out.data_ptr(), k, ci, co, _stream(wf))
-    if rc == -2:
-        return None
-    _hip.check(rc, 'v2w_pack_wino')
-    return out
+    return None if _declined(rc, 'v2w_pack_wino') else out
 
 
 def pack_split(wf, out=None, sc=None, bf16=False):
@@ -280,29 +279,39 @@ def conv1d(x, wf, bias, out, splitk_ws=None, **kw):
     return out
 
 
+def _conv1d_launch(problems, splitk_ws=None, *, nmin=2, over=None) -> bool:
+    """One launch of nmin <= n <= 4 problems (x, wf, bias, out, kwargs without `wpw`) that share B, C_in, C_out, L; `over`: per-problem
+    overrides of the kwargs.  False when there was nothing to launch in one piece or the library declined (V2W_E_SHAPE: nothing was launched)."""
+    n = len(problems)
+    if not nmin <= n <= 4:
+        return False
+    arr = (_hip.Conv1dArgs * n)()
+    lengths = len_mul = None
+    for i, (a, (x, wf, bias, out, kw)) in enumerate(zip(arr, problems)):
+        kw, lengths, len_mul = _pop_len(kw)          # (every problem of a launch carries the same lengths, or none does)
+        _conv1d_args(a, x, wf, bias, out, **{**kw, **(over[i] if over else {})})
+    x0 = problems[0][0]
+    if splitk_ws is not None:
+        _attach_slab(arr[0], splitk_ws, _splitk_bytes(arr, n), x0.device)
+    if lengths is not None:
+        rc = _hip.load().v2w_conv1d_fwd_len(arr, n, _len_ptr(lengths, len_mul), len_mul, _stream(x0))
+    else:
+        rc = _hip.load().v2w_conv1d_fwd_multi(arr, n, _stream(x0))
+    return not _declined(rc, 'v2w_conv1d_fwd_multi')
+
+
+def _without_wpw(problems):
+    return [(x, wf, bias, out, {q: v for q, v in kw.items() if q != 'wpw'}) for x, wf, bias, out, kw in problems]
+
+
 def conv1d_multi(problems, splitk_ws=None):
     """`problems`: list of (x, wf, bias, out, kwargs) sharing B, C_in, C_out, L.  One launch when the MFMA path takes them
     (heaviest first), otherwise one launch each."""
-    n = len(problems)
     if any(kw.get('wpw') is not None for *_r, kw in problems):
         return conv1d_wino_multi(problems, splitk_ws=splitk_ws)
-    problems = [(x, wf, bias, out, {q: v for q, v in kw.items() if q != 'wpw'}) for x, wf, bias, out, kw in problems]
-    if 1 < n <= 4:
-        arr = (_hip.Conv1dArgs * n)()
-        lengths = len_mul = None
-        for a, (x, wf, bias, out, kw) in zip(arr, problems):
-            kw, lengths, len_mul = _pop_len(kw)          # (every problem of a launch carries the same lengths, or none does)
-            _conv1d_args(a, x, wf, bias, out, **kw)
-        if splitk_ws is not None:
-            _attach_slab(arr[0], splitk_ws, _splitk_bytes(arr, n), problems[0][0].device)
-        if lengths is not None:
-            rc = _hip.load().v2w_conv1d_fwd_len(arr, n, _len_ptr(lengths, len_mul), len_mul, _stream(problems[0][0]))
-        else:
-            rc = _hip.load().v2w_conv1d_fwd_multi(arr, n, _stream(problems[0][0]))
-        if rc == 0:
-            return
-        if rc != -2:
-            _hip.check(rc, 'v2w_conv1d_fwd_multi')
+    problems = _without_wpw(problems)
+    if _conv1d_launch(problems, splitk_ws):
+        return
     for x, wf, bias, out, kw in problems:
         conv1d(x, wf, bias, out, splitk_ws=splitk_ws, **kw)
 
@@ -310,22 +319,11 @@ def conv1d_multi(problems, splitk_ws=None):
 def conv1d_wino_multi(problems, splitk_ws=None):
     """conv1d_multi on the Winograd F(2,3) kernel (ALGO_WINO): every problem's kwargs carry `wpw=` (its pack_wino stream) next to the
     f32 MFMA `algo` / `wp` it runs on when the Winograd kernel declines the launch (V2W_E_SHAPE: nothing was launched)."""
-    n = len(problems)
-    if 1 <= n <= 4 and all(kw.get('wpw') is not None for *_r, kw in problems):
-        arr = (_hip.Conv1dArgs * n)()
-        lengths = len_mul = None
-        for a, (x, wf, bias, out, kw) in zip(arr, problems):
-            kw2, lengths, len_mul = _pop_len({q: v for q, v in kw.items() if q != 'wpw'})
-            _conv1d_args(a, x, wf, bias, out, **{**kw2, 'algo': ALGO_WINO, 'wp': kw['wpw']})
-        if lengths is not None:
-            rc = _hip.load().v2w_conv1d_fwd_len(arr, n, _len_ptr(lengths, len_mul), len_mul, _stream(problems[0][0]))
-        else:
-            rc = _hip.load().v2w_conv1d_fwd_multi(arr, n, _stream(problems[0][0]))
-        if rc == 0:
+    plain = _without_wpw(problems)
+    if all(kw.get('wpw') is not None for *_r, kw in problems):
+        if _conv1d_launch(plain, nmin=1, over=[{'algo': ALGO_WINO, 'wp': kw['wpw']} for *_r, kw in problems]):
             return
-        if rc != -2:
-            _hip.check(rc, 'v2w_conv1d_fwd_multi')
-    conv1d_multi([(x, wf, bias, out, {q: v for q, v in kw.items() if q != 'wpw'}) for x, wf, bias, out, kw in problems], splitk_ws=splitk_ws)
+    conv1d_multi(plain, splitk_ws=splitk_ws)
 
 
 def conv1d_wino_sum(sources, out, *, dil, slope, out_div=0.0, in_affine=None, lengths=None, len_mul=1, order=None):
@@ -343,10 +341,7 @@ def conv1d_wino_sum(sources, out, *, dil, slope, out_div=0.0, in_affine=None, le
         rc = _hip.load().v2w_conv1d_wino_sum_fwd(arr, n, lp, int(len_mul), _stream(out))
     else:
         rc = _hip.load().v2w_conv1d_wino_sum_fwd_order(arr, n, lp, int(len_mul), (C.c_int32 * max(n, 1))(*order), _stream(out))
-    if rc == -2:
-        return False
-    _hip.check(rc, 'v2w_conv1d_wino_sum_fwd')
-    return True
+    return not _declined(rc, 'v2w_conv1d_wino_sum_fwd')
 
 
 def wino_multi_taken(n, B, c_out, L, dil):
@@ -372,10 +367,7 @@ def conv1d_wino_fan(x, branches, *, dil, slope, in_affine=None, res=None, res_af
     for a, (wpw, bias, out, k) in zip(arr, branches):
         _conv1d_args(a, x, None, bias, out, k=k, dil=dil, slope=slope, algo=ALGO_WINO, wp=wpw, in_affine=in_affine, res=res, res_affine=res_affine)
     rc = _hip.load().v2w_conv1d_wino_fan_fwd(arr, n, _stream(x))
-    if rc == -2:
-        return False
-    _hip.check(rc, 'v2w_conv1d_wino_fan_fwd')
-    return True
+    return not _declined(rc, 'v2w_conv1d_wino_fan_fwd')
 
 
 def wino_sum_order(ks):
@@ -426,10 +418,7 @@ def convt1d_wino(x, wpw, bias, out, *, k, u, slope=1.0, in_affine=None, stats_pa
     a.slope = slope
     ia, is_ = (None, None) if in_affine is None else in_affine
     rc = _hip.load().v2w_convt1d_wino_fwd(C.byref(a), _hip.ptr(ia), _hip.ptr(is_), _stream(x))
-    if rc == -2:
-        return False
-    _hip.check(rc, 'v2w_convt1d_wino_fwd')
-    return True
+    return not _declined(rc, 'v2w_convt1d_wino_fwd')
 
 
 def pack_bf16_convt(wf, u, out=None):
@@ -752,10 +741,7 @@ def resblock_pair_multi(problems):
         a.B, a.C, a.L, a.k, a.dil1, a.dil2 = B, Cc, L, q['k'], q['dil1'], q['dil2']
         a.res_mode = q['res_mode']; a.slope = q['slope']; a.out_div = q.get('out_div', 0.0)
     rc = _hip.load().v2w_resblock_pair_fwd(arr, n, _stream(problems[0]['x']))
-    if rc == -2:
-        return False
-    _hip.check(rc, 'v2w_resblock_pair_fwd')
-    return True
+    return not _declined(rc, 'v2w_resblock_pair_fwd')
 
 
 def resblock1_pairs_ok(B, Cc, L, ks, dil1s, dil2s, *, slope) -> bool:
@@ -813,10 +799,7 @@ def resblock1_pairs_bf16(ins, in_affine, branches, outs, *, slope, out_div=0.0, 
     a.nk, a.B, a.C, a.L = len(branches), B, Cc, L
     a.slope, a.out_div, a.bf16, a.io_bf16 = slope, out_div, 1, 3
     rc = _hip.load().v2w_resblock2_stage_split_fwd(C.byref(a), _stream(ins[0]))
-    if rc == -2:
-        return False
-    _hip.check(rc, 'v2w_resblock2_stage_split_fwd (rb1)')
-    return True
+    return not _declined(rc, 'v2w_resblock2_stage_split_fwd (rb1)')
 
 
 def resblock2_stage_split(x, in_affine, branches, out, *, slope, out_div, bf16=False, io_bf16=0, post=None, up=None):
@@ -843,10 +826,7 @@ def resblock2_stage_split(x, in_affine, branches, out, *, slope, out_div, bf16=F
         a.post_w, a.post_b, a.post_out = post[0].data_ptr(), _hip.ptr(post[1]), post[2].data_ptr()
         a.post_k, a.post_slope = post[3], post[4]
     rc = _hip.load().v2w_resblock2_stage_split_fwd(C.byref(a), _stream(x))
-    if rc == -2:
-        return False
-    _hip.check(rc, 'v2w_resblock2_stage_split_fwd')
-    return True
+    return not _declined(rc, 'v2w_resblock2_stage_split_fwd')
 
 
 def branch_convs_bf16(mode, ins, in_affine, wps, biases, outs, ks, dils, *, slope, out_div=0.0):
@@ -869,10 +849,7 @@ def branch_convs_bf16(mode, ins, in_affine, wps, biases, outs, ks, dils, *, slop
     a.nbr, a.mode, a.B, a.C, a.L = n, mode, B, Cc, L
     a.slope, a.out_div = slope, out_div
     rc = _hip.load().v2w_branch_convs_bf16_fwd(C.byref(a), _stream(x))
-    if rc == -2:
-        return False
-    _hip.check(rc, 'v2w_branch_convs_bf16_fwd')
-    return True
+    return not _declined(rc, 'v2w_branch_convs_bf16_fwd')
 
 
 def resblock2_stage(x, in_affine, branches, out, *, slope, out_div, post=None, bwd=None, lengths=None, len_mul=1):
@@ -910,10 +887,7 @@ def resblock2_stage(x, in_affine, branches, out, *, slope, out_div, post=None, b
         rc = _hip.load().v2w_resblock2_stage_fwd_len(C.byref(a), _len_ptr(lengths, len_mul), int(len_mul), _stream(x))
     else:
         rc = _hip.load().v2w_resblock2_stage_fwd(C.byref(a), _stream(x))
-    if rc == -2:
-        return False
-    _hip.check(rc, 'v2w_resblock2_stage_fwd')
-    return True
+    return not _declined(rc, 'v2w_resblock2_stage_fwd')
 
 
 def resblock2_stage_wino(x, in_affine, branches, out, *, slope, out_div, lengths=None, len_mul=1):
@@ -935,10 +909,7 @@ def resblock2_stage_wino(x, in_affine, branches, out, *, slope, out_div, lengths
         rc = _hip.load().v2w_resblock2_stage_wino_fwd_len(C.byref(a), _len_ptr(lengths, len_mul), int(len_mul), _stream(x))
     else:
         rc = _hip.load().v2w_resblock2_stage_wino_fwd(C.byref(a), _stream(x))
-    if rc == -2:
-        return False
-    _hip.check(rc, 'v2w_resblock2_stage_wino_fwd')
-    return True
+    return not _declined(rc, 'v2w_resblock2_stage_wino_fwd')
 
 
 def resblock2_stage_wino_tile(B, Cc, L, ks, dil1s, dil2s) -> int:
@@ -975,10 +946,7 @@ def resblock2_stage_small(x, in_affine, branches, out, *, slope, out_div):
     a.nk, a.B, a.C, a.L = len(branches), B, Cc, L
     a.slope = slope; a.out_div = out_div
     rc = _hip.load().v2w_resblock2_stage_small_fwd(C.byref(a), _stream(x))
-    if rc == -2:
-        return False
-    _hip.check(rc, 'v2w_resblock2_stage_small_fwd')
-    return True
+    return not _declined(rc, 'v2w_resblock2_stage_small_fwd')
 
 
 def wgrad(x, dy, *, k, dil=1, u=1, slope=1.0, x_affine=None, out=None):
