@@ -336,7 +336,7 @@ int v2w_resblock2_stage_split_config(const v2w_stage_split_args* a);
 /* Rows of up_stats_part a call with the fused upsampler (up_u != 0) fills; <= 0: that call would not run fused.  Host-only, as above. */
 int v2w_resblock2_stage_up_tiles(const v2w_stage_split_args* a);
 
-/* ---- the residual convolutions of a WIDE ResBlock2 stage (C % 64 == 0) on bf16 tensors (BASELINE configs[2]: bf16 compute / fp32
+/* ---- the residual convolutions of a WIDE ResBlock2 stage (C = 64 or 128) on bf16 tensors (BASELINE configs[2]: bf16 compute / fp32
  * accumulate, bf16 activation storage), one launch per conv position of the block instead of one per branch group
  * (csrc/v2w_conv_bf16_res.hip; models.py:135-141 with ResBlock2.forward, models.py:65-70, inlined):
  *   mode 0  t1_j = x + conv_{k_j,dil_j}(lrelu(x)) + bias_j  for j < nbr, x = in_a * in[0] + in_s (per (b, c); NULL: x = in[0]):
@@ -344,8 +344,11 @@ int v2w_resblock2_stage_up_tiles(const v2w_stage_split_args* a);
  *   mode 1  out[0] = ( sum_j [ in[j] + conv_{k_j,dil_j}(lrelu(in[j])) + bias_j ] ) / out_div   (out_div == 0: no division):
  *           one accumulator across the branches, nothing but out[0] is written.
  * in / out are bf16 (B, C, L) tensors, 16-byte aligned, L % 4 == 0; wps[j] = the fragments of v2w_pack_bf16 / v2w_split_pack_batch of
- * the (k_j, C, C) layer; k odd, dil * (k - 1) / 2 <= 32.  The residual is rebuilt from the staged (activated, bf16) operand: exact for
- * values >= 0, to 2^-9 relative below.  V2W_E_SHAPE: shape not served (the caller issues the per-layer launches instead). */
+ * the (k_j, C, C) layer; k odd.  Served: C % 64 == 0 whose resident tile - every channel of 256 positions and the largest halo
+ * h = max_j dil_j (k_j - 1) / 2 of the launch - fits the LDS twice per CU: C = 64 with h <= 32 and C = 128 with h <= 24; C >= 192 is not.
+ * in_a and in_s come together (both or neither, in either mode).  The residual is rebuilt from the staged (activated, bf16) operand: exact
+ * for values >= 0, to 2^-9 relative below.  V2W_E_ARG: a NULL tensor or weight pointer of a branch in use, half an affine, nbr outside
+ * 1 .. 3, a mode other than 0 / 1, slope <= 0.  V2W_E_SHAPE: shape not served (the caller issues the per-layer launches instead). */
 typedef struct {
     const void* in[3];
     const float* in_a; const float* in_s;

@@ -323,11 +323,12 @@ def dispatch(c):
 # Transposed conv on this kernel: the generator's (k, u) = (11, 5), (8, 4), (4, 2) and (9, 3); rows = C_out * UP on each of the three
 # tiles; L = 1, around one tile width and past two; VEC off by L % 4 != 0 or an unaligned `in`; the general epilogue by an unaligned
 # `out`; with and without stats_part.  bf16 tensors at u = 3, which the resident-tile kernel does not take.
-def convt(id, tile, *, k, u, B, ci, co, L, io=0, vec=None, rc=OK, stats=True, in_offb=0, out_offb=0, slope=0.1):
+def convt(id, tile, *, k, u, B, ci, co, L, io=0, vec=None, rc=OK, stats=None, in_offb=0, out_offb=0, slope=0.1):
+    """stats: whether the record carries stats_part; None: fp32 records do, bf16 records (tests/bf16res_cases.py passes True) do not."""
     vec = (L % 4 == 0 and in_offb == 0) if vec is None else vec
     cfg = tile + (32, vec, 2, io == 3, io == 3) if rc == OK else None
     return _case(id, [kernel_name(cfg)] if rc == OK else [], rc, op='convt', tile=tile, cfg=cfg, k=k, u=u, B=B, ci=ci, co=co, L=L, io=io,
-                 stats=stats and io == 0, in_offb=in_offb, out_offb=out_offb, slope=slope, n=ceil_div(k, u) * ci + 2,
+                 stats=(io == 0) if stats is None else bool(stats), in_offb=in_offb, out_offb=out_offb, slope=slope, n=ceil_div(k, u) * ci + 2,
                  big=B * co * L * u * ci * ceil_div(k, u) > 1 << 24)
 
 

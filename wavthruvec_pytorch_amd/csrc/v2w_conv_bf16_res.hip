@@ -1,4 +1,4 @@
-// The residual convolutions of a WIDE ResBlock2 stage (C = 64 / 128) on bf16 tensors, one launch per conv position of the block
+// The residual convolutions of a WIDE ResBlock2 stage (C = 64 with halos <= 32, C = 128 with halos <= 24: launch_res) on bf16 tensors, one launch per conv position of the block
 // instead of one (merged) launch per branch group - BASELINE configs[2] ("bf16 compute / fp32 accumulate", bf16 activation storage):
 //
 //   mode 0  "first convs":   t1_j = x + conv_{k_j,d1_j}(lrelu(x)) + b1_j   for every branch j, x = a*xr + s (the folded CondBN affine)
@@ -432,11 +432,14 @@ extern "C" int v2w_branch_convs_bf16_fwd(const v2w_branch_convs_args* a, void* s
     if (!a) return V2W_E_ARG;
     if (a->nbr < 1 || a->nbr > V2W_RS_MAXB || (a->mode != 0 && a->mode != 1)) return V2W_E_ARG;
     if (a->B <= 0 || a->C <= 0 || a->L <= 0 || !(a->slope > 0.f)) return V2W_E_ARG;
+    if ((a->in_a == nullptr) != (a->in_s == nullptr)) return V2W_E_ARG;   // the kernel reads in_s whenever in_a is set; an in_s alone would be dropped
     auto al16 = [](const void* x) { return (reinterpret_cast<uintptr_t>(x) & 15) == 0; };
     for (int j = 0; j < a->nbr; ++j) {
         if (!a->wps[j] || a->k[j] < 1 || a->dil[j] < 1) return V2W_E_ARG;
         if ((a->k[j] & 1) == 0) return V2W_E_SHAPE;
-        if (a->mode == 0 ? (!a->out[j] || !al16(a->out[j])) : (!a->in[j] || !al16(a->in[j]))) return a->mode == 0 && !a->out[j] ? V2W_E_ARG : V2W_E_SHAPE;
+        const void* const t = a->mode == 0 ? a->out[j] : a->in[j];     // the tensor every branch has of its own
+        if (!t) return V2W_E_ARG;
+        if (!al16(t)) return V2W_E_SHAPE;
     }
     if (!a->in[0] || !a->out[0]) return V2W_E_ARG;
     if (!al16(a->in[0]) || !al16(a->out[0])) return V2W_E_SHAPE;
