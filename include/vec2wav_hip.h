@@ -1079,6 +1079,53 @@ int v2w_sn_step(const v2w_sn_desc* descs_dev, int n, int training, const v2w_sn_
 int v2w_sn_bwd(const v2w_sn_desc* descs_dev, int n, const v2w_sn_grids* g, const float* keep, const float* const* dwf, float* const* dw,
                void* ws, long long ws_bytes, void* stream);
 
+/* ---- Sample-rate conversion and peak normalisation (ABI v35, additive): the two ends of the audio path.  The reference reads every training
+ * target through librosa.load(path, sr=16000) and normalize(audio) * 0.95 on a host core (vec2wav/dataset.py:16-20,133); a 16 kHz generator's
+ * output wants 44.1 or 48 kHz for playback.  Both are one band-limited rational-ratio resampler, here the polyphase form of
+ * torchaudio.functional.resample's Hann-windowed sinc (lowpass_filter_width lpw, rolloff):
+ *
+ *   g = gcd(orig, new), M = orig / g (input step), L = new / g (phases), base = min(M, L) * rolloff
+ *   t(p, k) = (k / M - p / L) * base;   h[p][k] = sinc(pi t) cos^2(pi t / (2 lpw)) base / M  where |t| < lpw, else 0
+ *   y[q L + p] = sum_k h[p][k] x[q M + k],  x = 0 outside [0, n);   N = ceil(L n / M) outputs for n inputs
+ *
+ * Per phase the non-zero taps are one run of at most NT = ceil(2 lpw M / base): the caller hands the run's first index k0[p] (int32, L of
+ * them) and the table h (fp32, (L, NT) row-major, a shorter run padded with 0 at its end).  k0 must not decrease with p and
+ * k0[L - 1] - k0[0] <= M (true of the formula: k0[p] = floor(M p / L - lpw M / base) + 1); taps that such a table would place outside the
+ * staged window read as 0.  34 multiply-adds per output at 441 : 160 against the 475 of the strided-conv form.
+ *
+ *   out[b][q L + p] = fma(h[p][NT - 1], x[..], ... fma(h[p][1], x[..], fma(h[p][0], x[b][q M + k0[p]], +0)))       fp32, tap order
+ *
+ * so |out - exact| <= (NT + 1) 2^-24 sum_j |h[p][j] x[..]|, and an output none of whose taps meets a non-zero sample is exactly 0.
+ * x is float32, or with in_i16 != 0 int16 PCM read as x / 32768 (exact).  Item b holds n_b = min(max(len[b], 0), Lin) samples (len: B int32
+ * on the device, NULL: every item Lin): out[b][0 .. N_b) is what the item alone gives, out[b][N_b .. Lout) is written as +0.0, and
+ * x[b][n_b ..] is never loaded.  M = L = NT = 1, h = {1}, k0 = {0} is the float32 copy of x (a -0.0 comes out +0.0) with the same per-item
+ * tail.  Offsets are 64-bit.  No atomics; the same bits from run to run.
+ *
+ * v2w_resample_plan (host only) fills g: `tile` outputs per workgroup of 256 threads - the largest of 4096, 2048, .. 256 whose LDS fits -,
+ * `tiles` = ceil(Lout / tile) per item, `grid` = B * tiles and `lds_bytes` =
+ *   4 * (L * (NT | 1) + L + ((tile - 1) / L + 2) * M + NT + 4)           (table rows at an odd pitch, k0, the input window, 4 floats)
+ * which must not exceed 64 KiB: V2W_E_SHAPE when it does at tile = 256, that is unless
+ *   L * ((NT | 1) + 1) + ((255 / L) + 2) * M + NT + 4 <= 16384
+ * (in short L * (NT + 2) + 2 M + 256 M / L below 16 Ki floats: 441 : 160 and 160 : 441 use 48 and 31 KiB; a ratio of two large coprime rates
+ * such as 16000 : 44101 does not fit), and when B * tiles passes 2^31 - 1.
+ *
+ * v2w_resample: one launch (resample_kernel).  peak_part != NULL: (B, tiles) floats, [b][tile] = the maximum of |out| over that tile (a
+ * plain store per workgroup).  V2W_E_ARG: x, y, h or k0 NULL, a pointer not aligned to its element, a size <= 0,
+ * Lout < ceil(L * Lin / M); the plan's V2W_E_SHAPE.  Nothing is launched on refusal.
+ *
+ * v2w_peak_scale: librosa.util.normalize(y) * peak per item, in place, one launch (peak_scale_kernel): m = max over the item's `parts`
+ * partials (exact in any order), s = peak / m, y[b][i] = y[b][i] * s - one division and one multiplication, |error| <= 2.5 * 2^-24 |y peak / m|
+ * with the float `peak` counted.  A row whose m is below FLT_MIN (or NaN) keeps its bits.  The partials are v2w_resample's, or any (B, parts)
+ * floats whose row maximum is the item's.  V2W_E_ARG: y or peak_part NULL or not 4-byte aligned, B, Lout or parts <= 0, peak not a
+ * finite positive float.  V2W_E_SHAPE: B * ceil(Lout / 4096) past 2^31 - 1. */
+typedef struct {
+    int32_t tile, tiles, grid, lds_bytes;
+} v2w_resample_grids;                /* 16 bytes; HOST memory, filled by v2w_resample_plan */
+int v2w_resample_plan(int M, int L, int NT, int B, int Lout, v2w_resample_grids* g);
+int v2w_resample(const void* x, int in_i16, float* y, int B, int Lin, int Lout, const float* h, const int32_t* k0, int M, int L, int NT,
+                 const int32_t* len, float* peak_part, void* stream);
+int v2w_peak_scale(float* y, int B, int Lout, const float* peak_part, int parts, float peak, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -175,6 +175,12 @@ class SnGrids(C.Structure):
 
 SN_MAX_LAYERS = 64
 
+
+class ResampleGrids(C.Structure):
+    """include/vec2wav_hip.h `v2w_resample_grids`: what v2w_resample_plan fills (host memory)."""
+    _fields_ = [('tile', C.c_int32), ('tiles', C.c_int32), ('grid', C.c_int32), ('lds_bytes', C.c_int32)]
+
+
 # name -> (restype, argtypes); must list every symbol include/vec2wav_hip.h declares
 SIGNATURES = {
     'v2w_abi_version': (C.c_int, []),
@@ -316,6 +322,10 @@ SIGNATURES = {
     'v2w_sn_plan': (C.c_longlong, [C.POINTER(SnDesc), C.c_int, C.POINTER(SnGrids)]),
     'v2w_sn_step': (C.c_int, [_fp, C.c_int, C.c_int, C.POINTER(SnGrids), _fp, _fp, C.c_longlong, _fp]),
     'v2w_sn_bwd': (C.c_int, [_fp, C.c_int, C.POINTER(SnGrids), _fp, C.POINTER(_fp), C.POINTER(_fp), _fp, C.c_longlong, _fp]),
+    # sample-rate conversion and peak normalisation: x, y, h, k0, len, peak_part are DEVICE memory, the grids HOST memory
+    'v2w_resample_plan': (C.c_int, [C.c_int] * 5 + [C.POINTER(ResampleGrids)]),
+    'v2w_resample': (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp]),
+    'v2w_peak_scale': (C.c_int, [_fp, C.c_int, C.c_int, _fp, C.c_int, C.c_float, _fp]),
 }
 
 # entry points that LAUNCH (their last argument is the stream); the others are host-only queries.  schedule.Recorder tapes the former.

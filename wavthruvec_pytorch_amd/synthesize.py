@@ -16,6 +16,10 @@ This closes the text2vec -> vec2wav hand-off with the reference's own wire forma
 Several utterances: `--feat a.npy b.npy c.npy --spk-emb s.pth --out wavs/ --batch 8` writes wavs/a.wav, wavs/b.wav, wavs/c.wav (`--out` is a
 directory; one `--spk-emb` for all files or one per file).  `--batch N` puts up to N utterances, sorted by length, into one padded forward
 with per-item lengths (Generator.forward(lengths=...), precision 'f32'); every file gets the samples - and the noise - of its own single run.
+
+`--sampling-rate` is the MODEL's rate (what the generator was trained at; it goes into the wav header).  `--out-rate R` delivers the audio at
+R Hz instead: every utterance is resampled on the GPU from `--sampling-rate` to R (audio.resample, the whole ragged batch in one call) and the
+header carries R.  Without it nothing changes.
 """
 from __future__ import annotations
 
@@ -130,6 +134,19 @@ def synthesize_many(g: Generator, feats: Sequence[torch.Tensor], spks: Sequence[
     return out
 
 
+@torch.no_grad()
+def resample_many(ys: Sequence[torch.Tensor], sampling_rate: int, out_rate: int) -> List[torch.Tensor]:
+    """(1, 1, N_i) waveforms at `sampling_rate` -> (1, 1, ceil(N_i * out_rate / sampling_rate)) at `out_rate`: one zero-padded batch with
+    per-item lengths through one audio.resample call."""
+    from . import audio
+    ns = [int(y.shape[-1]) for y in ys]
+    batch = ys[0].new_zeros((len(ys), max(ns)))
+    for i, y in enumerate(ys):
+        batch[i, :ns[i]] = y.reshape(-1)
+    out = audio.resample(batch, sampling_rate, out_rate, lengths=ns)
+    return [out[i:i + 1, :audio.resampled_length(n, sampling_rate, out_rate)].unsqueeze(0) for i, n in enumerate(ns)]
+
+
 def output_paths(feats: Sequence[str], out: str) -> List[str]:
     """`--out` is the .wav of a single `--feat`, else a directory that receives <feat name without .npy>.wav per file."""
     if len(feats) == 1:
@@ -149,7 +166,11 @@ def parse_args(argv=None):
     ap.add_argument('--batch', type=int, default=1, help='most utterances per forward (per-item lengths, precision f32); default 1')
     ap.add_argument('--num-wv-feat', type=int, default=None, help='latent width (default: taken from the .npy)')
     ap.add_argument('--resblock', default=1, help="'1' selects ResBlock1 (string!), anything else ResBlock2 (reference default)")
-    ap.add_argument('--sampling-rate', type=int, default=16000)
+    ap.add_argument('--sampling-rate', type=int, default=16000,
+                    help="the MODEL's sampling rate (the generator is a 16 kHz model); written into the wav header unless --out-rate is given")
+    ap.add_argument('--out-rate', type=int, default=None,
+                    help='resample every utterance on the GPU from --sampling-rate to this rate and write it into the wav header (default: '
+                         'absent, the audio is written at the model rate)')
     ap.add_argument('--remove-weight-norm', action='store_true')
     ap.add_argument('--seed', type=int, default=1234)
     ap.add_argument('--device', default='cuda:0')
@@ -160,6 +181,8 @@ def parse_args(argv=None):
         ap.error('--spk-emb: one file for all --feat files or one per file')
     if args.batch < 1:
         ap.error('--batch must be >= 1')
+    if args.out_rate is not None and args.out_rate < 1:
+        ap.error('--out-rate must be >= 1')
     return args
 
 
@@ -176,9 +199,12 @@ def main(argv=None) -> int:
     if len(outs) > 1:
         os.makedirs(args.out, exist_ok=True)
     ys = synthesize_many(g, feats, spks, seed=args.seed, batch=args.batch)
+    rate = args.sampling_rate
+    if args.out_rate is not None:
+        ys, rate = resample_many(ys, args.sampling_rate, args.out_rate), args.out_rate
     for path, y, feat in zip(outs, ys, feats):
-        write_wav(path, y, args.sampling_rate)
-        print(f'{path}: {y.shape[-1]} samples ({y.shape[-1] / args.sampling_rate:.2f} s) from {feat.shape[-1]} frames')
+        write_wav(path, y, rate)
+        print(f'{path}: {y.shape[-1]} samples ({y.shape[-1] / rate:.2f} s) from {feat.shape[-1]} frames')
     return 0
 
 
