@@ -137,11 +137,11 @@ def _beside(side, reads):
 
 # The merged ResBlock2 form of one stage, as its input-gradient launches and its weight-gradient step read and write it:
 #   dxs, unit      dL/d(stage output); every branch receives dr = dxs / nk through the per-(b, c) affine `unit` = (1 / nk, 0)
-#   rbs, names     the branches and their parameter-name prefixes;  order: the branch indices, heaviest kernel size first
+#   stg            the stage's record (forward_plan.Stage): the branches, their parameter-name prefixes, the heaviest-first order
 #   t1s, xr, aff   what the forward kept: t1_j, and the stage input x' = a * xr + s
 #   w2s, w1s       kernel and weights of every branch's conv2 / conv1 input-gradient conv (`_dgrad_weights`)
 #   dt1s, dx       written: dL/d(t1_j), and dL/dx' summed over the branches
-_Rb2Stage = namedtuple('_Rb2Stage', 'dxs unit rbs names order t1s xr aff w2s w1s dt1s dx')
+_Rb2Stage = namedtuple('_Rb2Stage', 'dxs unit stg t1s xr aff w2s w1s dt1s dx')
 
 
 def _dgrad_weights(sv, nm, use_bf):
@@ -161,19 +161,19 @@ def _rb2_dgrad_one_kernel(s):
     `_rb2_dgrad_three_launches` returns, or None (nothing launched) when the kernel does not take the stage."""
     B, C, Lo = s.dxs.shape
     p2, p1 = [q.get('wp') for q in s.w2s], [q.get('wp') for q in s.w1s]
-    ks, dd2, dd1 = [rb.kernel_size for rb in s.rbs], [rb.convs[1].dilation for rb in s.rbs], [rb.convs[0].dilation for rb in s.rbs]
+    ks, dd2, dd1 = s.stg.ks, s.stg.dil2s, s.stg.dil1s          # (the kernel takes conv2's dilations first)
     ntile = hipops.resblock2_stage_bwd_rows(B, C, Lo, ks, dd2, dd1)
     if not ntile or any(q is None for q in p1 + p2):       # (the kernel reads fp32 fragment streams only)
         return None
-    rsp = [torch.empty((ntile * C * 2,), device=s.dxs.device) for _ in s.rbs]       # (tile, wave) channel sums of dt1_j
-    branches = [dict(wp1=p2[j], b1=None, wp2=p1[j], b2=None, k=ks[j], dil1=dd2[j], dil2=dd1[j]) for j in range(len(s.rbs))]
+    rsp = [torch.empty((ntile * C * 2,), device=s.dxs.device) for _ in s.stg.rbs]       # (tile, wave) channel sums of dt1_j
+    branches = [dict(wp1=p2[j], b1=None, wp2=p1[j], b2=None, k=ks[j], dil1=dd2[j], dil2=dd1[j]) for j in range(len(s.stg.rbs))]
     ok = hipops.resblock2_stage(s.dxs, s.unit, branches, s.dx, slope=1.0, out_div=0.0, bwd=(s.t1s, s.dt1s, s.xr, s.aff, LRELU_SLOPE, rsp))
     return (ntile, rsp) if ok else None
 
 
 def _rb2_dconv1(s, j, out, **extra):
     """t1 = x' + conv1(lrelu x') + b1, x' = a*xr + s   ->   dx' = sum_j dt1_j + lrelu'(x') * conv(dt1_j; W1^T flipped)"""
-    return (s.dt1s[j], None, None, out, dict(k=s.rbs[j].kernel_size, dil=s.rbs[j].convs[0].dilation, slope=1.0, res=s.dt1s[j], mask=(s.xr, s.aff),
+    return (s.dt1s[j], None, None, out, dict(k=s.stg.rbs[j].kernel_size, dil=s.stg.rbs[j].convs[0].dilation, slope=1.0, res=s.dt1s[j], mask=(s.xr, s.aff),
                                              mask_slope=LRELU_SLOPE, **s.w1s[j], **extra))
 
 
@@ -182,17 +182,17 @@ def _rb2_dgrad_three_launches(s, rowsum):
     0 .. nk-2 in one launch and the last branch adding them (heaviest kernel size first), so the tile shape is chosen for three problems' worth
     of tiles instead of one.  Writes s.dt1s and s.dx; returns (ntile, [per branch: the per-tile channel sums of dt1_j - conv1_j's bias gradient,
     an epilogue of the f32 tile kernel - or None]), ntile 0 when the launch leaves none (`rowsum` False, or Lo % 4 != 0)."""
-    (B, C, Lo), nk = s.dxs.shape, len(s.rbs)
+    (B, C, Lo), nk = s.dxs.shape, len(s.stg.rbs)
     # (the launch's tile shape follows its WIDEST halo - the wide-halo tile variants are other shapes: probe with that branch)
-    kw, dw = max(((rb.kernel_size, rb.convs[1].dilation) for rb in s.rbs), key=lambda kd: kd[1] * (kd[0] - 1))
+    kw, dw = max(((rb.kernel_size, rb.convs[1].dilation) for rb in s.stg.rbs), key=lambda kd: kd[1] * (kd[0] - 1))
     ntile = hipops.conv_rowsum_tiles(B, nk, C, C, Lo, kw, dw) if Lo % 4 == 0 and rowsum else 0
     rsp = [torch.empty((ntile * C * 2,), device=s.dxs.device) if ntile else None for _ in range(nk)]
     # r_j = t1 + conv2(lrelu(t1)) + b2   ->   dt1 = dr + lrelu'(t1) * conv(dr; W2^T flipped),  dr = dxs / nk
     hipops.conv1d_multi([(s.dxs, None, None, s.dt1s[j],
-                          dict(k=s.rbs[j].kernel_size, dil=s.rbs[j].convs[1].dilation, slope=1.0, in_affine=s.unit, res=s.dxs, res_affine=s.unit,
-                               mask=(s.t1s[j], None), mask_slope=LRELU_SLOPE, rowsum=rsp[j], **s.w2s[j])) for j in s.order])
+                          dict(k=s.stg.rbs[j].kernel_size, dil=s.stg.rbs[j].convs[1].dilation, slope=1.0, in_affine=s.unit, res=s.dxs, res_affine=s.unit,
+                               mask=(s.t1s[j], None), mask_slope=LRELU_SLOPE, rowsum=rsp[j], **s.w2s[j])) for j in s.stg.heavy_first])
     parts = [torch.empty_like(s.dxs) for _ in range(nk - 1)]
-    hipops.conv1d_multi([_rb2_dconv1(s, j, parts[j]) for j in s.order if j < nk - 1])
+    hipops.conv1d_multi([_rb2_dconv1(s, j, parts[j]) for j in s.stg.heavy_first if j < nk - 1])
     hipops.conv1d_multi([_rb2_dconv1(s, nk - 1, s.dx, add=parts)])
     return ntile, rsp
 
@@ -200,8 +200,8 @@ def _rb2_dgrad_three_launches(s, rowsum):
 def _rb2_branch_grads(s, j, db2, ntile, rsp, wgrad):
     """{name: gradient} of branch j's parameters from what the input-gradient launches left.  dr = dxs / nk is never materialised: conv2's
     weight gradient, linear in dr, is scaled afterwards, and `db2` (shared by the branches) is handed in."""
-    c1, c2 = s.rbs[j].convs
-    k, nm, nk = s.rbs[j].kernel_size, s.names[j], len(s.rbs)
+    c1, c2 = s.stg.rbs[j].convs
+    k, nm, nk = s.stg.rbs[j].kernel_size, s.stg.names[j], len(s.stg.rbs)
     B, C, Lo = s.dxs.shape
     g = {nm + '.convs.1.bias': db2}
     _wn_grads(g, nm + '.convs.1', c2, wgrad(s.t1s[j], s.dxs, k=k, dil=c2.dilation, slope=LRELU_SLOPE).mul_(1.0 / nk))
@@ -238,15 +238,16 @@ class _Walk:
         gen, ws, B, nk, dxs = self.gen, self.ws, self.B, self.gen.num_kernels, self.d
         xr, aff = ws[f'act.up{i}'], (ws[f'bn.a{i}'], ws[f'bn.s{i}'])
         C, Lo = xr.shape[1:]
-        rbs, names = [gen.resblocks[i * nk + j] for j in range(nk)], [f'resblocks.{i * nk + j}' for j in range(nk)]
+        stg = gen.stage_record(i)
+        rbs, names = stg.rbs, stg.names
         unit = (torch.full((B, C), 1.0 / nk, device=self.dev), torch.zeros((B, C), device=self.dev))
         # the merged launches run on ALGO_MFMA, which has no direct-kernel fallback: every gradient conv of every branch must have a
         # tile configuration at ITS kernel size and dilation (a wide halo, e.g. k = 11 with dilation 7, has none: per-branch path)
         merged = gen.precision in ('f32', 'bf16') and gen.algo == hipops.ALGO_AUTO and 1 < nk <= 3 \
-            and all(isinstance(rb, ResBlock2) for rb in rbs) \
+            and stg.is_rb2 \
             and all(hipops.conv_tile_config(B * nk, C, C, Lo, rb.kernel_size, c.dilation) is not None for rb in rbs for c in rb.convs)
         if merged:
-            return self._residual_merged(i, rbs, names, unit, xr, aff)
+            return self._residual_merged(stg, unit, xr, aff)
         dr = hipops.affine_apply(dxs, *unit, torch.empty_like(dxs))
         db2 = hipops.channel_sum(dr)
         dx = torch.empty_like(dxs)
@@ -255,15 +256,15 @@ class _Walk:
                           db_out=db2, dst=dx, accumulate=j > 0)
         self.d = dx
 
-    def _residual_merged(self, i, rbs, names, unit, xr, aff):
+    def _residual_merged(self, stg, unit, xr, aff):
         """ResBlock2 with the branches' launches merged: the input gradients by one of two variants, then one weight / bias gradient step."""
-        gen, nk, dxs = self.gen, len(rbs), self.d
+        gen, dxs, i, rbs, names, nk = self.gen, self.d, stg.i, stg.rbs, stg.names, len(stg.rbs)
         B, C, Lo = dxs.shape
         # the generator's bf16 arithmetic (precision = 'bf16': the reference under torch.autocast): the wide stages' gradient convs on the bf16
         # kernel the forward used, the narrow stages' on the exact fp32 tile kernel
         use_bf = gen.precision == 'bf16' and ((C >= gen.split_min_channels and hipops.split_supported(C, C)) or (C == 32 and Lo % 4 == 0)) \
             and all(rb.kernel_size >= 3 and (rb.kernel_size & 1) for rb in rbs)
-        s = _Rb2Stage(dxs, unit, rbs, names, sorted(range(nk), key=[rb.kernel_size for rb in rbs].__getitem__, reverse=True), [self.ws[f'act.t1_{i}_{j}'] for j in range(nk)], xr, aff,
+        s = _Rb2Stage(dxs, unit, stg, [self.ws[f'act.t1_{i}_{j}'] for j in range(nk)], xr, aff,
                       [_dgrad_weights(self.sv, nm + '.convs.1', use_bf) for nm in names], [_dgrad_weights(self.sv, nm + '.convs.0', use_bf) for nm in names],
                       [torch.empty_like(dxs) for _ in range(nk)], torch.empty_like(dxs))
         done = _rb2_dgrad_one_kernel(s) if C in gen.fuse_stage and C in (16, 32) and gen.fuse_stage_backward else None
@@ -271,7 +272,7 @@ class _Walk:
         # weight / bias gradients: nothing downstream waits for them - side stream, beside the next stage's gradient convs.  The LAST stage of
         # the walk (stage 0: the widest convs) leaves the side stream a backlog the main stream has nothing left to run beside (it waited
         # ~2.5 ms for it at the end of the backward): its heaviest branch's weight gradients go to the main stream
-        on_main = [s.order[0]] if i == 0 and nk > 1 else []
+        on_main = [s.stg.heavy_first[0]] if i == 0 and nk > 1 else []
         with _beside(self.side, [s.dxs, s.xr, *s.aff, *s.dt1s, *s.t1s, *[r for r in rsp if r is not None]]) as made:
             db2 = hipops.channel_sum(s.dxs) * (1.0 / nk)        # (a memory-bound pass)
             made.append(db2)

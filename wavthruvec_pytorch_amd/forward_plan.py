@@ -14,12 +14,15 @@ A forward that will be back-propagated (`save`) gets every intermediate in a fre
 from __future__ import annotations
 
 import contextlib
+import functools
+from collections import namedtuple
 
 import torch
 
 from . import hipops
 
 LRELU_SLOPE = 0.1  # models.py:10
+POST_SLOPE = 0.01  # models.py:143 (F.leaky_relu's default, in front of conv_post)
 _Z_CHANNEL = 128   # models.py:110
 
 
@@ -106,9 +109,42 @@ def wino_up_selected(wino_up, i, precision, algo, c_in, c_out, k, u, *, save=Fal
             and not save and not lengths and bool(stream))
 
 
-def _branches(rbs, names, wps):
-    return [dict(wps1=wps[nm + '.convs.0'], b1=rb.convs[0].bias.detach(), wps2=wps[nm + '.convs.1'], b2=rb.convs[1].bias.detach(),
-                 k=rb.kernel_size, dil1=rb.convs[0].dilation, dil2=rb.convs[1].dilation) for nm, rb in zip(names, rbs)]
+class Stage(namedtuple('Stage', 'i C rbs names')):
+    """Residual stage `i` of a generator (Generator.stage_record): its width, its num_kernels residual blocks and their parameter-name
+    prefixes - and what the planner, the weight fold and the backward derive from them.  Where a method takes `n`: None means the two convs
+    of a ResBlock2 (`convs.0`, `convs.1`), 0 .. 2 pair n of a ResBlock1 (`convs1.n`, `convs2.n`); `c` is 0 / 1, the conv of the pair."""
+    __slots__ = ()
+
+    def convs(self, c, n=None):
+        return [rb.convs[c] if n is None else (rb.convs1, rb.convs2)[c][n] for rb in self.rbs]
+
+    def dils(self, c, n=None):
+        return [m.dilation for m in self.convs(c, n)]
+
+    def pairs(self, c):
+        """(kernel size, dilation of conv c) per branch: what wino_fan_selected (c = 0) and wino_sum_selected (c = 1) take."""
+        return list(zip(self.ks, self.dils(c)))
+
+    def layer(self, j, c, n=None):
+        return f'{self.names[j]}.convs.{c}' if n is None else f'{self.names[j]}.convs{c + 1}.{n}'
+
+    def layers(self, cs=(0, 1), n=None):
+        return {self.layer(j, c, n) for j in range(len(self.rbs)) for c in cs}
+
+    is_rb2 = property(lambda self: all(hasattr(rb, 'convs') for rb in self.rbs))     # (ResBlock2: `convs`; ResBlock1: `convs1` / `convs2`)
+    ks = property(lambda self: [rb.kernel_size for rb in self.rbs])
+    dil1s = property(lambda self: self.dils(0))
+    dil2s = property(lambda self: self.dils(1))
+    blocks = property(lambda self: list(zip(self.ks, self.dil1s, self.dil2s)))       # (k, dil1, dil2) per branch: what stage_wino_selected takes
+    is_std = property(lambda self: self.is_rb2 and self.blocks == STAGE_WINO_BLOCKS)
+    # the branch indices, heaviest kernel size first: the order of the problems of a merged launch, forward and backward
+    heavy_first = property(lambda self: sorted(range(len(self.rbs)), key=lambda j: -self.rbs[j].kernel_size))
+
+    def branches(self, w, key1, key2, n=None):
+        """The per-branch dicts the stage and pair wrappers of hipops take: the two convs' weights out of `w` under `key1` / `key2`, b1, b2, k, dil1, dil2."""
+        return [{key1: w[self.layer(j, 0, n)], 'b1': c1.bias.detach(), key2: w[self.layer(j, 1, n)], 'b2': c2.bias.detach(),
+                 'k': rb.kernel_size, 'dil1': c1.dilation, 'dil2': c2.dilation}
+                for j, (rb, c1, c2) in enumerate(zip(self.rbs, self.convs(0, n), self.convs(1, n)))]
 
 
 class ForwardPlanner:
@@ -231,6 +267,10 @@ class ForwardPlanner:
         self.wps32 = {}
         self.up_done = None        # rows of bn.part{i} when the kernel of stage i - 1 already ran ups[i] (fuse_up)
 
+    @functools.cached_property
+    def stg(self):      # the record of the stage being planned: `stage` sets it, a planner stood up at one step of a stage builds it on first use
+        return self.g.stage_record(self.stage_i)
+
     def buf(self, name, shape, dtype=torch.float32):
         return self.g._buf(name, shape, dtype=dtype, device=self.dev)
 
@@ -240,6 +280,12 @@ class ForwardPlanner:
         if self.lens is None:
             return {}
         return dict(lengths=self.lens, len_mul=self.lmul if mul is None else mul)
+
+    def lkw_out(self):       # `lkw` at the current stage's OUTPUT rate: the residual convs run behind its upsampler
+        return self.lkw(self.lmul * self.g.ups[self.stage_i].stride)
+
+    def wino_streams(self, kind='wpw'):     # {layer: Winograd stream} the weight fold left under 'wpw' (Generator.wino), 'wpw_stage', 'wpw_sum', 'wpw_up'
+        return self.g._fold_key.get(kind, {})
 
     # ---------------------------------------------------------------------------------------------------------------------------
     def weights(self):
@@ -305,7 +351,7 @@ class ForwardPlanner:
             return dict(algo=hipops.ALGO_BF16 if g.precision == 'bf16' else hipops.ALGO_SPLIT, wps=self.wps[nm])
         if self.st:
             raise RuntimeError(f'bf16 storage: layer {nm} has no bf16 kernel (set generator.bf16_storage = False)')
-        wpw = g._fold_key.get('wpw', {}).get(nm)
+        wpw = self.wino_streams().get(nm)
         if wpw is not None:     # the Winograd F(2,3) kernel, with this f32 MFMA stream for a launch it declines (hipops.conv1d_wino_multi)
             return dict(algo=self.algo, wp=self.wp[nm], wpw=wpw)
         return dict(algo=self.algo, wp=self.wp[nm])
@@ -319,7 +365,7 @@ class ForwardPlanner:
         self.L = self.T
 
     def stage(self, i):
-        self.stage_i = i
+        self.stage_i, self.stg = i, self.g.stage_record(i)
         up = self.g.ups[i]
         self.C, self.Lo = up.out_channels, self.L * up.stride
         self.xr = self.buf(f'act.up{i}', (self.B, self.C, self.Lo), dtype=self.adt)
@@ -381,7 +427,7 @@ class ForwardPlanner:
         """(Winograd stream, position tiles) when upsampler i runs in the upsampler form of the Winograd kernel (wino_up_selected, the library
         takes the shape, and - the one-conv kernel's rule - the launch has more than 128 workgroups), else (None, 0): today's launch."""
         g, up = self.g, self.g.ups[i]
-        wpw = g._fold_key.get('wpw_up', {}).get(f'ups.{i}')
+        wpw = self.wino_streams('wpw_up').get(f'ups.{i}')
         if (self.st or self.up_done is not None or f'ups.{i}' in self.wps
                 or not wino_up_selected(g.wino_up, i, g.precision, self.algo, up.in_channels, up.out_channels, up.kernel_size, up.stride,
                                         save=self.save is not None, lengths=self.lens is not None, stream=wpw is not None)):
@@ -429,18 +475,14 @@ class ForwardPlanner:
     # ---------------------------------------------------------------------------------------------------------------------------
     def residual(self, i):
         """K6 / K7: the num_kernels residual blocks read the same x = a * xr + s; their mean is the next input (models.py:133-141)."""
-        from .models import ResBlock2
-        g, nk = self.g, self.nk
-        self.rbs = [g.resblocks[i * nk + j] for j in range(nk)]
-        self.names = [f'resblocks.{i * nk + j}' for j in range(nk)]
+        g, nk, stg = self.g, self.nk, self.stg
         # a back-propagated forward in the bf16 arithmetic (fp32 tensors): the 32-channel stage's convs layer by layer on the bf16 kernel too
         # (32 x 256 tiles; fragments packed here from the folded weights - the arena holds this stage's in the fused kernel's unit order)
         self.wps32 = {}
         if (self.save is not None and g.precision == 'bf16' and not self.st and self.C == 32 and self.Lo % 4 == 0 and self.algo == hipops.ALGO_AUTO
-                and all(isinstance(rb, ResBlock2) and rb.kernel_size >= 3 and rb.kernel_size % 2 == 1 for rb in self.rbs)):
-            for nm in self.names:
-                for c in (0, 1):
-                    self.wps32[f'{nm}.convs.{c}'] = hipops.pack_split(self.wf[f'{nm}.convs.{c}'], bf16=True)
+                and stg.is_rb2 and all(k >= 3 and k % 2 == 1 for k in stg.ks)):
+            for nm in [stg.layer(j, c) for j in range(nk) for c in (0, 1)]:
+                self.wps32[nm] = hipops.pack_split(self.wf[nm], bf16=True)
         if not (self.algo != hipops.ALGO_DIRECT and nk <= 3):
             return self.residual_serial(i)
         B, C, Lo = self.B, self.C, self.Lo
@@ -449,11 +491,10 @@ class ForwardPlanner:
         # ((r0 + r1) + r2) / nk.
         self.t1s = [self.buf(f'act.t1_{i}_{j}', (B, C, Lo), dtype=self.adt) for j in range(nk)]
         self.outs = [self.buf(f'act.o_{i}_{j}', (B, C, Lo), dtype=self.adt) for j in range(nk - 1)] + [self.xs]
-        self.heavy_first = sorted(range(nk), key=lambda j: -self.rbs[j].kernel_size)
-        if not isinstance(self.rbs[0], ResBlock2):
+        if not stg.is_rb2:
             return self.residual1(i)
-        self.all_wps = all(f'{nm}.convs.{c}' in self.wps for nm in self.names for c in (0, 1))
-        self.all_wp = all(self.wp.get(f'{nm}.convs.{c}') is not None for nm in self.names for c in (0, 1))
+        self.all_wps = all(nm in self.wps for nm in stg.layers())
+        self.all_wp = all(self.wp.get(nm) is not None for nm in stg.layers())
         for cand in (self.rb2_stage_with_upsampler, self.rb2_narrow_stage_split, self.rb2_wide_stage_bf16, self.rb2_stage_f32,
                      self.rb2_stage_small, self.rb2_pairs, self.rb2_branch_convs_bf16, self.rb2_layers):
             if cand(i):
@@ -462,11 +503,9 @@ class ForwardPlanner:
                 raise RuntimeError('bf16 storage: the fused narrow-stage kernel did not take this shape (set generator.bf16_storage = False)')
 
     def launch(self, tag_sfx, probs):
-        probs = [probs[j] for j in self.heavy_first if j in probs]
-        if self.lens is not None:      # (the residual convs run at the stage's output rate)
-            lk = self.lkw(self.lmul * self.g.ups[self.stage_i].stride)
-            probs = [(j, (*pr[:4], {**pr[4], **lk})) for j, pr in probs]
-        tag = '+'.join(f'{self.names[j]}.{tag_sfx}' for j, _ in probs)
+        lk = self.lkw_out()
+        probs = [(j, (*pr[:4], {**pr[4], **lk})) for j, pr in (probs[j] for j in self.stg.heavy_first if j in probs)]
+        tag = '+'.join(f'{self.stg.names[j]}.{tag_sfx}' for j, _ in probs)
         self.timed(tag, hipops.conv1d_multi, [pr for _, pr in probs], splitk_ws=self.slab)
 
     def final_kw(self, j):
@@ -475,26 +514,33 @@ class ForwardPlanner:
         return dict(add=self.outs[:self.nk - 1], out_div=float(self.nk))
 
     def stage_tag(self, sfx=''):
-        return 'stage:' + '+'.join(f'{nm}.0&1' for nm in self.names) + sfx
+        return 'stage:' + '+'.join(f'{nm}.0&1' for nm in self.stg.names) + sfx
+
+    def branch_tag(self, c):       # tag of the one launch that runs conv c of every branch
+        return f'bconv{c}:' + '+'.join(f'{nm}.{c}' for nm in self.stg.names)
+
+    def post_args(self):
+        """The `post=` tuple of a stage kernel that runs the generator's tail (models.py:143-145) behind the last stage; y is allocated here."""
+        y = torch.empty((self.B, 1, self.Lo), device=self.dev, dtype=torch.float32)
+        return self.wf['conv_post'], self.g.conv_post.bias.detach(), y, self.g.conv_post.kernel_size, POST_SLOPE
 
     def rb2_stage_with_upsampler(self, i):
         """The stage with the NEXT stage's upsampler behind it in one kernel (bf16 tensors): xs is never written, the kernel stores
         act.up{i+1} and the BatchNorm partial sums of stage i + 1."""
-        g, C, B, Lo, rbs = self.g, self.C, self.B, self.Lo, self.rbs
+        g, C, B, Lo, stg = self.g, self.C, self.B, self.Lo, self.stg
         if not (self.st and g.fuse_up and i + 1 < self.ns and C >= 32 and (C >= 64 and g.fuse_wide_stage or C in self.fuse_stage)
                 and f'ups.{i + 1}' in self.wps and self.all_wps):
             return False
         nup = g.ups[i + 1]
         if not (nup.kernel_size == 2 * nup.stride and nup.stride in (2, 4) and nup.out_channels * 2 == C):
             return False
-        ntn = hipops.resblock2_stage_up_tiles(B, C, Lo, [rb.kernel_size for rb in rbs], [rb.convs[0].dilation for rb in rbs],
-                                              [rb.convs[1].dilation for rb in rbs], slope=LRELU_SLOPE,
+        ntn = hipops.resblock2_stage_up_tiles(B, C, Lo, stg.ks, stg.dil1s, stg.dil2s, slope=LRELU_SLOPE,
                                               up_k=nup.kernel_size, up_u=nup.stride, up_slope=LRELU_SLOPE)
         if not ntn:
             return False
         xr_n = self.buf(f'act.up{i + 1}', (B, nup.out_channels, Lo * nup.stride), dtype=self.adt)
         part_n = self.buf(f'bn.part{i + 1}', (ntn * nup.out_channels * 2,)) if self.training else None
-        ok = self.timed(self.stage_tag(f'+ups.{i + 1}'), hipops.resblock2_stage_split, self.xr, self.aff, _branches(rbs, self.names, self.wps), None,
+        ok = self.timed(self.stage_tag(f'+ups.{i + 1}'), hipops.resblock2_stage_split, self.xr, self.aff, stg.branches(self.wps, 'wps1', 'wps2'), None,
                         slope=LRELU_SLOPE, out_div=float(self.nk), bf16=True, io_bf16=3,
                         up=(self.wps[f'ups.{i + 1}'], nup.bias.detach(), xr_n, part_n, nup.kernel_size, nup.stride, LRELU_SLOPE))
         if ok:
@@ -504,19 +550,18 @@ class ForwardPlanner:
     def rb2_narrow_stage_split(self, i):
         """C = 32 / 16 on split / bf16 fragments: the whole residual section as one kernel - on bf16 tensors the last (16-channel) stage with
         the generator's tail behind it (models.py:143-145): the stage's output never leaves the chip, y is written instead."""
-        g, C, B, Lo, rbs = self.g, self.C, self.B, self.Lo, self.rbs
+        g, C = self.g, self.C
         if not (C in (16, 32) and C in self.fuse_stage and self.all_wps):
             return False
-        branches = _branches(rbs, self.names, self.wps)
+        branches = self.stg.branches(self.wps, 'wps1', 'wps2')
         # (the reference's block set and 7-tap tail: the weights-in-registers kernel takes them; any other set / k <= 9 tail would run on the
         # resident-tile template, measured slower than the two kernels: only with fuse_post = 'any')
-        std_set = [(rb.kernel_size, rb.convs[0].dilation, rb.convs[1].dilation) for rb in rbs] == [(3, 1, 3), (7, 1, 3), (11, 1, 3)]
         kp = g.conv_post.kernel_size
-        if self.st and g.fuse_post and i == self.ns - 1 and C == 16 and kp <= 9 and ((std_set and kp == 7) or g.fuse_post == 'any'):
-            y = torch.empty((B, 1, Lo), device=self.dev, dtype=torch.float32)
+        if self.st and g.fuse_post and i == self.ns - 1 and C == 16 and kp <= 9 and ((self.stg.is_std and kp == 7) or g.fuse_post == 'any'):
+            post = self.post_args()
             if self.timed(self.stage_tag('+conv_post'), hipops.resblock2_stage_split, self.xr, self.aff, branches, None, slope=LRELU_SLOPE,
-                          out_div=float(self.nk), bf16=True, io_bf16=3, post=(self.wf['conv_post'], g.conv_post.bias.detach(), y, kp, 0.01)):
-                self.y = y
+                          out_div=float(self.nk), bf16=True, io_bf16=3, post=post):
+                self.y = post[2]
                 return True
         return self.timed(self.stage_tag(), hipops.resblock2_stage_split, self.xr, self.aff, branches, self.xs, slope=LRELU_SLOPE,
                           out_div=float(self.nk), bf16=g.precision == 'bf16', io_bf16=3 if self.st else 0)
@@ -527,12 +572,8 @@ class ForwardPlanner:
         g = self.g
         if not (self.st and g.fuse_wide_stage and self.C >= 64 and self.all_wps):
             return False
-        return self.timed(self.stage_tag(), hipops.resblock2_stage_split, self.xr, self.aff, _branches(self.rbs, self.names, self.wps), self.xs,
+        return self.timed(self.stage_tag(), hipops.resblock2_stage_split, self.xr, self.aff, self.stg.branches(self.wps, 'wps1', 'wps2'), self.xs,
                           slope=LRELU_SLOPE, out_div=float(self.nk), bf16=True, io_bf16=3)
-
-    def _f32_branches(self, w, k1, k2):
-        return [dict(**{k1: w[nm + '.convs.0'], k2: w[nm + '.convs.1']}, b1=rb.convs[0].bias.detach(), b2=rb.convs[1].bias.detach(),
-                     k=rb.kernel_size, dil1=rb.convs[0].dilation, dil2=rb.convs[1].dilation) for nm, rb in zip(self.names, self.rbs)]
 
     def rb2_stage_f32(self, i):
         """The whole residual section of a narrow stage in ONE f32-MFMA kernel: x read once, t1_j in LDS, sum in registers - the last
@@ -540,21 +581,19 @@ class ForwardPlanner:
         g = self.g
         if self.st or not (self.C in self.fuse_stage and self.all_wp):
             return False
-        lk = self.lkw(self.lmul * g.ups[i].stride)
-        wpw = g._fold_key.get('wpw_stage', {})
-        if (all(f'{nm}.convs.{c}' in wpw for nm in self.names for c in (0, 1)) and stage_wino_selected(
-                g.wino_stage, g.precision, self.algo, self.C, [(rb.kernel_size, rb.convs[0].dilation, rb.convs[1].dilation) for rb in self.rbs])):
+        lk, stg, wpw = self.lkw_out(), self.stg, self.wino_streams('wpw_stage')
+        if all(nm in wpw for nm in stg.layers()) and stage_wino_selected(g.wino_stage, g.precision, self.algo, self.C, stg.blocks):
             # the Winograd F(2,3) form (its streams come from the same fold); a launch it declines runs on the direct form below
-            if self.timed(self.stage_tag(), hipops.resblock2_stage_wino, self.xr, self.aff, self._f32_branches(wpw, 'wpw1', 'wpw2'), self.xs,
+            if self.timed(self.stage_tag(), hipops.resblock2_stage_wino, self.xr, self.aff, stg.branches(wpw, 'wpw1', 'wpw2'), self.xs,
                           slope=LRELU_SLOPE, out_div=float(self.nk), **lk):
                 return True
-        branches = self._f32_branches(self.wp, 'wp1', 'wp2')
+        branches = stg.branches(self.wp, 'wp1', 'wp2')
         kp = g.conv_post.kernel_size
         if g.fuse_post and i == self.ns - 1 and self.C == 16 and kp <= 9 and kp % 2 == 1 and g.conv_post.in_channels == 16:
-            y = torch.empty((self.B, 1, self.Lo), device=self.dev, dtype=torch.float32)
+            post = self.post_args()
             if self.timed(self.stage_tag('+conv_post'), hipops.resblock2_stage, self.xr, self.aff, branches, None, slope=LRELU_SLOPE,
-                          out_div=float(self.nk), post=(self.wf['conv_post'], g.conv_post.bias.detach(), y, kp, 0.01), **lk):
-                self.y = y
+                          out_div=float(self.nk), post=post, **lk):
+                self.y = post[2]
                 return True
         return self.timed(self.stage_tag(), hipops.resblock2_stage, self.xr, self.aff, branches, self.xs, slope=LRELU_SLOPE, out_div=float(self.nk),
                           **lk)
@@ -562,38 +601,43 @@ class ForwardPlanner:
     def rb2_stage_small(self, i):
         """8 channels (the sixth stage of a x640 generator): below every MFMA tile - the whole section as one FMA kernel."""
         if not (self.C == 8 and 8 in self.fuse_stage and not self.st and self.nk <= 4
-                and all(self.wf.get(f'{nm}.convs.{c}') is not None for nm in self.names for c in (0, 1))):
+                and all(self.wf.get(nm) is not None for nm in self.stg.layers())):
             return False
-        return self.timed(self.stage_tag(), hipops.resblock2_stage_small, self.xr, self.aff, self._f32_branches(self.wf, 'wf1', 'wf2'), self.xs,
+        return self.timed(self.stage_tag(), hipops.resblock2_stage_small, self.xr, self.aff, self.stg.branches(self.wf, 'wf1', 'wf2'), self.xs,
                           slope=LRELU_SLOPE, out_div=float(self.nk))
 
     def launch_pairs(self, tag_sfx, probs):
         """probs: {j: dict}; the first nk - 1 branches in one launch, the summing branch after them."""
         nk, done = self.nk, True
-        for js in ([j for j in self.heavy_first if j in probs and j < nk - 1], [nk - 1] if nk - 1 in probs else []):
+        for js in ([j for j in self.stg.heavy_first if j in probs and j < nk - 1], [nk - 1] if nk - 1 in probs else []):
             if js and done:
-                done = self.timed('+'.join(f'{self.names[j]}.{tag_sfx}' for j in js), hipops.resblock_pair_multi, [probs[j] for j in js])
+                done = self.timed('+'.join(f'{self.stg.names[j]}.{tag_sfx}' for j in js), hipops.resblock_pair_multi, [probs[j] for j in js])
         return done
 
-    def fused_pair_ok(self, keys):
+    def fused_pair_ok(self, n=None):
         return (self.lens is None and not self.st and self.C in self.fuse_pairs and self.C in (16, 32)
-                and all(self.wp.get(f'{nm}.{c}') is not None for nm in self.names for c in keys))
+                and all(self.wp.get(nm) is not None for nm in self.stg.layers(n=n)))
+
+    def pair_problems(self, srcs, src_aff, dsts, res_mode, n=None, last=True):
+        """{j: problem dict of hipops.resblock_pair_multi}: both convs of a ResBlock2 branch (`n` None) or pair n of a ResBlock1 branch."""
+        return {j: dict(br, x=srcs[j], in_affine=src_aff, out=dsts[j], res_mode=res_mode, slope=LRELU_SLOPE, **(self.final_kw(j) if last else {}))
+                for j, br in enumerate(self.stg.branches(self.wp, 'wp1', 'wp2', n))}
 
     def rb2_pairs(self, i):
         """Narrow stages (C = 32 / 16): both convs of a pair in ONE kernel, the intermediate stays in LDS."""
-        if not self.fused_pair_ok(('convs.0', 'convs.1')):
+        if not self.fused_pair_ok():
             return False
-        rbs, names, wp = self.rbs, self.names, self.wp
-        return self.launch_pairs('0&1', {j: dict(x=self.xr, in_affine=self.aff, wp1=wp[names[j] + '.convs.0'], b1=rbs[j].convs[0].bias.detach(),
-                                                 wp2=wp[names[j] + '.convs.1'], b2=rbs[j].convs[1].bias.detach(), out=self.outs[j],
-                                                 k=rbs[j].kernel_size, dil1=rbs[j].convs[0].dilation, dil2=rbs[j].convs[1].dilation,
-                                                 res_mode=0, slope=LRELU_SLOPE, **self.final_kw(j)) for j in range(self.nk)})
+        return self.launch_pairs('0&1', self.pair_problems([self.xr] * self.nk, self.aff, self.outs, res_mode=0))
+
+    def conv_problems(self, c, srcs, dsts, extra, n=None):
+        """{j: (j, problem of hipops.conv1d_multi)}: conv c of every branch (`n`: of pair n of a ResBlock1); extra(j): the launch's other keywords."""
+        stg = self.stg
+        return {j: (j, (srcs[j], self.wf[stg.layer(j, c, n)], m.bias.detach(), dsts[j],
+                        dict(k=stg.ks[j], dil=m.dilation, slope=LRELU_SLOPE, **extra(j), **self.ck(stg.layer(j, c, n)))))
+                for j, m in enumerate(stg.convs(c, n))}
 
     def conv2_problems(self):
-        rbs, names = self.rbs, self.names
-        return {j: (j, (self.t1s[j], self.wf[names[j] + '.convs.1'], rbs[j].convs[1].bias.detach(), self.outs[j],
-                        dict(k=rbs[j].kernel_size, dil=rbs[j].convs[1].dilation, slope=LRELU_SLOPE, res=self.t1s[j],
-                             **self.ck(names[j] + '.convs.1'), **self.final_kw(j)))) for j in range(self.nk)}
+        return self.conv_problems(1, self.t1s, self.outs, lambda j: dict(res=self.t1s[j], **self.final_kw(j)))
 
     def launch_conv2(self, sfx, conv2):
         nk = self.nk
@@ -604,27 +648,23 @@ class ForwardPlanner:
     def rb2_branch_convs_bf16(self, i):
         """A wide stage on bf16 tensors the one-kernel form declined: the first convs of all branches in ONE launch (x staged once), then the
         second convs in one launch on one accumulator (v2w_branch_convs_bf16_fwd; o_j never written)."""
-        g, rbs, names = self.g, self.rbs, self.names
+        g, stg, nk = self.g, self.stg, self.nk
         if not (self.st and g.fuse_wide and self.C >= 64 and self.all_wps):
             return False
-        ks = [rb.kernel_size for rb in rbs]
-        if not self.timed('bconv0:' + '+'.join(f'{nm}.0' for nm in names), hipops.branch_convs_bf16, 0, [self.xr], self.aff,
-                          [self.wps[nm + '.convs.0'][0] for nm in names], [rb.convs[0].bias.detach() for rb in rbs], self.t1s,
-                          ks, [rb.convs[0].dilation for rb in rbs], slope=LRELU_SLOPE):
+        frags, biases = ([[self.wps[stg.layer(j, c)][0] for j in range(nk)] for c in (0, 1)],
+                         [[m.bias.detach() for m in stg.convs(c)] for c in (0, 1)])
+        if not self.timed(self.branch_tag(0), hipops.branch_convs_bf16, 0, [self.xr], self.aff, frags[0], biases[0], self.t1s,
+                          stg.ks, stg.dil1s, slope=LRELU_SLOPE):
             return False
-        if not self.timed('bconv1:' + '+'.join(f'{nm}.1' for nm in names), hipops.branch_convs_bf16, 1, self.t1s, None,
-                          [self.wps[nm + '.convs.1'][0] for nm in names], [rb.convs[1].bias.detach() for rb in rbs], [self.xs],
-                          ks, [rb.convs[1].dilation for rb in rbs], slope=LRELU_SLOPE, out_div=float(self.nk)):
+        if not self.timed(self.branch_tag(1), hipops.branch_convs_bf16, 1, self.t1s, None, frags[1], biases[1], [self.xs],
+                          stg.ks, stg.dil2s, slope=LRELU_SLOPE, out_div=float(nk)):
             self.launch_conv2('1', self.conv2_problems())
         return True
 
     def rb2_layers(self, i):
         """Layer by layer: conv1 of the three branches in ONE launch, conv2 of branches 0 .. nk - 2 in one, the last branch's conv2 adds them."""
-        rbs, names = self.rbs, self.names
         if not self.conv1_fan():
-            self.launch('0', {j: (j, (self.xr, self.wf[names[j] + '.convs.0'], rbs[j].convs[0].bias.detach(), self.t1s[j],
-                                      dict(k=rbs[j].kernel_size, dil=rbs[j].convs[0].dilation, slope=LRELU_SLOPE, in_affine=self.aff, res=self.xr,
-                                           res_affine=self.aff, **self.ck(names[j] + '.convs.0')))) for j in range(self.nk)})
+            self.launch('0', self.conv_problems(0, [self.xr] * self.nk, self.t1s, lambda j: dict(in_affine=self.aff, res=self.xr, res_affine=self.aff)))
         if not self.conv2_sum():
             self.launch_conv2('1', self.conv2_problems())
         return True
@@ -632,37 +672,34 @@ class ForwardPlanner:
     def conv1_fan(self):
         """The first convs of all branches as one Winograd launch that stages x once per tile (each t1_j the bits of its own launch); False:
         not selected or declined - rb2_layers then issues the multi-problem launch."""
-        g, rbs, names = self.g, self.rbs, self.names
-        wpw = g._fold_key.get('wpw', {})
-        if self.st or not wino_fan_selected(g.wino_fan, g.precision, self.algo, self.C, [(rb.kernel_size, rb.convs[0].dilation) for rb in rbs],
+        g, stg, wpw = self.g, self.stg, self.wino_streams()
+        if self.st or not wino_fan_selected(g.wino_fan, g.precision, self.algo, self.C, stg.pairs(0),
                                             save=self.save is not None, lengths=self.lens is not None,
-                                            streams=all(f'{nm}.convs.0' in wpw for nm in names)):
+                                            streams=all(nm in wpw for nm in stg.layers((0,)))):
             return False
-        return self.timed('bconv0:' + '+'.join(f'{nm}.0' for nm in names), hipops.conv1d_wino_fan, self.xr,
-                          [(wpw[f'{nm}.convs.0'], rb.convs[0].bias.detach(), t1, rb.kernel_size) for t1, nm, rb in zip(self.t1s, names, rbs)],
-                          dil=rbs[0].convs[0].dilation, slope=LRELU_SLOPE, in_affine=self.aff, res=self.xr, res_affine=self.aff,
+        return self.timed(self.branch_tag(0), hipops.conv1d_wino_fan, self.xr,
+                          [(wpw[stg.layer(j, 0)], c1.bias.detach(), self.t1s[j], stg.ks[j]) for j, c1 in enumerate(stg.convs(0))],
+                          dil=stg.dil1s[0], slope=LRELU_SLOPE, in_affine=self.aff, res=self.xr, res_affine=self.aff,
                           only_if_multi_wino=True)
 
     def conv2_sum(self):
         """The second convs of all branches as one Winograd launch on one accumulator (o_j never written); False: not selected or declined."""
-        g, rbs, names = self.g, self.rbs, self.names
+        g, stg = self.g, self.stg
         # (wino_sum: stages the fold gives streams of their own; wino_sum_wide: stages that reuse the streams `wino` folds - none without it)
         listed = tuple(g.wino_sum or ()) + tuple(g.wino_sum_wide or ())
-        if self.save is not None or self.st or not wino_sum_selected(listed, g.precision, self.algo, self.C,
-                                                                     [(rb.kernel_size, rb.convs[1].dilation) for rb in rbs]):
+        if self.save is not None or self.st or not wino_sum_selected(listed, g.precision, self.algo, self.C, stg.pairs(1)):
             return False
-        wpw = {**g._fold_key.get('wpw_sum', {}), **g._fold_key.get('wpw', {})}
-        if not all(f'{nm}.convs.1' in wpw for nm in names):
+        wpw = {**self.wino_streams('wpw_sum'), **self.wino_streams()}
+        if not all(nm in wpw for nm in stg.layers((1,))):
             return False
-        lk = self.lkw(self.lmul * g.ups[self.stage_i].stride)
-        return self.timed('bconv1:' + '+'.join(f'{nm}.1' for nm in names), hipops.conv1d_wino_sum,
-                          [(t1, wpw[f'{nm}.convs.1'], rb.convs[1].bias.detach(), rb.kernel_size) for t1, nm, rb in zip(self.t1s, names, rbs)],
-                          self.xs, dil=rbs[0].convs[1].dilation, slope=LRELU_SLOPE, out_div=float(self.nk), **lk)
+        return self.timed(self.branch_tag(1), hipops.conv1d_wino_sum,
+                          [(self.t1s[j], wpw[stg.layer(j, 1)], c2.bias.detach(), stg.ks[j]) for j, c2 in enumerate(stg.convs(1))],
+                          self.xs, dil=stg.dil2s[0], slope=LRELU_SLOPE, out_div=float(self.nk), **self.lkw_out())
 
     # ---------------------------------------------------------------------------------------------------------------------------
     def residual1(self, i):
         """ResBlock1 (models.py:37-44): three (dilated conv, conv) pairs per branch, merged over the branches."""
-        g, nk, B, C, Lo, rbs, names = self.g, self.nk, self.B, self.C, self.Lo, self.rbs, self.names
+        nk, B, C, Lo, stg = self.nk, self.B, self.C, self.Lo, self.stg
         xas = [self.buf(f'act.xa_{i}_{j}', (B, C, Lo), dtype=self.adt) for j in range(nk)]
         xbs = [self.buf(f'act.xb_{i}_{j}', (B, C, Lo), dtype=self.adt) for j in range(nk)]
         srcs, src_aff, t1s = [self.xr] * nk, self.aff, self.t1s
@@ -671,34 +708,25 @@ class ForwardPlanner:
             if self.save is not None:   # backward needs every sub-block's conv1 output: one buffer per n
                 t1s = [self.buf(f'act.t1_{i}_{j}_{n}', (B, C, Lo)) for j in range(nk)]
             last_kw = (lambda j: self.final_kw(j)) if n == 2 else (lambda j: {})
-            if self.st and hipops.resblock1_pairs_ok(B, C, Lo, [rb.kernel_size for rb in rbs], [rb.convs1[n].dilation for rb in rbs], [1] * nk, slope=LRELU_SLOPE):
+            if self.st and hipops.resblock1_pairs_ok(B, C, Lo, stg.ks, stg.dils(0, n), stg.dils(1, n), slope=LRELU_SLOPE):
                 # bf16 tensors: pair n of every branch as one resident-tile launch - the dilated conv's output stays in LDS, the pair's residual
                 # joins the output - and the last pair of the last branch adds the other branches' results.  (A pair whose resident tiles do not
                 # fit - 256 channels at dilation 5 - runs conv by conv on the chunked bf16 kernel below, still on bf16 tensors.)
-                brs = [dict(wps1=self.wps[f'{names[j]}.convs1.{n}'], b1=rbs[j].convs1[n].bias.detach(), wps2=self.wps[f'{names[j]}.convs2.{n}'],
-                            b2=rbs[j].convs2[n].bias.detach(), k=rbs[j].kernel_size, dil1=rbs[j].convs1[n].dilation, dil2=1) for j in range(nk)]
+                brs = stg.branches(self.wps, 'wps1', 'wps2', n)
                 for js in ([list(range(nk))] if n < 2 or nk == 1 else [list(range(nk - 1)), [nk - 1]]):
                     last = n == 2 and js[-1] == nk - 1
-                    tag = 'rb1:' + '+'.join(f'{names[j]}.{2 * n}&{2 * n + 1}' for j in js)
+                    tag = 'rb1:' + '+'.join(f'{stg.names[j]}.{2 * n}&{2 * n + 1}' for j in js)
                     if not self.timed(tag, hipops.resblock1_pairs_bf16, [srcs[j] for j in js], src_aff, [brs[j] for j in js], [dsts[j] for j in js],
                                       slope=LRELU_SLOPE, out_div=float(nk) if last else 0.0, add=self.outs[:nk - 1] if last and nk > 1 else None):
                         raise RuntimeError('bf16 storage: the ResBlock1 pair kernel declined a shape its query accepted')
                 srcs, src_aff = dsts, None
                 continue
             ok = False
-            if self.fused_pair_ok((f'convs1.{n}', f'convs2.{n}')):
-                ok = self.launch_pairs(f'{2 * n}&{2 * n + 1}',
-                                       {j: dict(x=srcs[j], in_affine=src_aff, wp1=self.wp[f'{names[j]}.convs1.{n}'], b1=rbs[j].convs1[n].bias.detach(),
-                                                wp2=self.wp[f'{names[j]}.convs2.{n}'], b2=rbs[j].convs2[n].bias.detach(), out=dsts[j],
-                                                k=rbs[j].kernel_size, dil1=rbs[j].convs1[n].dilation, dil2=1, res_mode=1, slope=LRELU_SLOPE,
-                                                **last_kw(j)) for j in range(nk)})
+            if self.fused_pair_ok(n):
+                ok = self.launch_pairs(f'{2 * n}&{2 * n + 1}', self.pair_problems(srcs, src_aff, dsts, res_mode=1, n=n, last=n == 2))
             if not ok:
-                self.launch(str(2 * n), {j: (j, (srcs[j], self.wf[f'{names[j]}.convs1.{n}'], rbs[j].convs1[n].bias.detach(), t1s[j],
-                                                 dict(k=rbs[j].kernel_size, dil=rbs[j].convs1[n].dilation, slope=LRELU_SLOPE, in_affine=src_aff,
-                                                      **self.ck(f'{names[j]}.convs1.{n}')))) for j in range(nk)})
-                conv2 = {j: (j, (t1s[j], self.wf[f'{names[j]}.convs2.{n}'], rbs[j].convs2[n].bias.detach(), dsts[j],
-                                 dict(k=rbs[j].kernel_size, dil=1, slope=LRELU_SLOPE, res=srcs[j], res_affine=src_aff,
-                                      **self.ck(f'{names[j]}.convs2.{n}'), **last_kw(j)))) for j in range(nk)}
+                self.launch(str(2 * n), self.conv_problems(0, srcs, t1s, lambda j: dict(in_affine=src_aff), n))
+                conv2 = self.conv_problems(1, t1s, dsts, lambda j: dict(res=srcs[j], res_affine=src_aff, **last_kw(j)), n)
                 if n < 2:
                     self.launch(str(2 * n + 1), conv2)
                 else:
@@ -710,7 +738,7 @@ class ForwardPlanner:
         from .models import ResBlock2
         g, nk, B, C, Lo = self.g, self.nk, self.B, self.C, self.Lo
         t1 = self.buf(f'act.t1_{i}', (B, C, Lo))
-        for j, (rb, name) in enumerate(zip(self.rbs, self.names)):
+        for j, (rb, name) in enumerate(zip(self.stg.rbs, self.stg.names)):
             k = rb.kernel_size
             last = dict(accumulate=(j > 0), out_div=(float(nk) if j == nk - 1 else 0.0))
             if isinstance(rb, ResBlock2):
@@ -745,7 +773,7 @@ class ForwardPlanner:
             self.S.join()
         if self.y is None:
             self.y = torch.empty((self.B, 1, self.L), device=self.dev, dtype=torch.float32)
-            self.timed('conv_post', hipops.conv_post_tanh, self.cur, self.wf['conv_post'], g.conv_post.bias.detach(), self.y, k=7, slope=0.01,
+            self.timed('conv_post', hipops.conv_post_tanh, self.cur, self.wf['conv_post'], g.conv_post.bias.detach(), self.y, k=7, slope=POST_SLOPE,
                        **self.lkw())
         return self.y
 

@@ -1,7 +1,7 @@
 """Tensor-level wrappers over the C ABI (one function per entry point of include/vec2wav_hip.h).
 
 torch is plumbing here: it owns device memory and the stream; every arithmetic step runs in the
-HIP kernels.  All wrappers require fp32 contiguous CUDA(ROCm) tensors and raise otherwise -
+HIP kernels.  All wrappers require contiguous CUDA(ROCm) tensors - fp32 unless the wrapper says bf16 - and
 there is deliberately no CPU path.
 """
 from __future__ import annotations
@@ -38,6 +38,18 @@ def _declined(rc: int, name: str) -> bool:
         return True
     _hip.check(rc, name)
     return False
+
+
+def _aff(pair):
+    """Device pointers of an optional per-sample affine `(a, s)`: NULL for a missing pair - or member: V2W_E_ARG where the library needs both."""
+    return (None, None) if pair is None else (_hip.ptr(pair[0]), _hip.ptr(pair[1]))
+
+
+def _addends(a, add):
+    """`add0` / `add1` of an args struct: the up to two tensors a launch adds before its division."""
+    add = list(add or [])
+    a.add0 = _hip.ptr(add[0]) if len(add) > 0 else None
+    a.add1 = _hip.ptr(add[1]) if len(add) > 1 else None
 
 
 def fold_conv_weight(v, g, out=None, scratch=None):
@@ -184,18 +196,16 @@ def _conv1d_args(a, x, wf, bias, out, *, k, dil=1, slope=1.0, in_affine=None, re
         a.in_ct = in_ct
     a.in_stride, a.in_phase, a.pad_left = in_stride, in_phase, pad_left
     a.in_ = x.data_ptr() + xoff
-    a.in_a, a.in_s = (_hip.ptr(in_affine[0]), _hip.ptr(in_affine[1])) if in_affine is not None else (None, None)
+    a.in_a, a.in_s = _aff(in_affine)
     a.wf = _hip.ptr(wf); a.wp = _hip.ptr(wp); a.bias = _hip.ptr(bias)
     if wps is not None:           # (fragments, scale record) of pack_split
         a.wps, a.winv = wps[0].data_ptr(), wps[1].data_ptr()
     a.res = _hip.ptr(res)
-    a.res_a, a.res_s = (_hip.ptr(res_affine[0]), _hip.ptr(res_affine[1])) if res_affine is not None else (None, None)
-    add = list(add or [])
-    a.add0 = _hip.ptr(add[0]) if len(add) > 0 else None
-    a.add1 = _hip.ptr(add[1]) if len(add) > 1 else None
+    a.res_a, a.res_s = _aff(res_affine)
+    _addends(a, add)
     if mask is not None:          # (mask_src, (mask_a, mask_s) | None)
         a.mask_src = mask[0].data_ptr()
-        a.mask_a, a.mask_s = (mask[1][0].data_ptr(), mask[1][1].data_ptr()) if mask[1] is not None else (None, None)
+        a.mask_a, a.mask_s = _aff(mask[1])
     a.mask_slope = mask_slope
     a.out = out.data_ptr() + ooff
     a.B, a.C_in, a.C_out, a.L, a.k, a.dil = B, ci, co, L, k, dil
@@ -210,6 +220,14 @@ def _len_ptr(lengths, len_mul):
     if int(len_mul) < 1:
         raise ValueError('len_mul must be >= 1')
     return lengths.data_ptr()
+
+
+def _fwd_or_len(fwd, fwd_len, lengths, len_mul):
+    """(entry point, its name, the arguments it takes in front of the stream): `fwd` and none - or, with per-item `lengths`, `fwd_len` and
+    (lengths pointer, len_mul)."""
+    if lengths is None:
+        return getattr(_hip.load(), fwd), fwd, ()
+    return getattr(_hip.load(), fwd_len), fwd_len, (_len_ptr(lengths, len_mul), int(len_mul))
 
 
 def _pop_len(kw):
@@ -272,10 +290,8 @@ def conv1d(x, wf, bias, out, splitk_ws=None, **kw):
     _conv1d_args(a, x, wf, bias, out, **kw)
     if splitk_ws is not None:
         _attach_slab(a, splitk_ws, _splitk_bytes(a, 1), x.device)
-    if lengths is not None:       # per-item valid lengths (v2w_conv1d_fwd_len; f32 MFMA / Winograd kernels only)
-        _hip.check(_hip.load().v2w_conv1d_fwd_len(C.byref(a), 1, _len_ptr(lengths, len_mul), len_mul, _stream(x)), 'v2w_conv1d_fwd_len')
-        return out
-    _hip.check(_hip.load().v2w_conv1d_fwd(C.byref(a), _stream(x)), 'v2w_conv1d_fwd')
+    fn, name, la = _fwd_or_len('v2w_conv1d_fwd', 'v2w_conv1d_fwd_len', lengths, len_mul)
+    _hip.check(fn(C.byref(a), *((1, *la) if la else ()), _stream(x)), name)     # (v2w_conv1d_fwd_len - f32 MFMA / Winograd kernels only - takes a count)
     return out
 
 
@@ -293,11 +309,8 @@ def _conv1d_launch(problems, splitk_ws=None, *, nmin=2, over=None) -> bool:
     x0 = problems[0][0]
     if splitk_ws is not None:
         _attach_slab(arr[0], splitk_ws, _splitk_bytes(arr, n), x0.device)
-    if lengths is not None:
-        rc = _hip.load().v2w_conv1d_fwd_len(arr, n, _len_ptr(lengths, len_mul), len_mul, _stream(x0))
-    else:
-        rc = _hip.load().v2w_conv1d_fwd_multi(arr, n, _stream(x0))
-    return not _declined(rc, 'v2w_conv1d_fwd_multi')
+    fn, _name, la = _fwd_or_len('v2w_conv1d_fwd_multi', 'v2w_conv1d_fwd_len', lengths, len_mul)
+    return not _declined(fn(arr, n, *la, _stream(x0)), 'v2w_conv1d_fwd_multi')
 
 
 def _without_wpw(problems):
@@ -378,28 +391,32 @@ def wino_sum_order(ks):
     return tuple(out)
 
 
+def _convt_shape(B, c_in, c_out, L, k, u):
+    """A ConvT1dArgs with the problem sizes filled in."""
+    a = _hip.ConvT1dArgs()
+    a.B, a.C_in, a.C_out, a.L, a.k, a.u = B, c_in, c_out, L, k, u
+    return a
+
+
 def convt1d(x, wf, bias, out, *, k, u, slope=1.0, algo=ALGO_AUTO, wp=None, stats_part=None, splitk_ws=None, lengths=None, len_mul=1):
     """Fused leaky_relu -> ConvTranspose1d(k, stride u, padding (k-u)//2) -> +bias.  lengths / len_mul: per-item valid lengths at the INPUT
     rate (see _len_ptr; v2w_convt1d_fwd_len); outputs past lengths[b] * len_mul * u are unspecified."""
     B, ci, L = x.shape
-    a = _hip.ConvT1dArgs()
+    a = _convt_shape(B, ci, out.shape[1], L, k, u)
     a.in_ = x.data_ptr(); a.wf = _hip.ptr(wf); a.wp = _hip.ptr(wp); a.bias = _hip.ptr(bias); a.out = out.data_ptr()
     a.stats_part = _hip.ptr(stats_part)
-    a.B, a.C_in, a.C_out, a.L, a.k, a.u = B, ci, out.shape[1], L, k, u
     a.slope = slope; a.algo = algo
     if splitk_ws is not None:
         _attach_slab(a, splitk_ws, _hip.load().v2w_convt1d_splitk_ws_bytes(C.byref(a)), x.device)
-    if lengths is not None:
-        _hip.check(_hip.load().v2w_convt1d_fwd_len(C.byref(a), _len_ptr(lengths, len_mul), int(len_mul), _stream(x)), 'v2w_convt1d_fwd_len')
-        return out
-    _hip.check(_hip.load().v2w_convt1d_fwd(C.byref(a), _stream(x)), 'v2w_convt1d_fwd')
+    fn, name, la = _fwd_or_len('v2w_convt1d_fwd', 'v2w_convt1d_fwd_len', lengths, len_mul)
+    _hip.check(fn(C.byref(a), *la, _stream(x)), name)
     return out
 
 
 def convt_wino_tiles(B, c_in, c_out, L, k, u):
     """(position tiles = rows of `stats_part`, workgroups) of the launch convt1d_wino would make for this problem, (0, 0) when the
     upsampler form of the Winograd kernel does not serve the shape (v2w_convt1d_wino_tiles; host only)."""
-    a = _hip.ConvT1dArgs(); a.B, a.C_in, a.C_out, a.L, a.k, a.u = B, c_in, c_out, L, k, u
+    a = _convt_shape(B, c_in, c_out, L, k, u)
     wgs = C.c_int32(0)
     tiles = _hip.load().v2w_convt1d_wino_tiles(C.byref(a), C.byref(wgs))
     return (int(tiles), int(wgs.value)) if tiles > 0 else (0, 0)
@@ -411,13 +428,11 @@ def convt1d_wino(x, wpw, bias, out, *, k, u, slope=1.0, in_affine=None, stats_pa
     fold's), `stats_part`: [convt_wino_tiles(...)[0]][C_out][2] per-tile (sum, sumsq).  Returns False (nothing launched) when the library
     declines the shape (V2W_E_SHAPE); the caller then runs convt1d."""
     B, ci, L = x.shape
-    a = _hip.ConvT1dArgs()
+    a = _convt_shape(B, ci, out.shape[1], L, k, u)
     a.in_ = x.data_ptr(); a.wp = _hip.ptr(wpw); a.bias = _hip.ptr(bias); a.out = out.data_ptr()
     a.stats_part = _hip.ptr(stats_part)
-    a.B, a.C_in, a.C_out, a.L, a.k, a.u = B, ci, out.shape[1], L, k, u
     a.slope = slope
-    ia, is_ = (None, None) if in_affine is None else in_affine
-    rc = _hip.load().v2w_convt1d_wino_fwd(C.byref(a), _hip.ptr(ia), _hip.ptr(is_), _stream(x))
+    rc = _hip.load().v2w_convt1d_wino_fwd(C.byref(a), *_aff(in_affine), _stream(x))
     return not _declined(rc, 'v2w_convt1d_wino_fwd')
 
 
@@ -436,10 +451,9 @@ def pack_bf16_convt(wf, u, out=None):
 
 def _convt_bf16_args(x, wps, bias, out, k, u, slope, stats_part, io_bf16=0):
     B, ci, L = x.shape
-    a = _hip.ConvT1dArgs()
+    a = _convt_shape(B, ci, out.shape[1], L, k, u)
     a.in_ = x.data_ptr(); a.wf = None; a.wp = _hip.ptr(wps); a.bias = _hip.ptr(bias); a.out = _hip.ptr(out)
     a.stats_part = _hip.ptr(stats_part)
-    a.B, a.C_in, a.C_out, a.L, a.k, a.u = B, ci, out.shape[1], L, k, u
     a.slope = slope; a.algo = ALGO_BF16; a.io_bf16 = io_bf16
     return a
 
@@ -586,7 +600,7 @@ def conv_tile_config(B, c_in, c_out, L, k, dil=1, u=1, prefix=False):
         a.pad_left = -1
         rc = _hip.load().v2w_conv1d_tile_config(C.byref(a), cfg)
     else:
-        a = _hip.ConvT1dArgs(); a.B, a.C_in, a.C_out, a.L, a.k, a.u = B, c_in, c_out, L, k, u
+        a = _convt_shape(B, c_in, c_out, L, k, u)
         rc = _hip.load().v2w_convt1d_tile_config(C.byref(a), cfg)
     if rc != 0:
         return None
@@ -606,7 +620,7 @@ def conv_bf16_config(B, nprob, c_in, c_out, L, k, dil=1, u=1, io_bf16=3):
             a.io_bf16 = io_bf16
         rc = _hip.load().v2w_conv1d_bf16_config(arr, nprob, cfg)
     else:
-        a = _hip.ConvT1dArgs(); a.B, a.C_in, a.C_out, a.L, a.k, a.u = B, c_in, c_out, L, k, u
+        a = _convt_shape(B, c_in, c_out, L, k, u)
         a.io_bf16 = io_bf16
         a.slope = 0.1              # (the generator's upsamplers; the resident-tile kernel rebuilds nothing from it but checks 0 < slope <= 1)
         rc = _hip.load().v2w_convt1d_bf16_config(C.byref(a), cfg)
@@ -632,7 +646,7 @@ def conv_rowsum_tiles(B, nprob, c_in, c_out, L, k, dil=1):
 def convt_stats_tiles(B, c_in, c_out, L, k, u):
     """Rows of the `stats_part` array the MFMA transposed conv fills for this problem (0: direct kernel, no fused stats)."""
     cfg = (C.c_int32 * 10)()
-    a = _hip.ConvT1dArgs(); a.B, a.C_in, a.C_out, a.L, a.k, a.u = B, c_in, c_out, L, k, u
+    a = _convt_shape(B, c_in, c_out, L, k, u)
     return int(cfg[9]) if _hip.load().v2w_convt1d_tile_config(C.byref(a), cfg) == 0 else 0
 
 
@@ -731,12 +745,9 @@ def resblock_pair_multi(problems):
         x = q['x']
         B, Cc, L = x.shape
         a.in_ = x.data_ptr()
-        aff = q.get('in_affine')
-        a.in_a, a.in_s = (aff[0].data_ptr(), aff[1].data_ptr()) if aff is not None else (None, None)
+        a.in_a, a.in_s = _aff(q.get('in_affine'))
         a.wp1 = q['wp1'].data_ptr(); a.bias1 = _hip.ptr(q['b1']); a.wp2 = q['wp2'].data_ptr(); a.bias2 = _hip.ptr(q['b2'])
-        add = list(q.get('add') or [])
-        a.add0 = _hip.ptr(add[0]) if len(add) > 0 else None
-        a.add1 = _hip.ptr(add[1]) if len(add) > 1 else None
+        _addends(a, q.get('add'))
         a.out = q['out'].data_ptr()
         a.B, a.C, a.L, a.k, a.dil1, a.dil2 = B, Cc, L, q['k'], q['dil1'], q['dil2']
         a.res_mode = q['res_mode']; a.slope = q['slope']; a.out_div = q.get('out_div', 0.0)
@@ -744,37 +755,73 @@ def resblock_pair_multi(problems):
     return not _declined(rc, 'v2w_resblock_pair_fwd')
 
 
-def resblock1_pairs_ok(B, Cc, L, ks, dil1s, dil2s, *, slope) -> bool:
-    """Shape query: would resblock1_pairs_bf16 take these problems (kernel sizes `ks`, dilations of the first / second conv of the pair)?"""
-    a = _hip.StageSplitArgs()
-    a.rb1 = 1
+def _stage_shape(a, B, Cc, L, ks, dil1s, dil2s):
+    """nk, B, C, L and the branches' k / dil1 / dil2 of a StageArgs or a StageSplitArgs; returns `a`."""
     for j, (k, d1, d2) in enumerate(zip(ks, dil1s, dil2s)):
         a.k[j], a.dil1[j], a.dil2[j] = k, d1, d2
     a.nk, a.B, a.C, a.L = len(ks), B, Cc, L
-    a.slope, a.out_div, a.bf16, a.io_bf16 = slope, 0.0, 1, 3
+    return a
+
+
+def _branch_shapes(branches):
+    """(ks, dil1s, dil2s) of a list of branch dicts."""
+    return [q['k'] for q in branches], [q['dil1'] for q in branches], [q['dil2'] for q in branches]
+
+
+def _post(a, post):
+    """post_* of a stage struct from (wf [k][C][1], bias | None, y (B, 1, L) fp32, k, slope): the generator's tail fused behind the C = 16 stage."""
+    if post is not None:
+        a.post_w, a.post_b, a.post_out = post[0].data_ptr(), _hip.ptr(post[1]), post[2].data_ptr()
+        a.post_k, a.post_slope = post[3], post[4]
+
+
+def _stage_args(x, in_affine, branches, out, slope, out_div, keys, post=None):
+    """A filled StageArgs; `keys`: the names under which the branch dicts hold the first / second conv's weights."""
+    a = _stage_shape(_hip.StageArgs(), *x.shape, *_branch_shapes(branches))
+    a.in_ = x.data_ptr(); a.in_a, a.in_s = _aff(in_affine)
+    for j, br in enumerate(branches):
+        a.wp1[j] = br[keys[0]].data_ptr(); a.bias1[j] = _hip.ptr(br['b1'])
+        a.wp2[j] = br[keys[1]].data_ptr(); a.bias2[j] = _hip.ptr(br['b2'])
+    a.out = _hip.ptr(out)
+    a.slope = slope; a.out_div = out_div
+    _post(a, post)
+    return a
+
+
+def _stage_split_args(B, Cc, L, ks, dil1s, dil2s, *, slope, out_div, bf16=True, io_bf16=3, rb1=False, branches=(), in_affine=None, post=None,
+                      up=None):
+    """A filled StageSplitArgs: the sizes and switches a shape query asks with and - launches - the branches' weights (dicts(wps1, b1, wps2,
+    b2)), the input affine, the fused tail and the fused upsampler (wps, bias, out, stats_part, k, u, slope; a query gives the last three)."""
+    a = _stage_shape(_hip.StageSplitArgs(), B, Cc, L, ks, dil1s, dil2s)
+    a.rb1, a.slope, a.out_div, a.bf16, a.io_bf16 = int(rb1), slope, out_div, int(bf16), io_bf16
+    a.in_a, a.in_s = _aff(in_affine)
+    for j, q in enumerate(branches):
+        a.wps1[j], a.sc1[j], a.bias1[j] = q['wps1'][0].data_ptr(), q['wps1'][1].data_ptr(), _hip.ptr(q['b1'])
+        a.wps2[j], a.sc2[j], a.bias2[j] = q['wps2'][0].data_ptr(), q['wps2'][1].data_ptr(), _hip.ptr(q['b2'])
+    if up is not None:
+        a.up_wps, a.up_bias, a.up_out, a.up_stats_part = (_hip.ptr(t) for t in up[:4])
+        a.up_k, a.up_u, a.up_slope = up[4:]
+    _post(a, post)
+    return a
+
+
+def resblock1_pairs_ok(B, Cc, L, ks, dil1s, dil2s, *, slope) -> bool:
+    """Shape query: would resblock1_pairs_bf16 take these problems (kernel sizes `ks`, dilations of the first / second conv of the pair)?"""
+    a = _stage_split_args(B, Cc, L, ks, dil1s, dil2s, slope=slope, out_div=0.0, rb1=True)
     return _hip.load().v2w_resblock2_stage_split_config(C.byref(a)) == 0
 
 
 def resblock2_stage_split_ok(B, Cc, L, ks, dil1s, dil2s, *, slope, bf16=True, io_bf16=3) -> bool:
     """Shape query: would resblock2_stage_split run this stage (nk branches of kernel sizes `ks`, dilations `dil1s` / `dil2s`) as one
     kernel on aligned tensors?  Asked of the library (v2w_resblock2_stage_split_config), nothing is launched."""
-    a = _hip.StageSplitArgs()
-    for j, (k, d1, d2) in enumerate(zip(ks, dil1s, dil2s)):
-        a.k[j], a.dil1[j], a.dil2[j] = k, d1, d2
-    a.nk, a.B, a.C, a.L = len(ks), B, Cc, L
-    a.slope, a.out_div, a.bf16, a.io_bf16 = slope, float(len(ks)), int(bf16), io_bf16
+    a = _stage_split_args(B, Cc, L, ks, dil1s, dil2s, slope=slope, out_div=float(len(ks)), bf16=bf16, io_bf16=io_bf16)
     return _hip.load().v2w_resblock2_stage_split_config(C.byref(a)) == 0
 
 
 def resblock2_stage_up_tiles(B, Cc, L, ks, dil1s, dil2s, *, slope, up_k, up_u, up_slope) -> int:
     """Rows of the `stats_part` array the stage kernel WITH the next stage's upsampler fused behind it fills (resblock2_stage_split(up=...)),
     or 0 when the library does not run this stage fused (shape query, nothing is launched)."""
-    a = _hip.StageSplitArgs()
-    for j, (k, d1, d2) in enumerate(zip(ks, dil1s, dil2s)):
-        a.k[j], a.dil1[j], a.dil2[j] = k, d1, d2
-    a.nk, a.B, a.C, a.L = len(ks), B, Cc, L
-    a.slope, a.out_div, a.bf16, a.io_bf16 = slope, float(len(ks)), 1, 3
-    a.up_k, a.up_u, a.up_slope = up_k, up_u, up_slope
+    a = _stage_split_args(B, Cc, L, ks, dil1s, dil2s, slope=slope, out_div=float(len(ks)), up=(None, None, None, None, up_k, up_u, up_slope))
     n = _hip.load().v2w_resblock2_stage_up_tiles(C.byref(a))
     return n if n > 0 else 0
 
@@ -784,20 +831,10 @@ def resblock1_pairs_bf16(ins, in_affine, branches, outs, *, slope, out_div=0.0, 
     outs[p] = (x_p + conv2_p(lrelu(conv1_p(lrelu x_p) + b1_p)) + b2_p [+ add[0] + add[1]]) / out_div with x_p = a * ins[p] + s.  `branches`:
     dicts(wps1, b1, wps2, b2, k, dil1, dil2) as for resblock2_stage_split; `add`: up to two bf16 tensors the LAST problem adds before the
     division.  Returns False when the shape is not taken."""
-    B, Cc, L = ins[0].shape
-    a = _hip.StageSplitArgs()
-    a.rb1 = 1
-    a.in_a, a.in_s = (in_affine[0].data_ptr(), in_affine[1].data_ptr()) if in_affine is not None else (None, None)
-    for j, q in enumerate(branches):
-        a.wps1[j], a.sc1[j], a.bias1[j] = q['wps1'][0].data_ptr(), q['wps1'][1].data_ptr(), _hip.ptr(q['b1'])
-        a.wps2[j], a.sc2[j], a.bias2[j] = q['wps2'][0].data_ptr(), q['wps2'][1].data_ptr(), _hip.ptr(q['b2'])
-        a.k[j], a.dil1[j], a.dil2[j] = q['k'], q['dil1'], q['dil2']
+    a = _stage_split_args(*ins[0].shape, *_branch_shapes(branches), slope=slope, out_div=out_div, rb1=True, branches=branches, in_affine=in_affine)
+    for j in range(len(branches)):
         a.in_b[j] = ins[j].data_ptr(); a.out_b[j] = outs[j].data_ptr()
-    add = list(add or [])
-    a.add0 = _hip.ptr(add[0]) if len(add) > 0 else None
-    a.add1 = _hip.ptr(add[1]) if len(add) > 1 else None
-    a.nk, a.B, a.C, a.L = len(branches), B, Cc, L
-    a.slope, a.out_div, a.bf16, a.io_bf16 = slope, out_div, 1, 3
+    _addends(a, add)
     rc = _hip.load().v2w_resblock2_stage_split_fwd(C.byref(a), _stream(ins[0]))
     return not _declined(rc, 'v2w_resblock2_stage_split_fwd (rb1)')
 
@@ -807,24 +844,9 @@ def resblock2_stage_split(x, in_affine, branches, out, *, slope, out_div, bf16=F
     with wps* = (fragments, scale record) of pack_split / SplitPlan.  Returns False when the shape is not taken.
     up = (wps of pack_bf16_convt, bias, out (B, C / 2, u L) bf16, stats_part | None, k, u, slope): the NEXT stage's upsampler run on the
     stage's output inside the same kernel (`out` may be None: it is not written)."""
-    B, Cc, L = x.shape
-    a = _hip.StageSplitArgs()
-    if up is not None:
-        a.up_wps, a.up_bias, a.up_out, a.up_stats_part = up[0].data_ptr(), _hip.ptr(up[1]), up[2].data_ptr(), _hip.ptr(up[3])
-        a.up_k, a.up_u, a.up_slope = up[4], up[5], up[6]
-    a.in_ = x.data_ptr()
-    a.in_a, a.in_s = (in_affine[0].data_ptr(), in_affine[1].data_ptr()) if in_affine is not None else (None, None)
-    for j, q in enumerate(branches):
-        a.wps1[j], a.sc1[j], a.bias1[j] = q['wps1'][0].data_ptr(), q['wps1'][1].data_ptr(), _hip.ptr(q['b1'])
-        a.wps2[j], a.sc2[j], a.bias2[j] = q['wps2'][0].data_ptr(), q['wps2'][1].data_ptr(), _hip.ptr(q['b2'])
-        a.k[j], a.dil1[j], a.dil2[j] = q['k'], q['dil1'], q['dil2']
-    a.out = _hip.ptr(out)
-    a.nk, a.B, a.C, a.L = len(branches), B, Cc, L
-    a.slope, a.out_div, a.bf16 = slope, out_div, int(bf16)
-    a.io_bf16 = io_bf16
-    if post is not None:      # (wf [k][C][1], bias | None, y (B, 1, L) fp32, k, slope): the generator's tail fused behind the C = 16 stage
-        a.post_w, a.post_b, a.post_out = post[0].data_ptr(), _hip.ptr(post[1]), post[2].data_ptr()
-        a.post_k, a.post_slope = post[3], post[4]
+    a = _stage_split_args(*x.shape, *_branch_shapes(branches), slope=slope, out_div=out_div, bf16=bf16, io_bf16=io_bf16, branches=branches,
+                          in_affine=in_affine, post=post, up=up)
+    a.in_ = x.data_ptr(); a.out = _hip.ptr(out)
     rc = _hip.load().v2w_resblock2_stage_split_fwd(C.byref(a), _stream(x))
     return not _declined(rc, 'v2w_resblock2_stage_split_fwd')
 
@@ -845,7 +867,7 @@ def branch_convs_bf16(mode, ins, in_affine, wps, biases, outs, ks, dils, *, slop
         a.in_[j] = t.data_ptr()
     for j, t in enumerate(outs):
         a.out[j] = t.data_ptr()
-    a.in_a, a.in_s = (_hip.ptr(in_affine[0]), _hip.ptr(in_affine[1])) if in_affine is not None else (None, None)
+    a.in_a, a.in_s = _aff(in_affine)
     a.nbr, a.mode, a.B, a.C, a.L = n, mode, B, Cc, L
     a.slope, a.out_div = slope, out_div
     rc = _hip.load().v2w_branch_convs_bf16_fwd(C.byref(a), _stream(x))
@@ -860,20 +882,7 @@ def resblock2_stage(x, in_affine, branches, out, *, slope, out_div, post=None, b
     lengths / len_mul (forward form): per-item valid lengths (see _len_ptr; v2w_resblock2_stage_fwd_len); with `post`, y[b, 0, lengths[b] *
     len_mul:] is exactly 0.
     Returns False (nothing launched) when the shape is not taken."""
-    B, Cc, L = x.shape
-    a = _hip.StageArgs()
-    a.in_ = x.data_ptr()
-    a.in_a, a.in_s = (in_affine[0].data_ptr(), in_affine[1].data_ptr()) if in_affine is not None else (None, None)
-    for j, br in enumerate(branches):
-        a.wp1[j] = br['wp1'].data_ptr(); a.bias1[j] = _hip.ptr(br['b1'])
-        a.wp2[j] = br['wp2'].data_ptr(); a.bias2[j] = _hip.ptr(br['b2'])
-        a.k[j], a.dil1[j], a.dil2[j] = br['k'], br['dil1'], br['dil2']
-    a.out = _hip.ptr(out)
-    a.nk, a.B, a.C, a.L = len(branches), B, Cc, L
-    a.slope = slope; a.out_div = out_div
-    if post is not None:
-        a.post_w, a.post_b, a.post_out = post[0].data_ptr(), _hip.ptr(post[1]), post[2].data_ptr()
-        a.post_k, a.post_slope = post[3], post[4]
+    a = _stage_args(x, in_affine, branches, out, slope, out_div, ('wp1', 'wp2'), post)
     if bwd is not None:
         t1s, dt1s, xr, xaff, mslope = bwd[:5]
         rowsums = bwd[5] if len(bwd) > 5 else None
@@ -881,70 +890,36 @@ def resblock2_stage(x, in_affine, branches, out, *, slope, out_div, post=None, b
             a.bwd_mask1[j] = t1s[j].data_ptr(); a.bwd_mid[j] = dt1s[j].data_ptr()
             a.bwd_rowsum[j] = _hip.ptr(rowsums[j]) if rowsums is not None else None
         a.bwd_mask2 = xr.data_ptr()
-        a.bwd_mask2_a, a.bwd_mask2_s = (xaff[0].data_ptr(), xaff[1].data_ptr()) if xaff is not None else (None, None)
+        a.bwd_mask2_a, a.bwd_mask2_s = _aff(xaff)
         a.bwd_slope = mslope
-    if lengths is not None:
-        rc = _hip.load().v2w_resblock2_stage_fwd_len(C.byref(a), _len_ptr(lengths, len_mul), int(len_mul), _stream(x))
-    else:
-        rc = _hip.load().v2w_resblock2_stage_fwd(C.byref(a), _stream(x))
-    return not _declined(rc, 'v2w_resblock2_stage_fwd')
+    fn, _name, la = _fwd_or_len('v2w_resblock2_stage_fwd', 'v2w_resblock2_stage_fwd_len', lengths, len_mul)
+    return not _declined(fn(C.byref(a), *la, _stream(x)), 'v2w_resblock2_stage_fwd')
 
 
 def resblock2_stage_wino(x, in_affine, branches, out, *, slope, out_div, lengths=None, len_mul=1):
     """Winograd F(2,3) form of `resblock2_stage` for the plain forward of a 32-channel stage (v2w_resblock2_stage_wino_fwd).  `branches`:
     list of dicts(wpw1, b1, wpw2, b2, k, dil1, dil2) with the pack_wino streams of the layers.  Returns False (nothing launched) when the
     shape is not taken."""
-    B, Cc, L = x.shape
-    a = _hip.StageArgs()
-    a.in_ = x.data_ptr()
-    a.in_a, a.in_s = (in_affine[0].data_ptr(), in_affine[1].data_ptr()) if in_affine is not None else (None, None)
-    for j, br in enumerate(branches):
-        a.wp1[j] = br['wpw1'].data_ptr(); a.bias1[j] = _hip.ptr(br['b1'])
-        a.wp2[j] = br['wpw2'].data_ptr(); a.bias2[j] = _hip.ptr(br['b2'])
-        a.k[j], a.dil1[j], a.dil2[j] = br['k'], br['dil1'], br['dil2']
-    a.out = out.data_ptr()
-    a.nk, a.B, a.C, a.L = len(branches), B, Cc, L
-    a.slope = slope; a.out_div = out_div
-    if lengths is not None:     # per-item valid lengths (see _len_ptr; v2w_resblock2_stage_wino_fwd_len)
-        rc = _hip.load().v2w_resblock2_stage_wino_fwd_len(C.byref(a), _len_ptr(lengths, len_mul), int(len_mul), _stream(x))
-    else:
-        rc = _hip.load().v2w_resblock2_stage_wino_fwd(C.byref(a), _stream(x))
-    return not _declined(rc, 'v2w_resblock2_stage_wino_fwd')
+    a = _stage_args(x, in_affine, branches, out, slope, out_div, ('wpw1', 'wpw2'))
+    fn, _name, la = _fwd_or_len('v2w_resblock2_stage_wino_fwd', 'v2w_resblock2_stage_wino_fwd_len', lengths, len_mul)
+    return not _declined(fn(C.byref(a), *la, _stream(x)), 'v2w_resblock2_stage_wino_fwd')
 
 
 def resblock2_stage_wino_tile(B, Cc, L, ks, dil1s, dil2s) -> int:
     """Outputs one tile of `resblock2_stage_wino` keeps (tiles start that many positions apart; 0: shape not taken).  Host only."""
-    a = _hip.StageArgs()
-    a.nk, a.B, a.C, a.L = len(ks), B, Cc, L
-    for j in range(len(ks)):
-        a.k[j], a.dil1[j], a.dil2[j] = ks[j], dil1s[j], dil2s[j]
-    return _hip.load().v2w_resblock2_stage_wino_tile(C.byref(a))
+    return _hip.load().v2w_resblock2_stage_wino_tile(C.byref(_stage_shape(_hip.StageArgs(), B, Cc, L, ks, dil1s, dil2s)))
 
 
 def resblock2_stage_bwd_rows(B, Cc, L, ks, dil1s, dil2s) -> int:
     """Rows of [C][2] floats per branch the input-gradient form of `resblock2_stage` writes into its `rowsums` buffers (0: shape not taken).
     dil1s / dil2s as handed to the kernel (conv2's dilations first)."""
-    a = _hip.StageArgs()
-    a.nk, a.B, a.C, a.L = len(ks), B, Cc, L
-    for j in range(len(ks)):
-        a.k[j], a.dil1[j], a.dil2[j] = ks[j], dil1s[j], dil2s[j]
-    return _hip.load().v2w_resblock2_stage_bwd_rows(C.byref(a))
+    return _hip.load().v2w_resblock2_stage_bwd_rows(C.byref(_stage_shape(_hip.StageArgs(), B, Cc, L, ks, dil1s, dil2s)))
 
 
 def resblock2_stage_small(x, in_affine, branches, out, *, slope, out_div):
     """The same section for an 8-channel stage (v2w_resblock2_stage_small_fwd: fp32 FMAs, x read once, t1_j in LDS).  `branches`: list of
     dicts(wf1, b1, wf2, b2, k, dil1, dil2) with the FOLDED weights [k][C][C].  Returns False when the shape is not taken."""
-    B, Cc, L = x.shape
-    a = _hip.StageArgs()
-    a.in_ = x.data_ptr()
-    a.in_a, a.in_s = (in_affine[0].data_ptr(), in_affine[1].data_ptr()) if in_affine is not None else (None, None)
-    for j, br in enumerate(branches):
-        a.wp1[j] = br['wf1'].data_ptr(); a.bias1[j] = _hip.ptr(br['b1'])
-        a.wp2[j] = br['wf2'].data_ptr(); a.bias2[j] = _hip.ptr(br['b2'])
-        a.k[j], a.dil1[j], a.dil2[j] = br['k'], br['dil1'], br['dil2']
-    a.out = out.data_ptr()
-    a.nk, a.B, a.C, a.L = len(branches), B, Cc, L
-    a.slope = slope; a.out_div = out_div
+    a = _stage_args(x, in_affine, branches, out, slope, out_div, ('wf1', 'wf2'))
     rc = _hip.load().v2w_resblock2_stage_small_fwd(C.byref(a), _stream(x))
     return not _declined(rc, 'v2w_resblock2_stage_small_fwd')
 
@@ -961,7 +936,7 @@ def wgrad(x, dy, *, k, dil=1, u=1, slope=1.0, x_affine=None, out=None):
     if out is None:
         out = torch.empty((k, ci, co), device=x.device, dtype=torch.float32)
     slab = torch.empty((ns * k * ci * co,), device=x.device, dtype=torch.float32)
-    xa, xs = (x_affine[0].data_ptr(), x_affine[1].data_ptr()) if x_affine is not None else (None, None)
+    xa, xs = _aff(x_affine)
     _hip.check(lib.v2w_wgrad(x.data_ptr(), xa, xs, dy.data_ptr(), out.data_ptr(), slab.data_ptr(), B, ci, co, Lq, k, dil, u, slope,
                              _stream(x)), 'v2w_wgrad')
     return out
@@ -981,7 +956,7 @@ def wgrad_bf16(x, dy, *, k, dil=1, slope=1.0, x_affine=None, out=None):
     if out is None:
         out = torch.empty((k, ci, co), device=x.device, dtype=torch.float32)
     slab = torch.empty((ns * k * ci * co,), device=x.device, dtype=torch.float32)
-    xa, xs = (x_affine[0].data_ptr(), x_affine[1].data_ptr()) if x_affine is not None else (None, None)
+    xa, xs = _aff(x_affine)
     rc = lib.v2w_wgrad_bf16(x.data_ptr(), xa, xs, dy.data_ptr(), out.data_ptr(), slab.data_ptr(), B, ci, co, Lq, k, dil, slope,
                             3 if x.dtype == torch.bfloat16 else 0, _stream(x))
     if rc == _hip.E_SHAPE:

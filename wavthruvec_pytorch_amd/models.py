@@ -489,18 +489,22 @@ class Generator(nn.Module):
         self._fold_key.update(state=state, wf=wf, wp=wp, wpd=wpd, wpw=wpw, wpw_stage=wpw_stage, wpw_sum=wpw_sum, wpw_up=wpw_up, vers=tuple(vers), gen=self._fold_key.get('gen', 0) + 1)
         return wf, wp
 
+    def stage_record(self, i):
+        """The `forward_plan.Stage` record of residual stage i: its width, its blocks and their parameter-name prefixes."""
+        from .forward_plan import Stage
+        js = range(i * self.num_kernels, (i + 1) * self.num_kernels)
+        return Stage(i, self.ups[i].out_channels, tuple(self.resblocks[j] for j in js), tuple(f'resblocks.{j}' for j in js))
+
+    def _rb2_stage_layers(self, selected, cs):
+        """Names of the convs `cs` of every ResBlock2 stage whose record `selected` accepts."""
+        stages = (self.stage_record(i) for i in range(self.num_upsamples))
+        return {nm for stg in stages if stg.is_rb2 and selected(stg) for nm in stg.layers(cs)}
+
     def _wino_stage_layers(self):
         """Names of the conv layers that get a Winograd stream for the fused 32-channel stage kernel: both convs of every block of a stage
         the planner runs in that form (forward_plan.stage_wino_selected) - none with `wino_stage` off."""
         from .forward_plan import stage_wino_selected
-        names, nk = set(), self.num_kernels
-        for i, up in enumerate(self.ups):
-            rbs = [self.resblocks[i * nk + j] for j in range(nk)]
-            if all(isinstance(rb, ResBlock2) for rb in rbs) and stage_wino_selected(
-                    self.wino_stage, self.precision, self.algo, up.out_channels,
-                    [(rb.kernel_size, rb.convs[0].dilation, rb.convs[1].dilation) for rb in rbs]):
-                names.update(f'resblocks.{i * nk + j}.convs.{c}' for j in range(nk) for c in (0, 1))
-        return names
+        return self._rb2_stage_layers(lambda stg: stage_wino_selected(self.wino_stage, self.precision, self.algo, stg.C, stg.blocks), (0, 1))
 
     def _wino_up_layers(self):
         """Names of the upsamplers that get the two-tap Winograd stream of the upsampler form (forward_plan.wino_up_selected) - none with
@@ -513,13 +517,7 @@ class Generator(nn.Module):
         """Names of the second convs (`convs.1`) of the stages whose branch sum runs as one Winograd launch (forward_plan.wino_sum_selected):
         the fold gives each a Winograd stream, also where `wino` leaves the layer on the direct form."""
         from .forward_plan import wino_sum_selected
-        names, nk = set(), self.num_kernels
-        for i, up in enumerate(self.ups):
-            rbs = [self.resblocks[i * nk + j] for j in range(nk)]
-            if all(isinstance(rb, ResBlock2) for rb in rbs) and wino_sum_selected(
-                    self.wino_sum, self.precision, self.algo, up.out_channels, [(rb.kernel_size, rb.convs[1].dilation) for rb in rbs]):
-                names.update(f'resblocks.{i * nk + j}.convs.1' for j in range(nk))
-        return names
+        return self._rb2_stage_layers(lambda stg: wino_sum_selected(self.wino_sum, self.precision, self.algo, stg.C, stg.pairs(1)), (1,))
 
     def _split_weights(self, device, all_ups=False, ups_stream=None, mark=None, between=None):
         """precision == 'f16x3': (hi, lo) half-precision fragments + scale record of every Conv1d layer the split kernel
@@ -630,24 +628,21 @@ class Generator(nn.Module):
         if hit is not None and hit[0] == key:
             return hit[1]
         ok = hipops.conv_bf16_config(B, 1, self.conv_pre.in_channels, self.conv_pre.out_channels, T, 7, 1, 1, io_bf16=2) is not None
-        L, nk = T, self.num_kernels
+        L = T
         for i, up in enumerate(self.ups):
             ok = ok and hipops.conv_bf16_config(B, 1, up.in_channels, up.out_channels, L, up.kernel_size, 1, up.stride, io_bf16=3) is not None
             L *= up.stride
-            C = up.out_channels
-            rbs = self.resblocks[i * nk:(i + 1) * nk]
-            if isinstance(rbs[0], ResBlock1):      # ResBlock1 on bf16 tensors: every (dilated conv, conv) pair of every branch on the pair kernel,
+            C, stg = up.out_channels, self.stage_record(i)
+            rbs = stg.rbs
+            if not stg.is_rb2:      # ResBlock1 on bf16 tensors: every (dilated conv, conv) pair of every branch on the pair kernel,
                 for n in range(3):                 # or - wide stages - both convs of the pair on the chunked bf16 tile kernel
-                    pair = hipops.resblock1_pairs_ok(B, C, L, [rb.kernel_size for rb in rbs], [rb.convs1[n].dilation for rb in rbs],
-                                                     [1] * len(rbs), slope=LRELU_SLOPE)
+                    pair = hipops.resblock1_pairs_ok(B, C, L, stg.ks, stg.dils(0, n), stg.dils(1, n), slope=LRELU_SLOPE)
                     convs = C >= 64 and all(rb.kernel_size >= 3 and
                                             hipops.conv_bf16_config(B, 1, C, C, L, rb.kernel_size, rb.convs1[n].dilation, 1, io_bf16=3) is not None and
                                             hipops.conv_bf16_config(B, 1, C, C, L, rb.kernel_size, 1, 1, io_bf16=3) is not None for rb in rbs)
                     ok = ok and all(rb.kernel_size % 2 == 1 for rb in rbs) and (pair or convs)
             elif C in (16, 32):       # the narrow stages exist as ONE fused kernel only: the library says whether it takes this block set
-                ok = ok and all(rb.kernel_size % 2 == 1 for rb in rbs) and hipops.resblock2_stage_split_ok(
-                    B, C, L, [rb.kernel_size for rb in rbs], [rb.convs[0].dilation for rb in rbs], [rb.convs[1].dilation for rb in rbs],
-                    slope=LRELU_SLOPE)
+                ok = ok and all(k % 2 == 1 for k in stg.ks) and hipops.resblock2_stage_split_ok(B, C, L, stg.ks, stg.dil1s, stg.dil2s, slope=LRELU_SLOPE)
             else:                   # a wide stage the one-kernel form declines runs conv by conv: every conv needs its bf16 tile kernel
                 for rb in rbs:
                     for c in rb.convs:
