@@ -647,6 +647,49 @@ int v2w_mel_finish_geo_len(const float* spec, const float* basis, float* out, in
                            const int32_t* len, int len_mul, int hop, int n_fft, void* stream);
 int v2w_mel_finish_geo_bwd(const float* spec, const float* basis, const float* basisT, const float* gout, float* dspec,
                            int B, int Cs, int FP, int F, int nb, int n_mels, void* stream);
+/* Fused mel L1 training loss (additive; train.py:172-176,204: F.l1_loss(y_mel, mel_spectrogram(y_g_hat)) and its backward), with or
+ * without per-item lengths.  The forward's first two steps are the existing ones (v2w_mel_phases / _len / _geo / _geo_len, then the DFT conv);
+ * the calls below replace v2w_mel_finish + an L1 and their backwards: the (B, n_mels, F) mel is never stored.
+ * tgt is the padded target, DENSE: (B, Ft, n_mels) read with (ts_f, ts_m) = (n_mels, 1), or (B, n_mels, Ft) with (ts_f, ts_m) = (1, Ft);
+ * it is never written.  len == NULL: every item counts F_b = F frames (Ft >= F).  len a DEVICE array of B int32 (len_mul >= 1, "Batches of
+ * unequal lengths"): F_b = min(frames(len[b] * len_mul), F, Ft), frames(n) as v2w_mel_finish_geo_len states it (pad = (n_fft - hop) / 2 rounded
+ * down).  With v[b][m][f] = logf(fmaxf(acc, 1e-5f)) as v2w_mel_finish[_geo] computes it (the same operations in the same order):
+ *   v2w_mel_loss_plan  host only: tiles = ceil(F / 16), or ceil(F / 8) where 16 frames of nb bins pass 64 KiB of LDS (as v2w_mel_finish_geo
+ *                      chooses); *scratch_bytes (may be NULL) = B * tiles * 8, the size of ws.  Returns tiles > 0 or a V2W_E_* code.
+ *   v2w_mel_loss_fwd   launch 1, grid (tiles, B): workgroup (g, b) adds |v - t| (one fp32 rounding each) over its frames f < F_b in fp64 -
+ *                      a thread's entries in index order, then the fixed-order workgroup reduction - and writes ONE partial ws[b * tiles + g];
+ *                      a workgroup at or past F_b writes 0.0 and reads nothing.  Launch 2, one workgroup: item b's partials are added in
+ *                      index order, S_b, and the items' sums in a fixed order:
+ *                        per_item[b] = S_b / (n_mels * F_b), 0 for F_b = 0                      (B floats; may be NULL)
+ *                        total[0]    = scale * sum_b S_b / (n_mels * sum_b F_b)                 (may be NULL)
+ *                        coef[0]     = scale / (n_mels * sum_b F_b)                             (may be NULL: the backward's factor)
+ *                      total and coef are 0 when no item has a frame.  No atomics: the same call gives the same bits, an item's per_item
+ *                      depends on no other item, and the frame counts never come to the host.
+ *   v2w_mel_loss_bwd   v2w_mel_finish_geo_bwd with d_acc = (gout[0] * coef[0]) * sgn(v - t) / acc where f < F_b and acc >= 1e-5f, else 0
+ *                      (sgn(0) = 0); gout and coef are DEVICE floats.  dspec is zero-filled by the caller: only rows < 2 * nb of the frames
+ *                      f < F_b are written.
+ * spec frames and target entries at or past F_b are never loaded (selects, not multiplies): NaN or Inf there reaches nothing.
+ *   v2w_mel_phases_len_bwd, v2w_mel_phases_geo_len_bwd: v2w_mel_phases_bwd / v2w_mel_phases_geo_bwd for item b of Lb = min(len[b] * len_mul, L)
+ *                      samples and F_b = frames(Lb): the right reflection is about the item's own last sample (2 (Lb - 1) - s + pad for
+ *                      Lb - 1 - pad <= s <= Lb - 2), the columns from the item's own roundup4(F_b + k - 1) on read as 0 whatever they
+ *                      hold, dy[b, Lb:] = +0.0, and an item with F_b = 0 is all +0.0.  The three additions keep their order:
+ *                      dy[b, :Lb] has the bits of the B = 1 plain call on a dense copy of dxp[b, :, :roundup4(F_b + k - 1)].
+ * V2W_E_ARG: a NULL operand (per_item, total, coef: all three NULL), ws not 8-byte aligned, scale NaN, Ft <= 0, (ts_f, ts_m) neither of the
+ * two dense layouts, len == NULL and Ft < F, len != NULL and len_mul < 1 / hop < 1 / n_fft < hop, and the cases of v2w_mel_finish_geo[_bwd]
+ * and of v2w_mel_phases_len / _geo_len.  V2W_E_SHAPE: theirs (B > 65535, nb > 2048 or nb + n_mels > 2048 in the backward, F * hop + n_fft
+ * past 2^31 - 1) and n_mels * Ft past 2^31 - 1. */
+int v2w_mel_loss_plan(int B, int F, int nb, int n_mels, long long* scratch_bytes);
+int v2w_mel_loss_fwd(const float* spec, const float* basis, const float* tgt, int ts_f, int ts_m,
+                     int B, int Cs, int FP, int F, int Ft, int nb, int n_mels,
+                     const int32_t* len, int len_mul, int hop, int n_fft, float scale,
+                     float* per_item, float* total, float* coef, void* ws, void* stream);
+int v2w_mel_loss_bwd(const float* spec, const float* basis, const float* basisT, const float* tgt, int ts_f, int ts_m,
+                     const float* gout, const float* coef, float* dspec,
+                     int B, int Cs, int FP, int F, int Ft, int nb, int n_mels,
+                     const int32_t* len, int len_mul, int hop, int n_fft, void* stream);
+int v2w_mel_phases_len_bwd(const float* dxp, float* dy, int B, int L, int hop, int pad, int FP, const int32_t* len, int len_mul, void* stream);
+int v2w_mel_phases_geo_len_bwd(const float* dxp, float* dy, int B, int L, int n_fft, int win, int hop, int CP, int pad, int left, int k,
+                               int FP, const int32_t* len, int len_mul, void* stream);
 
 /* ---- MPD / MSD discriminator forwards (models.py:158-275): the memory-bound ends; the convolutions run
  * through v2w_conv1d_fwd (in_ct / out_ct for groups, out_slope for the activated feature maps, dil = period for the (k, 1) Conv2d).

@@ -291,6 +291,12 @@ SIGNATURES = {
     'v2w_mel_finish_geo_len': (C.c_int, [_fp, _fp, _fp] + [C.c_int] * 6 + [_fp, C.c_int, C.c_int, C.c_int, _fp]),
     'v2w_mel_finish_geo_bwd': (C.c_int, [_fp] * 5 + [C.c_int] * 6 + [_fp]),
     'v2w_l1_masked_geo': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp]),
+    # the mel L1 training loss fused into the finish kernels, and the phase backward with per-item lengths (len may be NULL in the first two)
+    'v2w_mel_loss_plan': (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_longlong)]),
+    'v2w_mel_loss_fwd': (C.c_int, [_fp] * 3 + [C.c_int] * 9 + [_fp, C.c_int, C.c_int, C.c_int, C.c_float] + [_fp] * 5),
+    'v2w_mel_loss_bwd': (C.c_int, [_fp] * 4 + [C.c_int] * 2 + [_fp] * 3 + [C.c_int] * 7 + [_fp, C.c_int, C.c_int, C.c_int, _fp]),
+    'v2w_mel_phases_len_bwd': (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp]),
+    'v2w_mel_phases_geo_len_bwd': (C.c_int, [_fp, _fp] + [C.c_int] * 10 + [_fp, C.c_int, _fp]),
     # GAN training losses: host descriptor arrays, read before the call returns
     'v2w_l1_multi_plan': (C.c_int, [C.POINTER(L1Pair), C.c_int, C.POINTER(C.c_int32)]),
     'v2w_l1_multi_scratch_bytes': (C.c_longlong, [C.POINTER(L1Pair), C.c_int]),

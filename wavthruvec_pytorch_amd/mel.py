@@ -11,7 +11,8 @@ does magnitude -> filterbank -> log.  That is the reference geometry 1024 / 256 
 hop_size % 32 == 0).  Every other geometry with 1 <= hop_size <= n_fft, 1 <= win_size <= n_fft <= 2048 takes the `v2w_mel_*_geo` siblings of
 the two ends (`stft_geometry`): the conv then contracts over the window's support only - ceil(win_size / hop_size) taps over hop_size channels
 rounded up to 32, the first of them `left = (n_fft - win_size) // 2` samples into the frame.  Batches of unequal lengths (the reference's validation loop, batched: validate.py) take the per-item
-form of the two ends (`lengths=`) and the masked L1 `mel_l1`.  Constants (DFT rows, hann window, Slaney mel filterbank = librosa.filters.mel of the
+form of the two ends (`lengths=`) and the masked L1 `mel_l1`.  `mel_loss` is the training loss of train.py:172-176,204 in one call, the L1 fused
+into the finish kernel, with or without per-item lengths, forward and backward.  Constants (DFT rows, hann window, Slaney mel filterbank = librosa.filters.mel of the
 reference's librosa, restated because librosa is not a dependency here) are built once per configuration with numpy in fp64.
 """
 from __future__ import annotations
@@ -161,10 +162,10 @@ def _geo_args(c, B, L, FP):
     return B, L, c['n_fft'], c['win'], c['hop'], c['cp'], c['pad'], c['left'], c['k'], FP
 
 
-def _forward(y, cfg, lens=None, len_mul=1):
-    """-> (out, spec, geometry): the three launches of the forward; `spec` is what the backward needs.  lens (B int32 on the device): the
-    per-item form of the two ends (forward only); the DFT conv between them runs on the whole padded batch either way.  A geometry the first
-    entry points serve (stft_geometry: `old`) keeps them, and with them its bits; the others take the v2w_mel_*_geo calls."""
+def _spectrum(y, cfg, lens=None, len_mul=1):
+    """-> (spec, constants, geometry): the first two launches of the forward, the phases step and the DFT conv.  lens (B int32 on the device):
+    the per-item form of the phases step; the DFT conv runs on the whole padded batch either way.  A geometry the first entry points serve
+    (stft_geometry: `old`) keeps them, and with them its bits; the others take the v2w_mel_*_geo calls."""
     n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax = cfg
     B, L = y.shape
     c = _constants(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, y.device)
@@ -190,6 +191,16 @@ def _forward(y, cfg, lens=None, len_mul=1):
                    'v2w_mel_phases_geo_len')
     spec = torch.empty((B, c['cs'], FP), device=y.device)
     hipops.conv1d(xp, c['wf'], None, spec, k=c['k'], dil=1, slope=1.0, pad_left=0, wp=c['wp'])
+    return spec, c, (B, L, pad, F, FP)
+
+
+def _forward(y, cfg, lens=None, len_mul=1):
+    """-> (out, spec, geometry): the three launches of the forward; `spec` is what the backward needs.  lens: the per-item form of the two
+    ends (forward only)."""
+    num_mels = cfg[1]
+    spec, c, (B, L, pad, F, FP) = _spectrum(y, cfg, lens, len_mul)
+    hop = c['hop']
+    lib, st = _hip.load(), torch.cuda.current_stream(y.device).cuda_stream
     out = torch.empty((B, num_mels, F), device=y.device)
     old = c['old'] and c['nb'] * 64 <= 65536                  # (16 frames x 4 bytes per bin of the first kernels' LDS block)
     fin = (spec.data_ptr(), c['basis'].data_ptr(), out.data_ptr(), B, c['cs'], FP, F, c['nb'], num_mels)
@@ -205,14 +216,15 @@ def _forward(y, cfg, lens=None, len_mul=1):
 BWD_ROWS = 128         # DFT rows per launch of the input-gradient conv at the geometries the `_geo` calls serve (see _dft_conv_bwd)
 
 
-def _dft_conv_bwd(c, dspec, dxp):
+def _dft_conv_bwd(c, dspec, dxp, by_rows=False):
     """dspec (B, cs, FP) -> dxp (B, cp, FP): the DFT conv's input gradient.  One launch at the geometries the first entry points serve (their
-    bits).  Elsewhere the cs rows go BWD_ROWS at a time, each launch adding its sum to dxp (`accumulate`): a dot product of k * cs fp32
+    bits; `by_rows`: mel_loss, which has no earlier bits to keep, goes BWD_ROWS at a time there too - at 1024 / 256 / 1024 the one chain of
+    4 x 1088 terms put its d y at 2.7 - 9.5 times the oracle's float32 gap).  Elsewhere the cs rows go BWD_ROWS at a time, each launch adding its sum to dxp (`accumulate`): a dot product of k * cs fp32
     terms added in one chain drifts by about sqrt(k * cs / 2) roundings (51 at 1024 / 120 / 600, 72 at n_fft 2048), which put d y at 7.7 and
     4.8 times the float32 gap of torch.stft's FFT there; chains of k * BWD_ROWS terms joined by cs / BWD_ROWS additions bring it to 2.4 and
     1.6 (64 rows per launch measure the same, 256 rows 3.3 and 1.8: DESIGN.md 3d''')."""
     k, cs = c['k'], c['cs']
-    if c['old'] or cs <= BWD_ROWS:
+    if (c['old'] and not by_rows) or cs <= BWD_ROWS:
         hipops.conv1d(dspec, c['wT'], None, dxp, k=k, dil=1, slope=1.0, pad_left=k - 1, wp=c['wTp'])
         return
     if 'wT_rows' not in c:
@@ -246,13 +258,29 @@ def _backward(g, spec, geom, cfg):
     name = 'v2w_mel_finish_bwd' if c['old'] and (c['nb'] + num_mels) * 64 <= 65536 else 'v2w_mel_finish_geo_bwd'
     _hip.check(getattr(lib, name)(spec.data_ptr(), c['basis'].data_ptr(), c['basisT'].data_ptr(), g.data_ptr(), dspec.data_ptr(),
                                   B, c['cs'], FP, F, c['nb'], num_mels, st), name)
+    return _spectrum_backward(c, dspec, geom)
+
+
+def _spectrum_backward(c, dspec, geom, lens=None, len_mul=1, by_rows=False):
+    """d spec (B, cs, FP) -> d y (B, L): the backward of `_spectrum`.  lens: the per-item form of the phase backward (the reflection about
+    the item's own last sample, +0.0 past it); the DFT conv's input gradient runs on the whole padded batch either way."""
+    B, L, pad, F, FP = geom
+    dev = dspec.device
+    lib, st = _hip.load(), torch.cuda.current_stream(dev).cuda_stream
     dxp = torch.empty((B, c['cp'], FP), device=dev)
-    _dft_conv_bwd(c, dspec, dxp)
+    _dft_conv_bwd(c, dspec, dxp, by_rows)
     dy = torch.empty((B, L), device=dev)
     if c['old']:
-        _hip.check(lib.v2w_mel_phases_bwd(dxp.data_ptr(), dy.data_ptr(), B, L, c['hop'], pad, FP, st), 'v2w_mel_phases_bwd')
-    else:
+        if lens is None:
+            _hip.check(lib.v2w_mel_phases_bwd(dxp.data_ptr(), dy.data_ptr(), B, L, c['hop'], pad, FP, st), 'v2w_mel_phases_bwd')
+        else:
+            _hip.check(lib.v2w_mel_phases_len_bwd(dxp.data_ptr(), dy.data_ptr(), B, L, c['hop'], pad, FP, lens.data_ptr(), len_mul, st),
+                       'v2w_mel_phases_len_bwd')
+    elif lens is None:
         _hip.check(lib.v2w_mel_phases_geo_bwd(dxp.data_ptr(), dy.data_ptr(), *_geo_args(c, B, L, FP), st), 'v2w_mel_phases_geo_bwd')
+    else:
+        _hip.check(lib.v2w_mel_phases_geo_len_bwd(dxp.data_ptr(), dy.data_ptr(), *_geo_args(c, B, L, FP), lens.data_ptr(), len_mul, st),
+                   'v2w_mel_phases_geo_len_bwd')
     return dy
 
 
@@ -338,3 +366,111 @@ def mel_l1(a, b, lengths, len_mul=1, *, n_fft, hop_size):
         _hip.check(getattr(lib, name)(a.data_ptr(), b.data_ptr(), B, Cm, F, lens.data_ptr(), len_mul, hop_size, n_fft,
                                       per_item.data_ptr(), total.data_ptr(), ws.data_ptr(), st), name)
     return total[0], per_item
+
+
+def _loss_launch(spec, c, geom, tgt, frames_first, num_mels, lens, len_mul, scale):
+    """The fused finish + L1 and its finishing launch on `spec` -> (total (1,), per_item (B,), coef (1,)), all on the device."""
+    B, L, pad, F, FP = geom
+    dev = spec.device
+    lib, st = _hip.load(), torch.cuda.current_stream(dev).cuda_stream
+    Ft = tgt.shape[1] if frames_first else tgt.shape[2]
+    nbytes = C.c_longlong(0)
+    tiles = lib.v2w_mel_loss_plan(B, F, c['nb'], num_mels, C.byref(nbytes))
+    _hip.check(min(tiles, 0), 'v2w_mel_loss_plan')
+    ws = torch.empty((nbytes.value // 8,), dtype=torch.float64, device=dev)
+    per_item, total, coef = torch.empty((B,), device=dev), torch.empty((1,), device=dev), torch.empty((1,), device=dev)
+    strides = (num_mels, 1) if frames_first else (1, Ft)
+    _hip.check(lib.v2w_mel_loss_fwd(spec.data_ptr(), c['basis'].data_ptr(), tgt.data_ptr(), *strides, B, c['cs'], FP, F, Ft, c['nb'], num_mels,
+                                    lens.data_ptr() if lens is not None else None, len_mul, c['hop'], c['n_fft'], scale,
+                                    per_item.data_ptr(), total.data_ptr(), coef.data_ptr(), ws.data_ptr(), st), 'v2w_mel_loss_fwd')
+    return total, per_item, coef
+
+
+class _MelLossFn(torch.autograd.Function):
+    """total, per_item = mel_loss's two results; saves spec, the target, coef and its own copy of the lengths (the module's buffer is
+    rewritten by the next ragged call).  Backward: fused finish backward -> the DFT conv's input gradient -> phase backward."""
+
+    @staticmethod
+    def forward(ctx, y, tgt, cfg, lens, len_mul, scale, frames_first):
+        spec, c, geom = _spectrum(y.detach().contiguous().float(), cfg, lens, len_mul)
+        total, per_item, coef = _loss_launch(spec, c, geom, tgt, frames_first, cfg[1], lens, len_mul, scale)
+        ctx.save_for_backward(spec, tgt, coef, None if lens is None else lens.clone())
+        ctx.geom, ctx.cfg, ctx.len_mul, ctx.frames_first = geom, cfg, len_mul, frames_first
+        ctx.mark_non_differentiable(per_item)
+        return total.reshape(()), per_item
+
+    @staticmethod
+    @_hip.on_tensor_device
+    def backward(ctx, g, _g_per_item):
+        spec, tgt, coef, lens = ctx.saved_tensors
+        n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax = ctx.cfg
+        B, L, pad, F, FP = ctx.geom
+        dev = spec.device
+        c = _bwd_constants(_constants(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, dev))
+        lib, st = _hip.load(), torch.cuda.current_stream(dev).cuda_stream
+        g = g.detach().reshape(1).contiguous().float()
+        Ft = tgt.shape[1] if ctx.frames_first else tgt.shape[2]
+        strides = (num_mels, 1) if ctx.frames_first else (1, Ft)
+        dspec = torch.zeros_like(spec)
+        _hip.check(lib.v2w_mel_loss_bwd(spec.data_ptr(), c['basis'].data_ptr(), c['basisT'].data_ptr(), tgt.data_ptr(), *strides,
+                                        g.data_ptr(), coef.data_ptr(), dspec.data_ptr(), B, c['cs'], FP, F, Ft, c['nb'], num_mels,
+                                        lens.data_ptr() if lens is not None else None, ctx.len_mul, c['hop'], c['n_fft'], st),
+                   'v2w_mel_loss_bwd')
+        return _spectrum_backward(c, dspec, ctx.geom, lens, ctx.len_mul, by_rows=True), None, None, None, None, None, None
+
+
+@_hip.on_tensor_device
+def mel_loss(y_hat, y_mel, n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, *,
+             lengths=None, len_mul=1, scale=1.0, frames_first=True, per_item=False):
+    """The mel L1 training loss in one call, differentiable with respect to y_hat: scale * F.l1_loss(y_mel[:, :F], mel_spectrogram(y_hat,
+    ...).permute(0, 2, 1)) (train.py:172-176,204), with the L1 fused into the mel's last kernel - the (B, num_mels, F) mel is never stored.
+
+    y_hat (B, L) or (B, 1, L) float32 on the GPU; y_mel the padded target, (B, F_t, num_mels) when frames_first (train.py's y_mel) else
+    (B, num_mels, F_t), never differentiated.  Without lengths F_t >= F = mel_frames(L) is required.
+
+    lengths (B integers, a list or a tensor on any device; a device tensor is taken without a sync) and len_mul, as in mel_spectrogram: item b
+    holds n_b = min(lengths[b] * len_mul, L) samples and counts F_b = min(mel_frames(n_b), F, F_t) frames of the mel that y_hat[b:b+1, :n_b]
+    alone gives.  The loss is scale * (sum of |mel - target| over the valid entries) / (num_mels * sum_b F_b), mel_l1's `total`; 0 when no
+    entry is valid.  y_hat[b, n_b:] and the target past F_b have no effect, whatever they hold, and d y_hat[b, n_b:] is exactly +0.0.
+
+    -> the loss (0-dim), and with per_item=True also the detached (B,) per-item means (mel_l1's `per_item`).  Deterministic: fixed-order
+    fp64 sums, no atomics."""
+    g = stft_geometry(n_fft, hop_size, win_size)           # ValueError outside 1 <= hop_size, win_size <= n_fft <= 2048
+    num_mels = int(num_mels)
+    if y_hat.dim() == 3 and y_hat.shape[1] == 1:
+        y = y_hat.reshape(y_hat.shape[0], y_hat.shape[2])
+    elif y_hat.dim() == 2:
+        y = y_hat
+    else:
+        raise ValueError('mel_loss: y_hat must be (B, L) or (B, 1, L)')
+    B, L = y.shape
+    want = (B, -1, num_mels) if frames_first else (B, num_mels, -1)
+    if y_mel.dim() != 3 or any(w >= 0 and s != w for s, w in zip(y_mel.shape, want)):
+        raise ValueError('mel_loss: y_mel must be (B, F_t, num_mels) when frames_first, else (B, num_mels, F_t)')
+    Ft = y_mel.shape[1] if frames_first else y_mel.shape[2]
+    if torch.is_grad_enabled() and y_mel.requires_grad:
+        raise NotImplementedError('mel_loss: the target y_mel is not differentiated')
+    F = mel_frames(L, g['n_fft'], g['hop'])
+    src = None
+    if lengths is not None:
+        src = check_lengths(lengths, B, L, len_mul)
+        if Ft < 1:
+            raise ValueError('mel_loss: y_mel holds no frame')
+    elif Ft < F:
+        raise ValueError(f'mel_loss: y_mel holds {Ft} frames, y_hat gives {F}')
+    if not (y.is_cuda and y_mel.is_cuda):
+        raise RuntimeError('mel_loss runs on the MI355X HIP path only (no CPU fallback)')
+    if y.device != y_mel.device:
+        raise ValueError('mel_loss: y_hat and y_mel must be on one device')
+    cfg = (n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax)
+    tgt = y_mel.detach().contiguous().float()
+    lens = None if src is None else _lengths_buffer(src, y.device)
+    args = (tgt, cfg, lens, int(len_mul), float(scale), bool(frames_first))
+    if torch.is_grad_enabled() and y.requires_grad:
+        total, per = _MelLossFn.apply(y, *args)
+    else:
+        with torch.no_grad():
+            spec, c, geom = _spectrum(y.detach().contiguous().float(), cfg, lens, int(len_mul))
+            total, per, _coef = _loss_launch(spec, c, geom, tgt, bool(frames_first), num_mels, lens, int(len_mul), float(scale))
+            total = total.reshape(())
+    return (total, per.detach()) if per_item else total
