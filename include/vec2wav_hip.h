@@ -592,8 +592,8 @@ int v2w_mel_finish(const float* spec, const float* basis, float* out, int B, int
  *   v2w_mel_phases_bwd: dxp (B, hop, FP) -> dy (B, L): every sample sums the padded positions that read it (reflections fold back).
  * Between them the DFT conv's input gradient is v2w_conv1d_fwd with the tap-flipped transposed weights and pad_left = k - 1.
  * V2W_E_ARG: a NULL operand, B <= 0, L <= 1, hop <= 0, pad < 0, pad >= L (the reflection needs more than pad samples), FP <= 0 (phases);
- * F <= 0, FP < F, nb <= 0, Cs < 2 * nb, n_mels <= 0 (finish).  V2W_E_SHAPE, nothing launched: hop * FP or L + 2 * pad past 2^31 - 1 (the three
- * phase calls index with int: the largest each takes is 2^31 - 1); nb > 1024 (v2w_mel_finish, _len) or nb + n_mels > 1024 (v2w_mel_finish_bwd):
+ * F <= 0, FP < F, nb <= 0, Cs < 2 * nb, n_mels <= 0 (finish).  V2W_E_SHAPE, nothing launched: B > 65535 (the grid's second dimension); hop * FP
+ * or L + 2 * pad past 2^31 - 1 (the phase calls index with int: the largest each takes is 2^31 - 1); nb > 1024 (v2w_mel_finish, _len) or nb + n_mels > 1024 (v2w_mel_finish_bwd):
  * 64 bytes of LDS per bin, and per mel in the backward, of 64 KiB; n_mels * 16 past 2^31 - 1; F * hop + n_fft past 2^31 - 1 (v2w_mel_finish_len). */
 int v2w_mel_finish_bwd(const float* spec, const float* basis, const float* basisT, const float* gout, float* dspec,
                        int B, int Cs, int FP, int F, int nb, int n_mels, void* stream);
@@ -615,7 +615,8 @@ int v2w_mel_phases_bwd(const float* dxp, float* dy, int B, int L, int hop, int p
 int v2w_mel_phases_len(const float* y, float* xp, int B, int L, int hop, int pad, int FP, const int32_t* len, int len_mul, void* stream);
 int v2w_mel_finish_len(const float* spec, const float* basis, float* out, int B, int Cs, int FP, int F, int nb, int n_mels,
                        const int32_t* len, int len_mul, int hop, int n_fft, void* stream);
-/* Any frame geometry (additive: the calls above keep their conditions, kernels and bits): 1 <= hop <= n_fft, 1 <= win <= n_fft.  The caller
+/* Any frame geometry: 1 <= hop <= n_fft, 1 <= win <= n_fft.  The calls above keep their conditions and their bits: they are the calls below at
+ * win = n_fft = 2 * pad + hop, left = 0, CP = hop, k = ceil(n_fft / hop), on the same kernels.  The caller
  * states every quantity; nothing is derived from another: pad samples of reflection per side (mel_spectrogram: (n_fft - hop) / 2 rounded
  * down), left = (n_fft - win) / 2 zero weights before the window, k = ceil(win / hop) taps, CP >= hop channels (rounded up to the tile
  * kernel's channel block), FP >= F + k - 1 columns.  Frame f multiplies the window's support only, ypad[f * hop + left + t] for t < win,
@@ -630,7 +631,7 @@ int v2w_mel_finish_len(const float* spec, const float* basis, float* out, int B,
  *                           (1 <= s <= pad), then its right one 2 (L - 1) - s + pad (L - 1 - pad <= s <= L - 2), added in that order; the
  *                           padded position i is dxp[b][(i - left) % hop][(i - left) / hop] for 0 <= i - left < hop * FP and 0 elsewhere.
  *   v2w_mel_finish_geo, _geo_bwd: v2w_mel_finish and v2w_mel_finish_bwd for every nb: where those fit their 16 frames per workgroup into
- *                           64 KiB of LDS they are called (the same kernel, the same bits); otherwise 8 frames per workgroup (nb = 1025:
+ *                           64 KiB of LDS, their launch (the same kernel, the same bits); otherwise 8 frames per workgroup (nb = 1025:
  *                           n_fft 2048), every output the same operations in the same order.
  *   v2w_mel_finish_geo_len: v2w_mel_finish_len with pad = (n_fft - hop) / 2 rounded down and no condition on n_fft % hop or its parity.
  * V2W_E_ARG: a NULL operand, B <= 0, L <= 1, hop < 1, n_fft < hop, win < 1, win > n_fft, CP < hop, pad < 0, pad >= L, left < 0,

@@ -1,5 +1,5 @@
-"""The cases of tests/test_mel_kernels_gpu.py: one record per geometry of the mel-spectrogram ends (csrc/v2w_mel.hip: six kernels behind seven
-entry points), with the kernel each entry must launch, its return code and its seeded data.
+"""The cases of tests/test_mel_kernels_gpu.py: one record per geometry of the mel-spectrogram ends (csrc/v2w_mel.hip: the six kernels its seven first
+entry points launch, each an instantiation of a device template that the v2w_mel_*_geo calls run too), with the kernel each entry must launch, its return code and its seeded data.
 
 tests/test_mel_ref_cpu.py drives every record through the name sink (host-only, made-up addresses) and asserts kernels and return codes; the
 GPU tests run the same records on guarded buffers.  `call` builds the arguments of both runs from one table of addresses.  The shapes are

@@ -1,4 +1,4 @@
-"""fp64 CPU statements of what the seven entry points of csrc/v2w_mel.hip compute, as include/vec2wav_hip.h words them (not as the kernels
+"""fp64 CPU statements of what the seven first entry points of csrc/v2w_mel.hip compute, as include/vec2wav_hip.h words them (not as the kernels
 index), and what each entry may differ by (tests/test_mel_kernels_gpu.py; the records are tests/mel_cases.py's).  Numpy throughout; torch
 only for the autograd that gives v2w_mel_finish_bwd its value.  Every function takes the fp32 operands of the call and returns
 (value, bound) per entry; bound None means the kernel moves or adds floats in a fixed order and is held bit for bit.

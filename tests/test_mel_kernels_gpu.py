@@ -1,4 +1,4 @@
-"""Every record of tests/mel_cases.py on the device: the six kernels of csrc/v2w_mel.hip behind their seven entry points, each against the fp64
+"""Every record of tests/mel_cases.py on the device: the six kernels of csrc/v2w_mel.hip that its seven first entry points launch, each against the fp64
 statement of its own operation (tests/mel_ref.py), per entry.  tests/test_mel_ref_cpu.py asserts which kernel each call launches.
 
 The two phase kernels and their adjoint move or add floats in a fixed order and are held bit for bit; the finish kernels and their backward

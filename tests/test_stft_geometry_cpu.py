@@ -146,9 +146,9 @@ def test_name_sink_reports_the_kernels_and_the_entry_points_refuse_bad_arguments
     # B, L, n_fft, win, hop, CP, pad, left, k, FP
     geo = dict(B=3, L=400, n_fft=128, win=100, hop=25, CP=32, pad=51, left=14, k=4, FP=20)
     ok = tuple(geo.values())
-    assert _names(lib.v2w_mel_phases_geo, A, Bp, *ok) == (0, ['mel_phase_geo_kernel<false>'])
-    assert _names(lib.v2w_mel_phases_geo_len, A, Bp, *ok, Cp, 1) == (0, ['mel_phase_geo_kernel<true>'])
-    assert _names(lib.v2w_mel_phases_geo_bwd, A, Bp, *ok) == (0, ['mel_phase_geo_bwd_kernel'])
+    assert _names(lib.v2w_mel_phases_geo, A, Bp, *ok) == (0, ['mel_phase_kernel'])
+    assert _names(lib.v2w_mel_phases_geo_len, A, Bp, *ok, Cp, 1) == (0, ['mel_phase_len_kernel'])
+    assert _names(lib.v2w_mel_phases_geo_bwd, A, Bp, *ok) == (0, ['mel_phase_bwd_kernel'])
     bad = [dict(B=0), dict(L=1), dict(hop=0), dict(hop=129), dict(win=0), dict(win=129), dict(CP=24), dict(pad=-1), dict(pad=400), dict(left=-1),
            dict(left=29), dict(k=0), dict(k=3), dict(FP=0)]
     for d in bad:

@@ -90,6 +90,45 @@ def test_phase_kernels(env, geo):
     assert _bits_equal(A['xp'].get(), S.phases_len(y, g, FP, lens)), name
 
 
+def test_first_phase_entry_points_are_the_geo_calls_at_their_geometry(env):
+    """128 / 32 / 128 (pad 48, CP 32, k 4): the four first phase entry points hand their hop, pad, FP to the kernels of the _geo calls as
+    left = 0, CP = hop, k = n_fft / hop, n_fft = 2 pad + hop.  Each pair bit for bit on guarded buffers; the lengths are full, pad + 1 and
+    between, NaN at and past every item's own end and, in dxp, wherever the forward reads nothing."""
+    dev, _hip, lib, st = env
+    from wavthruvec_pytorch_amd import mel
+    g = mel.stft_geometry(128, 32, 128)
+    assert (g['pad'], g['cp'], g['k'], g['left']) == (48, 32, 4, 0)
+    B, L, lens = 3, 200, [200, 49, 124]
+    FP = S.columns(L, g)
+    rng = np.random.default_rng(128)
+    y = rng.standard_normal((B, L)).astype(np.float32)
+    y_len = y.copy()
+    for b, n in enumerate(lens):
+        y_len[b, n:] = np.nan
+    dxp = rng.standard_normal((B, 32, FP)).astype(np.float32)
+    dxp[:, S.gather_map(L, g, FP)[0] < 0] = np.nan
+    ld = torch.tensor(lens, dtype=torch.int32, device=dev)
+    first, geo, tail = (B, L, 32, 48, FP), _geo_ints(g, B, L, FP), (ld.data_ptr(), 1)
+
+    def pair(what, src, out_shape, f_first, f_geo, *more):
+        A = dict(src=_inp(dev, src), a=_out(dev, *out_shape), b=_out(dev, *out_shape))
+        t = _addr(A)
+        assert _twice(A, what, lambda: (f_first(t['src'], t['a'], *first, *more, st), f_geo(t['src'], t['b'], *geo, *more, st))) == (OK, OK)
+        _kept(A, {'a', 'b'}, what)
+        assert _bits_equal(A['a'].get(), A['b'].get()), what
+        return A['a'].get()
+
+    xp = pair('phases', y, (B, 32, FP), lib.v2w_mel_phases, lib.v2w_mel_phases_geo)
+    assert _bits_equal(xp, S.phases(y, g, FP))
+    xp = pair('phases_len', y_len, (B, 32, FP), lib.v2w_mel_phases_len, lib.v2w_mel_phases_geo_len, *tail)
+    assert _bits_equal(xp, S.phases_len(y_len, g, FP, lens))
+    dy = pair('phases_bwd', dxp, (B, L), lib.v2w_mel_phases_bwd, lib.v2w_mel_phases_geo_bwd)
+    assert _bits_equal(dy, S.phases_bwd(dxp, L, g))
+    dy = pair('phases_len_bwd', dxp, (B, L), lib.v2w_mel_phases_len_bwd, lib.v2w_mel_phases_geo_len_bwd, *tail)
+    assert np.isfinite(dy).all() and _bits_equal(dy[0], S.phases_bwd(dxp, L, g)[0]) and not dy[1, 49:].any() and not dy[2, 124:].any()
+    assert ld.cpu().tolist() == lens
+
+
 # ---------------------------------------------------------------------------------------------------------------
 # 2. the finish calls
 def _finish_data(seed, B, nb, n_mels, F, FP, Cs):

@@ -144,6 +144,17 @@ __device__ __forceinline__ T v2w_block_sum(T v, T* red) {
     return t;
 }
 
+// ---- batches of unequal lengths in mel_spectrogram's framing: the frames item b counts, min(frames of len[b] * len_mul samples, F).
+// pad = (n_fft - hop) / 2 rounded down; reflect padding needs more than pad samples, one frame needs n_fft padded ones.  The sample count
+// stays in 64 bits, so every len[b] and len_mul >= 1 is taken as it is (negative: no frame) - the mel kernels and the masked L1 agree.
+__device__ __forceinline__ int v2w_item_frames(const int32_t* __restrict__ len, int b, int len_mul, int hop, int n_fft, int F) {
+    const int pad = (n_fft - hop) / 2;
+    const long long n = (long long)len[b] * len_mul;
+    if (n <= pad || n + 2 * pad < n_fft) return 0;
+    const long long fr = (n + 2 * pad - n_fft) / hop + 1;
+    return fr < F ? (int)fr : F;
+}
+
 // ---- bf16 storage format on raw words: element 0 of a packed pair is the low half
 __device__ __forceinline__ unsigned int v2w_bf16x2(float lo, float hi) {
     typedef __bf16 b2 __attribute__((ext_vector_type(2)));

@@ -175,18 +175,10 @@ lsgan_multi_bwd_kernel(const LsArgs A) {
     }
 }
 
-// ---- masked mel L1 of a batch of unequal lengths (v2w_l1_masked): a, b (B, C, F) dense; item b counts its first Fb frames.  An item is
+// ---- masked mel L1 of a batch of unequal lengths (v2w_l1_masked): a, b (B, C, F) dense; item b counts its first Fb = v2w_item_frames frames.  An item is
 // ceil(C * F / 4) units of four floats, shared out over the gridDim.x workgroups of its grid row; workgroup (g, b) writes part[b * G + g].
 constexpr int kMaskedUnitsPerWg = kThreads * kUnroll;
 constexpr int kMaskedMaxWgs = 256;
-
-__device__ __forceinline__ int masked_frames(const int32_t* __restrict__ len, int b, int len_mul, int hop, int n_fft, int F) {
-    const int pad = (n_fft - hop) / 2;
-    const long long n = (long long)len[b] * len_mul;
-    if (n <= pad || n + 2 * pad < n_fft) return 0;           // reflect padding needs more than pad samples; one frame needs n_fft padded ones
-    const long long fr = (n + 2 * pad - n_fft) / hop + 1;
-    return fr < F ? (int)fr : F;
-}
 
 // VEC: F % 4 == 0 and both pointers 16-byte aligned - a unit lies in one row and is one 16-byte load per side.  A masked element is
 // selected away (its load, where a unit straddles Fb, is discarded): nothing at or past Fb reaches the sum.
@@ -196,7 +188,7 @@ l1_masked_kernel(const float* __restrict__ a, const float* __restrict__ b, const
                  int C, int F, double* __restrict__ part) {
     __shared__ double red[16];
     const int item = blockIdx.y, G = gridDim.x;
-    const int Fb = masked_frames(len, item, len_mul, hop, n_fft, F);
+    const int Fb = v2w_item_frames(len, item, len_mul, hop, n_fft, F);
     const int n = C * F;
     const int units = (n + 3) >> 2;
     const int chunk = (units + G - 1) / G;
@@ -251,7 +243,7 @@ l1_masked_finish_kernel(const double* __restrict__ part, const int32_t* __restri
     __shared__ double red[16];
     double tot = 0.0, cnt = 0.0;
     for (int b = threadIdx.x; b < B; b += kThreads) {
-        const int Fb = masked_frames(len, b, len_mul, hop, n_fft, F);
+        const int Fb = v2w_item_frames(len, b, len_mul, hop, n_fft, F);
         double s = 0.0;
         for (int g = 0; g < G; ++g) s += part[(size_t)b * G + g];
         const double ne = (double)C * (double)Fb;

@@ -6,11 +6,11 @@ Mirror of the reference's `dataset.mel_spectrogram(y, n_fft, num_mels, sampling_
 back-propagates through it, train.py:204).
 
 The STFT runs as ONE fused Conv1d on the f32 MFMA tile kernel: the reflect-padded signal is de-interleaved by hop phase
-(`v2w_mel_phases`), the windowed DFT rows are the conv weights (hop input channels x n_fft/hop taps), and `v2w_mel_finish`
-does magnitude -> filterbank -> log.  That is the reference geometry 1024 / 256 / 1024 and its like (win_size == n_fft, n_fft % hop_size == 0,
-hop_size % 32 == 0).  Every other geometry with 1 <= hop_size <= n_fft, 1 <= win_size <= n_fft <= 2048 takes the `v2w_mel_*_geo` siblings of
-the two ends (`stft_geometry`): the conv then contracts over the window's support only - ceil(win_size / hop_size) taps over hop_size channels
-rounded up to 32, the first of them `left = (n_fft - win_size) // 2` samples into the frame.  Batches of unequal lengths (the reference's validation loop, batched: validate.py) take the per-item
+(`v2w_mel_phases_geo`), the windowed DFT rows are the conv weights, and `v2w_mel_finish_geo` does magnitude -> filterbank -> log, for any
+geometry with 1 <= hop_size <= n_fft, 1 <= win_size <= n_fft <= 2048 (`stft_geometry`): the conv contracts over the window's support only -
+ceil(win_size / hop_size) taps over hop_size channels rounded up to 32, the first of them `left = (n_fft - win_size) // 2` samples into the
+frame.  At the reference geometry 1024 / 256 / 1024 and its like (win_size == n_fft, n_fft % hop_size == 0, hop_size % 32 == 0) that is hop
+input channels x n_fft/hop taps, what the first entry points (`v2w_mel_phases`, `v2w_mel_finish`; kept for C callers) run on the same kernels.  Batches of unequal lengths (the reference's validation loop, batched: validate.py) take the per-item
 form of the two ends (`lengths=`) and the masked L1 `mel_l1`.  `mel_loss` is the training loss of train.py:172-176,204 in one call, the L1 fused
 into the finish kernel, with or without per-item lengths, forward and backward.  Constants (DFT rows, hann window, Slaney mel filterbank = librosa.filters.mel of the
 reference's librosa, restated because librosa is not a dependency here) are built once per configuration with numpy in fp64.
@@ -68,7 +68,8 @@ def stft_geometry(n_fft, hop_size, win_size):
       k     taps of the DFT conv: frame f multiplies ypad[f * hop + left + t] for t < win_size only, so k = ceil(win_size / hop_size)
       cp    its input channels: hop_size rounded up to CHANNEL_BLOCK; the channels [hop_size, cp) are zeros on both operands
       nb    bins, n_fft // 2 + 1;  cs: the 2 nb DFT rows rounded up to the conv tile's row block (64)
-      old   win_size == n_fft, n_fft % hop_size == 0, hop_size % 32 == 0: the geometries the first entry points serve (and keep serving)"""
+      old   win_size == n_fft, n_fft % hop_size == 0, hop_size % 32 == 0: the geometries the first entry points serve (cp == hop_size, left == 0,
+            k == n_fft / hop_size: the same kernels, the same bits); here it only selects `_dft_conv_bwd`'s one-launch form"""
     n_fft, hop, win = int(n_fft), int(hop_size), int(win_size)
     if not 1 <= n_fft <= MAX_N_FFT:
         raise ValueError(f'mel_spectrogram (HIP): needs 1 <= n_fft <= {MAX_N_FFT}, got n_fft = {n_fft}')
@@ -157,41 +158,43 @@ def _lengths_buffer(src, device):
     return buf
 
 
-def _geo_args(c, B, L, FP):
-    """The leading integers of the three v2w_mel_phases_geo* calls."""
-    return B, L, c['n_fft'], c['win'], c['hop'], c['cp'], c['pad'], c['left'], c['k'], FP
+def _frame_counts(c, L, who):
+    """-> (F, FP): the frames of a signal of L samples and the columns of its phase buffer, with the two conditions on the length."""
+    pad = c['pad']
+    if pad >= L:
+        raise RuntimeError(f'{who}: reflect padding needs more than (n_fft - hop)/2 samples')
+    if L + 2 * pad < c['n_fft']:
+        raise RuntimeError(f'{who}: the padded signal is shorter than one frame of n_fft samples')
+    F = (L + 2 * pad - c['n_fft']) // c['hop'] + 1
+    return F, (F + c['k'] - 1 + 3) // 4 * 4
+
+
+_PHASES = {(False, False): 'v2w_mel_phases_geo', (True, False): 'v2w_mel_phases_geo_len',
+           (False, True): 'v2w_mel_phases_geo_bwd', (True, True): 'v2w_mel_phases_geo_len_bwd'}       # (lengths, backward)
+
+
+def _phases(lib, st, c, src, dst_ptr, B, L, FP, lens=None, len_mul=1, bwd=False):
+    """One phase launch on the caller's library handle and stream.  Forward: src = y (B, L) -> xp (B, cp, FP) at dst_ptr; backward: src = dxp
+    -> dy (B, L).  lens (B int32 on the device): the per-item form."""
+    name = _PHASES[lens is not None, bwd]
+    tail = () if lens is None else (lens.data_ptr(), len_mul)
+    _hip.check(getattr(lib, name)(src.data_ptr(), dst_ptr, B, L, c['n_fft'], c['win'], c['hop'], c['cp'], c['pad'], c['left'], c['k'], FP,
+                                  *tail, st), name)
 
 
 def _spectrum(y, cfg, lens=None, len_mul=1):
     """-> (spec, constants, geometry): the first two launches of the forward, the phases step and the DFT conv.  lens (B int32 on the device):
-    the per-item form of the phases step; the DFT conv runs on the whole padded batch either way.  A geometry the first entry points serve
-    (stft_geometry: `old`) keeps them, and with them its bits; the others take the v2w_mel_*_geo calls."""
+    the per-item form of the phases step; the DFT conv runs on the whole padded batch either way."""
     n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax = cfg
     B, L = y.shape
     c = _constants(n_fft, num_mels, sampling_rate, hop_size, win_size, fmin, fmax, y.device)
-    pad, hop = c['pad'], c['hop']
-    if pad >= L:
-        raise RuntimeError('mel_spectrogram: reflect padding needs more than (n_fft - hop)/2 samples')
-    if L + 2 * pad < c['n_fft']:
-        raise RuntimeError('mel_spectrogram: the padded signal is shorter than one frame of n_fft samples')
-    F = (L + 2 * pad - c['n_fft']) // hop + 1
-    FP = (F + c['k'] - 1 + 3) // 4 * 4
+    F, FP = _frame_counts(c, L, 'mel_spectrogram')
     lib, st = _hip.load(), torch.cuda.current_stream(y.device).cuda_stream
     xp = torch.empty((B, c['cp'], FP), device=y.device)
-    if c['old']:
-        if lens is None:
-            _hip.check(lib.v2w_mel_phases(y.data_ptr(), xp.data_ptr(), B, L, hop, pad, FP, st), 'v2w_mel_phases')
-        else:
-            _hip.check(lib.v2w_mel_phases_len(y.data_ptr(), xp.data_ptr(), B, L, hop, pad, FP, lens.data_ptr(), len_mul, st),
-                       'v2w_mel_phases_len')
-    elif lens is None:
-        _hip.check(lib.v2w_mel_phases_geo(y.data_ptr(), xp.data_ptr(), *_geo_args(c, B, L, FP), st), 'v2w_mel_phases_geo')
-    else:
-        _hip.check(lib.v2w_mel_phases_geo_len(y.data_ptr(), xp.data_ptr(), *_geo_args(c, B, L, FP), lens.data_ptr(), len_mul, st),
-                   'v2w_mel_phases_geo_len')
+    _phases(lib, st, c, y, xp.data_ptr(), B, L, FP, lens, len_mul)
     spec = torch.empty((B, c['cs'], FP), device=y.device)
     hipops.conv1d(xp, c['wf'], None, spec, k=c['k'], dil=1, slope=1.0, pad_left=0, wp=c['wp'])
-    return spec, c, (B, L, pad, F, FP)
+    return spec, c, (B, L, c['pad'], F, FP)
 
 
 def _forward(y, cfg, lens=None, len_mul=1):
@@ -199,17 +202,13 @@ def _forward(y, cfg, lens=None, len_mul=1):
     ends (forward only)."""
     num_mels = cfg[1]
     spec, c, (B, L, pad, F, FP) = _spectrum(y, cfg, lens, len_mul)
-    hop = c['hop']
     lib, st = _hip.load(), torch.cuda.current_stream(y.device).cuda_stream
     out = torch.empty((B, num_mels, F), device=y.device)
-    old = c['old'] and c['nb'] * 64 <= 65536                  # (16 frames x 4 bytes per bin of the first kernels' LDS block)
     fin = (spec.data_ptr(), c['basis'].data_ptr(), out.data_ptr(), B, c['cs'], FP, F, c['nb'], num_mels)
     if lens is None:
-        name = 'v2w_mel_finish' if old else 'v2w_mel_finish_geo'
-        _hip.check(getattr(lib, name)(*fin, st), name)
+        _hip.check(lib.v2w_mel_finish_geo(*fin, st), 'v2w_mel_finish_geo')
     else:
-        name = 'v2w_mel_finish_len' if old else 'v2w_mel_finish_geo_len'
-        _hip.check(getattr(lib, name)(*fin, lens.data_ptr(), len_mul, hop, c['n_fft'], st), name)
+        _hip.check(lib.v2w_mel_finish_geo_len(*fin, lens.data_ptr(), len_mul, c['hop'], c['n_fft'], st), 'v2w_mel_finish_geo_len')
     return out, spec, (B, L, pad, F, FP)
 
 
@@ -255,9 +254,8 @@ def _backward(g, spec, geom, cfg):
     lib, st = _hip.load(), torch.cuda.current_stream(dev).cuda_stream
     g = g.contiguous().float()
     dspec = torch.zeros_like(spec)
-    name = 'v2w_mel_finish_bwd' if c['old'] and (c['nb'] + num_mels) * 64 <= 65536 else 'v2w_mel_finish_geo_bwd'
-    _hip.check(getattr(lib, name)(spec.data_ptr(), c['basis'].data_ptr(), c['basisT'].data_ptr(), g.data_ptr(), dspec.data_ptr(),
-                                  B, c['cs'], FP, F, c['nb'], num_mels, st), name)
+    _hip.check(lib.v2w_mel_finish_geo_bwd(spec.data_ptr(), c['basis'].data_ptr(), c['basisT'].data_ptr(), g.data_ptr(), dspec.data_ptr(),
+                                          B, c['cs'], FP, F, c['nb'], num_mels, st), 'v2w_mel_finish_geo_bwd')
     return _spectrum_backward(c, dspec, geom)
 
 
@@ -270,17 +268,7 @@ def _spectrum_backward(c, dspec, geom, lens=None, len_mul=1, by_rows=False):
     dxp = torch.empty((B, c['cp'], FP), device=dev)
     _dft_conv_bwd(c, dspec, dxp, by_rows)
     dy = torch.empty((B, L), device=dev)
-    if c['old']:
-        if lens is None:
-            _hip.check(lib.v2w_mel_phases_bwd(dxp.data_ptr(), dy.data_ptr(), B, L, c['hop'], pad, FP, st), 'v2w_mel_phases_bwd')
-        else:
-            _hip.check(lib.v2w_mel_phases_len_bwd(dxp.data_ptr(), dy.data_ptr(), B, L, c['hop'], pad, FP, lens.data_ptr(), len_mul, st),
-                       'v2w_mel_phases_len_bwd')
-    elif lens is None:
-        _hip.check(lib.v2w_mel_phases_geo_bwd(dxp.data_ptr(), dy.data_ptr(), *_geo_args(c, B, L, FP), st), 'v2w_mel_phases_geo_bwd')
-    else:
-        _hip.check(lib.v2w_mel_phases_geo_len_bwd(dxp.data_ptr(), dy.data_ptr(), *_geo_args(c, B, L, FP), lens.data_ptr(), len_mul, st),
-                   'v2w_mel_phases_geo_len_bwd')
+    _phases(lib, st, c, dxp, dy.data_ptr(), B, L, FP, lens, len_mul, bwd=True)
     return dy
 
 
@@ -349,7 +337,6 @@ def mel_l1(a, b, lengths, len_mul=1, *, n_fft, hop_size):
     if a.dim() != 3 or a.shape != b.shape or a.device != b.device:
         raise ValueError('mel_l1: a and b must be (B, num_mels, F) tensors of one shape on one device')
     B, Cm, F = a.shape
-    old = n_fft % hop_size == 0 and (n_fft - hop_size) % 2 == 0           # what v2w_l1_masked takes; the same kernels either way
     len_mul = int(len_mul)
     src = check_lengths(lengths, B, None, len_mul)          # (frame counts past F are clamped to F)
     with torch.no_grad():
@@ -362,9 +349,8 @@ def mel_l1(a, b, lengths, len_mul=1, *, n_fft, hop_size):
         ws = torch.empty((B * G,), dtype=torch.float64, device=a.device)
         per_item = torch.empty((B,), device=a.device)
         total = torch.empty((1,), device=a.device)
-        name = 'v2w_l1_masked' if old else 'v2w_l1_masked_geo'
-        _hip.check(getattr(lib, name)(a.data_ptr(), b.data_ptr(), B, Cm, F, lens.data_ptr(), len_mul, hop_size, n_fft,
-                                      per_item.data_ptr(), total.data_ptr(), ws.data_ptr(), st), name)
+        _hip.check(lib.v2w_l1_masked_geo(a.data_ptr(), b.data_ptr(), B, Cm, F, lens.data_ptr(), len_mul, hop_size, n_fft,
+                                         per_item.data_ptr(), total.data_ptr(), ws.data_ptr(), st), 'v2w_l1_masked_geo')
     return total[0], per_item
 
 

@@ -28,16 +28,6 @@ def _constants(res, device):
     return mel._constants(n_fft, _MEL[0], _MEL[1], hop, win, 0, None, device)
 
 
-def _frames(c, L):
-    """-> (F, FP) as mel._forward counts them, with its two conditions on the length."""
-    if c['pad'] >= L:
-        raise RuntimeError('stft_loss: reflect padding needs more than (n_fft - hop)/2 samples')
-    if L + 2 * c['pad'] < c['n_fft']:
-        raise RuntimeError('stft_loss: the padded signal is shorter than one frame of n_fft samples')
-    F = (L + 2 * c['pad'] - c['n_fft']) // c['hop'] + 1
-    return F, (F + c['k'] - 1 + 3) // 4 * 4
-
-
 FWD_CHANNELS = 64      # input channels (hop phases) per launch of the forward DFT conv (see _dft_conv_fwd)
 
 
@@ -63,16 +53,6 @@ def _dft_conv_fwd(c, xp, spec):
         hipops.conv1d(xp[:, p:p + FWD_CHANNELS], w, None, spec, k=k, dil=1, slope=1.0, pad_left=0, wp=wp, in_ct=cp, accumulate=i > 0)
 
 
-def _phases(lib, st, c, src, dst_ptr, B, L, FP, bwd=False):
-    """One phase launch, chosen as mel._forward / mel._backward choose it (forward: src (B, L) -> xp at dst_ptr; backward: dxp -> dy)."""
-    tail = '_bwd' if bwd else ''
-    if c['old']:
-        _hip.check(getattr(lib, 'v2w_mel_phases' + tail)(src.data_ptr(), dst_ptr, B, L, c['hop'], c['pad'], FP, st), 'v2w_mel_phases' + tail)
-    else:
-        _hip.check(getattr(lib, 'v2w_mel_phases_geo' + tail)(src.data_ptr(), dst_ptr, *mel._geo_args(c, B, L, FP), st),
-                   'v2w_mel_phases_geo' + tail)
-
-
 def _items(cs, specs, B, geoms, dspecs=None):
     arr = (_hip.StftLossItem * len(cs))()
     for i, (d, c, spec, (F, FP)) in enumerate(zip(arr, cs, specs, geoms)):
@@ -88,12 +68,12 @@ def _forward(x, y, resolutions):
     dev = x.device
     lib, st = _hip.load(), torch.cuda.current_stream(dev).cuda_stream
     cs = [_constants(r, dev) for r in resolutions]
-    geoms = [_frames(c, L) for c in cs]
+    geoms = [mel._frame_counts(c, L, 'stft_loss') for c in cs]
     specs = []
     for c, (F, FP) in zip(cs, geoms):
         xp = torch.empty((2 * B, c['cp'], FP), device=dev)
-        _phases(lib, st, c, x, xp.data_ptr(), B, L, FP)
-        _phases(lib, st, c, y, xp[B:].data_ptr(), B, L, FP)
+        mel._phases(lib, st, c, x, xp.data_ptr(), B, L, FP)
+        mel._phases(lib, st, c, y, xp[B:].data_ptr(), B, L, FP)
         spec = torch.empty((2 * B, c['cs'], FP), device=dev)
         _dft_conv_fwd(c, xp, spec)
         specs.append(spec)
@@ -123,7 +103,7 @@ def _backward(g_sc, g_mag, sums, specs, geoms, resolutions, B, L):
         dxp = torch.empty((B, c['cp'], FP), device=dev)
         mel._dft_conv_bwd(c, dspec, dxp)
         d = torch.empty((B, L), device=dev)
-        _phases(lib, st, c, dxp, d.data_ptr(), B, L, FP, bwd=True)
+        mel._phases(lib, st, c, dxp, d.data_ptr(), B, L, FP, bwd=True)
         dx = d if dx is None else dx.add_(d)
     return dx
 
