@@ -19,7 +19,7 @@ OBJ_DIR = os.path.join(CSRC, '_obj')
 LIB_PATH = os.path.join(PKG_DIR, 'libvec2wav_hip.so')
 SOURCES = ['v2w_api.hip', 'v2w_conv_mfma.hip', 'v2w_conv_split.hip', 'v2w_conv_bf16.hip', 'v2w_conv_bf16_res.hip', 'v2w_convt_bf16_res.hip', 'v2w_stage_split.hip', 'v2w_stage_bf16.hip', 'v2w_stage_bf16_wide.hip', 'v2w_stage_bf16_n16.hip', 'v2w_stage_bf16_n16s.hip', 'v2w_stage_bf16_n32s.hip', 'v2w_resblock_fused.hip', 'v2w_stage_small.hip',
            'v2w_wgrad.hip', 'v2w_wgrad_bf16.hip', 'v2w_backward.hip', 'v2w_direct.hip', 'v2w_conv_post_bf16.hip', 'v2w_cbn.hip', 'v2w_fold.hip', 'v2w_mel.hip', 'v2w_disc.hip', 'v2w_conv_wino.hip', 'v2w_loss.hip', 'v2w_optim.hip', 'v2w_sn.hip', 'v2w_stft_loss.hip', 'v2w_resample.hip']
-HEADERS = ['v2w_common.h', 'v2w_tile.h', 'v2w_internal.h', 'v2w_wino.h', 'v2w_multi.h', os.path.join('..', '..', 'include', 'vec2wav_hip.h')]
+HEADERS = ['v2w_common.h', 'v2w_tile.h', 'v2w_bf16_tile.h', 'v2w_internal.h', 'v2w_wino.h', 'v2w_multi.h', os.path.join('..', '..', 'include', 'vec2wav_hip.h')]
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC']
 
 

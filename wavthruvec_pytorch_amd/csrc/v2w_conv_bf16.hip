@@ -22,7 +22,7 @@
 // The older split kernel (v2w_conv_split.hip, one workgroup barrier per (16-channel chunk, tap) stage) stays the f16x3 path; in bf16
 // mode a stage of it was 128 cycles of MFMA issue in ~1300 cycles.
 #include <type_traits>
-#include "v2w_tile.h"
+#include "v2w_bf16_tile.h"
 #include "v2w_internal.h"
 
 namespace {
@@ -188,15 +188,12 @@ conv_bf16_kernel(const MultiArgs m) {
 
     // ---- B operands: one 16-byte fragment per column block, refilled right after its last use in the running k-step
     u32x4 bb[NI];
-    auto mfma = [&](acc_t c, u32x4 a, u32x4 bfrag) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(b8, a), __builtin_bit_cast(b8, bfrag), c, 0, 0, 0);
-    };
     // one k-step: MI x NI MFMAs; `nxt` = this lane's 16 bytes of the NEXT k-step (same rows + 32 bytes, or the next tap's rows)
     auto kstep = [&](const u32x4 (&a)[MI], const unsigned char* nxt) {
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
 #pragma unroll
-            for (int i = 0; i < MI; ++i) acc[i][j] = mfma(acc[i][j], a[i], bb[j]);
+            for (int i = 0; i < MI; ++i) acc[i][j] = v2w_mfma_bf16_32(acc[i][j], a[i], bb[j]);
             bb[j] = *reinterpret_cast<const u32x4*>(nxt + j * 32 * ROWB);
         }
         __builtin_amdgcn_sched_barrier(0);

@@ -24,7 +24,7 @@
 // Weights: the fragments of v2w_pack_bf16 / v2w_split_pack_batch, straight from L2 through a four-slot register ring (as the chunk
 // kernel's PAIRS form: the tile's taps in pairs, fragments three k-steps ahead).
 #include <type_traits>
-#include "v2w_tile.h"
+#include "v2w_bf16_tile.h"
 
 namespace {
 
@@ -104,8 +104,7 @@ conv_bf16_res_kernel(const ResArgs a) {
         in_img[s] = pq < nq;
         const int pos = pos0 + pq * 4;
         in_seq[s] = in_img[s] && pos >= 0 && pos < L;           // L % 4 == 0 and pos % 4 == 0: a quad is inside or outside as a whole
-        poff[s] = (unsigned)(4 * scq[s] * L + (in_seq[s] ? pos : 0)) * 2u;
-        asm volatile("" : "+v"(poff[s]));
+        poff[s] = v2w_item_off(4 * scq[s] * L, in_seq[s], pos);
     }
     auto prefetch = [&](const unsigned short* in, int ch, u32x2 (&pf)[NPF][4]) {
 #pragma unroll
@@ -135,18 +134,8 @@ conv_bf16_res_kernel(const ResArgs a) {
             // slot (cq >> 1) of the row, swizzled by (row >> 2) & 3 - the same for the item's four rows
             unsigned char* dst = plane + row * 64 + ((((cq >> 1) ^ ((row >> 2) & 3)) << 4) | ((cq & 1) << 3));
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float v[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float xv = (e & 1) ? v2w_bf16_hi(pf[s][i][e >> 1]) : v2w_bf16_lo(pf[s][i][e >> 1]);
-                    if constexpr (MODE == 0) xv = fmaf(av[i], xv, sv[i]);
-                    v[i] = v2w_lrelu(xv, slope);
-                }
-                u32x2 w = {v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
-                if (!in_seq[s]) w = u32x2{0u, 0u};            // the padding of the ACTIVATED signal is exactly 0
-                *reinterpret_cast<u32x2*>(dst + e * 64) = w;
-            }
+            for (int e = 0; e < 4; ++e)         // (mode 1: no affine, av / sv are not read)
+                *reinterpret_cast<u32x2*>(dst + e * 64) = v2w_item_row<MODE == 0>(e, pf[s], av, sv, slope, in_seq[s]);
         }
     };
     // mode 1 stages under live accumulators: ONE plane of registers, item s of plane ch + 1 requested as soon as item s of plane ch is
@@ -204,9 +193,6 @@ conv_bf16_res_kernel(const ResArgs a) {
     acc_t acc[MI][NI];
     const unsigned lane16 = (unsigned)lane * 16u;
     u32x4 bb[1][NI];
-    auto mfma = [&](acc_t c, u32x4 av, u32x4 bv) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(b8, av), __builtin_bit_cast(b8, bv), c, 0, 0, 0);
-    };
     // one k-step: MI x NI MFMAs; `nxt` = this lane's 16 bytes, in column block 0 (the blocks are 2 KiB apart), of the k-step that operand
     // set `bs` serves next
     auto kstep = [&](auto bs_c, const u32x4 (&av)[MI], unsigned nxt) {
@@ -214,7 +200,7 @@ conv_bf16_res_kernel(const ResArgs a) {
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
 #pragma unroll
-            for (int i = 0; i < MI; ++i) acc[i][j] = mfma(acc[i][j], av[i], bb[bs][j]);
+            for (int i = 0; i < MI; ++i) acc[i][j] = v2w_mfma_bf16_32(acc[i][j], av[i], bb[bs][j]);
             bb[bs][j] = *reinterpret_cast<const u32x4*>(smem_r + nxt + j * 2048);
         }
         __builtin_amdgcn_sched_barrier(0);

@@ -22,7 +22,7 @@
 //     per wave, every weight fragment feeds two MFMAs, every staged input tile serves 128 channels instead of 32.  Accumulators start at the
 //     bias; the epilogue passes 32 positions at a time through a wave-private scratch [32 channels][5 x 32 outputs] (over the dead tile).
 #include <type_traits>
-#include "v2w_tile.h"
+#include "v2w_bf16_tile.h"
 #include "v2w_internal.h"
 
 namespace {
@@ -93,8 +93,7 @@ convt_bf16_res_kernel(const CtArgs a) {
             in_img[s] = pq < nq;
             const int pos = pos0 + pq * 4;
             in_seq[s] = in_img[s] && pos >= 0 && pos < L;
-            poff[s] = (unsigned)(4 * cq * L + (in_seq[s] ? pos : 0)) * 2u;
-            asm volatile("" : "+v"(poff[s]));
+            poff[s] = v2w_item_off(4 * cq * L, in_seq[s], pos);
         }
         auto prefetch = [&](int ch, u32x2 (&pf)[NPF][4]) {
 #pragma unroll
@@ -159,9 +158,6 @@ convt_bf16_res_kernel(const CtArgs a) {
             }
     {
         const unsigned lane16 = (unsigned)lane * 16u;
-        auto mfma = [&](acc_t c, u32x4 av, u32x4 bv) {
-            return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(b8, av), __builtin_bit_cast(b8, bv), c, 0, 0, 0);
-        };
         auto baddr = [&](int ch, int row) { return (unsigned)(ch * psz + row * 64 + ((hk ^ ((row >> 2) & 3)) << 4)); };
         const int K = KV;
         const int nst = 2 * nch * K;
@@ -201,7 +197,7 @@ convt_bf16_res_kernel(const CtArgs a) {
 #pragma unroll
             for (int j = 0; j < NI; ++j) {
 #pragma unroll
-                for (int i = 0; i < MI; ++i) acc[i][j] = mfma(acc[i][j], av[i], bb[bs][j]);
+                for (int i = 0; i < MI; ++i) acc[i][j] = v2w_mfma_bf16_32(acc[i][j], av[i], bb[bs][j]);
                 bb[bs][j] = *reinterpret_cast<const u32x4*>(smem_c + nxt + j * 2048);
             }
             __builtin_amdgcn_sched_barrier(0);

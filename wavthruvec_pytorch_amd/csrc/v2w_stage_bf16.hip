@@ -12,6 +12,7 @@
 //   * C = 16 uses the 32-row MFMA with the packed fragments' rows 16-31 zero (the pipe is idle most of the time anyway).
 // Weights: the bf16 fragments of v2w_pack_bf16 / v2w_split_pack_batch, [16-channel k-step][tap][2 KiB, first KiB used].
 #include <type_traits>
+#include "v2w_bf16_tile.h"
 #include "v2w_internal.h"
 
 namespace {
@@ -98,8 +99,7 @@ stage_bf16_kernel(const StageBfArgs p) {
             const int pq = (tid + s * NTHREADS) / NCQ;
             const int pos = pos0 + pq * 4;
             const bool ok = pq < xr4 && pos >= 0 && pos < L;
-            unsigned vo = (unsigned)(4 * cq * L + (ok ? pos : 0)) * ESI;
-            asm volatile("" : "+v"(vo));
+            const unsigned vo = v2w_item_off<ESI>(4 * cq * L, ok, pos);
 #pragma unroll
             for (int i = 0; i < 4; ++i) g[s][i] = *reinterpret_cast<const ld_t*>(inb + (size_t)i * L * ESI + vo);
         }
@@ -239,7 +239,7 @@ stage_bf16_kernel(const StageBfArgs p) {
                     const unsigned char* nxt = rows(q + 2);
 #pragma unroll
                     for (int j = 0; j < NI; ++j) {
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(b8, wa[q & 1]), __builtin_bit_cast(b8, bb[q & 1][j]), acc[j], 0, 0, 0);
+                        acc[j] = v2w_mfma_bf16_32(acc[j], wa[q & 1], bb[q & 1][j]);
                         bb[q & 1][j] = *reinterpret_cast<const u32x4*>(nxt + j * 32 * ROWB);
                     }
                     wa[q & 1] = *reinterpret_cast<const u32x4*>(wq + (q + 2 < KMAX * KS ? q + 2 : q) * 1024);   // (stale past K * KS: unused)
@@ -383,16 +383,11 @@ int launch_stage_bf16(const v2w_stage_split_args* q, hipStream_t stream) {
     constexpr int W = 256, ROWB = C == 32 ? 80 : 48;
     StageBfArgs p{};
     p.in = q->in; p.in_a = q->in_a; p.in_s = q->in_s; p.out = q->out;
-    p.nk = q->nk; p.B = q->B; p.L = q->L; p.slope = q->slope; p.out_div = q->out_div;
-    for (int j = 0; j < q->nk; ++j) {
-        p.w1[j] = static_cast<const unsigned char*>(q->wps1[j]); p.bias1[j] = q->bias1[j];
-        p.w2[j] = static_cast<const unsigned char*>(q->wps2[j]); p.bias2[j] = q->bias2[j];
-        p.K[j] = q->k[j]; p.d1[j] = q->dil1[j]; p.d2[j] = q->dil2[j];
-        if (q->k[j] > V2W_SB_KMAX) return V2W_E_SHAPE;
-        const int h1 = q->dil1[j] * (q->k[j] - 1) / 2, h2 = q->dil2[j] * (q->k[j] - 1) / 2;
-        if (h1 > p.h1max) p.h1max = h1;
-        if (h2 > p.h2max) p.h2max = h2;
-    }
+    p.B = q->B; p.L = q->L; p.slope = q->slope; p.out_div = q->out_div;
+    const StageBfBranches br = v2w_stage_bf_branches(q);
+    v2w_put_branch_ptrs<V2W_SB_MAXB>(p, br);
+    v2w_put_branch_geom(p, br);
+    for (int j = 0; j < q->nk; ++j) if (q->k[j] > V2W_SB_KMAX) return V2W_E_SHAPE;
     p.nto = (W - 2 * p.h2max) & ~3;
     if (p.nto < W / 2 || p.h1max > 32) return V2W_E_SHAPE;
     const int hsum = p.h1max + p.h2max;

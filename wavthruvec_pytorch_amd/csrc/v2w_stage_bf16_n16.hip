@@ -17,7 +17,7 @@
 // One operand read per MFMA is exactly the LDS's 256 B / clk / CU: the conv loops are LDS-bound (~0.13 ms at configs[2]), not weight-bound.
 #include <type_traits>
 #include <utility>
-#include "v2w_tile.h"
+#include "v2w_bf16_tile.h"
 #include "v2w_internal.h"
 
 namespace {
@@ -90,9 +90,6 @@ n16_stage_kernel(const N16Args a) {
         b2s[r] = s2;
     }
 
-    auto mfma = [&](f32x4 c, u32x4 av, u32x4 bv) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, av), __builtin_bit_cast(b8, bv), c, 0, 0, 0);
-    };
     const int col0 = 128 * wave + j;                                            // this lane's column in block 0 of its wave
     // one conv over a resident tile: K taps at dilation DIL, pairs P0 .. of weight set S; r0 = tile row of (column col0, tap 0)
     // The loop is ONE sequence of (pair, block) steps with a ring of RING operands in flight, written in inline assembly: left to itself hipcc
@@ -116,11 +113,11 @@ n16_stage_kernel(const N16Args a) {
             if constexpr (2 * p + 1 >= K) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[n]) : "v"(ab), "n"((2 * p * DIL + 16 * cb) * RB));
             else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[n]) : "v"(ab2), "n"((2 * p * DIL + 16 * cb) * RB));
         });
-        v2w_static_for(std::make_integer_sequence<int, N>{}, [&ring, &ab, &ab2, &acc, &wa, &mfma](auto n_c) {
+        v2w_static_for(std::make_integer_sequence<int, N>{}, [&ring, &ab, &ab2, &acc, &wa](auto n_c) {
             constexpr int n = decltype(n_c)::value;
             constexpr int left = (N - 1 - n) < (RING - 1) ? (N - 1 - n) : (RING - 1);
             asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(ring[n % RING]) : "n"(left));
-            acc[n % NB] = mfma(acc[n % NB], wa[S][P0 + n / NB], ring[n % RING]);
+            acc[n % NB] = v2w_mfma_bf16_16(acc[n % NB], wa[S][P0 + n / NB], ring[n % RING]);
             if constexpr (n + RING < N) {
                 constexpr int m = n + RING, p = m / NB, cb = m % NB;
                 if constexpr (2 * p + 1 >= K) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[n % RING]) : "v"(ab), "n"((2 * p * DIL + 16 * cb) * RB));
@@ -144,8 +141,7 @@ n16_stage_kernel(const N16Args a) {
             const int idx = tid + s * NTH, pq = idx >> 2;
             const int pos = pos0 + 4 * pq;
             const bool ok = idx < NIT && pos >= 0 && pos < L;
-            unsigned vo = (unsigned)(4 * cq * L + (ok ? pos : 0)) * 2u;
-            asm volatile("" : "+v"(vo));
+            const unsigned vo = v2w_item_off(4 * cq * L, ok, pos);
 #pragma unroll
             for (int i = 0; i < 4; ++i) pf[s][i] = *gptr<const u32x2>(inb + (size_t)i * L * 2 + vo);
         }
@@ -356,10 +352,7 @@ int launch_n16(const v2w_stage_split_args* q, hipStream_t stream) {
     N16Args p{};
     p.in = reinterpret_cast<const unsigned short*>(q->in); p.in_a = q->in_a; p.in_s = q->in_s;
     p.out = reinterpret_cast<unsigned short*>(q->out);
-    for (int j = 0; j < 3; ++j) {
-        p.w1[j] = static_cast<const unsigned char*>(q->wps1[j]); p.bias1[j] = q->bias1[j];
-        p.w2[j] = static_cast<const unsigned char*>(q->wps2[j]); p.bias2[j] = q->bias2[j];
-    }
+    v2w_put_branch_ptrs<3>(p, v2w_stage_bf_branches(q));
     p.B = q->B; p.L = q->L; p.slope = q->slope; p.inv_slope = 1.f / q->slope; p.out_div = q->out_div;
     p.nto = (W - 2 * N16_H2) & ~3;
     p.nadv = p.nto; p.hout = 0;
@@ -441,9 +434,6 @@ n16_pair_kernel(const N16PairArgs a) {
         b1[r] = a.bias1 ? a.bias1[4 * kg + r] : 0.f;
         b2[r] = a.bias2 ? a.bias2[4 * kg + r] : 0.f;
     }
-    auto mfma = [&](f32x4 c, u32x4 av, u32x4 bv) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, av), __builtin_bit_cast(b8, bv), c, 0, 0, 0);
-    };
     const int col0 = 128 * wave + j;
     const unsigned lds0 = (unsigned)reinterpret_cast<uintptr_t>(smem_n);
     // (the conv loop of n16_stage_kernel: a ring of 8 operands in flight, every offset an immediate)
@@ -461,11 +451,11 @@ n16_pair_kernel(const N16PairArgs a) {
             if constexpr (2 * p + 1 >= K) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[n]) : "v"(ab), "n"((2 * p * DIL + 16 * cb) * RB));
             else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[n]) : "v"(ab2), "n"((2 * p * DIL + 16 * cb) * RB));
         });
-        v2w_static_for(std::make_integer_sequence<int, N>{}, [&ring, &ab, &ab2, &acc, &wa, &mfma](auto n_c) {
+        v2w_static_for(std::make_integer_sequence<int, N>{}, [&ring, &ab, &ab2, &acc, &wa](auto n_c) {
             constexpr int n = decltype(n_c)::value;
             constexpr int left = (N - 1 - n) < (RING - 1) ? (N - 1 - n) : (RING - 1);
             asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(ring[n % RING]) : "n"(left));
-            acc[n % NB] = mfma(acc[n % NB], wa[S][n / NB], ring[n % RING]);
+            acc[n % NB] = v2w_mfma_bf16_16(acc[n % NB], wa[S][n / NB], ring[n % RING]);
             if constexpr (n + RING < N) {
                 constexpr int m = n + RING, p = m / NB, cb = m % NB;
                 if constexpr (2 * p + 1 >= K) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[n % RING]) : "v"(ab), "n"((2 * p * DIL + 16 * cb) * RB));
@@ -487,8 +477,7 @@ n16_pair_kernel(const N16PairArgs a) {
             const int idx = tid + s * NTH, pq = idx >> 2;
             const int pos = pos0 + 4 * pq;
             const bool ok = idx < NIT && pos >= 0 && pos < L;
-            unsigned vo = (unsigned)(4 * cq * L + (ok ? pos : 0)) * 2u;
-            asm volatile("" : "+v"(vo));
+            const unsigned vo = v2w_item_off(4 * cq * L, ok, pos);
 #pragma unroll
             for (int i = 0; i < 4; ++i) pf[s][i] = *gptr<const u32x2>(inb + (size_t)i * L * 2 + vo);
         }
@@ -672,8 +661,7 @@ V2W_TL_SETTER(v2w_timeline_set_n16)
 int v2w_resblock2_stage_bf16_n16(const v2w_stage_split_args* a, hipStream_t stream) {
     if (a->C != 16 || a->io_bf16 != 3 || !a->bf16 || a->nk != 3 || a->up_out) return V2W_E_SHAPE;
     if (a->post_out && (a->post_k != 7 || !a->post_w || (reinterpret_cast<uintptr_t>(a->post_out) & 15))) return V2W_E_SHAPE;     // the fused tail: 7 taps
-    for (int j = 0; j < 3; ++j)
-        if (a->k[j] != 3 + 4 * j || a->dil1[j] != 1 || a->dil2[j] != 3 || !a->wps1[j] || !a->wps2[j]) return V2W_E_SHAPE;
+    if (!v2w_is_reference_block_set(a)) return V2W_E_SHAPE;
     auto al16 = [](const void* x) { return (reinterpret_cast<uintptr_t>(x) & 15) == 0; };
     if (a->L % 4 != 0 || !al16(a->in) || !al16(a->out) || (!a->out && !a->post_out)) return V2W_E_SHAPE;
     if ((long long)16 * a->L * 2 >= (1ll << 31)) return V2W_E_SHAPE;            // 32-bit offsets inside one batch item

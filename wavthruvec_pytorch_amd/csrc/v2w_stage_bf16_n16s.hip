@@ -25,7 +25,7 @@
 // in front of slot 0, so that a window of three consecutive blocks is linear in memory at every step and every offset is an immediate.
 #include <type_traits>
 #include <utility>
-#include "v2w_tile.h"
+#include "v2w_bf16_tile.h"
 #include "v2w_internal.h"
 
 namespace {
@@ -171,10 +171,6 @@ n16s_stage_kernel(const N16SArgs a) {
     unsigned char* const stx = smem_s + S_XOFF + (cq >> 1) * S_XP + (4 * (cpos & 3)) * 16 + (cq & 1) * 8 + S_BLK;
     unsigned char* const str = smem_s + S_ROFF + (cq >> 1) * S_RP + (4 * (cpos & 3)) * 16 + (cq & 1) * 8;
 
-    auto mfma = [](f32x4 c, u32x4 av, u32x4 bv) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, av), __builtin_bit_cast(b8, bv), c, 0, 0, 0);
-    };
-
     u32x2 pf[4];
     float av[4], sv[4];
     f32x4 ts[2] = {b2s, b2s};                                                   // running sums of the t1_j of the blocks s - 1 and s - 2 (+ the b2_j)
@@ -193,8 +189,7 @@ n16s_stage_kernel(const N16SArgs a) {
         auto issue_x = [&](int k) {
             const int pos = p0 + 64 * k + 16 + 4 * cpos;
             const bool ok = pos >= 0 && pos < L;
-            unsigned vo = (unsigned)(4 * cq * L + (ok ? pos : 0)) * 2u;
-            asm volatile("" : "+v"(vo));
+            const unsigned vo = v2w_item_off(4 * cq * L, ok, pos);
 #pragma unroll
             for (int i = 0; i < 4; ++i) pf[i] = *gptr<const u32x2>(inb + (size_t)i * L * 2 + vo);
         };
@@ -254,7 +249,7 @@ n16s_stage_kernel(const N16SArgs a) {
             };
             S_STAMP(1);
             v2w_static_for(std::make_integer_sequence<int, RING>{}, rd);
-            v2w_static_for(std::make_integer_sequence<int, S_NM>{}, [&ring, &acc, &init, &W, &rd, &mfma](auto m_c) __attribute__((always_inline)) {
+            v2w_static_for(std::make_integer_sequence<int, S_NM>{}, [&ring, &acc, &init, &W, &rd](auto m_c) __attribute__((always_inline)) {
                 constexpr int m = decltype(m_c)::value;
                 constexpr SMm q = kStepProg<I>.mm[m];
                 if constexpr (kStepProg<I>.first_use(q.rd) == m) {
@@ -262,8 +257,8 @@ n16s_stage_kernel(const N16SArgs a) {
                     constexpr int left = (S_NR - 1 - q.rd) < (RING - 1) ? (S_NR - 1 - q.rd) : (RING - 1);
                     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(ring[q.rd % RING]) : "n"(left));
                 }
-                if constexpr (q.first) acc[q.acc] = mfma(init[q.acc], W[q.w], ring[q.rd % RING]);
-                else acc[q.acc] = mfma(acc[q.acc], W[q.w], ring[q.rd % RING]);
+                if constexpr (q.first) acc[q.acc] = v2w_mfma_bf16_16(init[q.acc], W[q.w], ring[q.rd % RING]);
+                else acc[q.acc] = v2w_mfma_bf16_16(acc[q.acc], W[q.w], ring[q.rd % RING]);
                 if constexpr (kStepProg<I>.last_use(q.rd) == m && q.rd + RING < S_NR) rd(std::integral_constant<int, q.rd + RING>{});
             });
             __builtin_amdgcn_sched_barrier(0);
@@ -361,10 +356,7 @@ int v2w_resblock2_stage_bf16_n16s(const v2w_stage_split_args* q, hipStream_t str
     if (q->L % 4 != 0 || (long long)16 * q->L * 2 >= (1ll << 31)) return V2W_E_SHAPE;
     N16SArgs p{};
     p.in = reinterpret_cast<const unsigned short*>(q->in); p.in_a = q->in_a; p.in_s = q->in_s;
-    for (int j = 0; j < 3; ++j) {
-        p.w1[j] = static_cast<const unsigned char*>(q->wps1[j]); p.bias1[j] = q->bias1[j];
-        p.w2[j] = static_cast<const unsigned char*>(q->wps2[j]); p.bias2[j] = q->bias2[j];
-    }
+    v2w_put_branch_ptrs<3>(p, v2w_stage_bf_branches(q));
     p.post_w = q->post_w; p.post_b = q->post_b; p.post_out = q->post_out;
     p.B = q->B; p.L = q->L; p.slope = q->slope; p.out_div = q->out_div; p.post_slope = q->post_slope;
     const int ncu = v2w_num_cus();

@@ -20,7 +20,7 @@
 // Per step and team: 50 ds_read_b128, 102 MFMAs; 58 KB of LDS, two teams per CU.
 #include <type_traits>
 #include <utility>
-#include "v2w_tile.h"
+#include "v2w_bf16_tile.h"
 #include "v2w_internal.h"
 
 namespace {
@@ -197,10 +197,6 @@ __device__ __forceinline__ void n32s_role(const N32SArgs& a, unsigned char* cons
     unsigned char* const stx = smem_t + T_XOFF + (cq >> 1) * T_XP + (4 * (cpos & 3)) * 16 + (cq & 1) * 8 + T_BLK;
     unsigned char* const str = smem_t + T_ROFF + (cq >> 1) * T_RP + (4 * (cpos & 3)) * 16 + (cq & 1) * 8;
 
-    auto mfma = [](f32x4 c, u32x4 av, u32x4 bv) {
-        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(b8, av), __builtin_bit_cast(b8, bv), c, 0, 0, 0);
-    };
-
     u32x2 pf[4];
     float av[4], sv[4];
     f32x4 osum[2][2];                                                           // role 2: its conv2 sums of the blocks s - 2 (this step) and s - 3 (the step before)
@@ -224,8 +220,7 @@ __device__ __forceinline__ void n32s_role(const N32SArgs& a, unsigned char* cons
         auto issue_x = [&](int k) {
             const int pos = p0 + 64 * k + 16 + 4 * cpos;
             const bool ok = pos >= 0 && pos < L;
-            unsigned vo = (unsigned)(4 * cq * L + (ok ? pos : 0)) * 2u;
-            asm volatile("" : "+v"(vo));
+            const unsigned vo = v2w_item_off(4 * cq * L, ok, pos);
 #pragma unroll
             for (int i = 0; i < 4; ++i) pf[i] = *gptr<const u32x2>(inb + (size_t)i * L * 2 + vo);
         };
@@ -278,7 +273,7 @@ __device__ __forceinline__ void n32s_role(const N32SArgs& a, unsigned char* cons
                 else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ring[n % T_RING]) : "v"(bt3), "n"(imm));
             };
             v2w_static_for(std::make_integer_sequence<int, (NR < RING ? NR : RING)>{}, rd);
-            v2w_static_for(std::make_integer_sequence<int, NM>{}, [&ring, &acc, &init, &W, &rd, &mfma](auto m_c) __attribute__((always_inline)) {
+            v2w_static_for(std::make_integer_sequence<int, NM>{}, [&ring, &acc, &init, &W, &rd](auto m_c) __attribute__((always_inline)) {
                 constexpr int m = decltype(m_c)::value;
                 constexpr TMm q = Prog::value->mm[m];
                 constexpr int NR = Prog::value->nr, RING = T_RING;
@@ -286,8 +281,8 @@ __device__ __forceinline__ void n32s_role(const N32SArgs& a, unsigned char* cons
                     constexpr int left = (NR - 1 - q.rd) < (RING - 1) ? (NR - 1 - q.rd) : (RING - 1);      // LDS reads return in order
                     asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(ring[q.rd % RING]) : "n"(left));
                 }
-                if constexpr (q.first) acc[q.acc] = mfma(init[q.acc], W[q.w], ring[q.rd % RING]);
-                else acc[q.acc] = mfma(acc[q.acc], W[q.w], ring[q.rd % RING]);
+                if constexpr (q.first) acc[q.acc] = v2w_mfma_bf16_16(init[q.acc], W[q.w], ring[q.rd % RING]);
+                else acc[q.acc] = v2w_mfma_bf16_16(acc[q.acc], W[q.w], ring[q.rd % RING]);
                 if constexpr (Prog::value->last_use(q.rd) == m && q.rd + RING < NR) rd(std::integral_constant<int, q.rd + RING>{});
             });
             __builtin_amdgcn_sched_barrier(0);
@@ -435,17 +430,13 @@ n32s_stage_kernel(const N32SArgs a) {
 int v2w_resblock2_stage_bf16_n32s(const v2w_stage_split_args* q, hipStream_t stream, int* up_tiles_out) {
     if (q->C != 32 || q->io_bf16 != 3 || !q->bf16 || q->nk != 3 || q->rb1 || q->post_out) return V2W_E_SHAPE;
     if (!q->up_out || q->up_u != 2 || q->up_k != 4 || !q->up_wps) return V2W_E_SHAPE;
-    for (int j = 0; j < 3; ++j)
-        if (q->k[j] != 3 + 4 * j || q->dil1[j] != 1 || q->dil2[j] != 3 || !q->wps1[j] || !q->wps2[j]) return V2W_E_SHAPE;
+    if (!v2w_is_reference_block_set(q)) return V2W_E_SHAPE;
     if (!(q->up_slope > 0.f && q->up_slope < 1.f) || !(q->slope > 0.f && q->slope < 1.f)) return V2W_E_SHAPE;     // lrelu as max(v, slope v)
     auto al16 = [](const void* x) { return (reinterpret_cast<uintptr_t>(x) & 15) == 0; };
     if (q->L % 4 != 0 || !al16(q->in) || !al16(q->up_out) || !al16(q->up_stats_part) || (long long)32 * q->L * 2 >= (1ll << 31)) return V2W_E_SHAPE;
     N32SArgs p{};
     p.in = reinterpret_cast<const unsigned short*>(q->in); p.in_a = q->in_a; p.in_s = q->in_s;
-    for (int j = 0; j < 3; ++j) {
-        p.w1[j] = static_cast<const unsigned char*>(q->wps1[j]); p.bias1[j] = q->bias1[j];
-        p.w2[j] = static_cast<const unsigned char*>(q->wps2[j]); p.bias2[j] = q->bias2[j];
-    }
+    v2w_put_branch_ptrs<3>(p, v2w_stage_bf_branches(q));
     p.up_w = static_cast<const unsigned char*>(q->up_wps); p.up_bias = q->up_bias;
     p.up_out = reinterpret_cast<unsigned short*>(q->up_out); p.up_stats = q->up_stats_part;
     p.B = q->B; p.L = q->L; p.slope = q->slope; p.out_div = q->out_div; p.up_slope = q->up_slope;

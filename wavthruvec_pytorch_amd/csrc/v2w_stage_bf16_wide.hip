@@ -16,7 +16,7 @@
 //     8-byte bf16 stores along positions;
 //   * weights: the fragments of v2w_pack_bf16 / v2w_split_pack_batch from L2 through a four-slot register ring, three k-steps ahead.
 #include <type_traits>
-#include "v2w_tile.h"
+#include "v2w_bf16_tile.h"
 #include "v2w_internal.h"
 
 namespace {
@@ -151,10 +151,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
             const int pq = rest % nq, ch = rest / nq;
             const int pos = tpos0 + pq * 4;
             const bool ok = idx < nitems && pos >= 0 && pos < L;
-            unsigned vo = (unsigned)((32 * (idx < nitems ? ch : 0) + 4 * cq) * L + (ok ? pos : 0)) * 2u;
-            asm volatile("" : "+v"(vo));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) pf[s][i] = *gptr<const u32x2>(inb + (size_t)i * L * 2 + vo);
+            v2w_item_load(pf[s], inb, L, v2w_item_off((32 * (idx < nitems ? ch : 0) + 4 * cq) * L, ok, pos));
         }
     };
     auto commit_x = [&]() {                                  // (b, pos0: the tile the loads were issued for; the affine table of b is complete)
@@ -171,26 +168,13 @@ wide_stage_bf16_kernel(const WideArgs a) {
             const int row = pq * 4;
             unsigned char* dst = smem_w + xbase + ch * xpsz + row * RB + ((((cq >> 1) ^ swz(row)) << 4) | ((cq & 1) << 3));
 #pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float v[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float xv = (e & 1) ? v2w_bf16_hi(pf[s][i][e >> 1]) : v2w_bf16_lo(pf[s][i][e >> 1]);
-                    v[i] = v2w_lrelu(fmaf(av[i], xv, sv[i]), slope);
-                }
-                u32x2 w = {v2w_bf16x2(v[0], v[1]), v2w_bf16x2(v[2], v[3])};
-                if (!ok) w = u32x2{0u, 0u};                 // the padding of the ACTIVATED signal is exactly 0
-                *reinterpret_cast<u32x2*>(dst + e * RB) = w;
-            }
+            for (int e = 0; e < 4; ++e) *reinterpret_cast<u32x2*>(dst + e * RB) = v2w_item_row<true>(e, pf[s], av, sv, slope, ok);
         }
     };
 
     const bool young = wave >= (WM * WN) / 2;                 // (uniform) the second-dispatched half of the workgroup's waves
     acc_t acc1[MI1][NI], oacc[MI][NI];
     unsigned lane16 = (unsigned)lane * 16u;
-    auto mfma = [&](acc_t c, u32x4 av, u32x4 bv) {
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(b8, av), __builtin_bit_cast(b8, bv), c, 0, 0, 0);
-    };
     // this lane's 16 bytes of k-step 0 at (plane ch, row): slot hk, swizzled by the row; with 64-byte rows k-step 1 is the address ^ 32
     auto baddr = [&](unsigned base, int psz, int ch, int row) {
         return base + (unsigned)(ch * psz + row * RB + ((hk ^ swz(row)) << 4));
@@ -278,7 +262,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
 #pragma unroll
                     for (int j = 0; j < NI; ++j) {
 #pragma unroll
-                        for (int i = 0; i < MI; ++i) acc[i][j] = mfma(acc[i][j], areg[P][sq][i], bb[sq][j]);
+                        for (int i = 0; i < MI; ++i) acc[i][j] = v2w_mfma_bf16_32(acc[i][j], areg[P][sq][i], bb[sq][j]);
                         bb[sq][j] = *reinterpret_cast<const u32x4*>(smem_w + (sq ? (xn ^ 32u) : xn) + j * CB);
                     }
                     __builtin_amdgcn_sched_barrier(0);
@@ -337,7 +321,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
 #pragma unroll
             for (int j = 0; j < NI; ++j) {
 #pragma unroll
-                for (int i = 0; i < MI; ++i) acc[i][j] = mfma(acc[i][j], av[i], bb[bs][j]);
+                for (int i = 0; i < MI; ++i) acc[i][j] = v2w_mfma_bf16_32(acc[i][j], av[i], bb[bs][j]);
                 bb[bs][j] = *reinterpret_cast<const u32x4*>(smem_w + nxt + j * CB);
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -435,7 +419,7 @@ wide_stage_bf16_kernel(const WideArgs a) {
 #pragma unroll
                     for (int j = 0; j < NI; ++j) {
 #pragma unroll
-                        for (int i = 0; i < MIX; ++i) acc[i][j] = mfma(acc[i][j], ar[sl + sq][i], bb[sq][j]);
+                        for (int i = 0; i < MIX; ++i) acc[i][j] = v2w_mfma_bf16_32(acc[i][j], ar[sl + sq][i], bb[sq][j]);
                         bb[sq][j] = *reinterpret_cast<const u32x4*>(smem_w + (sq ? (xn ^ 32u) : xn) + j * CB);
                     }
                     frag(ar[sl + sq], f2 + sq * K * V2W_FRAG_UNIT);
@@ -866,15 +850,10 @@ int launch_wide(const v2w_stage_split_args* q, hipStream_t stream, int* up_tiles
     WideArgs p{};
     p.in = reinterpret_cast<const unsigned short*>(q->in); p.in_a = q->in_a; p.in_s = q->in_s;
     p.out = reinterpret_cast<unsigned short*>(q->out);
-    p.nk = q->nk; p.B = q->B; p.C = q->C; p.L = q->L; p.slope = q->slope; p.inv_slope = 1.f / q->slope; p.out_div = q->out_div;
-    for (int j = 0; j < q->nk; ++j) {
-        p.w1[j] = static_cast<const unsigned char*>(q->wps1[j]); p.bias1[j] = q->bias1[j];
-        p.w2[j] = static_cast<const unsigned char*>(q->wps2[j]); p.bias2[j] = q->bias2[j];
-        p.K[j] = q->k[j]; p.d1[j] = q->dil1[j]; p.d2[j] = q->dil2[j];
-        const int h1 = q->dil1[j] * (q->k[j] - 1) / 2, h2 = q->dil2[j] * (q->k[j] - 1) / 2;
-        if (h1 > p.h1max) p.h1max = h1;
-        if (h2 > p.h2max) p.h2max = h2;
-    }
+    p.B = q->B; p.C = q->C; p.L = q->L; p.slope = q->slope; p.inv_slope = 1.f / q->slope; p.out_div = q->out_div;
+    const StageBfBranches br = v2w_stage_bf_branches(q);
+    v2w_put_branch_ptrs<V2W_WS_MAXB>(p, br);
+    v2w_put_branch_geom(p, br);
     if (p.h1max > 32 || p.h2max > 32) return V2W_E_SHAPE;
     if (q->post_out) {                         // the fused tail: C = 16 (one plane), an odd tap count <= 9, fp32 (B, 1, L) output
         if (CH != 16 || !q->post_w || q->post_k < 1 || q->post_k > 9 || !(q->post_k & 1)) return V2W_E_SHAPE;
