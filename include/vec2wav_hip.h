@@ -879,6 +879,32 @@ int v2w_stft_loss_multi(const v2w_stft_loss_item* items, int n, float* sc, float
                         void* stream);
 int v2w_stft_loss_multi_bwd(const v2w_stft_loss_item* items, int n, const double* sums, const float* g_sc, const float* g_mag,
                             const float* gterm_sc, const float* gterm_mag, void* stream);
+/* The same loss for a padded batch of unequal lengths (additive; "Batches of unequal lengths": `len` a DEVICE array of B int32, len_mul >= 1,
+ * the grids depend on the shapes only).  hop and n_fft are HOST arrays of n int32, the frame geometry of each resolution; the descriptors are
+ * the dense call's.  Item b of resolution r counts F_b = min(frames(len[b] * len_mul), F) frames, frames(n) as v2w_mel_finish_geo_len states it
+ * with pad = (n_fft[r] - hop[r]) / 2 rounded down (0 unless n > pad and n + 2 pad >= n_fft; with F the frames of the batch's L samples this
+ * is the frames of min(len[b] * len_mul, L)), and everything above holds with "the frames [0, F)" of item b read as [0, F_b):
+ *   forward   Sd, Sy, Sl over the entries (b, bin, f < F_b);  N_r = nb * sum_b F_b, counted ONCE on the device by the finishing launch (the
+ *             counts added as fp64 integers, exact) - no length and no frame count comes to the host;  sc[r] = sqrt(Sd) / sqrt(Sy),
+ *             mag[r] = Sl / N_r, both exactly 0 when N_r == 0 (no 0 / 0);  total as above.  sums holds FOUR doubles per resolution:
+ *             sums[4 r + {0, 1, 2, 3}] = (Sd, Sy, Sl, N_r), what v2w_stft_loss_multi_len_bwd reads (4 n doubles, 8-byte aligned).
+ *   backward  the dense call's lines, one fp32 operation each, with c_mag = g_mag_r / N_r from sums[4 r + 3] (computed in fp64, rounded once;
+ *             0 when N_r == 0) on the entries f < F_b.  Every float of dspec_x is written exactly once: the columns [F_b, FP) of item b and
+ *             the rows [2 nb, Cs) are +0.0.
+ * Work split, scratch and plan: the dense call's (v2w_stft_loss_plan, v2w_stft_loss_scratch_bytes) - a unit is four frames of one (item,
+ * bin) of the padded batch.  A unit whose four frames lie at or past F_b issues no load: the forward adds nothing for it, the backward
+ * stores its zeros.  Frames at or past F_b inside a partly valid unit are loaded and SELECTED away (never multiplied by a mask): NaN, Inf
+ * or stale workspace there reaches no stored value.  No atomics; the same call gives the same bits; the chunks and the order of every sum
+ * are the dense call's, so with every F_b == F the sums, sc, mag, total and dspec_x have the bits of v2w_stft_loss_multi / _multi_bwd.
+ * Roundings: the dense block's, with these differences only: a thread's chain and a workgroup's triple hold the valid entries alone (a
+ * skipped entry adds an exact 0.0 or nothing); N_r is an exact integer in fp64 (nb * sum_b F_b < 2^53); mag and c_mag divide by it.
+ * V2W_E_ARG / V2W_E_SHAPE: everything the dense calls refuse, with their codes; then V2W_E_ARG for a NULL hop / n_fft / len, len_mul < 1,
+ * hop[r] < 1 or n_fft[r] < hop[r]; V2W_E_SHAPE for B > 65535 or F * hop[r] + n_fft[r] past 2^31 - 1 (as the mel _len calls). */
+int v2w_stft_loss_multi_len(const v2w_stft_loss_item* items, int n, const int32_t* hop, const int32_t* n_fft, const int32_t* len,
+                            int len_mul, float* sc, float* mag, float* total, double* sums, void* scratch, void* stream);
+int v2w_stft_loss_multi_len_bwd(const v2w_stft_loss_item* items, int n, const int32_t* hop, const int32_t* n_fft, const int32_t* len,
+                                int len_mul, const double* sums, const float* g_sc, const float* g_mag, const float* gterm_sc,
+                                const float* gterm_mag, void* stream);
 
 /* ---- AdamW (additive in ABI v35; torch.optim.AdamW as train.py:96-99 constructs it and train.py:198,215 steps it: decoupled weight
  * decay, no amsgrad, no maximize): the step of up to V2W_ADAMW_MAX_ITEMS parameter tensors in ONE launch that reads p, g, m, v and

@@ -1,6 +1,9 @@
 #!/usr/bin/env python
 """Times the multi-resolution STFT loss (wavthruvec_pytorch_amd.stft_loss) against the same loss written with torch.stft and stock torch ops
 on the same GPU: forward and forward + backward at B = 32 x 81 920 (a training batch) and B = 2 x 8 192, the three default resolutions.
+At B = 32 x 81 920 also the ragged call on the same padded batch: lengths uniform in [64, 256] frames of 320 samples (seed 0, the draw of
+tools/mel_loss_bench.py), `lengths=` / `len_mul=320`, forward and forward + backward, and - for the spread of the run - the dense and the
+ragged forward + backward measured in turn three more times (`dense_vs_ragged_fwd_bwd_ms`).
 
 Device events around every iteration, warm-up first, the median reported.  For the two streaming kernels (the forward's sums launch with its
 finishing launch, and the backward's d spec launch) it also prints the achieved bytes/s against their algorithmic bytes: the forward reads
@@ -19,6 +22,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from wavthruvec_pytorch_amd import MultiResolutionSTFTLoss, _hip, stft_loss  # noqa: E402
 
 SHAPES = ((32, 81920), (2, 8192))
+RAGGED = (32, 81920)                      # the shape that also gets the ragged line
+HOP_TOTAL, T_MIN, T_MAX = 320, 64, 256    # samples per frame of the lengths (the generator's upsampling), frames per item
 
 
 def torch_loss(x, y, resolutions, windows):
@@ -93,6 +98,27 @@ def main():
             out[name] = round(median_ms(fn, args.warmup, args.iters), 4)
         a, b = hip_fwd(), torch_fwd()
         out['sc'], out['mag'] = [a[0].item(), b[0].item()], [a[1].item(), b[1].item()]          # (hip, torch)
+
+        if (B, L) == RAGGED:
+            ns = torch.randint(T_MIN, T_MAX + 1, (B,), generator=torch.Generator().manual_seed(0)).tolist()
+            lens = torch.tensor(ns, dtype=torch.int32, device=dev)
+
+            def len_fwd():
+                with torch.no_grad():
+                    return mod(x, y, lengths=lens, len_mul=HOP_TOTAL)
+
+            def len_both():
+                xg.grad = None
+                sc, mag = mod(xg, y, lengths=lens, len_mul=HOP_TOTAL)
+                (sc + mag).backward()
+
+            out['lengths'] = 'uniform in [%d, %d] frames of %d samples (seed 0): %d of %d samples valid' % (T_MIN, T_MAX, HOP_TOTAL,
+                                                                                                          sum(ns) * HOP_TOTAL, B * L)
+            out['hip_fwd_ms_lengths'] = round(median_ms(len_fwd, args.warmup, args.iters), 4)
+            out['hip_fwd_bwd_ms_lengths'] = round(median_ms(len_both, args.warmup, args.iters), 4)
+            out['dense_vs_ragged_fwd_bwd_ms'] = [[round(median_ms(fn, 2, args.iters), 4) for fn in (hip_both, len_both)] for _ in range(3)]
+            c = len_fwd()
+            out['sc_lengths'], out['mag_lengths'] = c[0].item(), c[1].item()
 
         # the streaming kernels alone, on the specs of one forward
         st = torch.cuda.current_stream(dev).cuda_stream

@@ -309,6 +309,11 @@ SIGNATURES = {
     'v2w_stft_loss_scratch_bytes': (C.c_longlong, [C.POINTER(StftLossItem), C.c_int]),
     'v2w_stft_loss_multi': (C.c_int, [C.POINTER(StftLossItem), C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),
     'v2w_stft_loss_multi_bwd': (C.c_int, [C.POINTER(StftLossItem), C.c_int, _fp, _fp, _fp, _fp, _fp, _fp]),
+    # ... with per-item lengths: hop / n_fft HOST arrays of n int32, len a DEVICE array of B int32, then len_mul; sums: 4 n doubles
+    'v2w_stft_loss_multi_len': (C.c_int, [C.POINTER(StftLossItem), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.c_int,
+                                          _fp, _fp, _fp, _fp, _fp, _fp]),
+    'v2w_stft_loss_multi_len_bwd': (C.c_int, [C.POINTER(StftLossItem), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _fp, C.c_int,
+                                              _fp, _fp, _fp, _fp, _fp, _fp]),
     # AdamW: host descriptor array and hyperparameters, read before the call returns
     'v2w_adamw_multi_plan': (C.c_int, [C.POINTER(AdamWItem), C.c_int, C.POINTER(C.c_int32)]),
     'v2w_adamw_multi': (C.c_int, [C.POINTER(AdamWItem), C.c_int, C.POINTER(AdamWHyper), _fp]),

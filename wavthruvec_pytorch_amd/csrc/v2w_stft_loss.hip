@@ -10,6 +10,11 @@
 // arithmetic (never multiplied by a mask): Inf or NaN made from the junk there reaches nothing.  The forward counts B * nb * ceil(F / 4) units.
 // The backward writes EVERY float of dspec_x once: its units are B * (nb + P) * (FP / 4), P = ceil((Cs - 2 nb) / 2) pairs of pad rows that get
 // +0.0 like the columns [F, FP) of the other rows, so the caller's buffer needs no zero fill.
+//
+// Per-item lengths (v2w_stft_loss_multi_len, _len_bwd): the same three device bodies with LEN = true.  Item b of resolution i counts
+// F_b = v2w_item_frames(len, b, len_mul, hop[i], n_fft[i], F) frames - F above becomes F_b, nothing else changes: the units, the grids and the
+// chunks are the dense call's (they depend on the shapes only), a unit at or past F_b loads nothing, and with every F_b == F every value has
+// the dense call's bits.  The finishing launch counts N = nb * sum_b F_b once and leaves it in sums[4 i + 3] for the backward.
 #include "v2w_multi.h"
 
 namespace {
@@ -23,6 +28,25 @@ struct SlArgs {
     int n;
 };
 struct SlGrads { const float* g_sc; const float* g_mag; const float* gterm_sc; const float* gterm_mag; };
+struct SlLen {                                   // LEN: the items' lengths (device) and every resolution's frame geometry
+    const int32_t* len;
+    int len_mul;
+    int hop[V2W_STFT_LOSS_MAX_ITEMS], n_fft[V2W_STFT_LOSS_MAX_ITEMS];
+};
+
+// LEN: the frames item b counts, kept from unit to unit (a thread's units change their item every nb * Q units or more, and the count
+// costs a 64-bit division)
+struct SlFrames {
+    unsigned b = ~0u;
+    int Fb = 0;
+    __device__ __forceinline__ int of(const SlLen& Ln, int i, unsigned item, int F) {
+        if (item != b) {
+            b = item;
+            Fb = v2w_item_frames(Ln.len, (int)item, Ln.len_mul, Ln.hop[i], Ln.n_fft[i], F);
+        }
+        return Fb;
+    }
+};
 
 // v2w_mel_finish's magnitude with the three operations under the root spelled out (no contraction left to the compiler): the two signals'
 // magnitudes are then the same function of their operands, and equal spectra give X == Y bit for bit
@@ -31,8 +55,8 @@ __device__ __forceinline__ float sl_mag(float re, float im) {
 }
 
 // part[3 wg + {0, 1, 2}] = the workgroup's sums of (Y - X)^2, Y^2 and |log Y - log X| (fp64)
-__global__ void __launch_bounds__(kThreads)
-stft_loss_sums_kernel(const SlArgs A, double* __restrict__ part) {
+template <bool LEN>
+__device__ __forceinline__ void sl_sums(const SlArgs& A, const SlLen& Ln, double* __restrict__ part) {
     __shared__ double red[16];
     const int wg = blockIdx.x;
     const int i = find_item(A.starts, A.n, wg);
@@ -46,6 +70,7 @@ stft_loss_sums_kernel(const SlArgs A, double* __restrict__ part) {
     const unsigned base = (unsigned)u0;                       // (units < 2^31: B * Cs * FP is)
 
     double sd = 0.0, sy = 0.0, sl = 0.0;
+    SlFrames fr;
     for (unsigned t0 = threadIdx.x; t0 < cnt; t0 += kThreads * kUnroll) {
         f32x4 xr[kUnroll], xi[kUnroll], yr[kUnroll], yi[kUnroll];
         int e1[kUnroll];                                      // frames of the unit that count
@@ -56,12 +81,14 @@ stft_loss_sums_kernel(const SlArgs A, double* __restrict__ part) {
             e1[k] = 0;
             if (t >= cnt) continue;
             const unsigned u = base + t, row = u / Q, q = u - row * Q, b = row / nb, c = row - b * nb;
+            const int Fb = LEN ? fr.of(Ln, i, b, F) : F;
+            const int left = Fb - (int)(q << 2);
+            if (LEN && left <= 0) continue;                   // the unit lies at or past the item's frames: no load, nothing added
             const size_t o = (size_t)b * plane + (size_t)c * FP + (q << 2);
             xr[k] = *reinterpret_cast<const f32x4*>(it.x + o);
             xi[k] = *reinterpret_cast<const f32x4*>(it.x + o + im_off);
             yr[k] = *reinterpret_cast<const f32x4*>(it.y + o);
             yi[k] = *reinterpret_cast<const f32x4*>(it.y + o + im_off);
-            const int left = F - (int)(q << 2);
             e1[k] = left < 4 ? left : 4;
         }
 #pragma unroll
@@ -85,12 +112,19 @@ stft_loss_sums_kernel(const SlArgs A, double* __restrict__ part) {
         part[3 * (size_t)wg + 2] = sl;
     }
 }
+__global__ void __launch_bounds__(kThreads) stft_loss_sums_kernel(const SlArgs A, double* __restrict__ part) {
+    sl_sums<false>(A, SlLen{}, part);
+}
+__global__ void __launch_bounds__(kThreads) stft_loss_sums_len_kernel(const SlArgs A, const SlLen Ln, double* __restrict__ part) {
+    sl_sums<true>(A, Ln, part);
+}
 
 // sums[3 r + s] = resolution r's partials of sum s: thread t adds the partials t, t + 256, ... in index order, the 256 sums go through the
-// fixed-order block reduction; sc[r] = sqrt(Sd) / sqrt(Sy), mag[r] = Sl / N, total = the means over r in list order; all in fp64
-__global__ void __launch_bounds__(kThreads)
-stft_loss_finish_kernel(const SlArgs A, const double* __restrict__ part, float* __restrict__ sc, float* __restrict__ mag,
-                        float* __restrict__ total, double* __restrict__ sums) {
+// fixed-order block reduction; sc[r] = sqrt(Sd) / sqrt(Sy), mag[r] = Sl / N, total = the means over r in list order; all in fp64.
+// LEN: N = nb * sum_b F_b (the counts added as fp64 integers: exact), sums[4 r + {0, 1, 2, 3}] = (Sd, Sy, Sl, N), sc = mag = 0 for N == 0
+template <bool LEN>
+__device__ __forceinline__ void sl_finish(const SlArgs& A, const SlLen& Ln, const double* __restrict__ part, float* __restrict__ sc,
+                                          float* __restrict__ mag, float* __restrict__ total, double* __restrict__ sums) {
     __shared__ double red[16];
     double tsc = 0.0, tmag = 0.0;
     for (int i = 0; i < A.n; ++i) {
@@ -103,10 +137,19 @@ stft_loss_finish_kernel(const SlArgs A, const double* __restrict__ part, float* 
 #pragma unroll
         for (int j = 0; j < 3; ++j) s[j] = v2w_block_sum(s[j], red);
         const SlItem& it = A.it[i];
-        const double N = (double)it.B * (double)it.nb * (double)it.F;
-        const double vsc = sqrt(s[0]) / sqrt(s[1]), vmag = s[2] / N;             // (Sy >= N * 1e-9 > 0)
+        double N = (double)it.B * (double)it.nb * (double)it.F;
+        if (LEN) {
+            double fr = 0.0;
+            for (int b = threadIdx.x; b < it.B; b += kThreads)
+                fr += (double)v2w_item_frames(Ln.len, b, Ln.len_mul, Ln.hop[i], Ln.n_fft[i], it.F);
+            N = (double)it.nb * v2w_block_sum(fr, red);
+        }
+        const bool any = !LEN || N > 0.0;
+        const double vsc = any ? sqrt(s[0]) / sqrt(s[1]) : 0.0, vmag = any ? s[2] / N : 0.0;             // (Sy >= N * 1e-9 > 0)
         if (threadIdx.x == 0) {
-            if (sums) { sums[3 * i] = s[0]; sums[3 * i + 1] = s[1]; sums[3 * i + 2] = s[2]; }
+            constexpr int S = LEN ? 4 : 3;
+            if (sums) { sums[S * i] = s[0]; sums[S * i + 1] = s[1]; sums[S * i + 2] = s[2]; }
+            if (LEN && sums) sums[S * i + 3] = N;
             if (sc) sc[i] = (float)vsc;
             if (mag) mag[i] = (float)vmag;
         }
@@ -118,10 +161,21 @@ stft_loss_finish_kernel(const SlArgs A, const double* __restrict__ part, float* 
         total[1] = (float)(tmag / (double)A.n);
     }
 }
-
-// dspec_x: see the head of this file and include/vec2wav_hip.h for the arithmetic, one fp32 operation per line there
 __global__ void __launch_bounds__(kThreads)
-stft_loss_bwd_kernel(const SlArgs A, const SlGrads G, const double* __restrict__ sums) {
+stft_loss_finish_kernel(const SlArgs A, const double* __restrict__ part, float* __restrict__ sc, float* __restrict__ mag,
+                        float* __restrict__ total, double* __restrict__ sums) {
+    sl_finish<false>(A, SlLen{}, part, sc, mag, total, sums);
+}
+__global__ void __launch_bounds__(kThreads)
+stft_loss_finish_len_kernel(const SlArgs A, const SlLen Ln, const double* __restrict__ part, float* __restrict__ sc, float* __restrict__ mag,
+                            float* __restrict__ total, double* __restrict__ sums) {
+    sl_finish<true>(A, Ln, part, sc, mag, total, sums);
+}
+
+// dspec_x: see the head of this file and include/vec2wav_hip.h for the arithmetic, one fp32 operation per line there.
+// LEN: sums holds four doubles per resolution, the fourth the forward's N (c_mag = 0 for N == 0)
+template <bool LEN>
+__device__ __forceinline__ void sl_bwd(const SlArgs& A, const SlLen& Ln, const SlGrads& G, const double* __restrict__ sums) {
     const int wg = blockIdx.x;
     const int i = find_item(A.starts, A.n, wg);
     const SlItem& it = A.it[i];
@@ -137,10 +191,13 @@ stft_loss_bwd_kernel(const SlArgs A, const SlGrads G, const double* __restrict__
     const float fn = (float)A.n;
     const float gs = (G.g_sc ? G.g_sc[0] / fn : 0.f) + (G.gterm_sc ? G.gterm_sc[i] : 0.f);
     const float gm = (G.g_mag ? G.g_mag[0] / fn : 0.f) + (G.gterm_mag ? G.gterm_mag[i] : 0.f);
-    const double Sd = sums[3 * i], Sy = sums[3 * i + 1];
+    constexpr int S = LEN ? 4 : 3;
+    const double Sd = sums[S * i], Sy = sums[S * i + 1];
+    const double N = LEN ? sums[S * i + 3] : (double)it.B * (double)nb * (double)F;
     const float csc = Sd > 0.0 ? (float)((double)gs / (sqrt(Sd) * sqrt(Sy))) : 0.f;          // torch's subgradient of a norm at 0
-    const float cmag = (float)((double)gm / ((double)it.B * (double)nb * (double)F));
+    const float cmag = !LEN || N > 0.0 ? (float)((double)gm / N) : 0.f;
 
+    SlFrames fr;
     for (unsigned t0 = threadIdx.x; t0 < cnt; t0 += kThreads * kUnroll) {
         f32x4 xr[kUnroll], xi[kUnroll], yr[kUnroll], yi[kUnroll];
         size_t oo[kUnroll];
@@ -161,7 +218,8 @@ stft_loss_bwd_kernel(const SlArgs A, const SlGrads G, const double* __restrict__
                 continue;
             }
             oo[k] = (size_t)b * plane + (size_t)c * FP + (q << 2);
-            const int left = F - (int)(q << 2);
+            const int Fb = LEN ? fr.of(Ln, i, b, F) : F;
+            const int left = Fb - (int)(q << 2);
             e1[k] = left < 0 ? 0 : (left < 4 ? left : 4);
             if (e1[k] > 0) {
                 xr[k] = *reinterpret_cast<const f32x4*>(it.x + oo[k]);
@@ -196,6 +254,13 @@ stft_loss_bwd_kernel(const SlArgs A, const SlGrads G, const double* __restrict__
             *reinterpret_cast<f32x4*>(it.dx + oo[k] + im_off) = dim;
         }
     }
+}
+__global__ void __launch_bounds__(kThreads) stft_loss_bwd_kernel(const SlArgs A, const SlGrads G, const double* __restrict__ sums) {
+    sl_bwd<false>(A, SlLen{}, G, sums);
+}
+__global__ void __launch_bounds__(kThreads)
+stft_loss_bwd_len_kernel(const SlArgs A, const SlLen Ln, const SlGrads G, const double* __restrict__ sums) {
+    sl_bwd<true>(A, Ln, G, sums);
 }
 
 // checks every descriptor and counts its units (four frames of one row pair; see the head of this file)
@@ -237,6 +302,33 @@ int sl_args(const v2w_stft_loss_item* items, int n, bool bwd, SlArgs* A) {
     return 0;
 }
 
+// the lengths and the frame geometries of a _len call, after the descriptors passed sl_items
+int sl_len(const v2w_stft_loss_item* items, int n, const int32_t* hop, const int32_t* n_fft, const int32_t* len, int len_mul, SlLen* Ln) {
+    if (!hop || !n_fft || !len || len_mul < 1) return V2W_E_ARG;
+    for (int i = 0; i < n; ++i)
+        if (hop[i] < 1 || n_fft[i] < hop[i]) return V2W_E_ARG;
+    for (int i = 0; i < n; ++i) {
+        if (items[i].B > 65535 || (long long)items[i].F * hop[i] + n_fft[i] > 0x7fffffffll) return V2W_E_SHAPE;
+        Ln->hop[i] = hop[i]; Ln->n_fft[i] = n_fft[i];
+    }
+    Ln->len = len; Ln->len_mul = len_mul;
+    return 0;
+}
+
+int sl_fwd_ptrs(const float* sc, const float* mag, const float* total, const double* sums, const void* scratch) {
+    if (!scratch || (!sc && !mag && !total && !sums)) return V2W_E_ARG;
+    if ((reinterpret_cast<uintptr_t>(scratch) & 7) || (reinterpret_cast<uintptr_t>(sums) & 7)) return V2W_E_ARG;
+    if ((sc && !ptr4(sc)) || (mag && !ptr4(mag)) || (total && !ptr4(total))) return V2W_E_ARG;
+    return 0;
+}
+
+int sl_bwd_ptrs(const double* sums, const SlGrads& G) {
+    if (!sums || (reinterpret_cast<uintptr_t>(sums) & 7) || (!G.g_sc && !G.g_mag && !G.gterm_sc && !G.gterm_mag)) return V2W_E_ARG;
+    if ((G.g_sc && !ptr4(G.g_sc)) || (G.g_mag && !ptr4(G.g_mag)) || (G.gterm_sc && !ptr4(G.gterm_sc)) || (G.gterm_mag && !ptr4(G.gterm_mag)))
+        return V2W_E_ARG;
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int v2w_stft_loss_plan(const v2w_stft_loss_item* items, int n, int32_t* starts) {
@@ -255,9 +347,7 @@ extern "C" long long v2w_stft_loss_scratch_bytes(const v2w_stft_loss_item* items
 
 extern "C" int v2w_stft_loss_multi(const v2w_stft_loss_item* items, int n, float* sc, float* mag, float* total, double* sums,
                                    void* scratch, void* stream) {
-    if (!scratch || (!sc && !mag && !total && !sums)) return V2W_E_ARG;
-    if ((reinterpret_cast<uintptr_t>(scratch) & 7) || (reinterpret_cast<uintptr_t>(sums) & 7)) return V2W_E_ARG;
-    if ((sc && !ptr4(sc)) || (mag && !ptr4(mag)) || (total && !ptr4(total))) return V2W_E_ARG;
+    if (const int rc = sl_fwd_ptrs(sc, mag, total, sums, scratch)) return rc;
     SlArgs A;
     if (const int rc = sl_args(items, n, false, &A)) return rc;
     hipStream_t st = (hipStream_t)stream;
@@ -270,13 +360,42 @@ extern "C" int v2w_stft_loss_multi(const v2w_stft_loss_item* items, int n, float
 
 extern "C" int v2w_stft_loss_multi_bwd(const v2w_stft_loss_item* items, int n, const double* sums, const float* g_sc, const float* g_mag,
                                        const float* gterm_sc, const float* gterm_mag, void* stream) {
-    if (!sums || (reinterpret_cast<uintptr_t>(sums) & 7) || (!g_sc && !g_mag && !gterm_sc && !gterm_mag)) return V2W_E_ARG;
-    if ((g_sc && !ptr4(g_sc)) || (g_mag && !ptr4(g_mag)) || (gterm_sc && !ptr4(gterm_sc)) || (gterm_mag && !ptr4(gterm_mag))) return V2W_E_ARG;
+    const SlGrads G = {g_sc, g_mag, gterm_sc, gterm_mag};
+    if (const int rc = sl_bwd_ptrs(sums, G)) return rc;
     SlArgs A;
     if (const int rc = sl_args(items, n, true, &A)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (v2w_dry(st)) return 0;
-    const SlGrads G = {g_sc, g_mag, gterm_sc, gterm_mag};
     V2W_LAUNCH(stft_loss_bwd_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A, G, sums);
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_stft_loss_multi_len(const v2w_stft_loss_item* items, int n, const int32_t* hop, const int32_t* n_fft, const int32_t* len,
+                                       int len_mul, float* sc, float* mag, float* total, double* sums, void* scratch, void* stream) {
+    if (const int rc = sl_fwd_ptrs(sc, mag, total, sums, scratch)) return rc;
+    SlArgs A;
+    SlLen Ln;
+    if (const int rc = sl_args(items, n, false, &A)) return rc;
+    if (const int rc = sl_len(items, n, hop, n_fft, len, len_mul, &Ln)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (v2w_dry(st)) return 0;
+    double* part = static_cast<double*>(scratch);
+    V2W_LAUNCH(stft_loss_sums_len_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A, Ln, part);
+    V2W_LAUNCH(stft_loss_finish_len_kernel, dim3(1), dim3(kThreads), 0, st, A, Ln, part, sc, mag, total, sums);
+    return v2w_launch_status();
+}
+
+extern "C" int v2w_stft_loss_multi_len_bwd(const v2w_stft_loss_item* items, int n, const int32_t* hop, const int32_t* n_fft,
+                                           const int32_t* len, int len_mul, const double* sums, const float* g_sc, const float* g_mag,
+                                           const float* gterm_sc, const float* gterm_mag, void* stream) {
+    const SlGrads G = {g_sc, g_mag, gterm_sc, gterm_mag};
+    if (const int rc = sl_bwd_ptrs(sums, G)) return rc;
+    SlArgs A;
+    SlLen Ln;
+    if (const int rc = sl_args(items, n, true, &A)) return rc;
+    if (const int rc = sl_len(items, n, hop, n_fft, len, len_mul, &Ln)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (v2w_dry(st)) return 0;
+    V2W_LAUNCH(stft_loss_bwd_len_kernel, dim3(A.starts[n]), dim3(kThreads), 0, st, A, Ln, G, sums);
     return v2w_launch_status();
 }
