@@ -793,6 +793,45 @@ int v2w_l1_mean_multi(const v2w_l1_pair* pairs, int n, float scale, float* term,
 int v2w_l1_mean_multi_bwd(const v2w_l1_pair* pairs, int n, float scale, const float* gout, void* stream);
 int v2w_lsgan_multi(const v2w_lsgan_item* items, int n, float* term, float* total, void* stream);
 int v2w_lsgan_multi_bwd(const v2w_lsgan_item* items, int n, const float* gout, const float* gterm, void* stream);
+/* The same terms over the maps and scores of a PADDED batch of B utterances of unequal lengths (additive in ABI v35; the dense entry points
+ * above and their kernels are unchanged).  The descriptors are the same structs.  New arguments: B, the items of the batch, and `ext`, a
+ * DEVICE array of n x B int32: ext[i * B + b] = the floats at the head of each of item b's rows of descriptor i that exist for that
+ * utterance.  The period of a period discriminator's (b, C, H, period) maps is FOLDED INTO the table (its entries are H_b * period, as
+ * v2w_map_extents writes them): the kernels take no `inner` argument.  rows % B == 0; row r belongs to item r / (rows / B) and counts its
+ * first v = min(max(ext, 0), valid) floats.  For the leading-dim halves of a real-plus-generated batch B is the half's batch and both
+ * halves use the same extents.  With rpi = rows / B and den_i = rpi * sum_b v_ib (formed on the device, exact in fp64; nothing is read back):
+ *   L1     term[i] = (sum of |a - b| over the counted floats) / den_i, 0 when den_i == 0; total[0] = scale * sum_i term[i] in list order.
+ *          backward: da = sgn(a - b) * ((scale * gout[0]) / den_i) on the counted floats and +0.0 on every other float of the dense
+ *          (rows x valid) gradient; db = -da on the counted floats, +0.0 on the others.  den_i == 0: both all +0.0.
+ *   LSGAN  term[i] = (sum of (target_i - s)^2 over the counted floats) / den_i, 0 when den_i == 0; total[0] = sum_i term[i].
+ *          backward: ds = 2 (s - target_i) * g_i / den_i on the counted floats, +0.0 on the others.
+ * A float that is not counted is SELECTED away, never multiplied by a mask: NaN or Inf there reaches no term and no gradient (the
+ * discriminators do compute values past an utterance's end).  A 16-byte unit that holds no counted float is not loaded at all; the others
+ * are loaded as the dense kernels load them (one 16-byte access where the unit is whole and on a 16-byte line) and masked per float.
+ * Work split: v2w_l1_multi_plan and v2w_l1_multi_scratch_bytes of the same descriptors - the units, the workgroups and the order of every
+ * sum are the dense call's and depend on the descriptors only, never on the extents (a workgroup with nothing to count writes a zero
+ * partial at once; in the backward it stores its zeros).  So: fp64 partials, no atomics, the same call gives the same bits, and with
+ * ext >= valid everywhere every output has the bits of the dense entry point.
+ * Besides the dense calls' errors - V2W_E_ARG: ext NULL or not 4-byte aligned, B < 1, rows % B != 0; V2W_E_SHAPE: rows >= 2^31. */
+int v2w_l1_mean_multi_len(const v2w_l1_pair* pairs, int n, const int32_t* ext, int B, float scale, float* term, float* total,
+                          void* scratch, void* stream);
+int v2w_l1_mean_multi_len_bwd(const v2w_l1_pair* pairs, int n, const int32_t* ext, int B, float scale, const float* gout, void* stream);
+int v2w_lsgan_multi_len(const v2w_lsgan_item* items, int n, const int32_t* ext, int B, float* term, float* total, void* stream);
+int v2w_lsgan_multi_len_bwd(const v2w_lsgan_item* items, int n, const int32_t* ext, int B, const float* gout, const float* gterm,
+                            void* stream);
+/* The extent table of a discriminator's maps from the utterances' lengths, one launch (additive).  len: DEVICE array of B int32, item b
+ * holds m = min(max(len[b] * len_mul, 0), L) samples (64-bit product).  chains: DEVICE array of n rows {period, pools, depth, size};
+ * layers: DEVICE array of n_layers rows {k, stride, pad}.  Row i: m <- ceil(m / period); `pools` times m <- m / 2 + 1
+ * (AvgPool1d(4, 2, padding=2)); for l < depth: m <- (m + 2 pad_l - k_l) / stride_l + 1 (0 when the numerator is negative); every step
+ * keeps 0 at 0; size > 0: m <- min(m, size).  ext[i * B + b] = m * period, the floats of a row that exist.  V2W_E_ARG: a NULL pointer,
+ * B < 1, n < 1, len_mul < 1, L < 0, n_layers < 0.  The kernel trusts the tables (period, stride >= 1, depth <= n_layers). */
+int v2w_map_extents(const int32_t* len, int len_mul, int L, int B, const int32_t* chains, int n, const int32_t* layers, int n_layers,
+                    int32_t* ext, void* stream);
+/* out[r][j] = j < m_b ? x[r][j] : +0.0 for `rows` dense rows of L floats, row r of item b = r / (rows / B), m_b as above (additive): what a
+ * trainer applies to the generated batch before the discriminators, and - on the gradient - the backward of itself.  A select: NaN past
+ * m_b does not pass, floats of x at or past m_b in a unit with no float before m_b are not loaded.  out may be x.  V2W_E_ARG: NULL
+ * pointers, rows < 1, B < 1, rows % B != 0, L < 1, len_mul < 1. */
+int v2w_mask_tail(const float* x, float* out, long long rows, int B, int L, const int32_t* len, int len_mul, void* stream);
 /* Masked mel L1 of a batch of unequal lengths (additive; forward only - the validation loop of train.py:246-289, batched): a, b (B, C, F)
  * dense fp32; `len` a DEVICE array of B int32, len_mul >= 1 as under "Batches of unequal lengths": item b counts its first
  * F_b = min(frames(len[b] * len_mul), F) frames, frames(n) as v2w_mel_finish_len states it with pad = (n_fft - hop) / 2.

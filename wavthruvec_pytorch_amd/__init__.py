@@ -15,9 +15,9 @@ from .optim import AdamW, clip_grad_norm_, ema_state_dict  # noqa: F401
 from . import stft_loss  # noqa: F401  (the module: stft_loss.stft_loss is the one-resolution function)
 from .stft_loss import MultiResolutionSTFTLoss  # noqa: F401
 from . import audio  # noqa: F401
-from .audio import resample, resample_table, resampled_length, peak_normalize  # noqa: F401
+from .audio import resample, resample_table, resampled_length, peak_normalize, mask_tail  # noqa: F401
 from .mel import mel_loss  # noqa: F401  (the mel L1 training loss in one call, with or without per-item lengths)
 
 __all__ = ['Generator', 'ResBlock1', 'ResBlock2', 'ConditionalBatchNorm1d', 'get_padding', 'init_weights',
            'hparams', 'LRELU_SLOPE', 'AdamW', 'clip_grad_norm_', 'ema_state_dict', 'MultiResolutionSTFTLoss', 'stft_loss',
-           'audio', 'resample', 'resample_table', 'resampled_length', 'peak_normalize', 'mel_loss']
+           'audio', 'resample', 'resample_table', 'resampled_length', 'peak_normalize', 'mask_tail', 'mel_loss']

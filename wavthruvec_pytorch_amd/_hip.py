@@ -304,6 +304,13 @@ SIGNATURES = {
     'v2w_l1_mean_multi_bwd': (C.c_int, [C.POINTER(L1Pair), C.c_int, C.c_float, _fp, _fp]),
     'v2w_lsgan_multi': (C.c_int, [C.POINTER(LsganItem), C.c_int, _fp, _fp, _fp]),
     'v2w_lsgan_multi_bwd': (C.c_int, [C.POINTER(LsganItem), C.c_int, _fp, _fp, _fp]),
+    # ... over a padded batch: ext a DEVICE table of n x B int32 (floats that count per row, the period folded in), then B
+    'v2w_l1_mean_multi_len': (C.c_int, [C.POINTER(L1Pair), C.c_int, _fp, C.c_int, C.c_float, _fp, _fp, _fp, _fp]),
+    'v2w_l1_mean_multi_len_bwd': (C.c_int, [C.POINTER(L1Pair), C.c_int, _fp, C.c_int, C.c_float, _fp, _fp]),
+    'v2w_lsgan_multi_len': (C.c_int, [C.POINTER(LsganItem), C.c_int, _fp, C.c_int, _fp, _fp, _fp]),
+    'v2w_lsgan_multi_len_bwd': (C.c_int, [C.POINTER(LsganItem), C.c_int, _fp, C.c_int, _fp, _fp, _fp]),
+    'v2w_map_extents': (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, _fp]),
+    'v2w_mask_tail': (C.c_int, [_fp, _fp, C.c_longlong, C.c_int, C.c_int, _fp, C.c_int, _fp]),
     # multi-resolution STFT loss: host descriptor array; sc / mag / total / sums / scratch and the gradients are DEVICE memory
     'v2w_stft_loss_plan': (C.c_int, [C.POINTER(StftLossItem), C.c_int, C.POINTER(C.c_int32)]),
     'v2w_stft_loss_scratch_bytes': (C.c_longlong, [C.POINTER(StftLossItem), C.c_int]),

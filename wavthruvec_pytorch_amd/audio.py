@@ -24,7 +24,7 @@ from typing import Dict, Tuple
 import numpy as np
 import torch
 
-from . import _hip, mel
+from . import _hip, hipops, mel
 
 _CONSTS: Dict[Tuple, dict] = {}
 
@@ -147,3 +147,39 @@ def resample(x, orig_freq, new_freq, *, lengths=None, lowpass_filter_width=6, ro
 def peak_normalize(y, peak=0.95, lengths=None):
     """librosa.util.normalize(y) * peak per item of y (B, n) or (n,), for audio that needs no rate change: `resample` at equal rates."""
     return resample(y, 1, 1, lengths=lengths, peak=peak)
+
+
+class _MaskTailFn(torch.autograd.Function):
+    """mask_tail on the GPU: the same kernel each way (the backward of a select is the select of the gradient).  `lens` is the call's own
+    int32 tensor, kept by reference."""
+
+    @staticmethod
+    def forward(ctx, y, lens, len_mul):
+        ctx.lens, ctx.len_mul = lens, len_mul
+        return hipops.mask_tail(y.detach().contiguous(), lens, len_mul)
+
+    @staticmethod
+    @_hip.on_tensor_device
+    def backward(ctx, g):
+        return hipops.mask_tail(g.contiguous().float(), ctx.lens, ctx.len_mul), None, None
+
+
+@_hip.on_tensor_device
+def mask_tail(y, lengths, len_mul=1):
+    """y (B, ..., L) float32 -> y with y[b, ..., n_b:] = +0.0, n_b = min(lengths[b] * len_mul, L) (mel.check_lengths' conventions), by select:
+    NaN or Inf past n_b does not pass, and n_b = L returns y's bits.  Differentiable: the gradient passes on the valid part and is +0.0
+    past it.  One launch each way (v2w_mask_tail); CPU tensors take the torch expression.
+    A trainer that batches padded utterances applies this to the generated batch before the discriminators - the train-mode generator
+    writes non-zero audio in the padding, which the discriminators would score and the `lengths=` losses would still see through the
+    convs' windows at an utterance's last positions."""
+    if not torch.is_tensor(y) or y.dim() < 2 or y.dtype != torch.float32:
+        raise ValueError('mask_tail: y must be a float32 tensor of shape (B, ..., L)')
+    B, L = y.shape[0], y.shape[-1]
+    src = mel.check_lengths(lengths, B, L, len_mul)
+    if not y.is_cuda:
+        n = (src.to(torch.int64) * int(len_mul)).clamp(0, L).view(B, *([1] * (y.dim() - 1)))
+        return torch.where(torch.arange(L).view(*([1] * (y.dim() - 1)), L) < n, y, torch.zeros((), dtype=y.dtype))
+    lens = src.to(device=y.device, dtype=torch.int32).contiguous()
+    if torch.is_grad_enabled() and y.requires_grad:
+        return _MaskTailFn.apply(y, lens, int(len_mul))
+    return hipops.mask_tail(y.detach().contiguous(), lens, int(len_mul))

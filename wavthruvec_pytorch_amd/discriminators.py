@@ -36,7 +36,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _hip, hipops
+from . import _hip, hipops, mel
 from .synthetic import DISC_P_LAYERS, DISC_P_POST, DISC_S_LAYERS, DISC_S_POST
 
 LRELU_SLOPE = 0.1   # models.py:9
@@ -407,6 +407,18 @@ class _DiscBase(nn.Module):
     def _geometry(self, t):
         raise NotImplementedError
 
+    def _chain(self):
+        """(period, [(k, stride, pad) of every layer]): what `map_extents` walks, read from the layers themselves."""
+        return getattr(self, 'period', 1), [(l.k, l.stride, l.padding) for l in self._layers()]
+
+    def map_extents(self, n, pools=0):
+        """Rows of each returned map (the score's are the last map's) that exist for an utterance of n samples, pure integers: n ->
+        ceil(n / period) (a partly filled last row counts: the trimmed utterance's own reflect pad would fill it), `pools` times
+        m -> m // 2 + 1 (AvgPool1d(4, 2, padding=2) in front of a scale discriminator), then m -> (m + 2 pad - k) // stride + 1 per layer.
+        0 stays 0.  A map holds extent * period valid floats at the head of each (b, c) row."""
+        period, layers = self._chain()
+        return _chain_extents(int(n), period, pools, layers)
+
     def _run(self, x):
         """x (B, 1, T) -> state for the views / the backward: per layer (buffer (B, C, pitch), rows U) + the weights used."""
         b, c, t = x.shape
@@ -552,6 +564,79 @@ class _DiscFn(torch.autograd.Function):
         return (None, dx, *flat)
 
 
+def _chain_extents(n, period, pools, layers):
+    m = -(-max(n, 0) // period)
+    for _ in range(pools):
+        m = m // 2 + 1 if m > 0 else 0
+    out = []
+    for k, stride, pad in layers:
+        num = m + 2 * pad - k
+        m = num // stride + 1 if m > 0 and num >= 0 else 0
+        out.append(m)
+    return out
+
+
+class MapLengths:
+    """What `MultiPeriodDiscriminator.map_lengths` / `MultiScaleDiscriminator.map_lengths` return and the three losses take as `lengths=`:
+    `table`, int32 (rows, B) on the discriminator's device - the floats at the head of each (b, c) row that exist for item b (rows of the
+    map x period) - and `B`.  Rows: one per feature map in the order the forward returns them (discriminator by discriminator:
+    `maps`), then one per score (`scores`), then the score rows once more (`scores_twice`: the real and the generated scores of
+    discriminator_loss in one table).  `counts[d]`: maps of discriminator d."""
+    __slots__ = ('table', 'B', 'counts')
+
+    def __init__(self, table, counts):
+        self.table, self.B, self.counts = table, int(table.shape[1]), tuple(counts)
+        assert table.dtype == torch.int32 and table.shape[0] == sum(counts) + 2 * len(counts)
+
+    @property
+    def maps(self):
+        return self.table[:sum(self.counts)]
+
+    @property
+    def scores(self):
+        n = sum(self.counts)
+        return self.table[n:n + len(self.counts)]
+
+    @property
+    def scores_twice(self):
+        return self.table[sum(self.counts):]
+
+    def __repr__(self):
+        return f'MapLengths(B={self.B}, maps={sum(self.counts)}, scores={len(self.counts)}, device={self.table.device})'
+
+
+def _map_lengths(module, discs, pools, lengths, len_mul, L):
+    """The MapLengths of `discs` (discriminator d behind pools[d] mean pools).  Host lengths: the integers of `map_extents`, one upload.
+    Device lengths: one launch of v2w_map_extents from the lengths and the constant chain table of the module (cached per device and L)
+    - nothing comes to the host."""
+    B = lengths.numel() if torch.is_tensor(lengths) else len(lengths)
+    src = mel.check_lengths(lengths, B, L, len_mul)
+    len_mul = int(len_mul)
+    chains = [d._chain() for d in discs]
+    layers = chains[0][1]
+    if any(c[1] != layers for c in chains):
+        raise NotImplementedError('map_lengths: the discriminators of one module share their layers\' (k, stride, pad)')
+    counts = [len(layers)] * len(discs)
+    # rows {period, pools, depth, size}: the maps, the scores, the scores again; size: the rows of the map of an L-sample batch (0: no clip)
+    sizes = [d.map_extents(L, pl) if L is not None else [0] * len(layers) for d, pl in zip(discs, pools)]
+    rows = [(c[0], pl, j + 1, sz[j]) for c, pl, sz in zip(chains, pools, sizes) for j in range(len(layers))]
+    score_rows = [(c[0], pl, len(layers), sz[-1]) for c, pl, sz in zip(chains, pools, sizes)]
+    rows += score_rows + score_rows
+    dev = src.device if src.is_cuda else next(module.parameters()).device
+    if not src.is_cuda:
+        cap = 2 ** 31 - 1 if L is None else int(L)
+        table = [[min(_chain_extents(min(n * len_mul, cap), per, pl, layers[:depth])[-1], size or 2 ** 31) * per
+                  for n in src.tolist()] for per, pl, depth, size in rows]
+        return MapLengths(torch.tensor(table, dtype=torch.int32).reshape(len(rows), B).to(dev), counts)
+    cache = module.__dict__.setdefault('_chain_tables', {})
+    key = (str(dev), L)
+    if key not in cache:
+        cache[key] = (torch.tensor(rows, dtype=torch.int32).to(dev), torch.tensor(layers, dtype=torch.int32).to(dev))
+    with torch.cuda.device(dev):
+        table = hipops.map_extents(src.to(torch.int32).contiguous(), len_mul, 2 ** 31 - 1 if L is None else int(L), *cache[key])
+    return MapLengths(table, counts)
+
+
 class DiscriminatorP(_DiscBase):
     """models.py:158-193."""
 
@@ -636,6 +721,12 @@ class MultiPeriodDiscriminator(nn.Module):
     def forward(self, y, y_hat):
         return _pairwise(self.discriminators, [(y, y_hat)] * len(self.discriminators))
 
+    def map_lengths(self, lengths, len_mul=1, L=None):
+        """The `MapLengths` of this module's maps and scores for a padded batch whose item b holds n_b = min(lengths[b] * len_mul, L)
+        samples (`mel.check_lengths`' conventions; lengths: a list or an integer tensor on any device; L: the batch's samples - given, every
+        extent is also clipped to the map's size, which the loss kernels do anyway).  See `feature_loss` for what the extents mean."""
+        return _map_lengths(self, list(self.discriminators), [0] * len(self.discriminators), lengths, len_mul, L)
+
 
 class DiscriminatorS(_DiscBase):
     """models.py:219-243."""
@@ -690,6 +781,10 @@ class MultiScaleDiscriminator(nn.Module):
         for pool in self.meanpools:
             pyramid.append((pool(pyramid[-1][0]), pool(pyramid[-1][1])))
         return _pairwise(self.discriminators, pyramid)
+
+    def map_lengths(self, lengths, len_mul=1, L=None):
+        """`MultiPeriodDiscriminator.map_lengths` for the three scales: discriminator j sits behind j mean pools."""
+        return _map_lengths(self, list(self.discriminators), list(range(len(self.discriminators))), lengths, len_mul, L)
 
 
 class frozen:
@@ -765,6 +860,46 @@ class _L1MultiFn(torch.autograd.Function):
         return (None, None, *da, *db)
 
 
+class _L1MultiLenFn(torch.autograd.Function):
+    """`_L1MultiFn` over the counted floats of a padded batch: `ext` (n, B) rows of a MapLengths table, kept by reference for the backward."""
+
+    @staticmethod
+    def forward(ctx, scale, n, ext, *maps):
+        ctx.scale, ctx.n, ctx.ext = scale, n, ext
+        ctx.save_for_backward(*maps)
+        return hipops.l1_mean_multi(list(zip(maps[:n], maps[n:])), scale, ext=ext)[1]
+
+    @staticmethod
+    @_hip.on_tensor_device
+    def backward(ctx, g):
+        maps, n = ctx.saved_tensors, ctx.n
+        need = ctx.needs_input_grad[3:]
+        da, db = hipops.l1_mean_multi_bwd(list(zip(maps[:n], maps[n:])), ctx.scale, g.contiguous(), need[:n], need[n:], ext=ctx.ext)
+        return (None, None, None, *da, *db)
+
+
+class _LsganLenFn(torch.autograd.Function):
+    """`_LsganFn` over the counted floats of a padded batch (`ext`: the score rows of a MapLengths table)."""
+
+    @staticmethod
+    def forward(ctx, targets, ext, *scores):
+        ctx.targets, ctx.ext = targets, ext
+        ctx.save_for_backward(*scores)
+        ctx.set_materialize_grads(False)
+        terms, total = hipops.lsgan_multi(scores, targets, ext=ext)
+        return total, terms
+
+    @staticmethod
+    def backward(ctx, g_total, g_terms):
+        scores = ctx.saved_tensors
+        if g_total is None and g_terms is None:
+            return (None,) * (2 + len(scores))
+        with torch.cuda.device(scores[0].device):
+            ds = hipops.lsgan_multi_bwd(scores, ctx.targets, None if g_total is None else g_total.contiguous(),
+                                        None if g_terms is None else g_terms.contiguous(), ctx.needs_input_grad[2:], ext=ctx.ext)
+        return (None, None, *ds)
+
+
 class _LsganFn(torch.autograd.Function):
     """(sum_i mean (t_i - s_i)^2, the n terms) of n score tensors with targets t_i in {0, 1}: one launch forward, one backward (gradients
     that arrive on the total and on single terms are added inside the kernel)."""
@@ -792,13 +927,44 @@ def _any_cpu(tensors):
     return any(not t.is_cuda for t in tensors)
 
 
-def _lsgan(scores, targets):
+def _lsgan(scores, targets, ext=None):
     """(total, terms (n,)) of the LSGAN terms of GPU score tensors: one launch per hipops.LOSS_MAX_ITEMS tensors."""
     cap = _hip.LOSS_MAX_ITEMS
-    outs = [_LsganFn.apply(tuple(targets[i:i + cap]), *scores[i:i + cap]) for i in range(0, len(scores), cap)]
+    if ext is None:
+        outs = [_LsganFn.apply(tuple(targets[i:i + cap]), *scores[i:i + cap]) for i in range(0, len(scores), cap)]
+    else:
+        outs = [_LsganLenFn.apply(tuple(targets[i:i + cap]), ext[i:i + cap], *scores[i:i + cap]) for i in range(0, len(scores), cap)]
     if len(outs) == 1:
         return outs[0]
     return sum(t for t, _ in outs), torch.cat([x for _, x in outs])
+
+
+def _ext_rows(lengths, which, tensors, what):
+    """The rows `which` ('maps', 'scores', 'scores_twice') of a MapLengths table for `tensors` (one row each), checked before anything is
+    launched."""
+    if not isinstance(lengths, MapLengths):
+        raise TypeError(f'{what}: lengths must be the MapLengths of the discriminator that made the maps (its map_lengths(...))')
+    rows = getattr(lengths, which)
+    if rows.shape[0] != len(tensors):
+        raise ValueError(f'{what}: {len(tensors)} tensors, but the MapLengths holds {rows.shape[0]} rows for them')
+    for t in tensors:
+        if t.dim() < 2 or t.shape[0] != lengths.B:
+            raise ValueError(f'{what}: the MapLengths is of a batch of {lengths.B}, a tensor is {tuple(t.shape)}')
+    if tensors and rows.device != tensors[0].device:
+        rows = rows.to(tensors[0].device)
+    return rows
+
+
+def _masked_term(x, ext_row):
+    """sum of x over the counted floats / their count (0 when there are none), in torch: x (B, C, ...) or (B, N), row (b, c) counts its
+    first ext_row[b] floats - the definition the HIP kernels implement, for CPU tensors."""
+    B = x.shape[0]
+    x3 = x.reshape(B, 1, -1) if x.dim() == 2 else x.flatten(2)
+    v = ext_row.to(torch.int64).clamp(0, x3.shape[2])
+    on = torch.arange(x3.shape[2], device=x.device).view(1, 1, -1) < v.view(B, 1, 1)
+    den = x3.shape[1] * int(v.sum())
+    s = torch.where(on, x3, torch.zeros((), dtype=x.dtype, device=x.device)).sum()
+    return s / den if den > 0 else s * 0
 
 
 def l1_mean_loss(a, b):
@@ -811,39 +977,69 @@ def l1_mean_loss(a, b):
     return _L1MultiFn.apply(1.0, 1, a, b)
 
 
-def feature_loss(fmap_r, fmap_g):
+def feature_loss(fmap_r, fmap_g, lengths=None):
     """2 x the sum over every feature map of mean |real - generated| (models.py:278-284).  GPU maps: all pairs of the call in one
-    autograd.Function (hipops.LOSS_MAX_ITEMS pairs per launch); CPU maps: the torch expressions."""
+    autograd.Function (hipops.LOSS_MAX_ITEMS pairs per launch); CPU maps: the torch expressions.
+
+    lengths: the `MapLengths` of the discriminator that made the maps (`mpd.map_lengths(lengths, len_mul)`), for a padded batch of
+    utterances of unequal lengths: every mean is over exactly the positions the utterance's own maps would have, and no position past them
+    receives a gradient (+0.0 there).  The VALUES at the last few of those positions are those of the padded batch: a deeper layer's
+    window there reaches into what the layer below computed past the utterance's end, where the trimmed utterance would see the conv's zero
+    padding - the call is not claimed to equal the loss of the trimmed signals (the discriminator convs are not masked).  Apply
+    `audio.mask_tail` to the generated batch first: the train-mode generator writes non-zero audio in the padding."""
     pairs = [(real, fake) for maps_r, maps_g in zip(fmap_r, fmap_g) for real, fake in zip(maps_r, maps_g)]
+    ext = None if lengths is None else _ext_rows(lengths, 'maps', [r for r, _ in pairs], 'feature_loss')
+    if lengths is not None:
+        for real, fake in pairs:
+            if real.shape != fake.shape:
+                raise ValueError(f'feature_loss: shapes differ: {tuple(real.shape)} and {tuple(fake.shape)}')
     if not pairs or _any_cpu(t for p in pairs for t in p):
+        if ext is not None:
+            return 2 * sum(_masked_term((real - fake).abs(), ext[i]) for i, (real, fake) in enumerate(pairs))
         terms = [_L1MeanFn.apply(real, fake) for real, fake in pairs]
         return 2 * sum(terms)
     cap = _hip.LOSS_MAX_ITEMS
+    if ext is not None:
+        parts = [_L1MultiLenFn.apply(2.0, len(grp), ext[i:i + cap], *[r for r, _ in grp], *[f for _, f in grp])
+                 for i, grp in ((i, pairs[i:i + cap]) for i in range(0, len(pairs), cap))]
+        return parts[0] if len(parts) == 1 else sum(parts)
     parts = [_L1MultiFn.apply(2.0, len(grp), *[r for r, _ in grp], *[f for _, f in grp])
              for grp in (pairs[i:i + cap] for i in range(0, len(pairs), cap))]
     return parts[0] if len(parts) == 1 else sum(parts)
 
 
-def discriminator_loss(disc_real_outputs, disc_generated_outputs):
+def discriminator_loss(disc_real_outputs, disc_generated_outputs, lengths=None):
     """LSGAN discriminator loss: sum over discriminators of mean (1 - D(y))^2 + mean D(y_hat)^2; also the per-discriminator
-    values as Python floats (models.py:287-299).  GPU scores: one launch, and one device-to-host copy for all the floats."""
+    values as Python floats (models.py:287-299).  GPU scores: one launch, and one device-to-host copy for all the floats.
+    lengths: the `MapLengths` of the discriminator that made the scores - the means are over the positions each utterance's own score
+    would have (see `feature_loss`)."""
     nr = min(len(disc_real_outputs), len(disc_generated_outputs))
     scores = list(disc_real_outputs[:nr]) + list(disc_generated_outputs[:nr])
+    ext = None if lengths is None else _ext_rows(lengths, 'scores_twice', scores, 'discriminator_loss')
     if not scores or _any_cpu(scores):
-        real_terms = [torch.mean((1 - score) ** 2) for score in disc_real_outputs]
-        fake_terms = [torch.mean(score ** 2) for score in disc_generated_outputs]
+        if ext is not None:
+            real_terms = [_masked_term((1 - score) ** 2, ext[i]) for i, score in enumerate(scores[:nr])]
+            fake_terms = [_masked_term(score ** 2, ext[nr + i]) for i, score in enumerate(scores[nr:])]
+        else:
+            real_terms = [torch.mean((1 - score) ** 2) for score in disc_real_outputs]
+            fake_terms = [torch.mean(score ** 2) for score in disc_generated_outputs]
         total = sum(r + f for r, f in zip(real_terms, fake_terms))
         return total, [t.item() for t in real_terms], [t.item() for t in fake_terms]
-    total, terms = _lsgan(scores, (1.0,) * nr + (0.0,) * nr)
+    total, terms = _lsgan(scores, (1.0,) * nr + (0.0,) * nr, ext)
     vals = terms.detach().tolist()
     return total, vals[:nr], vals[nr:]
 
 
-def generator_loss(disc_outputs):
-    """LSGAN generator loss: sum over discriminators of mean (1 - D(y_hat))^2, and the terms (models.py:302-310).  GPU scores: one launch."""
+def generator_loss(disc_outputs, lengths=None):
+    """LSGAN generator loss: sum over discriminators of mean (1 - D(y_hat))^2, and the terms (models.py:302-310).  GPU scores: one launch.
+    lengths: as in `discriminator_loss`."""
     scores = list(disc_outputs)
+    ext = None if lengths is None else _ext_rows(lengths, 'scores', scores, 'generator_loss')
     if not scores or _any_cpu(scores):
-        terms = [torch.mean((1 - score) ** 2) for score in disc_outputs]
+        if ext is not None:
+            terms = [_masked_term((1 - score) ** 2, ext[i]) for i, score in enumerate(scores)]
+        else:
+            terms = [torch.mean((1 - score) ** 2) for score in disc_outputs]
         return sum(terms), terms
-    total, terms = _lsgan(scores, (1.0,) * len(scores))
+    total, terms = _lsgan(scores, (1.0,) * len(scores), ext)
     return total, list(terms.unbind(0))

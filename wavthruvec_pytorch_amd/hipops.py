@@ -1390,6 +1390,45 @@ def loss_rows(t, like=None, aligned=True):
     return _rows_at(t, dims, k, aligned)
 
 
+def loss_rows_len(t, B, aligned=True):
+    """`loss_rows` for a map or score of a padded batch of B items - (B, C, U), (B, C, U, inner) or (B, N): the rows are the (b, c) rows
+    (the b rows of a score), never a longer run, so that every row lies in one item; None when the tensor has no such form."""
+    if t.dim() < 2 or t.shape[0] != B:
+        raise ValueError(f'a map or score of a batch of {B} items is (B, C, ...) or (B, N), got {tuple(t.shape)}')
+    if t.numel() == 0:
+        raise ValueError('loss of an empty tensor')
+    lead = 2 if t.dim() >= 3 else 1
+    valid = 1
+    for size, stride in reversed(list(zip(t.shape[lead:], t.stride()[lead:]))):
+        if size != 1 and stride != valid:
+            return None
+        valid *= size
+    rows = 1
+    pitch = None
+    for size, stride in reversed(list(zip(t.shape[:lead], t.stride()[:lead]))):
+        if size != 1:
+            if pitch is None:
+                pitch = stride
+            if stride != pitch * rows:
+                return None
+        rows *= size
+    pitch = valid if pitch is None else pitch
+    if pitch < valid or valid >= 2 ** 31 or pitch >= 2 ** 31:
+        return None
+    if aligned and pitch != valid and (pitch % 4 or t.data_ptr() % 16):
+        return None
+    return rows, valid, pitch
+
+
+def _ext_check(ext, n, dev):
+    """The extent table of n descriptors (`discriminators.MapLengths` rows): int32 (n, B), contiguous, on the tensors' device -> B."""
+    if not torch.is_tensor(ext) or ext.dtype != torch.int32 or ext.dim() != 2 or ext.shape[0] != n or not ext.is_contiguous():
+        raise ValueError(f'ext must be a contiguous int32 tensor of {n} rows, one per descriptor')
+    if ext.device != dev:
+        raise RuntimeError('the extent table must live on the device of the maps')
+    return int(ext.shape[1])
+
+
 def _loss_check(t, name):
     if not t.is_cuda:
         raise RuntimeError(f'{name} must live on a GPU: the HIP loss kernels have no CPU fallback')
@@ -1397,8 +1436,9 @@ def _loss_check(t, name):
         raise TypeError(f'{name} must be torch.float32, got {t.dtype}')
 
 
-def _l1_pair_array(pairs):
-    """ctypes descriptors of the pairs and the tensors they point into (contiguous copies where a view has no row form)."""
+def _l1_pair_array(pairs, B=None):
+    """ctypes descriptors of the pairs and the tensors they point into (contiguous copies where a view has no row form).  B: the pairs are
+    maps of a padded batch of B items, cut into their (b, c) rows (loss_rows_len)."""
     n = len(pairs)
     arr = (_hip.L1Pair * max(n, 1))()
     keep = []
@@ -1408,7 +1448,9 @@ def _l1_pair_array(pairs):
             raise RuntimeError('all tensors of one loss call must live on one device')
         a, b = a.detach(), b.detach()
         for _ in range(3):
-            fa, fb = loss_rows(a, b), loss_rows(b, a)
+            if B is not None and a.shape != b.shape:
+                raise ValueError(f'shapes differ: {tuple(a.shape)} and {tuple(b.shape)}')
+            fa, fb = (loss_rows(a, b), loss_rows(b, a)) if B is None else (loss_rows_len(a, B), loss_rows_len(b, B))
             if fa is not None and fb is not None:
                 break
             if fa is None:
@@ -1436,14 +1478,17 @@ def l1_plan(arr, n):
     return _multi_plan('v2w_l1_multi_plan', arr, n)
 
 
-def l1_mean_multi(pairs, scale=1.0):
+def l1_mean_multi(pairs, scale=1.0, ext=None):
     """pairs: [(a, b), ...] of equal-shaped fp32 GPU tensors (at most 64) -> (terms (n,), total ()): terms[i] = mean |a_i - b_i|,
     total = scale * sum(terms); one streaming and one finishing launch, deterministic.  The views the discriminators return are read
-    in place (loss_rows)."""
+    in place (loss_rows).
+    ext: int32 GPU tensor (n, B) - the pairs are maps (B, C, ...) of a padded batch and row (b, c) of pair i counts its first ext[i, b]
+    floats (v2w_l1_mean_multi_len: the mean is over the counted floats, 0 when there are none; the others are selected away)."""
     n = len(pairs)
     if n == 0:
         raise ValueError('no pairs')
-    arr, keep = _l1_pair_array(pairs)
+    B = None if ext is None else _ext_check(ext, n, pairs[0][0].device)
+    arr, keep = _l1_pair_array(pairs, B)
     dev = keep[0].device
     with torch.cuda.device(dev):
         lib = _hip.load()
@@ -1453,18 +1498,24 @@ def l1_mean_multi(pairs, scale=1.0):
         scratch = torch.empty((nbytes // 8,), device=dev, dtype=torch.float64)
         terms = torch.empty((n,), device=dev, dtype=torch.float32)
         total = torch.empty((), device=dev, dtype=torch.float32)
-        _hip.check(lib.v2w_l1_mean_multi(arr, n, float(scale), terms.data_ptr(), total.data_ptr(), scratch.data_ptr(), _stream(keep[0])),
-                   'v2w_l1_mean_multi')
+        if ext is None:
+            _hip.check(lib.v2w_l1_mean_multi(arr, n, float(scale), terms.data_ptr(), total.data_ptr(), scratch.data_ptr(), _stream(keep[0])),
+                       'v2w_l1_mean_multi')
+        else:
+            _hip.check(lib.v2w_l1_mean_multi_len(arr, n, ext.data_ptr(), B, float(scale), terms.data_ptr(), total.data_ptr(),
+                                                 scratch.data_ptr(), _stream(keep[0])), 'v2w_l1_mean_multi_len')
     return terms, total
 
 
-def l1_mean_multi_bwd(pairs, scale, gout, need_a=None, need_b=None):
-    """Gradients of `gout * l1_mean_multi(pairs, scale)[1]`: ([da_i | None], [db_i | None]), dense, shaped like the inputs; one launch.
-    gout: a one-element fp32 GPU tensor, read by the kernel.  need_a / need_b: per pair, which sides to write (default: all)."""
+def l1_mean_multi_bwd(pairs, scale, gout, need_a=None, need_b=None, ext=None):
+    """Gradients of `gout * l1_mean_multi(pairs, scale, ext)[1]`: ([da_i | None], [db_i | None]), dense, shaped like the inputs; one launch.
+    gout: a one-element fp32 GPU tensor, read by the kernel.  need_a / need_b: per pair, which sides to write (default: all).
+    ext: as in l1_mean_multi; every float that is not counted gets +0.0."""
     n = len(pairs)
     need_a = [True] * n if need_a is None else list(need_a)
     need_b = [True] * n if need_b is None else list(need_b)
-    arr, keep = _l1_pair_array(pairs)
+    B = None if ext is None else _ext_check(ext, n, pairs[0][0].device)
+    arr, keep = _l1_pair_array(pairs, B)
     dev = keep[0].device
     _loss_check(gout, 'gout')
     if gout.numel() != 1:
@@ -1475,11 +1526,15 @@ def l1_mean_multi_bwd(pairs, scale, gout, need_a=None, need_b=None):
         arr[i].da, arr[i].db = _hip.ptr(da[i]), _hip.ptr(db[i])
     if any(need_a) or any(need_b):
         with torch.cuda.device(dev):
-            _hip.check(_hip.load().v2w_l1_mean_multi_bwd(arr, n, float(scale), gout.data_ptr(), _stream(keep[0])), 'v2w_l1_mean_multi_bwd')
+            if ext is None:
+                _hip.check(_hip.load().v2w_l1_mean_multi_bwd(arr, n, float(scale), gout.data_ptr(), _stream(keep[0])), 'v2w_l1_mean_multi_bwd')
+            else:
+                _hip.check(_hip.load().v2w_l1_mean_multi_len_bwd(arr, n, ext.data_ptr(), B, float(scale), gout.data_ptr(), _stream(keep[0])),
+                           'v2w_l1_mean_multi_len_bwd')
     return da, db
 
 
-def _lsgan_array(scores, targets):
+def _lsgan_array(scores, targets, B=None):
     n = len(scores)
     if len(targets) != n:
         raise ValueError('one target per score tensor')
@@ -1490,37 +1545,46 @@ def _lsgan_array(scores, targets):
         if s.device != scores[0].device:
             raise RuntimeError('all tensors of one loss call must live on one device')
         s = s.detach()
-        form = loss_rows(s, aligned=False)
+        rows_of = (lambda t: loss_rows(t, aligned=False)) if B is None else (lambda t: loss_rows_len(t, B, aligned=False))
+        form = rows_of(s)
         if form is None:
             s = s.contiguous()
-            form = loss_rows(s, aligned=False)
+            form = rows_of(s)
         keep.append(s)
         d = arr[i]
         d.s, d.rows, d.valid, d.pitch, d.target = s.data_ptr(), form[0], form[1], form[2], float(t)
     return arr, keep
 
 
-def lsgan_multi(scores, targets):
+def lsgan_multi(scores, targets, ext=None):
     """scores: fp32 GPU tensors (at most 64), targets: 0 / 1 each -> (terms (n,), total ()): terms[i] = mean (target_i - s_i)^2,
-    total = sum(terms); one launch."""
+    total = sum(terms); one launch.  ext: int32 GPU tensor (n, B) - the scores are (B, N) (or (B, C, ...)) of a padded batch, each row
+    counts its first ext[i, b] floats (v2w_lsgan_multi_len)."""
     n = len(scores)
     if n == 0:
         raise ValueError('no scores')
-    arr, keep = _lsgan_array(scores, targets)
+    B = None if ext is None else _ext_check(ext, n, scores[0].device)
+    arr, keep = _lsgan_array(scores, targets, B)
     dev = keep[0].device
     terms = torch.empty((n,), device=dev, dtype=torch.float32)
     total = torch.empty((), device=dev, dtype=torch.float32)
     with torch.cuda.device(dev):
-        _hip.check(_hip.load().v2w_lsgan_multi(arr, n, terms.data_ptr(), total.data_ptr(), _stream(keep[0])), 'v2w_lsgan_multi')
+        if ext is None:
+            _hip.check(_hip.load().v2w_lsgan_multi(arr, n, terms.data_ptr(), total.data_ptr(), _stream(keep[0])), 'v2w_lsgan_multi')
+        else:
+            _hip.check(_hip.load().v2w_lsgan_multi_len(arr, n, ext.data_ptr(), B, terms.data_ptr(), total.data_ptr(), _stream(keep[0])),
+                       'v2w_lsgan_multi_len')
     return terms, total
 
 
-def lsgan_multi_bwd(scores, targets, gout=None, gterms=None, need=None):
+def lsgan_multi_bwd(scores, targets, gout=None, gterms=None, need=None, ext=None):
     """Gradients of lsgan_multi: ds_i = 2 (s_i - target_i) * (gout + gterms[i]) / numel_i, dense, shaped like the scores; one launch.
-    gout (one element) / gterms (n): fp32 GPU tensors, read by the kernel; one of them may be None."""
+    gout (one element) / gterms (n): fp32 GPU tensors, read by the kernel; one of them may be None.  ext: as in lsgan_multi (numel_i is the
+    count of the counted floats; the others get +0.0)."""
     n = len(scores)
     need = [True] * n if need is None else list(need)
-    arr, keep = _lsgan_array(scores, targets)
+    B = None if ext is None else _ext_check(ext, n, scores[0].device)
+    arr, keep = _lsgan_array(scores, targets, B)
     dev = keep[0].device
     for g, name, cnt in ((gout, 'gout', 1), (gterms, 'gterms', n)):
         if g is not None:
@@ -1532,8 +1596,42 @@ def lsgan_multi_bwd(scores, targets, gout=None, gterms=None, need=None):
         arr[i].ds = _hip.ptr(ds[i])
     if any(need):
         with torch.cuda.device(dev):
-            _hip.check(_hip.load().v2w_lsgan_multi_bwd(arr, n, _hip.ptr(gout), _hip.ptr(gterms), _stream(keep[0])), 'v2w_lsgan_multi_bwd')
+            if ext is None:
+                _hip.check(_hip.load().v2w_lsgan_multi_bwd(arr, n, _hip.ptr(gout), _hip.ptr(gterms), _stream(keep[0])), 'v2w_lsgan_multi_bwd')
+            else:
+                _hip.check(_hip.load().v2w_lsgan_multi_len_bwd(arr, n, ext.data_ptr(), B, _hip.ptr(gout), _hip.ptr(gterms), _stream(keep[0])),
+                           'v2w_lsgan_multi_len_bwd')
     return ds
+
+
+def map_extents(lens, len_mul, L, chains, layers):
+    """lens: int32 GPU tensor (B,); chains (n, 4) {period, pools, depth, size} and layers (n_layers, 3) {k, stride, pad}: int32 GPU tensors
+    -> ext (n, B) int32, the floats per row that exist for each item (include/vec2wav_hip.h v2w_map_extents); one launch, no sync."""
+    for t, name in ((lens, 'lens'), (chains, 'chains'), (layers, 'layers')):
+        if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
+            raise ValueError(f'{name} must be a contiguous int32 GPU tensor')
+    n, B = chains.shape[0], lens.numel()
+    ext = torch.empty((n, B), dtype=torch.int32, device=lens.device)
+    with torch.cuda.device(lens.device):
+        _hip.check(_hip.load().v2w_map_extents(lens.data_ptr(), int(len_mul), int(L), B, chains.data_ptr(), n, layers.data_ptr(),
+                                               layers.shape[0], ext.data_ptr(), _stream(lens)), 'v2w_map_extents')
+    return ext
+
+
+def mask_tail(x, lens, len_mul=1):
+    """x (B, ..., L) fp32 contiguous GPU tensor, lens int32 GPU (B,) -> x with x[b, ..., m_b:] = +0.0 by select, m_b = min(lens[b] * len_mul,
+    L) (v2w_mask_tail); one launch."""
+    _loss_check(x, 'x')
+    if x.dim() < 2 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError('mask_tail: x must be a non-empty contiguous (B, ..., L) tensor')
+    B, L = x.shape[0], x.shape[-1]
+    if lens.dtype != torch.int32 or lens.numel() != B or lens.device != x.device:
+        raise ValueError(f'lens must hold {B} int32 on the device of x')
+    out = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _hip.check(_hip.load().v2w_mask_tail(x.data_ptr(), out.data_ptr(), x.numel() // L, B, L, lens.data_ptr(), int(len_mul), _stream(x)),
+                   'v2w_mask_tail')
+    return out
 
 
 # ---- multi-tensor launches over flat tensors (csrc/v2w_multi.h): AdamW, the global-norm clip, the average of the weights
